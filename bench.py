@@ -16,7 +16,7 @@ flush rate as three runs per 32 768 SNPs at a smaller weight error, DESIGN.md 4.
   --workload ibs    configs[1]  snpgdsIBSNum   N = 10 000
   --workload king   snpgdsIBDKING robust       N = 10 000, 5 % missing
   --workload pca    snpgdsPCA covariance       N = 100 000
-At N = 1 the JSON line also carries short runs of the other paths, one row each in `summary` -- the LAST key of the line, so that
+At N = 1 with --full the JSON line also carries short runs of the other paths, one row each in `summary` -- the LAST key of the line, so that
 it survives the driver's 8 KB tail -- [value, ms per step, roofline fraction of the dominant kernel, kernel, kernel ms per step]: ibs,
 ibs_missing_0.02, king, king_missing_0, king_homo, the real-data path grm_missing_0.02, grm_feed_pinned_2bit (SURVEY 8(d)'s "end-to-end
 incl. feed": the same steps with every block coming from pinned host memory), grm_exact_row, grm_run8192, grm_fast and the north_star
@@ -32,6 +32,14 @@ block are computed once per node (--shared-stats).
 Round 6: config.sclk_mhz_median / power_w_median = shader clock and socket power sampled during the timed region (amdsmi), and
 roofline.sustained_peak_measured = what a register-only stream of the kernel's MFMA instruction and operand class sustains on THIS box in
 THIS run (snpgpu_diag_mfma_rate; config.sustained_probe holds every class) -- the kernels run against the socket power cap.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs: set-up, W warm-up steps, the K timed steps
+and the result line.  Everything else -- the `summary` sub-runs, the CPU baseline, the sustained-MFMA probe, clock / power telemetry,
+the rocprofv3 traffic passes and, for N > 1, the timed slab gather -- runs with --full (the --no-* flags still switch single parts off
+there).  --dump-outputs DIR writes what the timed path returned after its last step: the finalised packed triangle(s) as float64
+DIR/<name>.npy, the whole triangle when it is small, otherwise a fixed seeded sample of its entries (every diagonal entry plus
+uniformly drawn ones, their packed indices in DIR/sample_index.npy), at most 64 MB in all.  The diagonal is included while it fills
+at most half the sample (N up to ~1.9 M samples for one output, ~0.98 M for two or three); beyond that the sample is uniform only.
 """
 import argparse
 import json
@@ -348,6 +356,58 @@ def synth_blocks(n, b, missing, count, device_index):
     return out
 
 
+OUTPUT_NAMES = {"GRM_GCTA": ["grm"], "PCA_COV": ["cov_raw"], "IBS": ["ibs0", "ibs1", "ibs2"], "KING_ROBUST": ["ibs0", "kinship"],
+                "KING_HOMO": ["k0", "k1"]}
+DUMP_BYTES = 60 << 20                  # all files of --dump-outputs together (< 64 MB)
+
+
+def dump_index(n, n_out):
+    """Packed upper-triangle indices written by --dump-outputs: None = the whole triangle (it fits), else the sorted indices of every
+    diagonal entry plus entries drawn uniformly with a fixed seed -- identical for identical arguments.  The diagonal is part of the
+    sample only while it fills at most half of it (n <= cap // 2: n up to ~1.97 M for one output, ~0.98 M for two or three); for a
+    larger n the sample is the uniform draw alone."""
+    n_tri = n * (n + 1) // 2
+    if n_tri * 8 * n_out <= DUMP_BYTES:
+        return None
+    cap = DUMP_BYTES // (8 * (n_out + 1))                 # values of every output + the index itself
+    diag = np.arange(n, dtype=np.int64)
+    diag = diag * (2 * n - diag + 1) // 2 if n <= cap // 2 else np.empty(0, np.int64)
+    rnd = np.random.default_rng(SEED).integers(0, n_tri, size=cap - diag.size, dtype=np.int64)
+    idx = np.unique(np.concatenate([diag, rnd]))
+    return idx
+
+
+def dump_outputs(dirname, wl, outs, lo, hi, rank, dist):
+    """--dump-outputs: this rank's entries of the finalised slab [lo, hi) (packed indices), all ranks' gathered on rank 0 in index
+    order (slabs are contiguous and ordered by rank) and written there as float64 .npy files."""
+    import torch
+    names = OUTPUT_NAMES[wl["kind"]]
+    n = wl["n"]
+    idx = dump_index(n, len(names))
+    if idx is None:
+        mine = np.arange(lo, hi, dtype=np.int64)
+    else:
+        mine = idx[np.searchsorted(idx, lo):np.searchsorted(idx, hi)]
+    vals = []
+    for o in outs:
+        if mine.size:
+            sel = torch.from_numpy(mine - lo).to(o.device)
+            vals.append(o.index_select(0, sel).to(torch.float64).cpu().numpy())
+        else:
+            vals.append(np.empty(0, np.float64))
+    if dist is not None:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, vals)
+        vals = [np.concatenate([p[k] for p in parts]) for k in range(len(names))]
+    if rank != 0:
+        return
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in zip(names, vals):
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+    if idx is not None:
+        np.save(os.path.join(dirname, "sample_index.npy"), idx.astype(np.float64))
+
+
 def _time_oracle(fn, g):
     t0 = time.perf_counter()
     fn(g)
@@ -557,9 +617,9 @@ def roofline(wl, world, my_pairs, B, per_launch_ms, klaunch, env, syrk_ms_per_st
 
 
 def run_workload(wl, steps, warmup, rank, world, local, feed="device", env_over=None, dist=None, gather=False, telemetry=None,
-                 shared_stats=False):
-    """W warm-up steps, then K timed steps + one finalise (packed slab into a preallocated device buffer).
-    Returns (result dict for rank 0, or None)."""
+                 shared_stats=False, dump=None):
+    """W warm-up steps, then K timed steps + one finalise (packed slab into a preallocated device buffer); dump = a directory that
+    receives the finalised outputs (dump_outputs).  Returns (result dict for rank 0, or None)."""
     import torch
     from snprelate_amd import _lib
     from snprelate_amd.dist import panel_rows, slab_range
@@ -691,6 +751,9 @@ def run_workload(wl, steps, warmup, rank, world, local, feed="device", env_over=
             except Exception as e:           # never let the optional leg take the bench line down
                 gather_ms = "failed: %s" % str(e)[:200]
 
+        if dump:
+            dump_outputs(dump, wl, [o[: max(hi - lo, 0)] for o in outs], lo, hi, rank, dist)
+
         res = None
         if rank == 0:
             my_pairs = (r1 - r0) * n - (r0 + r1 - 1) * (r1 - r0) / 2.0
@@ -733,6 +796,11 @@ def dtype_of(wl, env):
     return "i8 (int8 MFMA, int32 accumulate: exact)"
 
 
+def use_shared_stats(mode, world):
+    """--shared-stats: "on", "off", or "auto" = on from four ranks"""
+    return mode == "on" or (mode == "auto" and world >= 4)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -743,9 +811,13 @@ def main():
     ap.add_argument("--samples", "--n", dest="n", type=int, default=0, help="override the number of samples (not the named config)")
     ap.add_argument("--block", type=int, default=0, help="override SNPs per step")
     ap.add_argument("--missing", type=float, default=None, help="override the missing-call rate of the synthetic data")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline as well: the summary sub-runs, the CPU baseline, "
+                    "the sustained-MFMA probe, clock / power telemetry, the rocprofv3 traffic passes and (N > 1) the timed slab gather")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the finalised outputs of the timed path (float64 .npy; a "
+                    "fixed seeded sample of large triangles, < 64 MB in all) to DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sub-results", action="store_true", help="skip the short ibs / king / grm_f32 / grm_missing runs")
-    ap.add_argument("--gather", action="store_true", help="(the default for --gpus N > 1 since round 6; kept for old command lines)")
+    ap.add_argument("--gather", action="store_true", help="multi-GPU: time the final gather of the slabs without --full as well")
     ap.add_argument("--no-gather", action="store_true", help="multi-GPU: skip the final RCCL gather of the slabs on rank 0 (north_star's "
                     "\"final RCCL gather over xGMI\": timed AFTER the timed region, reported as config.gather_ms, never part of `value`; "
                     "skipped by itself when the packed triangle would not fit next to rank 0's panel, N > 100 000)")
@@ -755,7 +827,7 @@ def main():
     ap.add_argument("--no-probe", action="store_true", help="skip the sustained-MFMA-rate probe (about 5 s) that fills "
                     "roofline.sustained_peak_measured and config.sustained_probe")
     ap.add_argument("--no-telemetry", action="store_true", help="do not sample shader clock / socket power during the timed region")
-    ap.add_argument("--pmc", action="store_true", help="(default when rocprofv3 is on PATH) MEASURE roofline.traffic: re-runs this "
+    ap.add_argument("--pmc", action="store_true", help="(with --full: the default when rocprofv3 is on PATH) MEASURE roofline.traffic: re-runs this "
                     "workload twice under `rocprofv3 --kernel-trace --pmc FETCH_SIZE` / `WRITE_SIZE` (separate passes, no other trace "
                     "domain) after the timed run and sums the dominant kernel's counters per step (adds about a minute)")
     ap.add_argument("--no-pmc", action="store_true", help="quote roofline.traffic from the committed profile instead of measuring it")
@@ -837,13 +909,13 @@ def main():
                 "rank_devices": devs, "distinct_devices": len(set(d.split(" ")[0].split("@")[1] for d in devs)),
                 "self_launched": bool(os.environ.get("SNPGPU_BENCH_SELF_LAUNCHED"))}
 
-    if not args.no_probe and not overridden or os.environ.get("SNPGPU_BENCH_PROBE"):
+    if args.full and not args.no_probe and not overridden or os.environ.get("SNPGPU_BENCH_PROBE"):
         # every rank at once (the node's power budget is shared); N = 1: 1.5 s per operand class, N > 1: the headline's class only
         PROBE.update(sustained_probe(local, 1.5 if world == 1 else 1.0, ("f16_uv_16x16x32", "f16_uv", "f16_exact_row", "fp4", "f16_zero") if world == 1 else ("f16_uv_16x16x32",)))
-    tele = None if args.no_telemetry else Telemetry(local)
-    do_gather = dist is not None and not args.no_gather and wl["n"] <= 100000
+    tele = Telemetry(local) if args.full and not args.no_telemetry else None
+    do_gather = dist is not None and (args.gather or (args.full and not args.no_gather)) and wl["n"] <= 100000
     main_res = run_workload(wl, args.steps, args.warmup, rank, world, local, feed=args.feed, dist=dist, gather=do_gather, telemetry=tele,
-                            shared_stats=args.shared_stats == "on" or (args.shared_stats == "auto" and world >= 4))
+                            shared_stats=use_shared_stats(args.shared_stats, world), dump=args.dump_outputs)
     out = None
     if rank == 0:
         out = {
@@ -872,7 +944,7 @@ def main():
     # dominant kernel, that kernel, its ms per step]; the long form of every run goes to --details FILE.
     details = {}
     summary = {}
-    if world == 1 and not args.no_sub_results and not overridden and args.workload == "grm" and args.feed == "device":
+    if args.full and world == 1 and not args.no_sub_results and not overridden and args.workload == "grm" and args.feed == "device":
         plan = [("ibs", WORKLOADS["ibs"], 40, 20, {}, "device"), ("ibs_missing_0.02", dict(WORKLOADS["ibs"], missing=0.02), 40, 20, {}, "device"),
                 ("king", WORKLOADS["king"], 40, 20, {}, "device"),
                 ("king_missing_0", dict(WORKLOADS["king"], missing=0.0), 40, 20, {}, "device"),
@@ -917,7 +989,7 @@ def main():
             out["feed_inclusive"] = {"workload": "configs[2], blocks from pinned host memory via snpgpu_feed(SNPGPU_HOST_PINNED), 2-bit rows",
                                      "value": fd["value"], "unit": fd["unit"], "ms_per_step": fd["ms_per_step"],
                                      "vs_resident": fd["value"] / out["value"]}
-    if rank == 0 and world == 1 and not args.no_pmc and args.feed == "device":
+    if args.full and rank == 0 and world == 1 and not args.no_pmc and args.feed == "device":
         import shutil
         if args.pmc or shutil.which("rocprofv3"):
             try:
@@ -930,7 +1002,7 @@ def main():
             r["traffic_over_algorithmic"] = r["traffic"] / r["algorithmic_bytes"]
         out["source_stamp"] = source_stamp()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl["kind"])
         if args.details:
             with open(args.details, "w") as f:

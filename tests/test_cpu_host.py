@@ -588,3 +588,40 @@ def test_bench_self_launch_needs_one_device_per_rank():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], capture_output=True,
                        text=True, timeout=300, env=env)
     assert r.returncode == 2 and "HIP device" in r.stderr and not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_eight_way_plan_covers_the_triangle_once():
+    """The plan `bench.py --gpus 8` runs at n = 20 000: eight row panels whose slabs of the packed triangle are contiguous, in rank
+    order, cover it exactly once (the rank_pairs bench.py reports sum to n (n + 1) / 2, none empty), and cost within 1.15 of each
+    other (256-row boundaries at this small n)."""
+    from snprelate_amd.dist import panel_cost, panel_rows, slab_range
+    n, world = 20000, 8
+    b = panel_rows(n, world)
+    assert len(b) == world + 1 and b[0] == 0 and b[-1] == n
+    pairs = [(b[r + 1] - b[r]) * n - (b[r] + b[r + 1] - 1) * (b[r + 1] - b[r]) / 2.0 for r in range(world)]
+    assert sum(pairs) == n * (n + 1) / 2 and min(pairs) > 0
+    slabs = [slab_range(n, b[r], b[r + 1]) for r in range(world)]
+    assert slabs[0][0] == 0 and slabs[-1][1] == n * (n + 1) // 2 and all(x[1] == y[0] for x, y in zip(slabs, slabs[1:]))
+    assert all(hi - lo == p for (lo, hi), p in zip(slabs, pairs))
+    cost = [panel_cost(n, b[i], b[i + 1], alpha=min(512.0, n / 32.0)) for i in range(world)]
+    assert max(cost) / (sum(cost) / world) < 1.15
+
+
+def test_bench_shared_stats_switch():
+    """--shared-stats auto: per-SNP statistics once per node from four ranks on; on / off as given"""
+    from bench import use_shared_stats
+    assert [use_shared_stats("auto", w) for w in (1, 2, 3, 4, 8)] == [False, False, False, True, True]
+    assert use_shared_stats("on", 2) and not use_shared_stats("off", 8)
+
+
+def test_bench_dump_index():
+    """--dump-outputs' sample of a large triangle: the same indices on every call, sorted, unique, inside the triangle, every diagonal
+    entry while the diagonal fills at most half the sample, and within the byte budget (values of every output + the index)."""
+    from bench import DUMP_BYTES, dump_index
+    assert dump_index(1500, 1) is None                           # 9 MB: the whole triangle
+    for n, k in ((100000, 1), (10000, 3), (4100, 3)):
+        idx = dump_index(n, k)
+        assert np.array_equal(idx, dump_index(n, k)) and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n * (n + 1) // 2
+        diag = np.arange(n, dtype=np.int64)
+        assert np.isin(diag * (2 * n - diag + 1) // 2, idx).all()
+        assert idx.size * 8 * (k + 1) <= DUMP_BYTES

@@ -22,7 +22,7 @@ run() {  # name, rocprof args..., -- bench args
 }
 if has bench; then
     # the driver's command (defaults) and its usual step counts: the line as the driver will see it, traffic measured by the run itself
-    python bench.py --steps 20 --warmup 5 --details "$OUT/bench_details.json" > "$OUT/bench_default.log" 2> "$OUT/bench_default.err"
+    python bench.py --full --steps 20 --warmup 5 --details "$OUT/bench_details.json" > "$OUT/bench_default.log" 2> "$OUT/bench_default.err"
     grep '^{' "$OUT/bench_default.log" | tail -1 > "$OUT/bench_default.json"
 fi
 if has trace; then
@@ -101,11 +101,12 @@ for name, m in (("f16_zero 32x32x16", _lib.DIAG_F16_ZERO), ("f16_uv 32x32x16", _
 PY
 fi
 if has multi; then
-    # round 6: the self-launching multi-rank bench on the one GPU (gloo: RCCL needs one device per rank) -- 2 and 8 ranks, defaults otherwise
-    SNPGPU_BENCH_BACKEND=gloo SNPGPU_BENCH_FORCE_DEVICE=0 python bench.py --gpus 2 --steps 4 --warmup 1 --samples 40000 > "$OUT/bench_gpus2_one_device.log" 2> "$OUT/bench_gpus2.err"
+    # the self-launching multi-rank bench: 2 ranks on the one GPU (gloo: RCCL needs one device per rank), defaults otherwise
+    SNPGPU_BENCH_BACKEND=gloo SNPGPU_BENCH_FORCE_DEVICE=0 python bench.py --full --gpus 2 --steps 4 --warmup 1 --samples 40000 > "$OUT/bench_gpus2_one_device.log" 2> "$OUT/bench_gpus2.err"
     grep '^{' "$OUT/bench_gpus2_one_device.log" | tail -1 > "$OUT/bench_gpus2_one_device.json"
-    SNPGPU_BENCH_BACKEND=gloo SNPGPU_BENCH_FORCE_DEVICE=0 python bench.py --gpus 8 --steps 4 --warmup 1 --samples 40000 > "$OUT/bench_gpus8_one_device.log" 2> "$OUT/bench_gpus8.err"
-    grep '^{' "$OUT/bench_gpus8_one_device.log" | tail -1 > "$OUT/bench_gpus8_one_device.json"
+    # eight ranks need eight devices (one rank per GPU, RCCL); bench.py refuses with exit code 2 on a box with fewer
+    python bench.py --full --gpus 8 --steps 4 --warmup 1 --samples 40000 > "$OUT/bench_gpus8.log" 2> "$OUT/bench_gpus8.err" &&
+        grep '^{' "$OUT/bench_gpus8.log" | tail -1 > "$OUT/bench_gpus8.json"
 fi
 if has uvc; then
     # round 6 (session 3): the 16x16x32 forms of the single-product kernel on one box, interleaved -- SNPGPU_SYRK_UV16 = 1 syrk_uv16_kernel
