@@ -431,6 +431,43 @@ int snpgpu_gnrEigMixSNPLoading(const double *eigval, const double *eigvec, int l
 int snpgpu_gnrEigMixSampLoading(int eigen_cnt, const double *snp_loadings, const double *afreq, int num_thread,
                                 int verbose, double *out);
 
+/* ---- (1d) linkage disequilibrium between SNP pairs: snpgdsLDMat ------------------------------------------------------------
+ * Every method is a function of the pair's 3 x 3 genotype table n_ab (samples with genotype a at the first SNP and b at the
+ * second, over the samples called at both), counted exactly on the matrix cores and finalised in fp64 with the reference's
+ * formulas and NaN rules (src/genLD.cpp:177-525).  Output layout of gnrLDMat (src/genLD.cpp:957-1010), column-major:
+ *   slide <= 0 : the full n_snp x n_snp symmetric matrix, diagonal included;
+ *   slide  > 0 : clamped to n_snp; column i holds LD(i, i + k) in row k - 1, k = 1 ... slide: slide x n_snp with NaN past the last
+ *                SNP, or with mat_trim slide x (n_snp - slide).
+ * Streaming as for the accumulators: SNP blocks of any size in file order.  The sliding-window form keeps the last `slide` rows of
+ * a block as the halo of the next one (device memory: one block plus its halo); the full form keeps the n_snp packed rows
+ * resident and works through the matrix by row panels. */
+typedef struct snpgpu_ld snpgpu_ld;
+enum snpgpu_ld_method { SNPGPU_LD_COMPOSITE = 1, SNPGPU_LD_R = 2, SNPGPU_LD_DPRIME = 3,
+                        SNPGPU_LD_CORR = 4, SNPGPU_LD_COV = 5 };   /* gnrLDMat's `method` codes */
+/* opts: device, stream and max_block_snps (SNPs per internal block of the sliding-window form; 0 = 16384) are used */
+int snpgpu_ld_create(int64_t n_samp, int64_t n_snp, int method, int64_t slide, int mat_trim, const snpgpu_opts *opts,
+                     snpgpu_ld **out);
+int snpgpu_ld_destroy(snpgpu_ld *ld);
+/* R's nrow / ncol of the result */
+int snpgpu_ld_out_dims(const snpgpu_ld *ld, int64_t *rows, int64_t *cols);
+/* the next n_snp SNPs (rows of `format`, in `mem`: host or the device's memory).  SNPGPU_DEVICE: the block must be complete when
+ * the call is made (the object's stream is not ordered after the caller's; e.g. synchronise the writing stream first).  Either way
+ * the call returns when the block has been read, so the caller may reuse or free it at once. */
+int snpgpu_ld_feed(snpgpu_ld *ld, const void *geno, int64_t n_snp, int format, int mem);
+/* after all n_snp SNPs were fed: the rows x cols matrix, column-major, into host or device memory */
+int snpgpu_ld_result(snpgpu_ld *ld, double *out, int out_mem);
+/* HIP-event timing on the object's stream: which = 0 table (count) kernel, 1 finaliser, 2 copies of finished values from the
+ * device to the result (host memory of the object, or the caller's buffer); summed ms and operations since enabled */
+int snpgpu_ld_set_timing(snpgpu_ld *ld, int enable);
+int snpgpu_ld_get_timing(snpgpu_ld *ld, int which, double *ms_sum, int64_t *launches);
+/* every pair of two row sets -> int32 tab[n_a][n_b][9], cell 3 a + b (a: genotype in set A, b: in set B); host in, host out.
+ * The primitive of LD pruning (candidate block x kept set). */
+int snpgpu_ld_pair_tables(const void *geno_a, int64_t n_a, const void *geno_b, int64_t n_b, int64_t n_samp, int format,
+                          int32_t *tab, int device);
+/* gnrLDMat(method, NumSlide, MatTrim, NumThread, Verbose), src/genLD.cpp:957-1010, on the working space's selected SNPs;
+ * out: host, snpgpu_ld_out_dims' rows x cols */
+int snpgpu_gnrLDMat(int method, int64_t slide, int mat_trim, int num_thread, int verbose, double *out);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------------------
  * What THIS device's matrix pipe sustains right now: a register-only stream of one MFMA instruction (never waiting on memory,
  * two waves per SIMD) run for `seconds`, rate taken over the second half.  The kernels of this library run against the socket

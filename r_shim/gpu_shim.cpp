@@ -8,10 +8,10 @@
 // R/IBS.R:36,68, R/IBD.R:383,399,594, R/PCA.R:70), `.InitFile2` and the working space (gnrSetGenoSpace /
 // gnrSelSNP_Base, src/SNPRelate.cpp:76-210), the GDS block reader CGenoReadBySNP (src/dGenGWAS.cpp:1218-1397), the
 // progress bar / interrupt polling, the `out.gds` row appends (GDS_Array_AppendData) and LAPACK-free results.
-// What goes: the bodies of the seven routines below -- the CIBSCount / CKINGRobust / CKINGHomo / CGCTA_AlgArith /
+// What goes: the bodies of the eight routines below -- the CIBSCount / CKINGRobust / CKINGHomo / CGCTA_AlgArith /
 // CExactPCA / CEigMix / CIndivBeta `Run` calls with their thread pools and SIMD loops -- and CalcEigen's dspevx call.
 //
-// Registration (src/SNPRelate.cpp:1154-1205): the seven entries of callMethods[] point at the functions below,
+// Registration (src/SNPRelate.cpp:1154-1205): the eight entries of callMethods[] point at the functions below,
 // names and arity unchanged -- see r_shim/registration.inc.  R_useDynamicSymbols(FALSE) stays.
 //
 //   routine replaced                                            reference body
@@ -23,6 +23,7 @@
 //                                                                grm_save_to_gds :1571-1584)
 //   gpu_gnrGRM_avg_val()                                        src/genPCA.cpp:1605-1611
 //   gpu_gnrPCA(EigenCnt, Algorithm, NumThread, ParamList, V.)   src/genPCA.cpp:1355-1452 (+ CalcEigen :1262-1346)
+//   gpu_gnrLDMat(method, NumSlide, MatTrim, NumThread, Verbose) src/genLD.cpp:957-1010
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -529,6 +530,45 @@ COREARRAY_DLL_EXPORT SEXP gpu_gnrPCA(SEXP EigenCnt, SEXP Algorithm, SEXP NumThre
             throw "Invalid 'algorithm'.";
 
         if (verbose) Rprintf("%s    Done.\n", TimeToStr());
+    COREARRAY_CATCH
+}
+
+// --------------------------------------------------------------------------------------------------------------
+// LD between SNP pairs: the kept reader streams the working space into an LD object (snpgpu_ld_*), which finalises the
+// sliding-window columns block by block (or the full matrix by row panels at the end) straight into R's matrix.
+COREARRAY_DLL_EXPORT SEXP gpu_gnrLDMat(SEXP method, SEXP NumSlide, SEXP MatTrim, SEXP NumThread, SEXP Verbose)
+{
+    const int n_slide = Rf_asInteger(NumSlide);
+    const int trim_flag = Rf_asLogical(MatTrim);
+    if (trim_flag == NA_INTEGER) Rf_error("'mat.trim' should be TRUE or FALSE");
+    if (Rf_asInteger(NumThread) <= 0) Rf_error("Invalid 'num.thread'.");
+    const bool verbose = SEXP_Verbose(Verbose);
+    COREARRAY_TRY
+        CachingSNPData("LD matrix", verbose);
+        CdBaseWorkSpace &space = MCWorkingGeno.Space();
+        const size_t n_samp = space.SampleNum();
+        struct LD {
+            snpgpu_ld *ld = nullptr;
+            ~LD() { if (ld) snpgpu_ld_destroy(ld); }
+        } obj;
+        snpgpu_opts o;
+        memset(&o, 0, sizeof(o));
+        o.device = opt_int("snpgpu.device", "SNPGPU_DEVICE", 0);
+        if (snpgpu_ld_create((int64_t)n_samp, (int64_t)space.SNPNum(), Rf_asInteger(method), n_slide, trim_flag ? 1 : 0, &o, &obj.ld))
+            gpu_fail();
+        int64_t rows = 0, cols = 0;
+        if (snpgpu_ld_out_dims(obj.ld, &rows, &cols)) gpu_fail();
+        const size_t block_snps = syrk_block();
+        std::vector<C_UInt8> buf(n_samp * block_snps);
+        CGenoReadBySNP reader(1, space, block_snps, verbose ? -1 : 0, false);
+        reader.Init();
+        while (reader.Read(&buf[0])) {
+            if (snpgpu_ld_feed(obj.ld, &buf[0], (int64_t)reader.Count(), SNPGPU_GENO_U8, SNPGPU_HOST)) gpu_fail();
+            reader.ProgressForward(reader.Count());
+        }
+        PROTECT(rv_ans = Rf_allocMatrix(REALSXP, (int)rows, (int)cols));
+        if (snpgpu_ld_result(obj.ld, REAL(rv_ans), SNPGPU_HOST)) gpu_fail();
+        UNPROTECT(1);
     COREARRAY_CATCH
 }
 

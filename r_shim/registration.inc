@@ -1,5 +1,5 @@
 // Registration delta for src/SNPRelate.cpp (R_init_SNPRelate, the callMethods[] table at :1154-1205).
-// The seven entries below REPLACE the entries of the same names; every other entry, R_registerRoutines and
+// The entries below REPLACE the entries of the same names; every other entry, R_registerRoutines and
 // R_useDynamicSymbols(info, FALSE) stay as they are.  Names and arity are unchanged, so R/*.R is untouched.
 //
 //   extern "C" declarations (top of the file, next to the other routine declarations):
@@ -10,6 +10,7 @@ extern SEXP gpu_gnrIBD_KING_Robust(SEXP, SEXP, SEXP, SEXP);
 extern SEXP gpu_gnrIBSAve(SEXP, SEXP, SEXP);
 extern SEXP gpu_gnrIBSNum(SEXP, SEXP);
 extern SEXP gpu_gnrPCA(SEXP, SEXP, SEXP, SEXP, SEXP);
+extern SEXP gpu_gnrLDMat(SEXP, SEXP, SEXP, SEXP, SEXP);
 //
 //   table entries:
 //     { "gnrGRM",             (DL_FUNC)&gpu_gnrGRM,             5 },
@@ -19,6 +20,7 @@ extern SEXP gpu_gnrPCA(SEXP, SEXP, SEXP, SEXP, SEXP);
 //     { "gnrIBSAve",          (DL_FUNC)&gpu_gnrIBSAve,          3 },
 //     { "gnrIBSNum",          (DL_FUNC)&gpu_gnrIBSNum,          2 },
 //     { "gnrPCA",             (DL_FUNC)&gpu_gnrPCA,             5 },
+//     { "gnrLDMat",           (DL_FUNC)&gpu_gnrLDMat,           5 },
 //
 // The CPU bodies (gnrGRM ... in src/genPCA.cpp, src/genIBS.cpp, src/genKING.cpp) may stay in the package as
 // unregistered functions -- e.g. behind options(snpgpu.enable = FALSE) with a second table -- or be deleted together

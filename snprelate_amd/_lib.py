@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("SNPGPU_LIB") or os.path.join(_HERE, "libsnpgpu.so")
 # enums of include/snpgpu.h
 IBS, KING_ROBUST, KING_HOMO, GRM_GCTA, PCA_COV, EIGMIX, INDIV_BETA = 1, 2, 3, 4, 5, 6, 7
 GENO_U8, GENO_PACKED2 = 0, 1
+LD_COMPOSITE, LD_R, LD_DPRIME, LD_CORR, LD_COV = 1, 2, 3, 4, 5
 HOST, DEVICE, HOST_PINNED = 0, 1, 2
 
 EXPORTS = [
@@ -42,6 +43,8 @@ EXPORTS = [
     "snpgpu_multi_king_robust", "snpgpu_multi_king_robust_counts", "snpgpu_multi_king_homo", "snpgpu_multi_grm_gcta",
     "snpgpu_multi_eigmix", "snpgpu_multi_pca_trace", "snpgpu_multi_pca_cov", "snpgpu_multi_finalize_inplace",
     "snpgpu_multi_topk_eigen", "snpgpu_diag_mfma_rate", "snpgpu_diag_device_pci", "snpgpu_multi_get_status",
+    "snpgpu_ld_create", "snpgpu_ld_destroy", "snpgpu_ld_out_dims", "snpgpu_ld_feed", "snpgpu_ld_result", "snpgpu_ld_set_timing",
+    "snpgpu_ld_get_timing", "snpgpu_ld_pair_tables", "snpgpu_gnrLDMat",
 ]
 
 
@@ -205,6 +208,15 @@ def lib():
     L.snpgpu_gnrPCACorr.argtypes = [c_int, vp, c_int, c_int, vp]
     L.snpgpu_gnrPCASNPLoading.argtypes = [vp, vp, c_int, dbl, c_int, c_int, c_int, vp, vp, vp]
     L.snpgpu_gnrPCASampLoading.argtypes = [c_int, vp, vp, vp, c_int, c_int, vp]
+    L.snpgpu_ld_create.argtypes = [i64, i64, c_int, i64, c_int, ctypes.POINTER(Opts), ctypes.POINTER(vp)]
+    L.snpgpu_ld_destroy.argtypes = [vp]
+    L.snpgpu_ld_out_dims.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.snpgpu_ld_feed.argtypes = [vp, vp, i64, c_int, c_int]
+    L.snpgpu_ld_result.argtypes = [vp, vp, c_int]
+    L.snpgpu_ld_set_timing.argtypes = [vp, c_int]
+    L.snpgpu_ld_get_timing.argtypes = [vp, c_int, ctypes.POINTER(dbl), ctypes.POINTER(i64)]
+    L.snpgpu_ld_pair_tables.argtypes = [vp, i64, vp, i64, i64, c_int, vp, c_int]
+    L.snpgpu_gnrLDMat.argtypes = [c_int, i64, c_int, c_int, c_int, vp]
     _lib = L
     return L
 
@@ -481,6 +493,94 @@ def panel_entries(handle, rows, cols):
     out = np.empty(r.size, np.float64)
     check(lib().snpgpu_panel_entries(handle, _ptr(r), _ptr(c), r.size, _ptr(out)))
     return out
+
+
+def ld_out_dims(n_snp, slide, mat_trim=False):
+    """(rows, cols) of gnrLDMat's result: slide <= 0 -> n_snp x n_snp; else slide clamped to n_snp, slide x n_snp, or
+    slide x (n_snp - slide) with mat_trim (src/genLD.cpp:983-1005)"""
+    n_snp, slide = int(n_snp), int(slide)
+    if slide <= 0:
+        return n_snp, n_snp
+    slide = min(slide, n_snp)
+    return slide, (n_snp - slide if mat_trim else n_snp)
+
+
+class LDMatrix:
+    """One streaming LD object (snpgpu_ld, include/snpgpu.h section 1d): feed SNP blocks in file order, then result()
+    returns the gnrLDMat matrix as a numpy array of R's dimensions (rows, cols)."""
+
+    def __init__(self, n_samp, n_snp, method=LD_COMPOSITE, slide=250, mat_trim=False, device=0, max_block_snps=0, stream=None):
+        self.n, self.L = int(n_samp), int(n_snp)
+        o = Opts(int(device), 0, 0, 0, int(max_block_snps), ctypes.c_void_p(stream) if stream else None)
+        h = ctypes.c_void_p()
+        check(lib().snpgpu_ld_create(self.n, self.L, int(method), int(slide), int(bool(mat_trim)), ctypes.byref(o), ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if self._h:
+            lib().snpgpu_ld_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def dims(self):
+        r, c = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(lib().snpgpu_ld_out_dims(self._h, ctypes.byref(r), ctypes.byref(c)))
+        return r.value, c.value
+
+    def feed(self, geno, fmt=None):
+        """geno: numpy uint8 [n_snp][n_samp] (U8) or [n_snp][ceil(n/4)] (PACKED2)."""
+        g = np.ascontiguousarray(geno, dtype=np.uint8)
+        if fmt is None:
+            fmt = GENO_U8 if g.shape[1] == self.n else GENO_PACKED2
+        exp = self.n if fmt == GENO_U8 else (self.n + 3) // 4
+        if g.ndim != 2 or g.shape[1] != exp:
+            raise ValueError("genotype block has the wrong shape")
+        check(lib().snpgpu_ld_feed(self._h, _ptr(g), g.shape[0], fmt, HOST))
+
+    def feed_device(self, dev_ptr, n_snp, fmt=GENO_PACKED2):
+        check(lib().snpgpu_ld_feed(self._h, ctypes.c_void_p(int(dev_ptr)), int(n_snp), fmt, DEVICE))
+
+    def result(self):
+        r, c = self.dims()
+        out = np.empty((c, r), np.float64)     # rows x cols column-major
+        check(lib().snpgpu_ld_result(self._h, _ptr(out), HOST))
+        return out.T
+
+    def set_timing(self, on=True):
+        check(lib().snpgpu_ld_set_timing(self._h, int(on)))
+
+    def get_timing(self, which):
+        """(summed ms, operations): which=0 table kernel, 1 finaliser, 2 device -> result copies."""
+        ms, n = ctypes.c_double(0), ctypes.c_int64(0)
+        check(lib().snpgpu_ld_get_timing(self._h, int(which), ctypes.byref(ms), ctypes.byref(n)))
+        return ms.value, n.value
+
+
+def ld_pair_tables(geno_a, geno_b, n_samp, fmt=None, device=0):
+    """int32 [n_a][n_b][3][3] genotype tables of every pair (row of A, row of B) (snpgpu_ld_pair_tables); rows in either format
+    (fmt None: U8 when a row holds n_samp bytes -- pass it explicitly for a single sample, where both forms have one byte)."""
+    n_samp = int(n_samp)
+    a = np.ascontiguousarray(geno_a, dtype=np.uint8)
+    b = np.ascontiguousarray(geno_b, dtype=np.uint8)
+    if fmt is None:
+        fmt = GENO_U8 if a.shape[1] == n_samp else GENO_PACKED2
+    exp = n_samp if fmt == GENO_U8 else (n_samp + 3) // 4
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != exp or b.shape[1] != exp:
+        raise ValueError("genotype rows have the wrong shape")
+    tab = np.empty((a.shape[0], b.shape[0], 3, 3), np.int32)
+    check(lib().snpgpu_ld_pair_tables(_ptr(a), a.shape[0], _ptr(b), b.shape[0], n_samp, fmt, _ptr(tab), int(device)))
+    return tab
 
 
 class MultiAccumulator:

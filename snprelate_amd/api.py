@@ -15,6 +15,7 @@ INTEGRATION.md):
     snpgdsEIGMIX                  R/PCA.R:311-338
     snpgdsPCA                     R/PCA.R:22-91    (algorithm="exact")
     snpgdsSNPRateFreq             R/AllUtilities.R (allele freq / MAF / missing rate)
+    snpgdsLDMat                   R/LD.R:53-92     (LD between SNP pairs)
 
 All arithmetic runs on the MI355X through libsnpgpu.so (`_lib`); there is no
 CPU fallback.  R's ``NULL`` is ``None``, ``NaN`` is ``float('nan')``; R lists
@@ -572,3 +573,47 @@ def snpgdsEIGMIX(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remove
                                            _lib._ptr(eigval), _lib._ptr(eigvec), _lib._ptr(af)))
     return dict(sample_id=ws["sample_id"], snp_id=ws["snp_id"], eigenval=eigval,
                 eigenvect=None if eigvec is None else eigvec.T, afreq=af, ibd=ibd, diagadj=bool(diagadj))
+
+
+LD_METHODS = ("composite", "r", "dprime", "corr", "cov")
+
+
+def snpgdsLDMat(gdsobj, sample_id=None, snp_id=None, slide=250, method="composite", mat_trim=False, num_thread=1,
+                with_id=True, verbose=True, device=0):
+    """Linkage disequilibrium between SNP pairs (R/LD.R:53-92 -> gnrLDMat, src/genLD.cpp:957-1010).
+    slide <= 0, None or NaN: the full n_snp x n_snp matrix; otherwise LD[k - 1, i] = LD(i, i + k), k = 1 ... slide (clamped to
+    n_snp): a slide x n_snp matrix with NaN past the last SNP, or slide x (n_snp - slide) with mat_trim.  Returns
+    dict(sample_id, snp_id, LD, slide), or the bare matrix with with_id=False."""
+    if isinstance(slide, (bool, np.bool_)) or not isinstance(slide, (int, float, np.integer, np.floating, type(None))):
+        raise TypeError("is.numeric(slide) is not TRUE")
+    if num_thread is None or not isinstance(num_thread, (int, float, np.integer, np.floating)) or not num_thread > 0:
+        raise ValueError("is.numeric(num.thread), num.thread > 0 is not TRUE")
+    if not isinstance(mat_trim, (bool, np.bool_)):
+        raise TypeError("is.logical(mat.trim) is not TRUE")
+    if not isinstance(verbose, (bool, np.bool_)):
+        raise TypeError("is.logical(verbose) is not TRUE")
+    if method not in LD_METHODS:
+        raise ValueError("'arg' should be one of %s" % ", ".join('"%s"' % m for m in LD_METHODS))
+    code = LD_METHODS.index(method) + 1
+    ws = _init_file(gdsobj, sample_id, snp_id, device)
+    n_snp = ws["n_snp"]
+    if slide is None or (isinstance(slide, (float, np.floating)) and math.isnan(slide)):
+        slide = -1
+    slide = int(slide)
+    if slide > n_snp:
+        slide = n_snp
+    if verbose:
+        print("Linkage Disequilibrium (LD) estimation on genotypes:")
+        print("    # of samples: %d" % ws["n_samp"])
+        print("    # of SNPs: %d" % n_snp)
+        print("    using %d thread%s" % (int(num_thread), "" if int(num_thread) == 1 else "s"))
+        if slide > 0:
+            print("    sliding window size: %d" % slide)
+        print("    method: %s" % ("composite", "R", "D'", "correlation", "covariance")[code - 1])
+    rows, cols = _lib.ld_out_dims(n_snp, slide, mat_trim)
+    out = np.empty((cols, rows), np.float64)          # rows x cols column-major
+    _lib.check(_lib.lib().snpgpu_gnrLDMat(code, slide, int(bool(mat_trim)), int(num_thread), int(bool(verbose)), _lib._ptr(out)))
+    m = out.T
+    if with_id:
+        return dict(sample_id=ws["sample_id"], snp_id=ws["snp_id"], LD=m, slide=slide)
+    return m

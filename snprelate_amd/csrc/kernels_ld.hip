@@ -1,0 +1,327 @@
+// Linkage disequilibrium between SNP pairs (snpgdsLDMat, src/genLD.cpp:957-1010): the 3 x 3 genotype table of every pair
+// on the MX-fp4 MFMA, then one fp64 thread per pair for the LD value.
+//
+// Every LD method of the reference is a function of ONE table per SNP pair (i, j): n_ab = number of samples with genotype a at
+// SNP i and b at SNP j, over the samples called at both (the Num_* / Sum_* lookup tables of src/genLD.cpp:103-168 are linear in
+// those nine cells).  n_ab = P_a(i) . P_b(j) with P_a the one-hot plane "genotype == a" over the samples: nine binary
+// contractions, run as v_mfma_scale_f32_32x32x64_f8f6f4 with both operands e2m1 (cbsz = blgp = 4, unit scales).  A plane bit is
+// the nibble 0b0010 = 1.0, so products are 0 / 1 and the fp32 sums exact while N < 2^24.
+//
+// Operand form.  Rows are SNPs in the staging layout of csrc/ld.hip: 2-bit codes, 4 samples per byte LSB first, `rbp` bytes per
+// row (a multiple of 32), every code of a sample >= n_samp forced to 3 (missing) by ld_stage_kernel, whatever the caller's
+// padding held.  Lane l of a wave takes SNP row (l & 31) and, per 128-sample step, the 16 bytes at 32 s + 16 (l >> 5): two
+// k-steps of 32 samples.  A dword of 16 codes splits into two nibble dwords (even / odd samples) with shifts, and each plane is
+// ONE v_bitop3_b32 of (bit 0 of the code, bit 1 of the code, 0x22222222).  The sample order inside K differs from file order;
+// both operands use the same one, which is all a contraction needs.
+#include "snpgpu_internal.h"
+
+#include <cmath>
+#include <cfloat>
+
+namespace snpgpu {
+
+namespace {
+
+typedef float ld_f32x16 __attribute__((ext_vector_type(16)));
+typedef int ld_i32x4 __attribute__((ext_vector_type(4)));
+typedef int ld_i32x8 __attribute__((ext_vector_type(8)));
+
+constexpr uint32_t LD_NIB = 0x22222222u;   // bit 1 of every nibble: e2m1 1.0
+// v_bitop3_b32 truth tables over (a = code bit 0, b = code bit 1, c = LD_NIB); a = 0xF0, b = 0xCC, c = 0xAA
+constexpr int LD_P0 = 0x02;   // ~a & ~b & c : code 0
+constexpr int LD_P1 = 0x20;   //  a & ~b & c : code 1
+constexpr int LD_P2 = 0x08;   // ~a &  b & c : code 2   (code 3 = missing sets no plane)
+
+struct Planes { ld_i32x4 p[3]; };
+
+// 32 samples (two dwords of codes) -> the three one-hot operand registers of one k-step
+__device__ __forceinline__ Planes ld_planes(uint32_t w0, uint32_t w1)
+{
+    Planes r;
+    const uint32_t e0a = w0 << 1, e0b = w0, o0a = w0 >> 1, o0b = w0 >> 2;   // even samples: bits 4k, 4k+1 -> 4k+1; odd: 4k+2, 4k+3
+    const uint32_t e1a = w1 << 1, e1b = w1, o1a = w1 >> 1, o1b = w1 >> 2;
+#define LD_PLANE(P, T)                                                                  \
+    r.p[P][0] = (int)__builtin_amdgcn_bitop3_b32(e0a, e0b, LD_NIB, T);                 \
+    r.p[P][1] = (int)__builtin_amdgcn_bitop3_b32(o0a, o0b, LD_NIB, T);                 \
+    r.p[P][2] = (int)__builtin_amdgcn_bitop3_b32(e1a, e1b, LD_NIB, T);                 \
+    r.p[P][3] = (int)__builtin_amdgcn_bitop3_b32(o1a, o1b, LD_NIB, T);
+    LD_PLANE(0, LD_P0)
+    LD_PLANE(1, LD_P1)
+    LD_PLANE(2, LD_P2)
+#undef LD_PLANE
+    return r;
+}
+
+__device__ __forceinline__ void ld_mfma9(ld_f32x16 (&c)[9], const Planes &a, const Planes &b)
+{
+#pragma unroll
+    for (int x = 0; x < 3; x++)
+#pragma unroll
+        for (int y = 0; y < 3; y++) {
+            const ld_i32x8 av = __builtin_shufflevector(a.p[x], a.p[x], 0, 1, 2, 3, -1, -1, -1, -1);
+            const ld_i32x8 bv = __builtin_shufflevector(b.p[y], b.p[y], 0, 1, 2, 3, -1, -1, -1, -1);
+            c[3 * x + y] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, c[3 * x + y], 4, 4, 0, 0, 0, 0);
+        }
+}
+
+// One workgroup = a 64 x 64 tile of SNP pairs, four waves of 32 x 32.  BAND = false: rows A [0, n_a) x rows B [0, n_b), tile
+// (blockIdx.x, blockIdx.y), tab[(i n_b + j) 9 + 3 a + b].  BAND = true: A = B = the resident rows, i in [i_lo, i_lo + n_a),
+// partners j = i + k, k = 1 ... slide, j < n_b; row tile blockIdx.x, column tile = row tile + blockIdx.y (tiles wholly outside
+// the band return at once), tab[((i - i_lo) slide + k - 1) 9 + 3 a + b].  Both buffers hold whole 64-row tiles (rows past n_a /
+// n_b are read, never written).
+template <bool BAND>
+__global__ __launch_bounds__(256, 2) void ld_count_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ B, int64_t rbp,
+                                                          int n_a, int n_b, int slide, int32_t *__restrict__ tab)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 31, kh = lane >> 5;
+    const int wr = wave >> 1, wc = wave & 1;
+    const int ti0 = blockIdx.x * 64;                 // first A row of the tile (relative to A)
+    int tj0;                                         // first B row of the tile
+    if (BAND) {
+        tj0 = ti0 + blockIdx.y * 64;                 // B row index of A row ti0 is ti0 (A = B + i_lo rows, see launcher)
+        if ((int)blockIdx.y * 64 - 63 > slide || tj0 >= n_b) return;
+    } else {
+        tj0 = blockIdx.y * 64;
+    }
+    const uint8_t *pa = A + (int64_t)(ti0 + 32 * wr + li) * rbp + 16 * kh;
+    const uint8_t *pb = B + (int64_t)(tj0 + 32 * wc + li) * rbp + 16 * kh;
+    ld_f32x16 c[9];
+#pragma unroll
+    for (int q = 0; q < 9; q++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) c[q][r] = 0.f;
+    const int steps = (int)(rbp / 32);
+    uint4 va = *reinterpret_cast<const uint4 *>(pa), vb = *reinterpret_cast<const uint4 *>(pb);
+    for (int s = 0; s < steps; s++) {
+        const uint4 ca = va, cb = vb;
+        if (s + 1 < steps) {                          // next step's words while this one's MFMAs run
+            va = *reinterpret_cast<const uint4 *>(pa + 32 * (s + 1));
+            vb = *reinterpret_cast<const uint4 *>(pb + 32 * (s + 1));
+        }
+        ld_mfma9(c, ld_planes(ca.x, ca.y), ld_planes(cb.x, cb.y));
+        ld_mfma9(c, ld_planes(ca.z, ca.w), ld_planes(cb.z, cb.w));
+    }
+    // c[q][r]: A row 32 wr + 4 kh + (r & 3) + 8 (r >> 2) of the tile, B row 32 wc + li
+    const int j = tj0 + 32 * wc + li;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int i = ti0 + 32 * wr + 4 * kh + (r & 3) + 8 * (r >> 2);
+        int32_t *dst;
+        if (BAND) {
+            // A row i sits at B row i (+ i_lo, folded into both pointers by the launcher)
+            const int k = j - i;
+            if (i >= n_a || j >= n_b || k < 1 || k > slide) continue;
+            dst = tab + ((int64_t)i * slide + (k - 1)) * 9;
+        } else {
+            if (i >= n_a || j >= n_b) continue;
+            dst = tab + ((int64_t)i * n_b + j) * 9;
+        }
+#pragma unroll
+        for (int q = 0; q < 9; q++) dst[q] = (int32_t)c[q][r];
+    }
+}
+
+// Copy `n` caller rows (SNPGPU_GENO_PACKED2 rows of `rb` bytes, or SNPGPU_GENO_U8 rows of n_samp bytes) into staging rows of `rbp`
+// bytes: codes of samples >= n_samp and every byte past the row become 3, U8 values > 2 become 3.  One thread per output byte.
+__global__ void ld_stage_kernel(const uint8_t *__restrict__ src, int format, int64_t n, int64_t n_samp, int64_t rb, int64_t rbp,
+                                uint8_t *__restrict__ dst)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * rbp) return;
+    const int64_t row = t / rbp, b = t - row * rbp;
+    uint32_t v = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int64_t s = 4 * b + q;
+        uint32_t code = 3;
+        if (s < n_samp) {
+            if (format == SNPGPU_GENO_U8) {
+                const uint32_t g = src[row * n_samp + s];
+                code = g > 2 ? 3u : g;
+            } else {
+                code = (src[row * rb + b] >> (2 * q)) & 3u;
+            }
+        }
+        v |= code << (2 * q);
+    }
+    dst[t] = (uint8_t)v;
+}
+
+// ---- LD value of one table (fp64, the reference's formulas and NaN rules) -------------------------------------------------------
+// The reference's operations in its order, and no contraction into FMAs (the pragma in each body), so that the value matches a
+// plain fp64 evaluation of the same formulas.
+
+__device__ __forceinline__ double ld_plog(double v) { return log(v + DBL_EPSILON); }
+
+// haplotype proportions by EM, src/genLD.cpp:254-331
+__device__ void ld_haplo(long nAA, long nAB, long nBA, long nBB, long nDH2, double &pAA, double &pAB, double &pBA, double &pBB)
+{
+#pragma clang fp contract(off)
+    const double f = 0.01;
+    const double tol_rel = sqrt(DBL_EPSILON);
+    const double tot = (double)(nAA + nAB + nBA + nBB + nDH2);
+    if (tot > 0 && nDH2 > 0) {
+        const double div = nAA + nAB + nBA + nBB + 4.0 * f;
+        pAA = (nAA + f) / div; pAB = (nAB + f) / div; pBA = (nBA + f) / div; pBB = (nBB + f) / div;
+        const long nDH = nDH2 / 2;
+        double old = nAA * ld_plog(pAA) + nAB * ld_plog(pAB) + nBA * ld_plog(pBA) + nBB * ld_plog(pBB) +
+                     nDH * ld_plog(pAA * pBB + pAB * pBA);
+        double tol = fabs(tol_rel * old);
+        if (tol < DBL_EPSILON) tol = DBL_EPSILON;
+        for (int it = 1; it <= 1000; it++) {
+            const double x = pAA * pBB, y = pAB * pBA;
+            const double dAA = x / (x + y) * nDH;
+            const double dAB = nDH - dAA;
+            pAA = (nAA + dAA) / tot; pAB = (nAB + dAB) / tot; pBA = (nBA + dAB) / tot; pBB = (nBB + dAA) / tot;
+            const double ll = nAA * ld_plog(pAA) + nAB * ld_plog(pAB) + nBA * ld_plog(pBA) + nBB * ld_plog(pBB) +
+                              nDH * ld_plog(pAA * pBB + pAB * pBA);
+            if (fabs(ll - old) <= tol) break;
+            old = ll;
+        }
+    } else {
+        pAA = nAA / tot; pAB = nAB / tot; pBA = nBA / tot; pBB = nBB / tot;
+    }
+}
+
+// n[3 a + b]: a = genotype of the first SNP, b = of the second
+__device__ double ld_value(int method, const long (&n)[9])
+{
+#pragma clang fp contract(off)
+    const long r0 = n[0] + n[1] + n[2], r1 = n[3] + n[4] + n[5], r2 = n[6] + n[7] + n[8];   // first SNP's genotype counts
+    const long c0 = n[0] + n[3] + n[6], c1 = n[1] + n[4] + n[7], c2 = n[2] + n[5] + n[8];   // second SNP's
+    const long tot = r0 + r1 + r2;
+    const double NaN = __builtin_nan("");
+    switch (method) {
+    case SNPGPU_LD_COMPOSITE: {                        // src/genLD.cpp:177-213
+        if (tot <= 0) return NaN;
+        const double delta = double(n[8] + n[0] - n[2] - n[6]) / (2 * tot) - double(r0 - r2) * double(c0 - c2) / (2.0 * tot * tot);
+        const double pa = double(2 * r0 + r1) / (2 * tot);
+        const double pA = 1 - pa, pAA = double(r2) / tot;
+        const double pb = double(2 * c0 + c1) / (2 * tot);
+        const double pB = 1 - pb, pBB = double(c2) / tot;
+        const double DA = pAA - pA * pA, DB = pBB - pB * pB;
+        const double t = (pA * pa + DA) * (pB * pb + DB);
+        return t > 0 ? delta / sqrt(t) : NaN;
+    }
+    case SNPGPU_LD_R:
+    case SNPGPU_LD_DPRIME: {                           // src/genLD.cpp:334-446
+        const long hAA = 2 * n[8] + n[7] + n[5], hAB = n[3] + 2 * n[6] + n[7];
+        const long hBA = n[1] + 2 * n[2] + n[5], hBB = 2 * n[0] + n[1] + n[3];
+        double pAA, pAB, pBA, pBB;
+        ld_haplo(hAA, hAB, hBA, hBB, 2 * n[4], pAA, pAB, pBA, pBB);
+        const double pA = pAA + pAB, p_A = pAA + pBA, pB = pBA + pBB, p_B = pAB + pBB;
+        const double D = pAA - pA * p_A;
+        if (method == SNPGPU_LD_R) return D / sqrt(pA * p_A * pB * p_B);
+        double den;
+        if (D >= 0) { const double u = pA * p_B, v = pB * p_A; den = (v < u) ? v : u; }          // std::min
+        else { const double u = -pA * p_A, v = -pB * p_B; den = (u < v) ? v : u; }                // std::max
+        return D / den;
+    }
+    case SNPGPU_LD_CORR: {                             // src/genLD.cpp:449-506
+        if (tot <= 0) return NaN;
+        const long X = r1 + 2 * r2, XX = r1 + 4 * r2, Y = c1 + 2 * c2, YY = c1 + 4 * c2;
+        const long XY = n[4] + 2 * n[5] + 2 * n[7] + 4 * n[8];
+        const double d1 = XX - double(X) * X / tot, d2 = YY - double(Y) * Y / tot;
+        const double v = d1 * d2;
+        return v > 0 ? (XY - double(X) * Y / tot) / sqrt(v) : NaN;
+    }
+    case SNPGPU_LD_COV: {                              // src/genLD.cpp:509-525
+        if (tot <= 1) return NaN;
+        const long X = r1 + 2 * r2, Y = c1 + 2 * c2, XY = n[4] + 2 * n[5] + 2 * n[7] + 4 * n[8];
+        return (XY - double(X) * Y / tot) / (tot - 1);
+    }
+    default: return NaN;
+    }
+}
+
+// Band finaliser: tables [n_i][slide][9] of rows i = i0 ... (global SNP index i0 + t) -> out[t slide + k - 1]; partners past the last
+// SNP (global index >= n_snp) give NaN.
+__global__ void ld_final_band_kernel(const int32_t *__restrict__ tab, int64_t n_i, int slide, int64_t i0, int64_t n_snp, int method,
+                                     double *__restrict__ out)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_i * slide) return;
+    const int64_t i = i0 + t / slide, j = i + (t % slide) + 1;
+    if (j >= n_snp) { out[t] = __builtin_nan(""); return; }
+    long n[9];
+#pragma unroll
+    for (int q = 0; q < 9; q++) n[q] = tab[t * 9 + q];
+    out[t] = ld_value(method, n);
+}
+
+// Rectangle finaliser of a full-matrix row panel: tables [n_i][n_j][9] of rows i0 + t x columns 0 ... n_j - 1 -> out[t n_j + j].
+// A pair below the diagonal is evaluated on the transposed table, i.e. exactly as the pair (j, i): the matrix is symmetric bit
+// for bit, as the reference's (it computes each unordered pair once).
+__global__ void ld_final_rect_kernel(const int32_t *__restrict__ tab, int64_t n_i, int64_t n_j, int64_t i0, int method,
+                                     double *__restrict__ out)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_i * n_j) return;
+    const int64_t i = i0 + t / n_j, j = t % n_j;
+    long n[9];
+    if (i <= j) {
+#pragma unroll
+        for (int q = 0; q < 9; q++) n[q] = tab[t * 9 + q];
+    } else {
+#pragma unroll
+        for (int q = 0; q < 9; q++) n[3 * (q % 3) + q / 3] = tab[t * 9 + q];
+    }
+    out[t] = ld_value(method, n);
+}
+
+constexpr int FIN_THREADS = 256;
+
+}  // namespace
+
+int launch_ld_stage(hipStream_t st, const void *src, int format, int64_t n, int64_t n_samp, int64_t rbp, uint8_t *dst)
+{
+    const int64_t total = n * rbp;
+    if (total <= 0) return 0;
+    hipLaunchKernelGGL(ld_stage_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint8_t *)src, format, n,
+                       n_samp, (n_samp + 3) / 4, rbp, dst);
+    SNPGPU_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_ld_count_rect(hipStream_t st, const uint8_t *A, int n_a, const uint8_t *B, int n_b, int64_t rbp, int32_t *tab)
+{
+    if (n_a <= 0 || n_b <= 0) return 0;
+    hipLaunchKernelGGL(ld_count_kernel<false>, dim3((unsigned)((n_a + 63) / 64), (unsigned)((n_b + 63) / 64)), dim3(256), 0, st, A,
+                       B, rbp, n_a, n_b, 0, tab);
+    SNPGPU_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_ld_count_band(hipStream_t st, const uint8_t *rows, int i_lo, int n_i, int n_rows, int slide, int64_t rbp, int32_t *tab)
+{
+    if (n_i <= 0) return 0;
+    // A = B = rows shifted by i_lo: row indices inside the kernel are relative to i_lo on both sides
+    const uint8_t *base = rows + (int64_t)i_lo * rbp;
+    hipLaunchKernelGGL(ld_count_kernel<true>, dim3((unsigned)((n_i + 63) / 64), (unsigned)((63 + slide) / 64 + 1)), dim3(256), 0, st,
+                       base, base, rbp, n_i, n_rows - i_lo, slide, tab);
+    SNPGPU_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_ld_final_band(hipStream_t st, const int32_t *tab, int64_t n_i, int slide, int64_t i0, int64_t n_snp, int method, double *out)
+{
+    const int64_t total = n_i * slide;
+    if (total <= 0) return 0;
+    hipLaunchKernelGGL(ld_final_band_kernel, dim3((unsigned)((total + FIN_THREADS - 1) / FIN_THREADS)), dim3(FIN_THREADS), 0, st, tab,
+                       n_i, slide, i0, n_snp, method, out);
+    SNPGPU_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_ld_final_rect(hipStream_t st, const int32_t *tab, int64_t n_i, int64_t n_j, int64_t i0, int method, double *out)
+{
+    const int64_t total = n_i * n_j;
+    if (total <= 0) return 0;
+    hipLaunchKernelGGL(ld_final_rect_kernel, dim3((unsigned)((total + FIN_THREADS - 1) / FIN_THREADS)), dim3(FIN_THREADS), 0, st, tab,
+                       n_i, n_j, i0, method, out);
+    SNPGPU_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+}  // namespace snpgpu

@@ -124,6 +124,12 @@ int launch_sym_panel_matmul(hipStream_t st, const double *P, int64_t ld, int64_t
                             int64_t N, double scale, const double *Q, int m, double *Y, double *qt_scratch, bool fp32_products = false,
                             const float *P32 = nullptr);
 int launch_panel_to_f32(hipStream_t st, const double *src, float *dst, size_t n_elems);
+// linkage disequilibrium (kernels_ld.hip): staging rows of rbp bytes (a multiple of 32), 64-row tiles read whole
+int launch_ld_stage(hipStream_t st, const void *src, int format, int64_t n, int64_t n_samp, int64_t rbp, uint8_t *dst);
+int launch_ld_count_rect(hipStream_t st, const uint8_t *A, int n_a, const uint8_t *B, int n_b, int64_t rbp, int32_t *tab);
+int launch_ld_count_band(hipStream_t st, const uint8_t *rows, int i_lo, int n_i, int n_rows, int slide, int64_t rbp, int32_t *tab);
+int launch_ld_final_band(hipStream_t st, const int32_t *tab, int64_t n_i, int slide, int64_t i0, int64_t n_snp, int method, double *out);
+int launch_ld_final_rect(hipStream_t st, const int32_t *tab, int64_t n_i, int64_t n_j, int64_t i0, int method, double *out);
 // PCA projections (kernels_proj.hip)
 int launch_proj_snp(hipStream_t st, int corr, const uint32_t *w2, int64_t ncols_pad, int64_t N, int64_t n_snp,
                     const double *et, int kp, int k, const int32_t *sum, const int32_t *num, int bayesian, double *out,

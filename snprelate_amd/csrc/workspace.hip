@@ -1084,4 +1084,27 @@ int snpgpu_gnrEigMixSampLoading(int eigen_cnt, const double *snp_loadings, const
     return snpgpu_proj_samp_loading(g.p, out, SNPGPU_HOST);
 }
 
+// gnrLDMat(method, NumSlide, MatTrim, NumThread, Verbose), src/genLD.cpp:957-1010: the selected SNPs in WS_BLOCK blocks
+int snpgpu_gnrLDMat(int method, int64_t slide, int mat_trim, int num_thread, int, double *out)
+{
+    if (need_ws("snpgpu_gnrLDMat")) return 1;
+    if (num_thread <= 0) { set_error("Invalid 'num.thread'."); return 1; }
+    if (!out) { set_error("snpgpu_gnrLDMat: out is NULL"); return 1; }
+    snpgpu_opts o{};
+    o.device = g_ws.device;
+    snpgpu_ld *ld = nullptr;
+    const int64_t L = (int64_t)g_ws.sel.size();
+    if (snpgpu_ld_create(g_ws.n_samp, L, method, slide, mat_trim, &o, &ld)) return 1;
+    std::vector<uint8_t> buf;
+    int rc = 0;
+    for (int64_t i0 = 0; i0 < L && !rc; i0 += WS_BLOCK) {
+        const int64_t i1 = std::min(L, i0 + WS_BLOCK);
+        gather_block(i0, i1, buf);
+        rc = snpgpu_ld_feed(ld, buf.data(), i1 - i0, SNPGPU_GENO_PACKED2, SNPGPU_HOST);
+    }
+    if (!rc) rc = snpgpu_ld_result(ld, out, SNPGPU_HOST);
+    snpgpu_ld_destroy(ld);
+    return rc;
+}
+
 }  // extern "C"
