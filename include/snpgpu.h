@@ -468,6 +468,37 @@ int snpgpu_ld_pair_tables(const void *geno_a, int64_t n_a, const void *geno_b, i
  * out: host, snpgpu_ld_out_dims' rows x cols */
 int snpgpu_gnrLDMat(int method, int64_t slide, int mat_trim, int num_thread, int verbose, double *out);
 
+/* ---- (1e) IBD by maximum likelihood: snpgdsIBDMLE (method "EM") and snpgdsIBDMLELogLik -----------------------------------------
+ * gnrIBD_MLE (src/genIBD.cpp:1465-1548) on resident rows: allele frequencies as InitAFreq (:1122-1165; allele_freq: host
+ * [n_snp] or NULL = sum / 2n over the calls, non-finite -> -1), start values from the IBS counters and Est_PLINK_Kinship with
+ * the plain-monomial E[IBS | IBD] of Init_EPrIBD_IBS(afreq, NULL, false) and no constraint (:823), clamped to >= 0.005
+ * (:824-832), then EMAlg (:582-656) per pair with max_niter / reltol, and LOGLIK_ADJUST's six candidates when coeff_correct.
+ * geno: SNPGPU_GENO_PACKED2 rows [n_snp][ceil(n_samp/4)] in `mem` (host or the device's memory).  Outputs in out_mem: full
+ * n_samp x n_samp k0, k1 and (may be NULL) int32 niter, 0 on the diagonal; afreq_out: host [n_snp] (may be NULL), -1 where
+ * InitAFreq gives -1.  row_begin / row_end: the pairs (i, j > i) with row_begin <= i < row_end and their mirrors only (0, 0 = the
+ * whole matrix); other entries are left as they were.  n_samp < 2 or n_snp < 1 is an error. */
+int snpgpu_ibd_mle(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, const double *allele_freq,
+                   int max_niter, double reltol, int coeff_correct, int64_t row_begin, int64_t row_end, double *k0, double *k1,
+                   int32_t *niter, double *afreq_out, int out_mem, int device);
+/* Do_MLE_LogLik / Do_MLE_LogLik_k01 (src/genIBD.cpp:1289-1330): EM_LogLik of every pair i <= j (diagonal included) at (k0, k1)
+ * taken from the n x n matrices k0 / k1 (in out_mem), or at the global (k0_all, k1_all) when both are NULL; out: n x n, out_mem */
+int snpgpu_ibd_loglik(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, const double *allele_freq,
+                      const double *k0, const double *k1, double k0_all, double k1_all, double *out, double *afreq_out,
+                      int out_mem, int device);
+/* of the last snpgpu_ibd_mle on this thread: stats[0] EM kernel ms, [1] ms of all its kernels (EM, candidates, output),
+ * [2] lane-sweeps that advanced a pair, [3] lane-sweeps issued (HIP events; counts from the kernel) */
+int snpgpu_ibd_mle_stats(double *stats);
+/* gnrIBD_MLE(AlleleFreq, KinshipConstraint, MaxIterCnt, RelTol, CoeffCorrect, method, IfOutNum, NumThread, Verbose) on the
+ * working space's selected SNPs.  method 0 (EM) only: 1 (downhill simplex) and 2 (Jacquard) return an error.  kinship_constraint
+ * is accepted and has no effect, as in the reference.  k0, k1: host n x n; afreq: host [n_snp] (may be NULL); niter: host n x n
+ * int32, written when out_num_iter != 0 */
+int snpgpu_gnrIBD_MLE(const double *allele_freq, int kinship_constraint, int max_niter, double reltol, int coeff_correct,
+                      int method, int out_num_iter, int num_thread, int verbose, double *k0, double *k1, double *afreq,
+                      int32_t *niter);
+/* gnrIBD_LogLik(AFreq, k0, k1) / gnrIBD_LogLik_k01(AFreq, k0, k1): out host n x n; afreq may be NULL (estimated) */
+int snpgpu_gnrIBD_LogLik(const double *afreq, const double *k0, const double *k1, double *out);
+int snpgpu_gnrIBD_LogLik_k01(const double *afreq, double k0, double k1, double *out);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------------------
  * What THIS device's matrix pipe sustains right now: a register-only stream of one MFMA instruction (never waiting on memory,
  * two waves per SIMD) run for `seconds`, rate taken over the second half.  The kernels of this library run against the socket
@@ -485,6 +516,9 @@ enum snpgpu_diag_mode {
     SNPGPU_DIAG_F16_EXACT_ROW_16X16X32 = 6 /* the operands of mode 1 through v_mfma_f32_16x16x32_f16                            */
 };
 int snpgpu_diag_mfma_rate(int device, int mode, double seconds, double *tflops, double *implied_mhz);
+/* What the fp64 vector pipe sustains right now: a register-only stream of independent v_fma_f64 chains (never waiting on memory)
+ * run for `seconds`, rate over the second half.  tflops: TFLOP/s counting an FMA as two flops */
+int snpgpu_diag_fp64_rate(int device, double seconds, double *tflops);
 /* PCI address "dddd:bb:dd.f" of HIP device `device` (hipDeviceGetPCIBusId): which physical GPU a rank really drives */
 int snpgpu_diag_device_pci(int device, char *buf, int len);
 

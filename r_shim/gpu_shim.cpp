@@ -24,6 +24,11 @@
 //   gpu_gnrGRM_avg_val()                                        src/genPCA.cpp:1605-1611
 //   gpu_gnrPCA(EigenCnt, Algorithm, NumThread, ParamList, V.)   src/genPCA.cpp:1355-1452 (+ CalcEigen :1262-1346)
 //   gpu_gnrLDMat(method, NumSlide, MatTrim, NumThread, Verbose) src/genLD.cpp:957-1010
+//   gpu_gnrIBD_MLE(AlleleFreq, KinshipConstraint, MaxIterCnt,    src/genIBD.cpp:1465-1548 (method 0 = EM; the Jacquard
+//                  RelTol, CoeffCorrect, method, IfOutNum,       form, .Call(gnrIBD_MLE_Jacquard, ...), stays on the kept
+//                  NumThread, Verbose)                           CPU routine)
+//   gpu_gnrIBD_LogLik(AFreq, k0, k1)                            src/genIBD.cpp:1289-1310 and its .Call wrapper
+//   gpu_gnrIBD_LogLik_k01(AFreq, k0, k1)                        src/genIBD.cpp:1312-1330 and its .Call wrapper
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -570,6 +575,118 @@ COREARRAY_DLL_EXPORT SEXP gpu_gnrLDMat(SEXP method, SEXP NumSlide, SEXP MatTrim,
         if (snpgpu_ld_result(obj.ld, REAL(rv_ans), SNPGPU_HOST)) gpu_fail();
         UNPROTECT(1);
     COREARRAY_CATCH
+}
+
+}  // extern "C"
+
+// --------------------------------------------------------------------------------------------------------------
+// IBD by maximum likelihood: the kept reader packs the working space into 2-bit rows in host memory, which one
+// snpgpu_ibd_mle / snpgpu_ibd_loglik call takes to the device (the EM needs every SNP of a pair in every iteration).
+namespace {
+
+struct PackedSpace {
+    std::vector<C_UInt8> rows;
+    size_t n_samp = 0, n_snp = 0;
+    void read(const char *msg, bool verbose)
+    {
+        CachingSNPData(msg, verbose);
+        CdBaseWorkSpace &space = MCWorkingGeno.Space();
+        n_samp = space.SampleNum();
+        n_snp = space.SNPNum();
+        if (n_samp < 2) throw ErrCoreArray("%s", "at least two samples are needed");
+        if (n_snp < 1) throw ErrCoreArray("%s", "no SNP in the working dataset");
+        const size_t rb = (n_samp + 3) / 4, block = syrk_block();
+        rows.assign(n_snp * rb, 0xFF);
+        std::vector<C_UInt8> buf(n_samp * block);
+        CGenoReadBySNP reader(1, space, block, verbose ? -1 : 0, false);
+        reader.Init();
+        size_t l0 = 0;
+        while (reader.Read(&buf[0])) {
+            const size_t cnt = reader.Count();
+            for (size_t l = 0; l < cnt; l++) {
+                C_UInt8 *r = &rows[(l0 + l) * rb];
+                for (size_t s = 0; s < n_samp; s++) {
+                    const unsigned g = buf[l * n_samp + s] > 2 ? 3u : buf[l * n_samp + s];
+                    r[s >> 2] = (C_UInt8)((r[s >> 2] & ~(3u << (2 * (s & 3)))) | (g << (2 * (s & 3))));
+                }
+            }
+            l0 += cnt;
+            reader.ProgressForward(cnt);
+        }
+    }
+};
+
+double as_real(SEXP x) { return REAL(Rf_coerceVector(x, REALSXP))[0]; }
+
+}  // namespace
+
+extern "C" {
+
+COREARRAY_DLL_EXPORT SEXP gpu_gnrIBD_MLE(SEXP AlleleFreq, SEXP KinshipConstraint, SEXP MaxIterCnt, SEXP RelTol,
+                                         SEXP CoeffCorrect, SEXP method, SEXP IfOutNum, SEXP NumThread, SEXP Verbose)
+{
+    const bool verbose = SEXP_Verbose(Verbose);
+    const int mle_method = Rf_asInteger(method);
+    const bool out_num = Rf_asLogical(IfOutNum) == TRUE;
+    (void)KinshipConstraint;          // accepted, no effect: Est_PLINK_Kinship is called without the constraint (:823)
+    if (Rf_asInteger(NumThread) <= 0) Rf_error("Invalid 'num.thread'.");
+    COREARRAY_TRY
+        PackedSpace ps;
+        ps.read("MLE IBD", verbose);
+        const int n = (int)ps.n_samp;
+        if (mle_method != 0) {
+            snpgpu_gnrIBD_MLE(nullptr, 0, 0, 0, 0, mle_method, 0, 1, 0, nullptr, nullptr, nullptr, nullptr);   // sets the message
+            gpu_fail();
+        }
+        const int max_niter = Rf_asInteger(MaxIterCnt);
+        const double reltol = as_real(RelTol);
+        const int coeff_correct = Rf_asLogical(CoeffCorrect) == TRUE ? 1 : 0;
+        // every allocation goes into the protected list at once: the next one may collect anything unprotected
+        PROTECT(rv_ans = Rf_allocVector(VECSXP, 4));
+        SET_VECTOR_ELT(rv_ans, 0, Rf_allocMatrix(REALSXP, n, n));
+        SET_VECTOR_ELT(rv_ans, 1, Rf_allocMatrix(REALSXP, n, n));
+        SET_VECTOR_ELT(rv_ans, 2, Rf_allocVector(REALSXP, (R_xlen_t)ps.n_snp));
+        if (out_num) SET_VECTOR_ELT(rv_ans, 3, Rf_allocMatrix(INTSXP, n, n));
+        SEXP k0 = VECTOR_ELT(rv_ans, 0), k1 = VECTOR_ELT(rv_ans, 1), afreq = VECTOR_ELT(rv_ans, 2);
+        if (snpgpu_ibd_mle(&ps.rows[0], (int64_t)ps.n_snp, (int64_t)ps.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST,
+                           Rf_isNull(AlleleFreq) ? nullptr : REAL(AlleleFreq), max_niter, reltol, coeff_correct, 0, 0,
+                           REAL(k0), REAL(k1), out_num ? INTEGER(VECTOR_ELT(rv_ans, 3)) : nullptr, REAL(afreq), SNPGPU_HOST,
+                           opt_int("snpgpu.device", "SNPGPU_DEVICE", 0)))
+            gpu_fail();
+        UNPROTECT(1);
+    COREARRAY_CATCH
+}
+
+// k0 / k1: n x n matrices, or R_NilValue with the global pair (k0_all, k1_all)
+static SEXP ibd_loglik(SEXP AFreq, SEXP k0, SEXP k1, double k0_all, double k1_all)
+{
+    COREARRAY_TRY
+        PackedSpace ps;
+        ps.read("MLE IBD log likelihood", false);
+        const int n = (int)ps.n_samp;
+        // the working space must be the one the coefficients were estimated on (snpgpu_ibd_loglik reads n_snp / n x n)
+        if (!Rf_isNull(AFreq) && Rf_xlength(AFreq) != (R_xlen_t)ps.n_snp)
+            throw ErrCoreArray("%s", "'afreq' should have one entry per SNP of the working space");
+        if (!Rf_isNull(k0) && (Rf_xlength(k0) != (R_xlen_t)n * n || Rf_xlength(k1) != (R_xlen_t)n * n))
+            throw ErrCoreArray("%s", "'k0' and 'k1' should be n x n matrices of the working space's samples");
+        PROTECT(rv_ans = Rf_allocMatrix(REALSXP, n, n));
+        if (snpgpu_ibd_loglik(&ps.rows[0], (int64_t)ps.n_snp, (int64_t)ps.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST,
+                              Rf_isNull(AFreq) ? nullptr : REAL(AFreq), Rf_isNull(k0) ? nullptr : REAL(k0),
+                              Rf_isNull(k0) ? nullptr : REAL(k1), k0_all, k1_all, REAL(rv_ans), nullptr, SNPGPU_HOST,
+                              opt_int("snpgpu.device", "SNPGPU_DEVICE", 0)))
+            gpu_fail();
+        UNPROTECT(1);
+    COREARRAY_CATCH
+}
+
+COREARRAY_DLL_EXPORT SEXP gpu_gnrIBD_LogLik(SEXP AFreq, SEXP k0, SEXP k1)
+{
+    return ibd_loglik(AFreq, k0, k1, 0, 0);
+}
+
+COREARRAY_DLL_EXPORT SEXP gpu_gnrIBD_LogLik_k01(SEXP AFreq, SEXP k0, SEXP k1)
+{
+    return ibd_loglik(AFreq, R_NilValue, R_NilValue, as_real(k0), as_real(k1));
 }
 
 }  // extern "C"

@@ -11,6 +11,9 @@ extern SEXP gpu_gnrIBSAve(SEXP, SEXP, SEXP);
 extern SEXP gpu_gnrIBSNum(SEXP, SEXP);
 extern SEXP gpu_gnrPCA(SEXP, SEXP, SEXP, SEXP, SEXP);
 extern SEXP gpu_gnrLDMat(SEXP, SEXP, SEXP, SEXP, SEXP);
+extern SEXP gpu_gnrIBD_MLE(SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP);
+extern SEXP gpu_gnrIBD_LogLik(SEXP, SEXP, SEXP);
+extern SEXP gpu_gnrIBD_LogLik_k01(SEXP, SEXP, SEXP);
 //
 //   table entries:
 //     { "gnrGRM",             (DL_FUNC)&gpu_gnrGRM,             5 },
@@ -21,6 +24,9 @@ extern SEXP gpu_gnrLDMat(SEXP, SEXP, SEXP, SEXP, SEXP);
 //     { "gnrIBSNum",          (DL_FUNC)&gpu_gnrIBSNum,          2 },
 //     { "gnrPCA",             (DL_FUNC)&gpu_gnrPCA,             5 },
 //     { "gnrLDMat",           (DL_FUNC)&gpu_gnrLDMat,           5 },
+//     { "gnrIBD_MLE",         (DL_FUNC)&gpu_gnrIBD_MLE,         9 },
+//     { "gnrIBD_LogLik",      (DL_FUNC)&gpu_gnrIBD_LogLik,      3 },
+//     { "gnrIBD_LogLik_k01",  (DL_FUNC)&gpu_gnrIBD_LogLik_k01,  3 },
 //
 // The CPU bodies (gnrGRM ... in src/genPCA.cpp, src/genIBS.cpp, src/genKING.cpp) may stay in the package as
 // unregistered functions -- e.g. behind options(snpgpu.enable = FALSE) with a second table -- or be deleted together

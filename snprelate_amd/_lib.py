@@ -45,6 +45,8 @@ EXPORTS = [
     "snpgpu_multi_topk_eigen", "snpgpu_diag_mfma_rate", "snpgpu_diag_device_pci", "snpgpu_multi_get_status",
     "snpgpu_ld_create", "snpgpu_ld_destroy", "snpgpu_ld_out_dims", "snpgpu_ld_feed", "snpgpu_ld_result", "snpgpu_ld_set_timing",
     "snpgpu_ld_get_timing", "snpgpu_ld_pair_tables", "snpgpu_gnrLDMat",
+    "snpgpu_ibd_mle", "snpgpu_ibd_loglik", "snpgpu_ibd_mle_stats", "snpgpu_gnrIBD_MLE", "snpgpu_gnrIBD_LogLik",
+    "snpgpu_gnrIBD_LogLik_k01", "snpgpu_diag_fp64_rate",
 ]
 
 
@@ -217,6 +219,13 @@ def lib():
     L.snpgpu_ld_get_timing.argtypes = [vp, c_int, ctypes.POINTER(dbl), ctypes.POINTER(i64)]
     L.snpgpu_ld_pair_tables.argtypes = [vp, i64, vp, i64, i64, c_int, vp, c_int]
     L.snpgpu_gnrLDMat.argtypes = [c_int, i64, c_int, c_int, c_int, vp]
+    L.snpgpu_ibd_mle.argtypes = [vp, i64, i64, c_int, c_int, vp, c_int, dbl, c_int, i64, i64, vp, vp, vp, vp, c_int, c_int]
+    L.snpgpu_ibd_loglik.argtypes = [vp, i64, i64, c_int, c_int, vp, vp, vp, dbl, dbl, vp, vp, c_int, c_int]
+    L.snpgpu_ibd_mle_stats.argtypes = [vp]
+    L.snpgpu_gnrIBD_MLE.argtypes = [vp, c_int, c_int, dbl, c_int, c_int, c_int, c_int, c_int, vp, vp, vp, vp]
+    L.snpgpu_gnrIBD_LogLik.argtypes = [vp, vp, vp, vp]
+    L.snpgpu_gnrIBD_LogLik_k01.argtypes = [vp, dbl, dbl, vp]
+    L.snpgpu_diag_fp64_rate.argtypes = [c_int, dbl, ctypes.POINTER(dbl)]
     _lib = L
     return L
 
@@ -795,3 +804,52 @@ class Projector:
         out = np.empty((self.k, self.n), dtype=np.float64)
         check(lib().snpgpu_proj_samp_loading(self._h, _ptr(out), HOST))
         return out
+
+
+def diag_fp64_rate(seconds=2.0, device=0):
+    """TFLOP/s a register-only v_fma_f64 stream sustains on `device` right now (snpgpu_diag_fp64_rate)."""
+    r = ctypes.c_double(0)
+    check(lib().snpgpu_diag_fp64_rate(int(device), float(seconds), ctypes.byref(r)))
+    return r.value
+
+
+def ibd_mle(geno, n_samp, allele_freq=None, max_niter=1000, reltol=float(np.sqrt(np.finfo(float).eps)), coeff_correct=True,
+            rows=(0, 0), device=0, geno_dev_ptr=None, n_snp=None, out=None):
+    """snpgpu_ibd_mle on 2-bit rows [n_snp][ceil(n_samp/4)] (numpy, or device memory via geno_dev_ptr + n_snp):
+    returns (k0, k1, niter, afreq) with k0 / k1 / niter full n x n and afreq as InitAFreq leaves it (-1 = none).
+    rows = (r0, r1): only the pairs of those upper-triangle rows (and their mirrors) are written, into `out` = (k0, k1, niter)
+    when given."""
+    if geno_dev_ptr is None:
+        geno = np.ascontiguousarray(geno, np.uint8)
+        n_snp, ptr, mem = geno.shape[0], _ptr(geno), HOST
+    else:
+        ptr, mem = ctypes.c_void_p(int(geno_dev_ptr)), DEVICE
+    af_in = None if allele_freq is None else np.ascontiguousarray(allele_freq, np.float64)
+    if out is None:
+        out = (np.empty((n_samp, n_samp), np.float64), np.empty((n_samp, n_samp), np.float64),
+               np.empty((n_samp, n_samp), np.int32))
+    k0, k1, nit = out
+    af = np.empty(n_snp, np.float64)
+    check(lib().snpgpu_ibd_mle(ptr, int(n_snp), int(n_samp), GENO_PACKED2, mem, _ptr(af_in), int(max_niter), float(reltol),
+                               int(bool(coeff_correct)), int(rows[0]), int(rows[1]), _ptr(k0), _ptr(k1), _ptr(nit), _ptr(af),
+                               HOST, int(device)))
+    return k0, k1, nit, af
+
+
+def ibd_mle_stats():
+    """(EM kernel ms, all kernels ms, useful lane-sweeps, issued lane-sweeps) of the last ibd_mle on this thread"""
+    s = np.zeros(4, np.float64)
+    check(lib().snpgpu_ibd_mle_stats(_ptr(s)))
+    return float(s[0]), float(s[1]), int(s[2]), int(s[3])
+
+
+def ibd_loglik(geno, n_samp, allele_freq=None, k0=None, k1=None, k0_all=float("nan"), k1_all=float("nan"), device=0):
+    """snpgpu_ibd_loglik: EM_LogLik of every pair at the n x n (k0, k1), or at the global pair when k0 / k1 are None"""
+    geno = np.ascontiguousarray(geno, np.uint8)
+    af_in = None if allele_freq is None else np.ascontiguousarray(allele_freq, np.float64)
+    m0 = None if k0 is None else np.ascontiguousarray(k0, np.float64)
+    m1 = None if k1 is None else np.ascontiguousarray(k1, np.float64)
+    out = np.empty((n_samp, n_samp), np.float64)
+    check(lib().snpgpu_ibd_loglik(_ptr(geno), geno.shape[0], int(n_samp), GENO_PACKED2, HOST, _ptr(af_in), _ptr(m0), _ptr(m1),
+                                  float(k0_all), float(k1_all), _ptr(out), None, HOST, int(device)))
+    return out

@@ -16,6 +16,8 @@ INTEGRATION.md):
     snpgdsPCA                     R/PCA.R:22-91    (algorithm="exact")
     snpgdsSNPRateFreq             R/AllUtilities.R (allele freq / MAF / missing rate)
     snpgdsLDMat                   R/LD.R:53-92     (LD between SNP pairs)
+    snpgdsIBDMLE                  R/IBD.R:79-156   (IBD by maximum likelihood, method "EM")
+    snpgdsIBDMLELogLik            R/IBD.R:162-205
 
 All arithmetic runs on the MI355X through libsnpgpu.so (`_lib`); there is no
 CPU fallback.  R's ``NULL`` is ``None``, ``NaN`` is ``float('nan')``; R lists
@@ -617,3 +619,84 @@ def snpgdsLDMat(gdsobj, sample_id=None, snp_id=None, slide=250, method="composit
     if with_id:
         return dict(sample_id=ws["sample_id"], snp_id=ws["snp_id"], LD=m, slide=slide)
     return m
+
+
+IBDMLE_METHODS = ("EM", "downhill.simplex", "Jacquard")
+RELATEDNESS = {"": None, "self": (0.0, 0.0), "fullsib": (0.25, 0.5), "offspring": (0.0, 1.0), "halfsib": (0.5, 0.5),
+               "cousin": (0.75, 0.25), "unrelated": (1.0, 0.0)}
+
+
+def snpgdsIBDMLE(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True, maf=float("nan"),
+                 missing_rate=0.01, kinship=False, kinship_constraint=False, allele_freq=None, method="EM", max_niter=1000,
+                 reltol=math.sqrt(np.finfo(float).eps), coeff_correct=True, out_num_iter=True, num_thread=1, verbose=True,
+                 device=0):
+    """IBD coefficients by maximum likelihood (R/IBD.R:79-156 -> gnrIBD_MLE, src/genIBD.cpp:1465-1548), method "EM" only.
+    Returns dict(sample_id, snp_id, afreq, k0, k1, niter[, kinship]): k0 / k1 / niter are n x n with 0 on the diagonal,
+    niter is None when out_num_iter is False; afreq < 0 becomes NaN.  kinship_constraint is accepted and has no effect, as in
+    the reference (Est_PLINK_Kinship is called without the constraint)."""
+    if method not in IBDMLE_METHODS:
+        raise ValueError("'arg' should be one of %s" % ", ".join('"%s"' % m for m in IBDMLE_METHODS))
+    if method != "EM":
+        raise NotImplementedError('snpgdsIBDMLE: method "%s" is not built on the GPU path (only "EM")' % method)
+    for name, v in (("kinship", kinship), ("kinship.constraint", kinship_constraint), ("coeff.correct", coeff_correct),
+                    ("out.num.iter", out_num_iter)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise TypeError("is.logical(%s) is not TRUE" % name)
+    for name, v in (("max.niter", max_niter), ("reltol", reltol)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise TypeError("is.numeric(%s) is not TRUE" % name)
+    ws = _init_file2("Identity-By-Descent analysis (MLE) on genotypes:", gdsobj, sample_id, snp_id, autosome_only,
+                     remove_monosnp, maf, missing_rate, num_thread, verbose, device, allele_freq=allele_freq)
+    n, L = ws["n_samp"], ws["n_snp"]
+    if n < 2:
+        raise ValueError("snpgdsIBDMLE: at least two samples are needed")
+    if L < 1:
+        raise ValueError("snpgdsIBDMLE: no SNP in the working dataset")
+    af_in = ws["allele_freq"]
+    if verbose and af_in is not None:
+        print("Specifying allele frequencies, mean: %0.3f, sd: %0.3f" % (np.nanmean(af_in), np.nanstd(af_in, ddof=1)))
+    k0 = np.empty((n, n), np.float64)
+    k1 = np.empty((n, n), np.float64)
+    niter = np.empty((n, n), np.int32) if out_num_iter else None
+    af = np.empty(L, np.float64)
+    _lib.check(_lib.lib().snpgpu_gnrIBD_MLE(_lib._ptr(af_in), int(bool(kinship_constraint)), int(max_niter), float(reltol),
+                                            int(bool(coeff_correct)), 0, int(bool(out_num_iter)), ws["num_thread"],
+                                            int(bool(verbose)), _lib._ptr(k0), _lib._ptr(k1), _lib._ptr(af),
+                                            _lib._ptr(niter)))
+    af[af < 0] = np.nan
+    ans = dict(sample_id=ws["sample_id"], snp_id=ws["snp_id"], afreq=af, k0=k0, k1=k1, niter=niter)
+    if kinship:
+        ans["kinship"] = 0.5 * (1 - k0 - k1) + 0.25 * k1
+    return ans
+
+
+def snpgdsIBDMLELogLik(gdsobj, ibdobj, k0=float("nan"), k1=float("nan"), relatedness="", device=0):
+    """Log-likelihood of IBD coefficients (R/IBD.R:162-205 -> gnrIBD_LogLik / gnrIBD_LogLik_k01, src/genIBD.cpp:1289-1330):
+    n x n, diagonal included.  relatedness presets override k0 / k1; with finite k0 and k1 every pair is evaluated at them,
+    otherwise at the pair's own ibdobj["k0"], ibdobj["k1"]."""
+    if not isinstance(ibdobj, dict) or not {"sample_id", "snp_id", "afreq", "k0", "k1"} <= set(ibdobj):
+        raise TypeError("inherits(ibdobj, \"snpgdsIBDClass\") is not TRUE")
+    if relatedness not in RELATEDNESS:
+        raise ValueError("'arg' should be one of %s" % ", ".join('"%s"' % m for m in RELATEDNESS))
+    for name, v in (("k0", k0), ("k1", k1)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise TypeError("is.numeric(%s), is.vector(%s), length(%s) == 1L is not TRUE" % (name, name, name))
+    if RELATEDNESS[relatedness] is not None:
+        k0, k1 = RELATEDNESS[relatedness]
+    ws = _init_file(gdsobj, ibdobj["sample_id"], ibdobj["snp_id"], device)
+    afreq = np.ascontiguousarray(ibdobj["afreq"], np.float64)
+    n = ws["n_samp"]
+    # snpgpu_gnrIBD_LogLik reads one frequency per SNP and n x n coefficients of the working space
+    if afreq.ndim != 1 or afreq.shape[0] != ws["n_snp"]:
+        raise ValueError("'ibdobj$afreq' should have one entry per SNP of 'ibdobj$snp.id' (%d), not %s"
+                         % (ws["n_snp"], afreq.shape))
+    out = np.empty((n, n), np.float64)
+    if np.isfinite(k0) and np.isfinite(k1):
+        _lib.check(_lib.lib().snpgpu_gnrIBD_LogLik_k01(_lib._ptr(afreq), float(k0), float(k1), _lib._ptr(out)))
+    else:
+        m0 = np.ascontiguousarray(ibdobj["k0"], np.float64)
+        m1 = np.ascontiguousarray(ibdobj["k1"], np.float64)
+        if m0.shape != (n, n) or m1.shape != (n, n):
+            raise ValueError("'ibdobj$k0' and 'ibdobj$k1' should be %d x %d matrices, not %s and %s" % (n, n, m0.shape, m1.shape))
+        _lib.check(_lib.lib().snpgpu_gnrIBD_LogLik(_lib._ptr(afreq), _lib._ptr(m0), _lib._ptr(m1), _lib._ptr(out)))
+    return out

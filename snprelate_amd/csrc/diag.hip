@@ -106,6 +106,23 @@ __global__ __launch_bounds__(256, 2) void diag_fp4_16x16x128_kernel(const v8i *_
 uint32_t lcg(uint32_t &s) { s = s * 1664525u + 1013904223u; return s >> 8; }
 
 }  // namespace
+
+// fp64 vector stream: 8 independent v_fma_f64 chains per lane, operands that never leave registers
+constexpr int FP64_CHAINS = 8, FP64_ITERS = 4096;
+__global__ __launch_bounds__(256) void diag_fp64_kernel(const double *__restrict__ src, double *__restrict__ out)
+{
+    double a[FP64_CHAINS];
+    const double b = src[threadIdx.x & 63], c = src[64 + (threadIdx.x & 63)];
+    for (int t = 0; t < FP64_CHAINS; t++) a[t] = src[128 + t];
+    for (int it = 0; it < FP64_ITERS; it++) {
+#pragma unroll
+        for (int t = 0; t < FP64_CHAINS; t++) a[t] = fma(a[t], b, c);
+    }
+    double s = 0;
+    for (int t = 0; t < FP64_CHAINS; t++) s += a[t];
+    if (s == 1.2345) out[0] = s;
+}
+
 }  // namespace snpgpu
 
 using namespace snpgpu;
@@ -218,4 +235,57 @@ extern "C" int snpgpu_diag_device_pci(int device, char *buf, int len)
     if (!buf || len < 16) { set_error("snpgpu_diag_device_pci: buffer of at least 16 bytes needed"); return 1; }
     SNPGPU_HIP_CHECK(hipDeviceGetPCIBusId(buf, len, device));
     return 0;
+}
+
+extern "C" int snpgpu_diag_fp64_rate(int device, double seconds, double *tflops)
+{
+    if (!tflops || !(seconds > 0.0) || seconds > 30.0) { set_error("snpgpu_diag_fp64_rate: invalid arguments"); return 1; }
+    SNPGPU_HIP_CHECK(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    SNPGPU_HIP_CHECK(hipGetDeviceProperties(&prop, device));
+    std::vector<double> h(256);
+    for (int i = 0; i < 64; i++) { h[i] = 0.999 + 1e-6 * i; h[64 + i] = 1e-3 * (i % 7); }
+    for (int i = 128; i < 256; i++) h[i] = 0.5 + 1e-3 * i;
+    void *d_src = nullptr, *d_out = nullptr;
+    hipStream_t st = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int rc = 1;
+    do {
+        if (hipMalloc(&d_src, h.size() * sizeof(double)) != hipSuccess || hipMalloc(&d_out, 64) != hipSuccess) { set_error("snpgpu_diag_fp64_rate: hipMalloc failed"); break; }
+        if (hipMemcpy(d_src, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { set_error("snpgpu_diag_fp64_rate: copy failed"); break; }
+        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { set_error("snpgpu_diag_fp64_rate: stream"); break; }
+        bool ok = true;
+        for (auto &e : ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+        if (!ok) { set_error("snpgpu_diag_fp64_rate: events"); break; }
+        const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        const int blocks = cus * 2 * 4;       // 8 waves per CU resident (2 per SIMD), 4 rounds per launch
+        const double flop_per_launch = 2.0 * FP64_CHAINS * FP64_ITERS * 256.0 * blocks;
+        auto run_for = [&](double secs, long &n) {
+            const auto t0 = std::chrono::steady_clock::now();
+            n = 0;
+            do {
+                for (int i = 0; i < 8; i++)
+                    hipLaunchKernelGGL(diag_fp64_kernel, dim3(blocks), dim3(256), 0, st, (const double *)d_src, (double *)d_out);
+                n += 8;
+                if (hipStreamSynchronize(st) != hipSuccess) return false;
+            } while (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < secs);
+            return true;
+        };
+        long n1 = 0, n2 = 0;
+        if (!run_for(seconds * 0.5, n1)) { set_error("snpgpu_diag_fp64_rate: kernel failed"); break; }
+        (void)hipEventRecord(ev[0], st);
+        if (!run_for(seconds * 0.5, n2)) { set_error("snpgpu_diag_fp64_rate: kernel failed"); break; }
+        (void)hipEventRecord(ev[1], st);
+        if (hipEventSynchronize(ev[1]) != hipSuccess) { set_error("snpgpu_diag_fp64_rate: sync failed"); break; }
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+        if (!(ms > 0.f)) { set_error("snpgpu_diag_fp64_rate: no time measured"); break; }
+        *tflops = flop_per_launch * (double)n2 / ((double)ms * 1e-3) / 1e12;
+        rc = 0;
+    } while (0);
+    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+    if (st) (void)hipStreamDestroy(st);
+    if (d_src) (void)hipFree(d_src);
+    if (d_out) (void)hipFree(d_out);
+    return rc;
 }

@@ -1,0 +1,317 @@
+// C ABI of libsnpgpu: IBD coefficients by maximum likelihood (snpgdsIBDMLE, method "EM") and the log-likelihood of given
+// coefficients (snpgdsIBDMLELogLik), on resident 2-bit rows.  Kernels: kernels_ibd.hip.
+//
+// gnrIBD_MLE (src/genIBD.cpp:1465-1548) step by step:
+//   InitAFreq (:1122-1165)             caller's frequencies (non-finite -> -1) or sum / 2n over the calls (ibd_freq_kernel)
+//   Init_EPrIBD_IBS(afreq, , false)    E[IBS | IBD] from plain monomials over the SNPs with 0 <= p <= 1 (host, SNP order)
+//   Est_PLINK_Kinship(.., false)       the IBS counters of an SNPGPU_IBS context + launch_fin_mom with constraint 0
+//   EMAlg + LOGLIK_ADJUST              ibd_em_kernel, then ibd_loglik_kernel<6> when coeff_correct
+// Output: full n x n k0 / k1 / niter, 0 on the diagonal.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "snpgpu_internal.h"
+
+namespace snpgpu {
+size_t ibd_snp_bytes();
+int launch_ibd_freq(hipStream_t st, const uint8_t *rows, int64_t rb, int64_t n_snp, int64_t n_samp, double *af);
+int launch_ibd_prepare(hipStream_t st, const uint8_t *rows, int64_t rb, int64_t n_snp, int64_t n_samp, const double *af,
+                       int64_t w4, void *tab, uint8_t *usable, uint32_t *gt);
+int launch_ibd_em(hipStream_t st, int n_waves, const uint32_t *gt, int64_t w4, const void *tab, const double *mom_k0,
+                  const double *mom_k1, const int64_t *rowoff, int64_t n_rows, int64_t r0, int64_t n_samp, int64_t n_pairs,
+                  int max_niter, double reltol, unsigned long long *queue, double *k0, double *k1, double *loglik,
+                  int32_t *niter);
+int launch_ibd_candidates(hipStream_t st, const uint32_t *gt, int64_t w4, const void *tab, const int64_t *rowoff,
+                          int64_t n_rows, int64_t r0, int64_t n_samp, int64_t n_pairs, const double *loglik, double *k0,
+                          double *k1);
+int launch_ibd_loglik(hipStream_t st, const uint32_t *gt, int64_t w4, const void *tab, const int64_t *rowoff, int64_t n_rows,
+                      int64_t n_samp, int64_t n_pairs, const double *km0, const double *km1, double ks0, double ks1,
+                      double *out);
+int launch_ibd_expand(hipStream_t st, const int64_t *rowoff, int64_t n_rows, int64_t r0, int64_t n_samp, int64_t n_pairs,
+                      const double *k0, const double *k1, const int32_t *niter, double *o0, double *o1, int32_t *on);
+}  // namespace snpgpu
+
+using namespace snpgpu;
+
+namespace {
+
+thread_local double g_stats[4] = {0, 0, 0, 0};   // EM kernel ms, all kernels ms, useful / issued lane-sweeps
+
+struct Bufs {
+    std::vector<DevBuf *> all;
+    ~Bufs() { for (DevBuf *b : all) { b->release(); delete b; } }
+    DevBuf *get(size_t bytes, int &rc)
+    {
+        DevBuf *b = new DevBuf;
+        all.push_back(b);
+        if (!rc) rc = b->alloc(bytes);
+        return b;
+    }
+};
+
+struct Stream {
+    hipStream_t s = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~Stream()
+    {
+        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+
+// the genotype words and per-SNP tables both sweeps read, and the frequencies of InitAFreq
+struct Prep {
+    int64_t n_snp = 0, n_samp = 0, rb = 0, w4 = 0;
+    const uint8_t *rows = nullptr;     // device
+    DevBuf *gt = nullptr, *tab = nullptr;
+    std::vector<double> af;            // MLEAlleleFreq (host)
+};
+
+int check_args(const char *fn, const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem)
+{
+    if (!geno) { set_error(std::string(fn) + ": geno is NULL"); return 1; }
+    if (n_samp < 2) { set_error(std::string(fn) + ": at least two samples are needed"); return 1; }
+    if (n_snp < 1) { set_error(std::string(fn) + ": no SNP in the working dataset"); return 1; }
+    if (format != SNPGPU_GENO_PACKED2) { set_error(std::string(fn) + ": genotypes must be SNPGPU_GENO_PACKED2 rows"); return 1; }
+    if (mem != SNPGPU_HOST && mem != SNPGPU_DEVICE) { set_error(std::string(fn) + ": invalid memory kind"); return 1; }
+    return 0;
+}
+
+int prepare(const char *fn, Stream &st, Bufs &bufs, const void *geno, int64_t n_snp, int64_t n_samp, int mem,
+            const double *allele_freq, Prep &P)
+{
+    int rc = 0;
+    P.n_snp = n_snp; P.n_samp = n_samp; P.rb = (n_samp + 3) / 4;
+    P.w4 = (n_snp + 63) / 64;
+    const size_t row_bytes = (size_t)n_snp * (size_t)P.rb;
+    if (mem == SNPGPU_HOST) {
+        DevBuf *r = bufs.get(row_bytes, rc);
+        if (rc) return 1;
+        SNPGPU_HIP_CHECK(hipMemcpyAsync(r->p, geno, row_bytes, hipMemcpyHostToDevice, st.s));
+        P.rows = (const uint8_t *)r->p;
+    } else {
+        P.rows = (const uint8_t *)geno;
+    }
+    DevBuf *daf = bufs.get(sizeof(double) * n_snp, rc);
+    DevBuf *usable = bufs.get((size_t)n_snp, rc);
+    P.tab = bufs.get(ibd_snp_bytes() * (size_t)P.w4 * 64, rc);
+    P.gt = bufs.get((size_t)n_samp * (size_t)P.w4 * 16, rc);
+    if (rc) return 1;
+    P.af.assign((size_t)n_snp, -1.0);
+    if (allele_freq) {
+        for (int64_t l = 0; l < n_snp; l++)
+            if (std::isfinite(allele_freq[l])) P.af[l] = allele_freq[l];
+        SNPGPU_HIP_CHECK(hipMemcpyAsync(daf->p, P.af.data(), sizeof(double) * n_snp, hipMemcpyHostToDevice, st.s));
+    } else {
+        if (launch_ibd_freq(st.s, P.rows, P.rb, n_snp, n_samp, (double *)daf->p)) return 1;
+        SNPGPU_HIP_CHECK(hipMemcpyAsync(P.af.data(), daf->p, sizeof(double) * n_snp, hipMemcpyDeviceToHost, st.s));
+    }
+    if (launch_ibd_prepare(st.s, P.rows, P.rb, n_snp, n_samp, (const double *)daf->p, P.w4, P.tab->p,
+                           (uint8_t *)usable->p, (uint32_t *)P.gt->p))
+        return 1;
+    SNPGPU_HIP_CHECK(hipStreamSynchronize(st.s));
+    (void)fn;
+    return 0;
+}
+
+// rowoff[k] = index of the first pair of row r0 + k (pairs i < j, or i <= j with the diagonal)
+std::vector<int64_t> row_offsets(int64_t n, int64_t r0, int64_t r1, bool diag)
+{
+    std::vector<int64_t> off((size_t)(r1 - r0 + 1), 0);
+    for (int64_t r = r0; r < r1; r++) off[(size_t)(r - r0 + 1)] = off[(size_t)(r - r0)] + (n - r - (diag ? 0 : 1));
+    return off;
+}
+
+int open_stream(int device, Stream &st)
+{
+    int ndev = 0;
+    SNPGPU_HIP_CHECK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) { set_error("invalid device ordinal"); return 1; }
+    SNPGPU_HIP_CHECK(hipSetDevice(device));
+    SNPGPU_HIP_CHECK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    for (auto &e : st.ev) SNPGPU_HIP_CHECK(hipEventCreate(&e));
+    return 0;
+}
+
+// a device view of an n x n output: the caller's buffer, or a device copy that is written back afterwards
+struct OutMat {
+    void *user = nullptr, *dev = nullptr;
+    size_t bytes = 0;
+    int mem = 0;
+    DevBuf *tmp = nullptr;
+    int open(Bufs &bufs, void *u, size_t b, int m, bool keep, hipStream_t s)
+    {
+        user = u; bytes = b; mem = m;
+        if (!u) return 0;
+        if (m == SNPGPU_DEVICE) { dev = u; return 0; }
+        int rc = 0;
+        tmp = bufs.get(b, rc);
+        if (rc) return 1;
+        dev = tmp->p;
+        if (keep) SNPGPU_HIP_CHECK(hipMemcpyAsync(dev, u, b, hipMemcpyHostToDevice, s));
+        return 0;
+    }
+    int close(hipStream_t s)
+    {
+        if (user && mem != SNPGPU_DEVICE) SNPGPU_HIP_CHECK(hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, s));
+        return 0;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int snpgpu_ibd_mle(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, const double *allele_freq,
+                   int max_niter, double reltol, int coeff_correct, int64_t row_begin, int64_t row_end, double *k0, double *k1,
+                   int32_t *niter, double *afreq_out, int out_mem, int device)
+{
+    const char *fn = "snpgpu_ibd_mle";
+    if (check_args(fn, geno, n_snp, n_samp, format, mem)) return 1;
+    if (!k0 || !k1) { set_error("snpgpu_ibd_mle: k0 / k1 is NULL"); return 1; }
+    if (out_mem != SNPGPU_HOST && out_mem != SNPGPU_DEVICE) { set_error("snpgpu_ibd_mle: invalid out_mem"); return 1; }
+    int64_t r0 = row_begin, r1 = row_end;
+    const bool whole = (r0 == 0 && r1 == 0) || (r0 == 0 && r1 == n_samp);
+    if (r0 == 0 && r1 == 0) r1 = n_samp;
+    if (r0 < 0 || r1 > n_samp || r0 >= r1) { set_error("snpgpu_ibd_mle: invalid row range"); return 1; }
+    for (double &s : g_stats) s = 0;
+
+    Stream st;
+    Bufs bufs;
+    if (open_stream(device, st)) return 1;
+    Prep P;
+    if (prepare(fn, st, bufs, geno, n_snp, n_samp, mem, allele_freq, P)) return 1;
+    if (afreq_out) std::copy(P.af.begin(), P.af.end(), afreq_out);
+
+    // Init_EPrIBD_IBS(afreq, NULL, false), src/genIBD.cpp:253-338: plain monomials, SNPs with a finite p in [0, 1]
+    double e00 = 0, e01 = 0, e02 = 0, e11 = 0, e12 = 0;
+    long n_valid = 0;
+    for (int64_t l = 0; l < n_snp; l++) {
+        const double p = P.af[l];
+        if (!(p >= 0 && p <= 1)) continue;
+        const double q = 1 - p;
+        e00 += 2 * p * p * q * q;
+        e01 += 4 * p * p * p * q + 4 * p * q * q * q;
+        e02 += q * q * q * q + p * p * p * p + 4 * p * p * q * q;
+        e11 += 2 * p * p * q + 2 * p * q * q;
+        e12 += p * p * p + q * q * q + p * p * q + p * q * q;
+        n_valid++;
+    }
+    const double e[5] = {e00 / n_valid, e01 / n_valid, e02 / n_valid, e11 / n_valid, e12 / n_valid};
+
+    // PLINK start values on the IBS counters (Est_PLINK_Kinship with constraint = false, :823)
+    int rc = 0;
+    const size_t tri = (size_t)n_samp * (size_t)(n_samp + 1) / 2;
+    DevBuf *mk0 = bufs.get(sizeof(double) * tri, rc), *mk1 = bufs.get(sizeof(double) * tri, rc);
+    if (rc) return 1;
+    {
+        snpgpu_opts o{};
+        o.device = device;
+        o.max_block_snps = 32768;
+        snpgpu_ctx *c = nullptr;
+        if (snpgpu_create(SNPGPU_IBS, n_samp, &o, &c)) return 1;
+        for (int64_t i0 = 0; i0 < n_snp && !rc; i0 += 32768)
+            rc = snpgpu_feed(c, P.rows + (size_t)i0 * P.rb, std::min<int64_t>(32768, n_snp - i0), SNPGPU_GENO_PACKED2,
+                             SNPGPU_DEVICE);
+        if (!rc) rc = snpgpu_ibd_mom(c, e, 0, (double *)mk0->p, (double *)mk1->p, 1, SNPGPU_DEVICE);
+        if (!rc) rc = snpgpu_sync(c);
+        snpgpu_destroy(c);
+        if (rc) return 1;
+        SNPGPU_HIP_CHECK(hipSetDevice(device));
+    }
+
+    const std::vector<int64_t> off = row_offsets(n_samp, r0, r1, false);
+    const int64_t n_rows = r1 - r0, n_pairs = off.back();
+    DevBuf *drow = bufs.get(sizeof(int64_t) * off.size(), rc), *queue = bufs.get(3 * sizeof(unsigned long long), rc);
+    DevBuf *pk0 = bufs.get(sizeof(double) * n_pairs, rc), *pk1 = bufs.get(sizeof(double) * n_pairs, rc);
+    DevBuf *pl = bufs.get(sizeof(double) * n_pairs, rc), *pn = bufs.get(sizeof(int32_t) * n_pairs, rc);
+    if (rc) return 1;
+    SNPGPU_HIP_CHECK(hipMemcpyAsync(drow->p, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, st.s));
+    SNPGPU_HIP_CHECK(hipMemsetAsync(queue->p, 0, 3 * sizeof(unsigned long long), st.s));
+
+    hipDeviceProp_t prop;
+    int cus = 256;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+    const int64_t want = (n_pairs + 63) / 64;
+    const int n_waves = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)cus * 16));
+
+    SNPGPU_HIP_CHECK(hipEventRecord(st.ev[0], st.s));
+    if (launch_ibd_em(st.s, n_waves, (const uint32_t *)P.gt->p, P.w4, P.tab->p, (const double *)mk0->p,
+                      (const double *)mk1->p, (const int64_t *)drow->p, n_rows, r0, n_samp, n_pairs, max_niter, reltol,
+                      (unsigned long long *)queue->p, (double *)pk0->p, (double *)pk1->p, (double *)pl->p,
+                      (int32_t *)pn->p))
+        return 1;
+    SNPGPU_HIP_CHECK(hipEventRecord(st.ev[1], st.s));
+    if (coeff_correct &&
+        launch_ibd_candidates(st.s, (const uint32_t *)P.gt->p, P.w4, P.tab->p, (const int64_t *)drow->p, n_rows, r0, n_samp,
+                              n_pairs, (const double *)pl->p, (double *)pk0->p, (double *)pk1->p))
+        return 1;
+    SNPGPU_HIP_CHECK(hipEventRecord(st.ev[2], st.s));
+
+    const size_t nn = (size_t)n_samp * (size_t)n_samp;
+    OutMat o0, o1, on;
+    if (o0.open(bufs, k0, nn * sizeof(double), out_mem, !whole, st.s) ||
+        o1.open(bufs, k1, nn * sizeof(double), out_mem, !whole, st.s) ||
+        on.open(bufs, niter, nn * sizeof(int32_t), out_mem, !whole, st.s))
+        return 1;
+    if (launch_ibd_expand(st.s, (const int64_t *)drow->p, n_rows, r0, n_samp, n_pairs, (const double *)pk0->p,
+                          (const double *)pk1->p, (const int32_t *)pn->p, (double *)o0.dev, (double *)o1.dev,
+                          (int32_t *)on.dev))
+        return 1;
+    SNPGPU_HIP_CHECK(hipEventRecord(st.ev[3], st.s));
+    if (o0.close(st.s) || o1.close(st.s) || on.close(st.s)) return 1;
+    unsigned long long q[3] = {0, 0, 0};
+    SNPGPU_HIP_CHECK(hipMemcpyAsync(q, queue->p, sizeof(q), hipMemcpyDeviceToHost, st.s));
+    SNPGPU_HIP_CHECK(hipStreamSynchronize(st.s));
+    float ms_em = 0, ms_all = 0;
+    (void)hipEventElapsedTime(&ms_em, st.ev[0], st.ev[1]);
+    (void)hipEventElapsedTime(&ms_all, st.ev[0], st.ev[3]);
+    g_stats[0] = ms_em; g_stats[1] = ms_all; g_stats[2] = (double)q[1]; g_stats[3] = (double)q[2];
+    return 0;
+}
+
+int snpgpu_ibd_loglik(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, const double *allele_freq,
+                      const double *k0, const double *k1, double k0_all, double k1_all, double *out, double *afreq_out,
+                      int out_mem, int device)
+{
+    const char *fn = "snpgpu_ibd_loglik";
+    if (check_args(fn, geno, n_snp, n_samp, format, mem)) return 1;
+    if (!out) { set_error("snpgpu_ibd_loglik: out is NULL"); return 1; }
+    if ((k0 == nullptr) != (k1 == nullptr)) { set_error("snpgpu_ibd_loglik: give both k0 and k1 matrices, or neither"); return 1; }
+    if (out_mem != SNPGPU_HOST && out_mem != SNPGPU_DEVICE) { set_error("snpgpu_ibd_loglik: invalid out_mem"); return 1; }
+    Stream st;
+    Bufs bufs;
+    if (open_stream(device, st)) return 1;
+    Prep P;
+    if (prepare(fn, st, bufs, geno, n_snp, n_samp, mem, allele_freq, P)) return 1;
+    if (afreq_out) std::copy(P.af.begin(), P.af.end(), afreq_out);
+    int rc = 0;
+    const std::vector<int64_t> off = row_offsets(n_samp, 0, n_samp, true);
+    DevBuf *drow = bufs.get(sizeof(int64_t) * off.size(), rc);
+    if (rc) return 1;
+    SNPGPU_HIP_CHECK(hipMemcpyAsync(drow->p, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, st.s));
+    const size_t nn = (size_t)n_samp * (size_t)n_samp;
+    OutMat m0, m1, o;
+    if (k0) {
+        if (m0.open(bufs, (void *)k0, nn * sizeof(double), out_mem, true, st.s) ||
+            m1.open(bufs, (void *)k1, nn * sizeof(double), out_mem, true, st.s))
+            return 1;
+    }
+    if (o.open(bufs, out, nn * sizeof(double), out_mem, false, st.s)) return 1;
+    if (launch_ibd_loglik(st.s, (const uint32_t *)P.gt->p, P.w4, P.tab->p, (const int64_t *)drow->p, n_samp, n_samp,
+                          off.back(), (const double *)m0.dev, (const double *)m1.dev, k0_all, k1_all, (double *)o.dev))
+        return 1;
+    if (o.close(st.s)) return 1;
+    SNPGPU_HIP_CHECK(hipStreamSynchronize(st.s));
+    return 0;
+}
+
+int snpgpu_ibd_mle_stats(double *stats)
+{
+    if (!stats) { set_error("snpgpu_ibd_mle_stats: stats is NULL"); return 1; }
+    for (int k = 0; k < 4; k++) stats[k] = g_stats[k];
+    return 0;
+}
+
+}  // extern "C"

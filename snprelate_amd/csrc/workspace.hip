@@ -1107,4 +1107,51 @@ int snpgpu_gnrLDMat(int method, int64_t slide, int mat_trim, int num_thread, int
     return rc;
 }
 
+// gnrIBD_MLE(AlleleFreq, KinshipConstraint, MaxIterCnt, RelTol, CoeffCorrect, method, IfOutNum, NumThread, Verbose),
+// src/genIBD.cpp:1465-1548, on the selected SNPs (method 0 = EM only)
+static int ws_rows(const char *fn, std::vector<uint8_t> &buf)
+{
+    if (need_ws(fn)) return 1;
+    const int64_t L = (int64_t)g_ws.sel.size();
+    if (g_ws.n_samp < 2) { set_error(std::string(fn) + ": at least two samples are needed"); return 1; }
+    if (L < 1) { set_error(std::string(fn) + ": no SNP in the working dataset"); return 1; }
+    gather_block(0, L, buf);
+    return 0;
+}
+
+int snpgpu_gnrIBD_MLE(const double *allele_freq, int, int max_niter, double reltol, int coeff_correct, int method,
+                      int out_num_iter, int num_thread, int, double *k0, double *k1, double *afreq, int32_t *niter)
+{
+    if (method == 1 || method == 2) {
+        set_error(std::string("snpgpu_gnrIBD_MLE: method \"") + (method == 1 ? "downhill.simplex" : "Jacquard") +
+                  "\" is not built on the GPU path (only \"EM\")");
+        return 1;
+    }
+    if (method != 0) { set_error("Invalid MLE method!"); return 1; }
+    if (num_thread <= 0) { set_error("Invalid 'num.thread'."); return 1; }
+    std::vector<uint8_t> buf;
+    if (ws_rows("snpgpu_gnrIBD_MLE", buf)) return 1;
+    return snpgpu_ibd_mle(buf.data(), (int64_t)g_ws.sel.size(), g_ws.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, allele_freq,
+                          max_niter, reltol, coeff_correct, 0, 0, k0, k1, out_num_iter ? niter : nullptr, afreq, SNPGPU_HOST,
+                          g_ws.device);
+}
+
+// gnrIBD_LogLik(AFreq, k0, k1) and gnrIBD_LogLik_k01(AFreq, k0, k1), src/genIBD.cpp:1289-1330 and their .Call wrappers
+int snpgpu_gnrIBD_LogLik(const double *afreq, const double *k0, const double *k1, double *out)
+{
+    if (!k0 || !k1) { set_error("snpgpu_gnrIBD_LogLik: k0 / k1 is NULL"); return 1; }
+    std::vector<uint8_t> buf;
+    if (ws_rows("snpgpu_gnrIBD_LogLik", buf)) return 1;
+    return snpgpu_ibd_loglik(buf.data(), (int64_t)g_ws.sel.size(), g_ws.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, afreq, k0, k1,
+                             0, 0, out, nullptr, SNPGPU_HOST, g_ws.device);
+}
+
+int snpgpu_gnrIBD_LogLik_k01(const double *afreq, double k0, double k1, double *out)
+{
+    std::vector<uint8_t> buf;
+    if (ws_rows("snpgpu_gnrIBD_LogLik_k01", buf)) return 1;
+    return snpgpu_ibd_loglik(buf.data(), (int64_t)g_ws.sel.size(), g_ws.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, afreq,
+                             nullptr, nullptr, k0, k1, out, nullptr, SNPGPU_HOST, g_ws.device);
+}
+
 }  // extern "C"
