@@ -461,12 +461,50 @@ int snpgpu_ld_result(snpgpu_ld *ld, double *out, int out_mem);
 int snpgpu_ld_set_timing(snpgpu_ld *ld, int enable);
 int snpgpu_ld_get_timing(snpgpu_ld *ld, int which, double *ms_sum, int64_t *launches);
 /* every pair of two row sets -> int32 tab[n_a][n_b][9], cell 3 a + b (a: genotype in set A, b: in set B); host in, host out.
- * The primitive of LD pruning (candidate block x kept set). */
+ * Any pair set, e.g. the reference tables of the pruning tests (snpgpu_ld_prune itself counts its band with the sliding-window
+ * launches). */
 int snpgpu_ld_pair_tables(const void *geno_a, int64_t n_a, const void *geno_b, int64_t n_b, int64_t n_samp, int format,
                           int32_t *tab, int device);
 /* gnrLDMat(method, NumSlide, MatTrim, NumThread, Verbose), src/genLD.cpp:957-1010, on the working space's selected SNPs;
  * out: host, snpgpu_ld_out_dims' rows x cols */
 int snpgpu_gnrLDMat(int method, int64_t slide, int mat_trim, int num_thread, int verbose, double *out);
+
+/* LD pruning of one chromosome: Perform_LD_Pruning (src/genLD.cpp:807-924), the greedy forward pass from start_idx and the
+ * backward pass below it, with the reference's sliding-window list (an entry outside the window of the candidate is erased for
+ * good) and test |LD(kept, candidate)| > ld_threshold (the kept SNP is the first argument; NaN never prunes).  Erasure depends on
+ * the positions only, so the pairs the scan can test lie within a band of width W that the host computes from pos_bp and the two
+ * limits; their tables are counted on the matrix cores in streamed row blocks (one block plus a halo of W rows resident, table
+ * launches within a fixed byte budget), the finaliser turns each into one threshold bit with the LD methods of snpgdsLDMat, and
+ * the sequential scan runs on the host over those bits.
+ *   geno: SNPGPU_GENO_PACKED2 or SNPGPU_GENO_U8 rows [n_snp] in `mem` (host, or complete device memory as for snpgpu_ld_feed)
+ *   start_idx: 0-based; pos_bp: host int32 [n_snp]; slide_max_bp / slide_max_n: the reference's int window limits (differences of
+ *   positions are taken exactly in 64 bits); method 1 ... 4 (composite, r, dprime, corr); keep: host uint8 [n_snp], 1 = kept
+ *   opts: device, stream and max_block_snps (rows per streamed block, 0 = 16384; small values force several blocks) are used
+ *   info: may be NULL.  n_samp < 2^24. */
+typedef struct snpgpu_ld_prune_info {
+    int64_t width;          /* W: largest distance y - x of a pair (x, y) the scan can test                                    */
+    int64_t band_pairs;     /* pairs (x, x + k), k = 1 ... W, x + k < n_snp: tables counted and finalised                        */
+    int64_t n_kept;         /* SNPs kept                                                                                         */
+    int64_t table_launches; /* band table launches (each followed by one finaliser launch and one copy)                          */
+    int64_t table_tiles;    /* 64 x 64 pair tiles those launches computed                                                        */
+    double ms_stage;        /* HIP events: rows into the staging layout (host -> device copies, staging kernel, halo copies)     */
+    double ms_tables;       /*   band table kernel                                                                               */
+    double ms_bits;         /*   threshold-bit finaliser                                                                         */
+    double ms_copy;         /*   bit rows device -> host                                                                         */
+    double ms_scan;         /* host clock: window, band width and the scan                                                      */
+} snpgpu_ld_prune_info;
+int snpgpu_ld_prune(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, int64_t start_idx, const int32_t *pos_bp,
+                    int32_t slide_max_bp, int32_t slide_max_n, double ld_threshold, int method, uint8_t *keep,
+                    const snpgpu_opts *opts, snpgpu_ld_prune_info *info);
+/* The threshold bits snpgpu_ld_prune scans, for a band of the given width (diagnostics and tests): bits host uint64
+ * [n_snp][ceil(width / 64)], bit (k - 1) % 64 of word (k - 1) / 64 of row x = |LD(x, x + k)| > ld_threshold for x >= start_idx and
+ * |LD(x + k, x)| > ld_threshold for x < start_idx; 0 past the last SNP.  info as above (n_kept 0, ms_scan 0). */
+int snpgpu_ld_prune_bits(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, int64_t start_idx, int64_t width,
+                         double ld_threshold, int method, uint64_t *bits, const snpgpu_opts *opts, snpgpu_ld_prune_info *info);
+/* gnrLDpruning(StartIdx, pos_bp, slide_max_bp, slide_max_n, LD_threshold, method, NumThread, verbose), src/genLD.cpp:1014-1035,
+ * on the working space's selected SNPs; start_idx 0-based (the routine's StartIdx - 1), pos_bp [n selected], keep: host uint8 */
+int snpgpu_gnrLDpruning(int64_t start_idx, const int32_t *pos_bp, int32_t slide_max_bp, int32_t slide_max_n, double ld_threshold,
+                        int method, int num_thread, int verbose, uint8_t *keep);
 
 /* ---- (1e) IBD by maximum likelihood: snpgdsIBDMLE (method "EM") and snpgdsIBDMLELogLik -----------------------------------------
  * gnrIBD_MLE (src/genIBD.cpp:1465-1548) on resident rows: allele frequencies as InitAFreq (:1122-1165; allele_freq: host

@@ -29,6 +29,9 @@
 //                  NumThread, Verbose)                           CPU routine)
 //   gpu_gnrIBD_LogLik(AFreq, k0, k1)                            src/genIBD.cpp:1289-1310 and its .Call wrapper
 //   gpu_gnrIBD_LogLik_k01(AFreq, k0, k1)                        src/genIBD.cpp:1312-1330 and its .Call wrapper
+//   gpu_gnrLDpruning(StartIdx, pos_bp, slide_max_bp,             src/genLD.cpp:1014-1035 (+ Perform_LD_Pruning :807-924)
+//                    slide_max_n, LD_threshold, method,
+//                    NumThread, verbose)
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -587,13 +590,13 @@ namespace {
 struct PackedSpace {
     std::vector<C_UInt8> rows;
     size_t n_samp = 0, n_snp = 0;
-    void read(const char *msg, bool verbose)
+    void read(const char *msg, bool verbose, size_t min_samp = 2)
     {
         CachingSNPData(msg, verbose);
         CdBaseWorkSpace &space = MCWorkingGeno.Space();
         n_samp = space.SampleNum();
         n_snp = space.SNPNum();
-        if (n_samp < 2) throw ErrCoreArray("%s", "at least two samples are needed");
+        if (n_samp < min_samp) throw ErrCoreArray("%s", min_samp > 1 ? "at least two samples are needed" : "no sample in the working dataset");
         if (n_snp < 1) throw ErrCoreArray("%s", "no SNP in the working dataset");
         const size_t rb = (n_samp + 3) / 4, block = syrk_block();
         rows.assign(n_snp * rb, 0xFF);
@@ -617,6 +620,8 @@ struct PackedSpace {
 };
 
 double as_real(SEXP x) { return REAL(Rf_coerceVector(x, REALSXP))[0]; }
+
+constexpr unsigned int R_LGLSXP = 10;   // LGLSXP of <Rinternals.h>: gnrLDpruning returns a logical vector (R/LD.R does L[flag] <- rv)
 
 }  // namespace
 
@@ -687,6 +692,39 @@ COREARRAY_DLL_EXPORT SEXP gpu_gnrIBD_LogLik(SEXP AFreq, SEXP k0, SEXP k1)
 COREARRAY_DLL_EXPORT SEXP gpu_gnrIBD_LogLik_k01(SEXP AFreq, SEXP k0, SEXP k1)
 {
     return ibd_loglik(AFreq, R_NilValue, R_NilValue, as_real(k0), as_real(k1));
+}
+
+// LD pruning of the working space (one chromosome, set by the R loop): the kept reader packs it into 2-bit rows in host memory,
+// and one snpgpu_ld_prune call counts the window's pair tables on the device and runs the greedy scan.  Coercions as gnrLDpruning:
+// Rf_asInteger(StartIdx) - 1, Rf_asInteger of both window limits (R's double.xmax for an infinite slide.max.bp becomes NA_integer_,
+// so that no SNP is in any window), Rf_asReal of the threshold.
+COREARRAY_DLL_EXPORT SEXP gpu_gnrLDpruning(SEXP StartIdx, SEXP pos_bp, SEXP slide_max_bp, SEXP slide_max_n, SEXP LD_threshold,
+                                           SEXP method, SEXP NumThread, SEXP verbose)
+{
+    const int start = Rf_asInteger(StartIdx) - 1;
+    const int max_bp = Rf_asInteger(slide_max_bp), max_n = Rf_asInteger(slide_max_n);
+    const int ld_method = Rf_asInteger(method);
+    const bool vb = Rf_asLogical(verbose) == TRUE;
+    if (Rf_asInteger(NumThread) <= 0) Rf_error("Invalid 'num.thread'.");
+    COREARRAY_TRY
+        const double threshold = as_real(LD_threshold);
+        PackedSpace ps;
+        ps.read("LD pruning", vb, 1);
+        SEXP pos = PROTECT(Rf_coerceVector(pos_bp, INTSXP));
+        if (Rf_xlength(pos) != (R_xlen_t)ps.n_snp) throw ErrCoreArray("%s", "'pos_bp' should have one entry per SNP of the working space");
+        std::vector<uint8_t> keep(ps.n_snp, 0);
+        snpgpu_opts o;
+        memset(&o, 0, sizeof(o));
+        o.device = opt_int("snpgpu.device", "SNPGPU_DEVICE", 0);
+        if (snpgpu_ld_prune(&ps.rows[0], (int64_t)ps.n_snp, (int64_t)ps.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, start,
+                            INTEGER(pos), max_bp, max_n, threshold, ld_method, &keep[0], &o, nullptr))
+            gpu_fail();
+        rv_ans = Rf_allocVector(R_LGLSXP, (R_xlen_t)ps.n_snp);
+        PROTECT(rv_ans);
+        int *p = INTEGER(rv_ans);            // a logical vector's data are ints (TRUE = 1)
+        for (size_t i = 0; i < ps.n_snp; i++) p[i] = keep[i] ? TRUE : 0;
+        UNPROTECT(2);
+    COREARRAY_CATCH
 }
 
 }  // extern "C"

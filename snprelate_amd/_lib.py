@@ -47,6 +47,7 @@ EXPORTS = [
     "snpgpu_ld_get_timing", "snpgpu_ld_pair_tables", "snpgpu_gnrLDMat",
     "snpgpu_ibd_mle", "snpgpu_ibd_loglik", "snpgpu_ibd_mle_stats", "snpgpu_gnrIBD_MLE", "snpgpu_gnrIBD_LogLik",
     "snpgpu_gnrIBD_LogLik_k01", "snpgpu_diag_fp64_rate",
+    "snpgpu_ld_prune", "snpgpu_ld_prune_bits", "snpgpu_gnrLDpruning",
 ]
 
 
@@ -226,6 +227,12 @@ def lib():
     L.snpgpu_gnrIBD_LogLik.argtypes = [vp, vp, vp, vp]
     L.snpgpu_gnrIBD_LogLik_k01.argtypes = [vp, dbl, dbl, vp]
     L.snpgpu_diag_fp64_rate.argtypes = [c_int, dbl, ctypes.POINTER(dbl)]
+    i32 = ctypes.c_int32
+    L.snpgpu_ld_prune.argtypes = [vp, i64, i64, c_int, c_int, i64, vp, i32, i32, dbl, c_int, vp, ctypes.POINTER(Opts),
+                                  ctypes.POINTER(LDPruneInfo)]
+    L.snpgpu_ld_prune_bits.argtypes = [vp, i64, i64, c_int, c_int, i64, i64, dbl, c_int, vp, ctypes.POINTER(Opts),
+                                       ctypes.POINTER(LDPruneInfo)]
+    L.snpgpu_gnrLDpruning.argtypes = [i64, vp, i32, i32, dbl, c_int, c_int, c_int, vp]
     _lib = L
     return L
 
@@ -590,6 +597,66 @@ def ld_pair_tables(geno_a, geno_b, n_samp, fmt=None, device=0):
     tab = np.empty((a.shape[0], b.shape[0], 3, 3), np.int32)
     check(lib().snpgpu_ld_pair_tables(_ptr(a), a.shape[0], _ptr(b), b.shape[0], n_samp, fmt, _ptr(tab), int(device)))
     return tab
+
+
+class LDPruneInfo(ctypes.Structure):
+    """snpgpu_ld_prune_info (include/snpgpu.h section 1d)"""
+    _fields_ = [("width", ctypes.c_int64), ("band_pairs", ctypes.c_int64), ("n_kept", ctypes.c_int64),
+                ("table_launches", ctypes.c_int64), ("table_tiles", ctypes.c_int64), ("ms_stage", ctypes.c_double),
+                ("ms_tables", ctypes.c_double), ("ms_bits", ctypes.c_double), ("ms_copy", ctypes.c_double),
+                ("ms_scan", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _prune_input(geno, n_samp, fmt, n_snp):
+    """(pointer, n_snp, format, memory kind) of host rows (numpy) or device rows (an int address with n_snp and fmt given)"""
+    if isinstance(geno, int):
+        if n_snp is None or fmt is None:
+            raise ValueError("device rows need n_snp and fmt")
+        return ctypes.c_void_p(geno), int(n_snp), int(fmt), DEVICE, None
+    g = np.ascontiguousarray(geno, dtype=np.uint8)
+    if fmt is None:
+        fmt = GENO_U8 if g.shape[1] == n_samp else GENO_PACKED2
+    exp = n_samp if fmt == GENO_U8 else (n_samp + 3) // 4
+    if g.ndim != 2 or g.shape[1] != exp:
+        raise ValueError("genotype rows have the wrong shape")
+    return _ptr(g), g.shape[0], int(fmt), HOST, g
+
+
+def ld_prune(geno, n_samp, pos_bp, start_idx, slide_max_bp, slide_max_n, ld_threshold, method=LD_COMPOSITE, fmt=None, n_snp=None,
+             device=0, max_block_snps=0, stream=None):
+    """Perform_LD_Pruning on one chromosome (snpgpu_ld_prune): (bool keep [n_snp], info dict).  geno: host rows (numpy, U8 or
+    PACKED2; fmt None: U8 when a row holds n_samp bytes) or a device address (int) with n_snp and fmt; start_idx 0-based;
+    the window limits are the reference's int32 values."""
+    n_samp = int(n_samp)
+    ptr, n, fmt, mem, _keep_alive = _prune_input(geno, n_samp, fmt, n_snp)
+    pos = np.ascontiguousarray(pos_bp, dtype=np.int32)
+    if pos.shape != (n,):
+        raise ValueError("pos_bp should hold one int32 per SNP")
+    keep = np.zeros(n, np.uint8)
+    o = Opts(device=int(device), max_block_snps=int(max_block_snps), stream=stream)
+    info = LDPruneInfo()
+    check(lib().snpgpu_ld_prune(ptr, n, n_samp, fmt, mem, int(start_idx), _ptr(pos), int(slide_max_bp), int(slide_max_n),
+                                float(ld_threshold), int(method), _ptr(keep), ctypes.byref(o), ctypes.byref(info)))
+    return keep.astype(bool), info.as_dict()
+
+
+def ld_prune_bits(geno, n_samp, start_idx, width, ld_threshold, method=LD_COMPOSITE, fmt=None, n_snp=None, device=0,
+                  max_block_snps=0):
+    """The threshold bits snpgpu_ld_prune scans for a band of `width` (snpgpu_ld_prune_bits): bool [n_snp][width], entry
+    [x, k - 1] for the pair (x, x + k); and the info dict."""
+    n_samp = int(n_samp)
+    ptr, n, fmt, mem, _keep_alive = _prune_input(geno, n_samp, fmt, n_snp)
+    wpr = (int(width) + 63) // 64
+    words = np.zeros((n, max(wpr, 1)), np.uint64)
+    o = Opts(device=int(device), max_block_snps=int(max_block_snps))
+    info = LDPruneInfo()
+    check(lib().snpgpu_ld_prune_bits(ptr, n, n_samp, fmt, mem, int(start_idx), int(width), float(ld_threshold), int(method),
+                                     _ptr(words), ctypes.byref(o), ctypes.byref(info)))
+    bits = np.unpackbits(words[:, :wpr].view(np.uint8).reshape(n, -1), axis=1, bitorder="little").astype(bool)
+    return bits[:, :int(width)], info.as_dict()
 
 
 class MultiAccumulator:

@@ -18,6 +18,7 @@ INTEGRATION.md):
     snpgdsLDMat                   R/LD.R:53-92     (LD between SNP pairs)
     snpgdsIBDMLE                  R/IBD.R:79-156   (IBD by maximum likelihood, method "EM")
     snpgdsIBDMLELogLik            R/IBD.R:162-205
+    snpgdsLDpruning               R/LD.R:100-243   (LD-based SNP pruning)
 
 All arithmetic runs on the MI355X through libsnpgpu.so (`_lib`); there is no
 CPU fallback.  R's ``NULL`` is ``None``, ``NaN`` is ``float('nan')``; R lists
@@ -25,6 +26,8 @@ are dicts with the same field names.
 """
 import ctypes
 import math
+import time
+import warnings
 
 import numpy as np
 
@@ -700,3 +703,136 @@ def snpgdsIBDMLELogLik(gdsobj, ibdobj, k0=float("nan"), k1=float("nan"), related
             raise ValueError("'ibdobj$k0' and 'ibdobj$k1' should be %d x %d matrices, not %s and %s" % (n, n, m0.shape, m1.shape))
         _lib.check(_lib.lib().snpgpu_gnrIBD_LogLik(_lib._ptr(afreq), _lib._ptr(m0), _lib._ptr(m1), _lib._ptr(out)))
     return out
+
+
+LD_PRUNE_METHODS = ("composite", "r", "dprime", "corr")
+LD_PRUNE_START = ("random.f500", "random", "first", "last")
+_INT_MAX = 2 ** 31 - 1
+_NA_INTEGER = -2 ** 31
+
+
+def _is_na(x):
+    return x is None or (isinstance(x, (float, np.floating)) and math.isnan(x))
+
+
+def _is_number(x):
+    return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, np.bool_))
+
+
+def _as_integer(x):
+    """Rf_asInteger of a numeric scalar: truncation toward zero; NaN or a value outside the int range is NA_integer_ (INT_MIN),
+    with R's warning"""
+    x = float(x)
+    if math.isnan(x) or x >= _INT_MAX + 1.0 or x <= _NA_INTEGER:
+        warnings.warn("NAs introduced by coercion to integer range", RuntimeWarning, stacklevel=3)
+        return _NA_INTEGER
+    return int(x)
+
+
+def _pretty(x):
+    """prettyNum(x, ",", scientific=FALSE)"""
+    x = float(x)
+    if math.isinf(x):
+        return "Inf" if x > 0 else "-Inf"
+    if x.is_integer():
+        return "{:,}".format(int(x))
+    return "{:,}".format(float("%.7g" % x))
+
+
+def snpgdsLDpruning(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True, maf=0.005, missing_rate=0.01,
+                    method="composite", slide_max_bp=500000, slide_max_n=float("nan"), ld_threshold=0.2, start_pos="random.f500",
+                    num_thread=1, autosave=None, verbose=True, device=0, seed=None):
+    """LD-based SNP pruning (R/LD.R:100-243 -> gnrLDpruning, src/genLD.cpp:1014-1035, once per chromosome): a dict
+    {"chr<ch>": kept snp ids} in the order the chromosomes first appear in the file (0 / "" excluded), chromosomes without a
+    selected SNP left out, as R's list.
+
+    Per chromosome the working space is its selected SNPs in file order and Perform_LD_Pruning runs on it (snpgpu_ld_prune: the
+    pair tables of the window on the GPU, the greedy scan on the host).  The window limits are coerced as R does: NA / Inf
+    slide_max_n becomes .Machine$integer.max; NA / Inf slide_max_bp becomes .Machine$double.xmax, which Rf_asInteger turns into
+    NA_integer_ -- no SNP is then inside any window and every selected SNP is kept (the reference's behaviour, with R's coercion
+    warning); finite values are truncated toward zero.
+
+    start_pos "random.f500" / "random" draw the 1-based start index uniformly from 1 ... min(n, 500) / 1 ... n per chromosome,
+    in chromosome order, from numpy.random.default_rng(seed): the ranges are R's, the stream is not (R's sample.int cannot be
+    reproduced).  autosave (saveRDS, R only) is validated as in R; a file name raises NotImplementedError."""
+    # the R function's argument checks, before anything reaches the device
+    if not (_is_na(slide_max_bp) or _is_number(slide_max_bp)):
+        raise TypeError("is.na(slide.max.bp) | is.numeric(slide.max.bp) is not TRUE")
+    if not (_is_na(slide_max_n) or _is_number(slide_max_n)):
+        raise TypeError("is.na(slide.max.n) | is.numeric(slide.max.n) is not TRUE")
+    if not _is_number(ld_threshold):
+        raise TypeError("is.numeric(ld.threshold) is not TRUE")
+    if not math.isfinite(ld_threshold):
+        raise ValueError("is.finite(ld.threshold) is not TRUE")
+    if not _is_number(num_thread):
+        raise TypeError("is.numeric(num.thread) is not TRUE")
+    if not num_thread > 0:
+        raise ValueError("num.thread > 0L is not TRUE")
+    if autosave is not None and not isinstance(autosave, str):
+        raise TypeError("is.null(autosave) | is.character(autosave) is not TRUE")
+    if isinstance(autosave, str) and autosave == "":
+        raise ValueError("'autosave' should be NULL or a file name.")
+    if start_pos not in LD_PRUNE_START:
+        raise ValueError("'arg' should be one of %s" % ", ".join('"%s"' % m for m in LD_PRUNE_START))
+    if not isinstance(verbose, (bool, np.bool_)):
+        raise TypeError("is.logical(verbose) is not TRUE")
+    if method not in LD_PRUNE_METHODS:
+        raise ValueError('method should be one of "composite", "r", "dprime" and "corr"')
+    if autosave is not None:
+        raise NotImplementedError("snpgdsLDpruning: 'autosave' writes an R object (saveRDS), which only R can do")
+    if not isinstance(gdsobj, GenoFile):
+        raise TypeError("'gdsobj' should be a SNP GDS object (snpgdsOpen / GenoFile)")
+    if gdsobj.snp_position is None:
+        raise ValueError("GDS node 'snp.position' not found")
+    code = LD_PRUNE_METHODS.index(method) + 1
+
+    ws = _init_file2("SNP pruning based on LD:", gdsobj, sample_id, snp_id, autosome_only, remove_monosnp, maf, missing_rate,
+                     num_thread, verbose, device)
+    bp, mn = slide_max_bp, slide_max_n
+    if verbose:
+        print("    sliding window: %s basepairs, %s SNPs" % (_pretty(bp if not _is_na(bp) and math.isfinite(bp) else math.inf),
+                                                              _pretty(mn if not _is_na(mn) and math.isfinite(mn) else math.inf)))
+        print("    |LD| threshold: %g" % ld_threshold)
+        print("    method: %s" % ("composite", "R", "D'", "correlation")[code - 1])
+    bp = _as_integer(np.finfo(np.float64).max if _is_na(bp) or not math.isfinite(bp) else bp)
+    mn = _as_integer(_INT_MAX if _is_na(mn) or not math.isfinite(mn) else mn)
+
+    total_ids = gdsobj.snp_id
+    chrom = np.asarray(gdsobj.snp_chromosome)
+    position = gdsobj.snp_position
+    snp_flag = np.isin(total_ids, ws["snp_id"])
+    ws_chrom = chrom[snp_flag]                       # chromosome of each working-space SNP (file order)
+    _, first = np.unique(chrom, return_index=True)
+    chrset = [c for c in chrom[np.sort(first)] if not (c == 0 if np.issubdtype(chrom.dtype, np.number) else c == "")]
+    rng = np.random.default_rng(seed)
+    L = _lib.lib()
+    res, ntotal = {}, 0
+    for ch in chrset:
+        flag = snp_flag & (chrom == ch)
+        n_tmp = int(flag.sum())
+        if n_tmp <= 0:
+            continue
+        rows = np.ascontiguousarray(ws["packed"][ws_chrom == ch])
+        _lib.check(L.snpgpu_ws_set_geno(_lib._ptr(rows), n_tmp, ws["n_samp"], _lib.GENO_PACKED2, int(device)))
+        if start_pos == "random.f500":
+            startidx = int(rng.integers(1, min(n_tmp, 500) + 1))
+        elif start_pos == "random":
+            startidx = int(rng.integers(1, n_tmp + 1))
+        else:
+            startidx = 1 if start_pos == "first" else n_tmp
+        pos = np.ascontiguousarray(position[flag], np.int32)
+        keep = np.zeros(n_tmp, np.uint8)
+        _lib.check(L.snpgpu_gnrLDpruning(startidx - 1, _lib._ptr(pos), bp, mn, float(ld_threshold), code, int(num_thread),
+                                         int(bool(verbose)), _lib._ptr(keep)))
+        rv = keep.astype(bool)
+        res["chr%s" % ch] = total_ids[flag][rv]
+        ntmp = int(rv.sum())
+        ntotal += ntmp
+        if verbose:
+            # Perform_LD_Pruning's two progress bars (CdProgression type 2: 20 '=' per pass that has SNPs to visit)
+            print("Chrom %s: |%s|%s|" % (ch, "=" * 20 if n_tmp - startidx > 0 else "", "=" * 20 if startidx > 1 else ""))
+            ntot = int((chrom == ch).sum())
+            print("    %0.2f%%, %s / %s (%s)" % (100.0 * ntmp / ntot, _pretty(ntmp), _pretty(ntot), time.ctime()))
+    if verbose:
+        print("%s markers are selected in total." % _pretty(ntotal))
+    return res

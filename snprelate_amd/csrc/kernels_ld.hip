@@ -270,6 +270,38 @@ __global__ void ld_final_rect_kernel(const int32_t *__restrict__ tab, int64_t n_
     out[t] = ld_value(method, n);
 }
 
+// Pruning finaliser (snpgpu_ld_prune, csrc/ld_prune.hip): band tables [n_i][w][9] of rows i = i0 + t (chromosome indices) -> one
+// threshold bit per pair, bits[t wpr + (k - 1) / 64] bit (k - 1) % 64 = |LD(pair (i, i + k))| > threshold, 0 when k > w or
+// i + k >= n_snp (the band kernel wrote no table there) and when the value is NaN.  The kept SNP is the first argument of the
+// reference's _CalcLD: i itself in the forward pass (i >= start), the later SNP i + k in the backward pass (i < start), whose
+// table is the transpose -- the same orientation rule as ld_final_rect_kernel's, so r / dprime see the EM in the same order.
+// One wave per output word: lane l takes k = 64 word + l + 1, and the word is the wave's ballot.
+__global__ __launch_bounds__(256) void ld_prune_bits_kernel(const int32_t *__restrict__ tab, int64_t n_i, int w, int64_t wpr, int64_t i0,
+                                                            int64_t n_snp, int64_t start, int method, double threshold,
+                                                            unsigned long long *__restrict__ bits)
+{
+    const int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;   // output word (uniform across the wave)
+    const int lane = threadIdx.x & 63;
+    if (g >= n_i * wpr) return;
+    const int64_t t = g / wpr, i = i0 + t;
+    const int64_t k = (g - t * wpr) * 64 + lane + 1;
+    bool bit = false;
+    if (k <= w && i + k < n_snp) {
+        const int32_t *c = tab + (t * w + (k - 1)) * 9;
+        long n[9];
+        if (i >= start) {
+#pragma unroll
+            for (int q = 0; q < 9; q++) n[q] = c[q];
+        } else {
+#pragma unroll
+            for (int q = 0; q < 9; q++) n[3 * (q % 3) + q / 3] = c[q];
+        }
+        bit = fabs(ld_value(method, n)) > threshold;      // NaN: false, as `fabs(NaN) > LD_threshold` in the reference
+    }
+    const unsigned long long word = __ballot(bit);
+    if (lane == 0) bits[g] = word;
+}
+
 constexpr int FIN_THREADS = 256;
 
 }  // namespace
@@ -320,6 +352,18 @@ int launch_ld_final_rect(hipStream_t st, const int32_t *tab, int64_t n_i, int64_
     if (total <= 0) return 0;
     hipLaunchKernelGGL(ld_final_rect_kernel, dim3((unsigned)((total + FIN_THREADS - 1) / FIN_THREADS)), dim3(FIN_THREADS), 0, st, tab,
                        n_i, n_j, i0, method, out);
+    SNPGPU_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_ld_prune_bits(hipStream_t st, const int32_t *tab, int64_t n_i, int w, int64_t i0, int64_t n_snp, int64_t start, int method,
+                         double threshold, uint64_t *bits)
+{
+    const int64_t wpr = (w + 63) / 64;
+    const int64_t threads = n_i * wpr * 64;
+    if (threads <= 0) return 0;
+    hipLaunchKernelGGL(ld_prune_bits_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, tab, n_i, w, wpr, i0, n_snp,
+                       start, method, threshold, (unsigned long long *)bits);
     SNPGPU_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -130,6 +130,9 @@ int launch_ld_count_rect(hipStream_t st, const uint8_t *A, int n_a, const uint8_
 int launch_ld_count_band(hipStream_t st, const uint8_t *rows, int i_lo, int n_i, int n_rows, int slide, int64_t rbp, int32_t *tab);
 int launch_ld_final_band(hipStream_t st, const int32_t *tab, int64_t n_i, int slide, int64_t i0, int64_t n_snp, int method, double *out);
 int launch_ld_final_rect(hipStream_t st, const int32_t *tab, int64_t n_i, int64_t n_j, int64_t i0, int method, double *out);
+// LD pruning: threshold bits of band tables [n_i][w][9] -> uint64 [n_i][ceil(w / 64)] (pairs with i0 + t < start transposed)
+int launch_ld_prune_bits(hipStream_t st, const int32_t *tab, int64_t n_i, int w, int64_t i0, int64_t n_snp, int64_t start, int method,
+                         double threshold, uint64_t *bits);
 // PCA projections (kernels_proj.hip)
 int launch_proj_snp(hipStream_t st, int corr, const uint32_t *w2, int64_t ncols_pad, int64_t N, int64_t n_snp,
                     const double *et, int kp, int k, const int32_t *sum, const int32_t *num, int bayesian, double *out,

@@ -1107,6 +1107,24 @@ int snpgpu_gnrLDMat(int method, int64_t slide, int mat_trim, int num_thread, int
     return rc;
 }
 
+// gnrLDpruning(StartIdx, pos_bp, slide_max_bp, slide_max_n, LD_threshold, method, NumThread, verbose), src/genLD.cpp:1014-1035:
+// the selected SNPs (one chromosome, as the R loop sets them) in one host block
+int snpgpu_gnrLDpruning(int64_t start_idx, const int32_t *pos_bp, int32_t slide_max_bp, int32_t slide_max_n, double ld_threshold,
+                        int method, int num_thread, int, uint8_t *keep)
+{
+    if (need_ws("snpgpu_gnrLDpruning")) return 1;
+    if (num_thread <= 0) { set_error("Invalid 'num.thread'."); return 1; }
+    if (!pos_bp || !keep) { set_error("snpgpu_gnrLDpruning: NULL argument"); return 1; }
+    const int64_t L = (int64_t)g_ws.sel.size();
+    if (L < 1) { set_error("snpgpu_gnrLDpruning: no SNP in the working dataset"); return 1; }
+    std::vector<uint8_t> buf;
+    gather_block(0, L, buf);
+    snpgpu_opts o{};
+    o.device = g_ws.device;
+    return snpgpu_ld_prune(buf.data(), L, g_ws.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, start_idx, pos_bp, slide_max_bp, slide_max_n,
+                           ld_threshold, method, keep, &o, nullptr);
+}
+
 // gnrIBD_MLE(AlleleFreq, KinshipConstraint, MaxIterCnt, RelTol, CoeffCorrect, method, IfOutNum, NumThread, Verbose),
 // src/genIBD.cpp:1465-1548, on the selected SNPs (method 0 = EM only)
 static int ws_rows(const char *fn, std::vector<uint8_t> &buf)

@@ -57,7 +57,7 @@ class GenoFile:
     """
 
     def __init__(self, genotype=None, sample_id=None, snp_id=None, snp_chromosome=None,
-                 packed=None, n_samp=None):
+                 packed=None, n_samp=None, snp_position=None):
         if packed is None:
             genotype = np.asarray(genotype, dtype=np.uint8)
             n_snp, n_samp = genotype.shape
@@ -74,6 +74,9 @@ class GenoFile:
                        else np.asarray(snp_id))
         self.snp_chromosome = (np.ones(n_snp, np.int32) if snp_chromosome is None
                                else np.asarray(snp_chromosome))
+        # snp.position (int32 base pairs), read by snpgdsLDpruning; None when the file has no such node
+        self.snp_position = None if snp_position is None else np.asarray(snp_position, np.int32)
+        assert self.snp_position is None or len(self.snp_position) == self.n_snp
         # snpgdsOption() defaults (R/AllUtilities.R:1910-1991)
         self.autosome_start, self.autosome_end = 1, 22
         assert len(self.sample_id) == self.n_samp and len(self.snp_id) == self.n_snp
@@ -201,6 +204,10 @@ def open_gds(path):
         chrom = np.frombuffer(b, np.uint8, count=dims[0]).astype(np.int32)
     else:
         chrom = np.frombuffer(b, "<i4", count=dims[0]).copy()
+    position = None
+    if "snp.position" in entries:
+        dims, b, _ = raw("snp.position")
+        position = np.frombuffer(b, "<i4", count=dims[0]).copy()
     dims, b, attr = raw("genotype")
     if b"ZIP" in streams[entries["genotype"]][:64] and len(b) * 4 < dims[0] * dims[1]:
         raise ValueError("compressed genotype nodes are not supported by this reader")
@@ -217,7 +224,7 @@ def open_gds(path):
     else:
         # snp.order: dims = [n_samp][n_snp]
         geno = np.ascontiguousarray(g.T)
-    return GenoFile(genotype=geno, sample_id=sample_id, snp_id=snp_id, snp_chromosome=chrom)
+    return GenoFile(genotype=geno, sample_id=sample_id, snp_id=snp_id, snp_chromosome=chrom, snp_position=position)
 
 
 # ---------------------------------------------------------------------------
