@@ -51,7 +51,8 @@ enum snpgpu_kind {
     SNPGPU_GRM_GCTA    = 4, /* CGCTA_AlgArith   src/genPCA.cpp:1131-1238 */
     SNPGPU_PCA_COV     = 5, /* CExactPCA        src/genPCA.cpp:378-465 (also GRM "Eigenstrat") */
     SNPGPU_EIGMIX      = 6, /* CEigMix_AlgArith src/genEIGMIX.cpp:43-160 (also GRM "EIGMIX") */
-    SNPGPU_INDIV_BETA  = 7  /* CIndivBeta       src/genBeta.cpp:57-252 (also GRM "IndivBeta") */
+    SNPGPU_INDIV_BETA  = 7, /* CIndivBeta       src/genBeta.cpp:57-252 (also GRM "IndivBeta") */
+    SNPGPU_DISS        = 8  /* individual dissimilarity, IBS::DoDissCalculate src/genIBS.cpp:333-419 */
 };
 
 enum snpgpu_geno_format { SNPGPU_GENO_U8 = 0, SNPGPU_GENO_PACKED2 = 1 };
@@ -148,6 +149,12 @@ int snpgpu_king_robust(snpgpu_ctx *ctx, const int32_t *family, double *ibs0, dou
                        int packed, int mem);
 /* gnrIBD_KING_Homo finaliser, src/genKING.cpp:516-560 */
 int snpgpu_king_homo(snpgpu_ctx *ctx, double *k0, double *k1, int packed, int mem);
+/* gnrDiss finaliser, src/genIBS.cpp:652-683: SumGeno / SumAFreq off the diagonal, 2 SumGeno / SumAFreq on it
+ * (IEEE division: 0/0 = NaN, x/0 = Inf, as the reference) */
+int snpgpu_diss(snpgpu_ctx *ctx, double *out, int packed, int mem);
+/* the dissimilarity sums themselves (diagnostics, tests), packed slab: SumGeno = sum of g_i (2 - g_j) + (2 - g_i) g_j and
+ * SumAFreq = sum of 8 p (1 - p), both over the SNPs where both samples are called */
+int snpgpu_diss_sums(snpgpu_ctx *ctx, uint32_t *geno_sum, double *wsum, int mem);
 /* GCTA GRM: numerator / (2 (nLocus - Denom)), src/genPCA.cpp:1232-1236 + grm_output :1586-1602 */
 int snpgpu_grm_gcta(snpgpu_ctx *ctx, double *out, int packed, int mem);
 /* PCA covariance.  normalize != 0 applies C *= (n-1)/trace (src/genPCA.cpp:1386-1390;
@@ -295,6 +302,7 @@ int snpgpu_multi_ibs_ave(snpgpu_multi *m, double *out, int mem);
 int snpgpu_multi_king_robust(snpgpu_multi *m, const int32_t *family, double *ibs0, double *kinship, int mem);
 int snpgpu_multi_king_robust_counts(snpgpu_multi *m, uint32_t *out5, int mem);
 int snpgpu_multi_king_homo(snpgpu_multi *m, double *k0, double *k1, int mem);
+int snpgpu_multi_diss(snpgpu_multi *m, double *out, int mem);
 int snpgpu_multi_grm_gcta(snpgpu_multi *m, double *out, int mem);
 int snpgpu_multi_eigmix(snpgpu_multi *m, int diagadj, double scale, double *out, int mem);
 int snpgpu_multi_pca_trace(snpgpu_multi *m, double *trace);
@@ -374,6 +382,8 @@ int snpgpu_gnrIBD_KING_Robust(const int32_t *family, int num_thread, int use_mat
                               double *ibs0, double *kinship);
 /* gnrIBD_KING_Homo(NumThread, useMatrix, Verbose), src/genKING.cpp:493-570 */
 int snpgpu_gnrIBD_KING_Homo(int num_thread, int use_matrix, int verbose, double *k0, double *k1);
+/* gnrDiss(NumThread, Verbose), src/genIBS.cpp:652-683: out = the full n x n matrix */
+int snpgpu_gnrDiss(int num_thread, int verbose, double *out);
 /* gnrGRM(NumThread, Method, GDS, useMatrix, Verbose), src/genPCA.cpp:1614-1717;
  * methods on this path: "GCTA", "Eigenstrat", "Corr", "EIGMIX", "IndivBeta" */
 int snpgpu_gnrGRM(int num_thread, const char *method, int use_matrix, int verbose, double *out);

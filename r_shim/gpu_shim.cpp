@@ -312,6 +312,22 @@ COREARRAY_DLL_EXPORT SEXP gpu_gnrIBD_KING_Homo(SEXP NumThread, SEXP useMatrix, S
     COREARRAY_CATCH
 }
 
+// gnrDiss, src/genIBS.cpp:652-683: always the full n x n matrix
+COREARRAY_DLL_EXPORT SEXP gpu_gnrDiss(SEXP NumThread, SEXP Verbose)
+{
+    const bool verbose = SEXP_Verbose(Verbose);
+    COREARRAY_TRY
+        CachingSNPData("Dissimilarity", verbose);
+        const size_t n = MCWorkingGeno.Space().SampleNum();
+        Accumulator acc;
+        acc.stream(SNPGPU_DISS, false, syrk_block(), verbose);        // SumGeno counters + the masked weight sum
+        PROTECT(rv_ans = Rf_allocMatrix(REALSXP, (int)n, (int)n));
+        if (snpgpu_diss(acc.ctx, REAL(rv_ans), 0, SNPGPU_HOST)) gpu_fail();
+        if (verbose) Rprintf("%s    Done.\n", TimeToStr());
+        UNPROTECT(1);
+    COREARRAY_CATCH
+}
+
 // --------------------------------------------------------------------------------------------------------------
 COREARRAY_DLL_EXPORT SEXP gpu_gnrGRM_avg_val() { return Rf_ScalarReal(grm_avg_val); }
 

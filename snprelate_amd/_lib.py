@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("SNPGPU_LIB") or os.path.join(_HERE, "libsnpgpu.so")
 
 # enums of include/snpgpu.h
 IBS, KING_ROBUST, KING_HOMO, GRM_GCTA, PCA_COV, EIGMIX, INDIV_BETA = 1, 2, 3, 4, 5, 6, 7
+DISS = 8
 GENO_U8, GENO_PACKED2 = 0, 1
 LD_COMPOSITE, LD_R, LD_DPRIME, LD_CORR, LD_COV = 1, 2, 3, 4, 5
 HOST, DEVICE, HOST_PINNED = 0, 1, 2
@@ -48,6 +49,7 @@ EXPORTS = [
     "snpgpu_ibd_mle", "snpgpu_ibd_loglik", "snpgpu_ibd_mle_stats", "snpgpu_gnrIBD_MLE", "snpgpu_gnrIBD_LogLik",
     "snpgpu_gnrIBD_LogLik_k01", "snpgpu_diag_fp64_rate",
     "snpgpu_ld_prune", "snpgpu_ld_prune_bits", "snpgpu_gnrLDpruning",
+    "snpgpu_diss", "snpgpu_diss_sums", "snpgpu_gnrDiss", "snpgpu_multi_diss",
 ]
 
 
@@ -144,6 +146,10 @@ def lib():
     L.snpgpu_king_robust_counts.argtypes = [vp, vp, c_int]
     L.snpgpu_king_robust.argtypes = [vp, vp, vp, vp, c_int, c_int]
     L.snpgpu_king_homo.argtypes = [vp, vp, vp, c_int, c_int]
+    L.snpgpu_diss.argtypes = [vp, vp, c_int, c_int]
+    L.snpgpu_diss_sums.argtypes = [vp, vp, vp, c_int]
+    L.snpgpu_gnrDiss.argtypes = [c_int, c_int, vp]
+    L.snpgpu_multi_diss.argtypes = [vp, vp, c_int]
     L.snpgpu_grm_gcta.argtypes = [vp, vp, c_int, c_int]
     L.snpgpu_pca_cov.argtypes = [vp, vp, c_int, c_int, dbl, ctypes.POINTER(dbl), c_int]
     L.snpgpu_pca_eigen.argtypes = [vp, c_int, vp, vp, c_int]
@@ -438,6 +444,22 @@ class Accumulator:
         b = np.empty(self._shape(packed), np.float64)
         check(lib().snpgpu_king_homo(self._h, _ptr(a), _ptr(b), int(packed), HOST))
         return a, b
+
+    def diss(self, packed=False, out_ptr=None):
+        """Individual dissimilarity (gnrDiss); out_ptr: optional DEVICE pointer receiving the result."""
+        if out_ptr is not None:
+            check(lib().snpgpu_diss(self._h, ctypes.c_void_p(int(out_ptr)), int(packed), DEVICE))
+            return None
+        o = np.empty(self._shape(packed), np.float64)
+        check(lib().snpgpu_diss(self._h, _ptr(o), int(packed), HOST))
+        return o
+
+    def diss_sums(self):
+        """(SumGeno uint32, SumAFreq fp64), packed slab: numerator and denominator of the dissimilarity."""
+        g = np.empty(self.slab_size(), np.uint32)
+        w = np.empty(self.slab_size(), np.float64)
+        check(lib().snpgpu_diss_sums(self._h, _ptr(g), _ptr(w), HOST))
+        return g, w
 
     def grm_gcta(self, packed=False, out_ptr=None):
         """out_ptr: optional DEVICE pointer receiving the result (then nothing is returned)."""
@@ -770,6 +792,11 @@ class MultiAccumulator:
     def king_robust_counts(self, out=None):
         o = out if out is not None else np.zeros((tri_size(self.n), 5), np.uint32)
         check(lib().snpgpu_multi_king_robust_counts(self._h, _ptr(o), HOST))
+        return o
+
+    def diss(self, out=None):
+        o = out if out is not None else self._tri(np.float64)
+        check(lib().snpgpu_multi_diss(self._h, _ptr(o), HOST))
         return o
 
     def grm_gcta(self, out=None, out_ptr=None):

@@ -19,6 +19,7 @@ INTEGRATION.md):
     snpgdsIBDMLE                  R/IBD.R:79-156   (IBD by maximum likelihood, method "EM")
     snpgdsIBDMLELogLik            R/IBD.R:162-205
     snpgdsLDpruning               R/LD.R:100-243   (LD-based SNP pruning)
+    snpgdsDiss                    R/IBD.R:432-450  (individual dissimilarity)
 
 All arithmetic runs on the MI355X through libsnpgpu.so (`_lib`); there is no
 CPU fallback.  R's ``NULL`` is ``None``, ``NaN`` is ``float('nan')``; R lists
@@ -542,6 +543,19 @@ def snpgdsIBDMoM(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remove
     if kinship:
         ans["kinship"] = 0.5 * (1 - k0 - k1) + 0.25 * k1
     return ans
+
+
+def snpgdsDiss(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True,
+               maf=float("nan"), missing_rate=0.01, num_thread=1, verbose=True, device=0):
+    """Individual dissimilarity (R/IBD.R:432-450 -> gnrDiss, src/genIBS.cpp:652-683): the full n x n matrix.
+
+    R's result carries the class "snpgdsDissClass"; here it is a dict like every other result."""
+    ws = _init_file2("Individual dissimilarity analysis on genotypes:", gdsobj, sample_id, snp_id,
+                     autosome_only, remove_monosnp, maf, missing_rate, num_thread, verbose, device)
+    n = ws["n_samp"]
+    d = np.empty((n, n), np.float64)
+    _lib.check(_lib.lib().snpgpu_gnrDiss(ws["num_thread"], int(verbose), _lib._ptr(d)))
+    return dict(sample_id=ws["sample_id"], snp_id=ws["snp_id"], diss=d)
 
 
 def snpgdsIndivBeta(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True,

@@ -129,7 +129,7 @@ static void free_ctx(snpgpu_ctx *c)
 {
     (void)hipSetDevice(c->device);
     DevBuf *all[] = {&c->raw, &c->packed, &c->sum, &c->num, &c->lut[0], &c->lut[1], &c->rowp, &c->colp, &c->wt, &c->w2,
-                     &c->scalars, &c->family, &c->miss_diag, &c->nhet, &c->dvals, &c->samp_het, &c->samp_dmiss, &c->samp_dsq, &c->acc_u32, &c->acc_f64, &c->i8_work, &c->mm256, &c->sp_work, &c->h3_work, &c->x1_work, &c->eig_qt, &c->acc_f32, &c->ccoef, &c->tcorr, &c->colterm, &c->uvcoef, &c->uvterm, &c->uvkpart, &c->uvsp, &c->uvlut, &c->uvpace, &c->uvslot, &c->uvcand, &c->homo_lut[0], &c->homo_lut[1], &c->homo_wts, &c->homo_tc, &c->homo_msum, &c->homo_work, &c->wt12, &c->het, &c->het_blk, &c->i8_work_nm, &c->tg_pc_tab,
+                     &c->scalars, &c->family, &c->miss_diag, &c->nhet, &c->dvals, &c->samp_het, &c->samp_dmiss, &c->samp_dsq, &c->acc_u32, &c->acc_f64, &c->i8_work, &c->mm256, &c->sp_work, &c->h3_work, &c->x1_work, &c->eig_qt, &c->acc_f32, &c->ccoef, &c->tcorr, &c->colterm, &c->uvcoef, &c->uvterm, &c->uvkpart, &c->uvsp, &c->uvlut, &c->uvpace, &c->uvslot, &c->uvcand, &c->homo_lut[0], &c->homo_lut[1], &c->homo_wts, &c->homo_tc, &c->homo_msum, &c->homo_work, &c->diss_called, &c->wt12, &c->het, &c->het_blk, &c->i8_work_nm, &c->tg_pc_tab,
                      &c->tg_mm_tab};
     for (DevBuf *b : all) b->release();
     for (int k = 0; k < 2; k++) {
@@ -179,7 +179,7 @@ int snpgpu_create(int kind, int64_t n_samp, const snpgpu_opts *opts, snpgpu_ctx 
 {
     if (!out) { set_error("snpgpu_create: out is NULL"); return 1; }
     *out = nullptr;
-    if (kind < SNPGPU_IBS || kind > SNPGPU_INDIV_BETA) { set_error("snpgpu_create: invalid kind"); return 1; }
+    if (kind < SNPGPU_IBS || kind > SNPGPU_DISS) { set_error("snpgpu_create: invalid kind"); return 1; }
     if (n_samp <= 0 || n_samp > 0x7fffffffLL) { set_error("snpgpu_create: invalid number of samples"); return 1; }
     snpgpu_opts o{};
     if (opts) o = *opts;
@@ -253,6 +253,10 @@ int snpgpu_create(int kind, int64_t n_samp, const snpgpu_opts *opts, snpgpu_ctx 
         c->use_mm = true; c->n_lut = 2; c->lut_mode[0] = LUT_EIGMIX_NUM; c->lut_mode[1] = LUT_EIGMIX_MISSW;
         break;
     case SNPGPU_INDIV_BETA: c->use_pc = true; c->pc_mode = PM_BETA; break;
+    case SNPGPU_DISS:      // SumGeno on the MX-fp4 counter kernels, SumAFreq = 8 x KING-homo's first weight sum
+        c->use_pc = true; c->pc_mode = PM_DISS;
+        c->use_mm = true; c->n_lut = 1; c->lut_mode[0] = LUT_HOMO_W1;
+        break;
     }
     c->n_u32 = c->use_pc ? pair_mode_counters(c->pc_mode) : 0;
     c->n_f64 = c->n_lut;
@@ -292,8 +296,9 @@ int snpgpu_create(int kind, int64_t n_samp, const snpgpu_opts *opts, snpgpu_ctx 
             if (const char *e = getenv("SNPGPU_GCTA_MISS_FP4")) c->miss_fp4 = atoi(e) != 0;
             if (!rc) rc |= build_worklist(c, tr, tc, I8_SUPER, c->i8_work, c->i8_blocks, wpc0);
             // blocks without missing calls: binary 3-product kernel (IBS and KING-robust), 128 x 128 tiles
-            if (!rc && (c->pc_mode == PM_IBS || c->pc_mode == PM_KING_ROBUST || c->pc_mode == PM_KING_HOMO) &&
-                !getenv("SNPGPU_I8_NO_NOMISS")) {
+            // (the dissimilarity counter has no other form for such blocks: always)
+            if (!rc && (((c->pc_mode == PM_IBS || c->pc_mode == PM_KING_ROBUST || c->pc_mode == PM_KING_HOMO) &&
+                         !getenv("SNPGPU_I8_NO_NOMISS")) || c->pc_mode == PM_DISS)) {
                 // per sample: #het, then #(g == 2), over the blocks the two-product kernel took
                 rc |= c->het.alloc(sizeof(uint32_t) * (size_t)(2 * c->ncols_pad));
                 if (!rc) rc |= (hipMemset(c->het.p, 0, sizeof(uint32_t) * (size_t)(2 * c->ncols_pad)) != hipSuccess);
@@ -424,6 +429,15 @@ int snpgpu_create(int kind, int64_t n_samp, const snpgpu_opts *opts, snpgpu_ctx 
     // hi / lo operand.  Needs the two-scalar form of the blocks without missing calls (the binary counter kernel's contexts);
     // SNPGPU_HOMO_UV=0: the two-product kernels as before
     c->homo_uv = kind == SNPGPU_KING_HOMO && c->mm_h3 && c->het.p != nullptr && !(getenv("SNPGPU_HOMO_UV") && !atoi(getenv("SNPGPU_HOMO_UV")));
+    // individual dissimilarity: the first weight of that path only, and the MX-fp4 counters; no other form exists (no silent fall-back)
+    if (kind == SNPGPU_DISS && !rc) {
+        c->homo_uv = c->mm_h3 && c->het.p != nullptr;
+        if (!c->homo_uv || !c->pc_i8 || !c->nomiss_fp4 || !c->general_fp4) {
+            set_error("the dissimilarity kind needs the MX-fp4 counter kernels and the fp16 weight product (SNPGPU_PAIR_BACKEND, "
+                      "SNPGPU_PAIR_FP4, SNPGPU_PAIR_FP4_GENERAL or SNPGPU_SYRK select a form it does not have)");
+            rc = 1;
+        }
+    }
     // the single-product kernel on v_mfma_f32_16x16x32_f16 (round 6: the same products and fp32 runs, half the accumulator traffic per flop
     // under the socket power cap).  SNPGPU_SYRK_UV16: 0 = the 32x32x16 form (syrk_uv_kernel); 1 = syrk_uv16_kernel (operands looked up in
     // LDS tables -- what KING-homo's binary tables and EIGMIX always take); 2 = syrk_uv16c_kernel (GRM / PCA contexts: nibble words, one
@@ -444,12 +458,15 @@ int snpgpu_create(int kind, int64_t n_samp, const snpgpu_opts *opts, snpgpu_ctx 
     }
     if (c->homo_uv && !rc) {
         const int64_t Bpad = std::max<int64_t>(round_up(c->Bmax, 1024), 2 * UV_CHS);
-        for (int i = 0; i < 2; i++) rc |= c->homo_lut[i].alloc(64 * (size_t)(Bpad + 2048));
+        for (int i = 0; i < (kind == SNPGPU_DISS ? 1 : 2); i++) rc |= c->homo_lut[i].alloc(64 * (size_t)(Bpad + 2048));
         rc |= c->homo_wts.alloc(sizeof(double2) * (size_t)(Bpad + 2048));
         rc |= c->homo_tc.alloc(sizeof(double2) * (size_t)(Bpad / (8 * (H3_LUTCH / 16)) + 16) * (size_t)c->ncols_pad);   // one partial per 256 SNPs
         rc |= c->homo_msum.alloc(sizeof(double) * 2 * (size_t)c->ncols_pad);
         if (!rc) rc |= (hipMemset(c->homo_msum.p, 0, c->homo_msum.bytes) != hipSuccess);
-        if (!rc) rc |= build_worklist(c, X1_TILE, X1_TILE, H3_SUPER / 2, c->homo_work, c->homo_blocks, 1, 2);   // both weights in one launch
+        if (!rc) rc |= build_worklist(c, X1_TILE, X1_TILE, H3_SUPER / 2, c->homo_work, c->homo_blocks, 1,
+                                      kind == SNPGPU_DISS ? 1 : 2);   // both weights in one launch (dissimilarity: the first)
+        if (kind == SNPGPU_DISS && !rc) rc |= c->diss_called.alloc(sizeof(uint32_t) * (size_t)c->ncols_pad);
+        if (c->diss_called.p && !rc) rc |= (hipMemset(c->diss_called.p, 0, c->diss_called.bytes) != hipSuccess);
     }
     if (!rc) {
         hipError_t e = hipSuccess;
@@ -770,7 +787,7 @@ static int feed_impl(snpgpu_ctx *c, const void *geno, int64_t n_snp, int format,
             return 1;
         // KING-homo: in a block without missing calls the masked weight sums are the same for every pair -- the table
         // pass adds them to two scalars, the SYRK of both tables exits (and the two-product counter kernel takes the block)
-        const bool homo_nm = (c->kind == SNPGPU_KING_HOMO && c->het.p != nullptr);
+        const bool homo_nm = ((c->kind == SNPGPU_KING_HOMO || c->kind == SNPGPU_DISS) && c->het.p != nullptr);
         for (int i = 0; i < c->n_lut; i++) {
             unsigned long long *nl = (i == 0 && c->kind == SNPGPU_GRM_GCTA) ? c->d_nlocus() : nullptr;
             const bool eig0 = (c->kind == SNPGPU_EIGMIX && i == 0);
@@ -821,16 +838,21 @@ static int feed_impl(snpgpu_ctx *c, const void *geno, int64_t n_snp, int format,
             if (c->homo_uv) {
                 // KING-homo block with missing calls: tables, effective weights, totals and per-sample missing sums of BOTH weights
                 // once (i == 0), then one single-product launch per weight into its plane
+                const bool one_w = (c->kind == SNPGPU_DISS);      // the first weight only
+                if (i == 0 && one_w && launch_diss_called(st, packed, c->RB, n_snp, (const int32_t *)c->sum.p, (const int32_t *)c->num.p,
+                                                          c->col0, c->N - c->col0, (uint32_t *)c->diss_called.p))
+                    return 1;
                 if (i == 0 && launch_homo_uv(st, (const int32_t *)c->sum.p, (const int32_t *)c->num.p, n_snp, n_pad, (uint2 *)c->homo_lut[0].p,
                                              (uint2 *)c->homo_lut[1].p, (double2 *)c->homo_wts.p, c->d_homo_w(), (const uint32_t *)c->wt.p,
-                                             c->ncols_pad, (double2 *)c->homo_tc.p, (double *)c->homo_msum.p, c->d_missing(), c->uv16 ? 1 : 0))
+                                             c->ncols_pad, (double2 *)c->homo_tc.p, (double *)c->homo_msum.p, c->d_missing(), c->uv16 ? 1 : 0,
+                                             one_w ? 1 : 2))
                     return 1;
                 // (both weights in ONE launch: work items (tile, weight), the copy index picks table and plane)
                 EvScope ev(c, 1);
                 if (i == 0 && launch_syrk_uv(st, (const int4 *)c->homo_work.p, c->homo_blocks, (const uint32_t *)c->wt.p, c->ncols_pad,
                                              (const uint2 *)c->homo_lut[0].p, n_q, (double *)c->acc_f64.p, c->ncols_pad, c->acc_tiles_c,
                                              c->d_missing(), c->N - c->row0, 0, 1, 1,
-                                             (int64_t)((const char *)c->homo_lut[1].p - (const char *)c->homo_lut[0].p), (int64_t)c->plane(),
+                                             one_w ? 0 : (int64_t)((const char *)c->homo_lut[1].p - (const char *)c->homo_lut[0].p), (int64_t)c->plane(),
                                              c->uv16 ? 1 : 0))
                     return 1;
                 continue;
@@ -974,6 +996,11 @@ int check_out(snpgpu_ctx *c, int kind_a, int kind_b, int packed, const char *fn,
     if (c->kind != kind_a && c->kind != kind_b) { set_error(std::string(fn) + ": wrong context kind"); return 1; }
     if (!packed && !c->full) { set_error(std::string(fn) + ": full-matrix output needs a full (non-panel) context"); return 1; }
     if (settle && settle_colterm(c)) return 1;
+    if (c->het_pending && c->pc_mode == PM_DISS) {
+        SNPGPU_HIP_CHECK(hipSetDevice(c->device));
+        if (launch_diss_settle(c->stream, (uint32_t *)c->acc_u32.p, c->rows_pad, c->ncols_pad, (uint32_t *)c->het.p)) return 1;
+        c->het_pending = false;
+    }
     if (c->het_pending) {       // rank-one terms of the blocks the binary pair kernel took
         SNPGPU_HIP_CHECK(hipSetDevice(c->device));
         const bool homo = (c->pc_mode == PM_KING_HOMO);     // planes {ibs1, 2 ibs0} instead of {n, ibs1, 2 ibs0, ...}
@@ -1061,6 +1088,34 @@ int snpgpu_king_homo(snpgpu_ctx *c, double *k0, double *k1, int packed, int mem)
     if (launch_fin_king_homo(c->stream, c->geom(), (const uint32_t *)c->acc_u32.p, (const double *)c->acc_f64.p, fscale,
                              (double *)b0.dev, (double *)b1.dev, packed, c->het.p ? c->d_homo_w() : nullptr,
                              c->homo_uv ? (const double *)c->homo_msum.p : nullptr))
+        return 1;
+    if (b0.commit() || b1.commit()) return 1;
+    return finish(c);
+}
+
+int snpgpu_diss(snpgpu_ctx *c, double *out, int packed, int mem)
+{
+    if (check_out(c, SNPGPU_DISS, SNPGPU_DISS, packed, "snpgpu_diss")) return 1;
+    OutBuf b(c, out, out_elems(c, packed) * sizeof(double), mem);
+    if (b.prepare()) return 1;
+    if (launch_fin_diss(c->stream, c->geom(), (const uint32_t *)c->acc_u32.p, (const double *)c->acc_f64.p,
+                        std::ldexp(1.0, -2 * H3_HOMO_SHIFT), c->d_homo_w(), (const double *)c->homo_msum.p,
+                        (const uint32_t *)c->diss_called.p, (double *)b.dev, nullptr, nullptr, packed))
+        return 1;
+    if (b.commit()) return 1;
+    return finish(c);
+}
+
+int snpgpu_diss_sums(snpgpu_ctx *c, uint32_t *geno_sum, double *wsum, int mem)
+{
+    if (check_out(c, SNPGPU_DISS, SNPGPU_DISS, 1, "snpgpu_diss_sums")) return 1;
+    if (!geno_sum || !wsum) { set_error("snpgpu_diss_sums: NULL output"); return 1; }
+    const size_t n = out_elems(c, 1);
+    OutBuf b0(c, geno_sum, n * sizeof(uint32_t), mem), b1(c, wsum, n * sizeof(double), mem);
+    if (b0.prepare() || b1.prepare()) return 1;
+    if (launch_fin_diss(c->stream, c->geom(), (const uint32_t *)c->acc_u32.p, (const double *)c->acc_f64.p,
+                        std::ldexp(1.0, -2 * H3_HOMO_SHIFT), c->d_homo_w(), (const double *)c->homo_msum.p,
+                        (const uint32_t *)c->diss_called.p, nullptr, (uint32_t *)b0.dev, (double *)b1.dev, 1))
         return 1;
     if (b0.commit() || b1.commit()) return 1;
     return finish(c);

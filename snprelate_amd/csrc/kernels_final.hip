@@ -175,6 +175,36 @@ int launch_fin_king_homo(hipStream_t st, const PanelGeom &g, const uint32_t *acc
     return run_fin(st, g, packed, f);
 }
 
+// ---- individual dissimilarity -------------------------------------------------
+// gnrDiss, src/genIBS.cpp:652-683: SumGeno / SumAFreq, twice that on the diagonal; IEEE division, no guard (0/0 = NaN, x/0 = Inf).
+// SumAFreq = 8 x KING-homo's first weight sum, the sum of p (1 - p) over the SNPs both samples are called at (the same p,
+// genIBS.cpp:353-362), in the same form: C - M_i - M_j + B_ij with B in the fp64 plane (tables x 2^16: fscale) for blocks with missing
+// calls, C in w_const (the totals of all blocks).  That difference of sums is not exactly 0 where the true sum is: a sample never
+// called at an SNP of nonzero weight (called[] == 0) has SumAFreq = 0 exactly with every sample, so 0 / 0 = NaN as in the reference.
+// out == nullptr: the packed sums {SumGeno, SumAFreq} (diagnostics).
+struct FinDiss {
+    const uint32_t *acc; const double *facc; double fscale; const double *wc, *msum; const uint32_t *called; int64_t col0;
+    double *out; uint32_t *gsum; double *wsum;
+    __device__ void apply(int64_t rel, int64_t relf, int64_t i, int64_t j, OutPos p) const
+    {
+        const uint32_t sg = acc[rel];
+        double saf = facc[relf] * fscale + (wc ? wc[0] : 0.0);
+        if (msum) saf -= msum[i - col0] + msum[j - col0];
+        saf *= 8.0;                                                     // exact: a power of two
+        if (!called[i - col0] || !called[j - col0]) saf = 0.0;
+        if (!out) { gsum[p.a] = sg; wsum[p.a] = saf; return; }
+        const double v = (i == j) ? 2 * ((double)sg / saf) : (double)sg / saf;
+        out[p.a] = v;
+        if (p.b >= 0) out[p.b] = v;
+    }
+};
+int launch_fin_diss(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const double *facc, double fscale, const double *w_const,
+                    const double *msum, const uint32_t *called, double *out, uint32_t *geno_sum, double *wsum, int packed)
+{
+    FinDiss f{acc, facc, fscale, w_const, msum, called, g.col0, out, geno_sum, wsum};
+    return run_fin(st, g, out ? packed : 1, f);
+}
+
 // ---- GCTA / covariance ---------------------------------------------------------
 // Denom(i,j) = #polymorphic SNPs where i or j is missing = M(i,i) + M(j,j) - M(i,j) with
 // M = both-missing counts; result = num / (2 (nLocus - Denom)), no guard (genPCA.cpp:1232-1236).
@@ -435,6 +465,54 @@ __global__ __launch_bounds__(256) void het_settle_kernel(uint32_t *__restrict__ 
             if (hc) acc[4 * plane + e] += hc;
         }
     }
+}
+
+// The same for the dissimilarity counter (one plane): SumGeno = 2 S_r + 2 S_c - 2 g.g' in a block without missing calls, S = H + 2 T the
+// sample's genotype sum over those blocks; the pair kernel added - 2 g.g'.
+__global__ __launch_bounds__(256) void diss_settle_kernel(uint32_t *__restrict__ acc, int64_t rows_pad, int64_t ncols_pad,
+                                                          const uint32_t *__restrict__ het)
+{
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= ncols_pad) return;
+    const uint32_t sc = het[c] + 2u * het[ncols_pad + c];
+    for (int64_t r = blockIdx.y; r < rows_pad; r += gridDim.y) {
+        const uint32_t sr = het[r] + 2u * het[ncols_pad + r];     // panel-relative rows and columns start at the same sample
+        if (sr + sc) acc[r * ncols_pad + c] += 2u * (sr + sc);
+    }
+}
+
+// a column sample is flagged at its first call at an SNP with 0 < p < 1 (sum, num over all samples); flagged samples skip the block
+__global__ __launch_bounds__(256) void diss_called_kernel(const uint8_t *__restrict__ packed, int64_t RB, int64_t n_snp,
+                                                          const int32_t *__restrict__ sum, const int32_t *__restrict__ num, int64_t col0,
+                                                          int64_t ncols, uint32_t *__restrict__ called)
+{
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= ncols || called[j]) return;
+    const int64_t s = col0 + j, b = s >> 2;
+    const int sh = 2 * (int)(s & 3);
+    for (int64_t k = 0; k < n_snp; k++) {
+        const int32_t sk = sum[k], nk = num[k];
+        if (sk > 0 && sk < 2 * nk && ((packed[k * RB + b] >> sh) & 3) != 3) { called[j] = 1u; return; }
+    }
+}
+
+int launch_diss_called(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, const int32_t *sum, const int32_t *num,
+                       int64_t col0, int64_t ncols, uint32_t *called)
+{
+    if (n_snp <= 0 || ncols <= 0) return 0;
+    hipLaunchKernelGGL(diss_called_kernel, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, st, packed, RB, n_snp, sum, num, col0, ncols,
+                       called);
+    SNPGPU_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_diss_settle(hipStream_t st, uint32_t *acc, int64_t rows_pad, int64_t ncols_pad, uint32_t *het)
+{
+    dim3 grid((unsigned)((ncols_pad + 255) / 256), (unsigned)std::min<int64_t>(rows_pad, 4096));
+    hipLaunchKernelGGL(diss_settle_kernel, grid, dim3(256), 0, st, acc, rows_pad, ncols_pad, het);
+    SNPGPU_HIP_CHECK(hipGetLastError());
+    SNPGPU_HIP_CHECK(hipMemsetAsync(het, 0, sizeof(uint32_t) * (size_t)(2 * ncols_pad), st));
+    return 0;
 }
 
 int launch_het_settle(hipStream_t st, uint32_t *acc, int64_t plane, int64_t rows_pad, int64_t ncols_pad, uint32_t *het,

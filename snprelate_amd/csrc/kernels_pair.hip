@@ -2536,6 +2536,8 @@ __global__ __launch_bounds__(256, 1) void pair_mfma_fp4_nomiss_kernel(
                     atomicAdd(p, (uint32_t)nv);
                     atomicAdd(p + acc_plane, 0u - 2u * (uint32_t)hh);
                     atomicAdd(p + 2 * acc_plane, (uint32_t)(hh + 9 * npad - gg));
+                } else if (MODE == PM_DISS) {                     // {SumGeno - 2 (S_i + S_j)}: - 2 g.g' (+ the rank-one terms at settle time)
+                    atomicAdd(p, 0u - 2u * (uint32_t)(gg - 9 * npad));
                 } else {                                          // PM_HOMO_NOMISS: {ibs1 - H_i - H_j, 2 ibs0 - ...}
                     atomicAdd(p, 0u - 2u * (uint32_t)hh);
                     atomicAdd(p + acc_plane, (uint32_t)(hh + 9 * npad - gg));
@@ -2646,6 +2648,29 @@ template <> struct Fp4Scheme<PM_KING_HOMO> {
     {
         cnt[0] = (uint32_t)a[0]; cnt[1] = (uint32_t)(a[1] - a[2]);
     }
+};
+
+// individual dissimilarity (blocks with missing calls): a = g / 2 and b = (2 - g) / 2, both 0 where the call is missing, and the two
+// products a.b' + b.a' into ONE accumulator: the sum of g (2 - g') + (2 - g) g' / 4 over the SNPs both samples are called at, so the
+// flush's x 4 gives SumGeno itself (terms <= 1 per SNP and pair in quarters: < 2^18 per launch, exact in fp32).  With the het
+// indicator h (bit 0 = 1/2), e2 = [g == 2] and e0 = [g == 0] at bit 0: a = h | e2 << 1 (1/2 or 1), b = h | e0 << 1; h, e2, e0 are
+// one v_bitop3_b32 each, the two ORs one v_lshl_or_b32 each.  2 MFMAs per 64 SNPs (the KING-robust counters: 5); 128 x 128 per wave
+// in AGPRs (one accumulator), so that the decode of the two value types is shared by twice the MFMAs of a 128 x 64 tile.
+template <> struct Fp4Scheme<PM_DISS> {
+#ifndef FP4_DISS_TN
+#define FP4_DISS_TN 4
+#endif
+    static constexpr int NS = 2, NA = 1, NT = 2, TM = 4, TN = FP4_DISS_TN, C = 1, WPS = 1;
+    static constexpr bool NEED_X3 = false;
+    static __device__ __forceinline__ constexpr int ta(int s) { return s; }         // a b
+    static __device__ __forceinline__ constexpr int tb(int s) { return 1 - s; }     // b a
+    static __device__ __forceinline__ constexpr int acc(int) { return 0; }
+    static __device__ __forceinline__ void types(uint32_t x, uint32_t t, uint32_t, uint32_t, int (&o)[NT])         // {a, b}
+    {
+        const uint32_t M = 0x11111111u, h = M & x & ~t, e2 = M & t & ~x, e0 = M & ~(x | t);
+        o[0] = (int)(h | (e2 << 1)); o[1] = (int)(h | (e0 << 1));
+    }
+    static __device__ __forceinline__ void emit(const int *a, uint32_t *cnt) { cnt[0] = (uint32_t)a[0]; }     // {SumGeno}
 };
 
 template <int MODE> struct Fp4GenPipe {
@@ -2806,6 +2831,7 @@ bool pair_fp4_tile(int mode, int *tile_r, int *tile_c, int *wg_per_cu)
     else if (mode == PM_KING_ROBUST) { *tile_r = 64 * Fp4Scheme<PM_KING_ROBUST>::TM; *tile_c = 64 * Fp4Scheme<PM_KING_ROBUST>::TN; }
     else if (mode == PM_BETA) { *tile_r = 64 * Fp4Scheme<PM_BETA>::TM; *tile_c = 64 * Fp4Scheme<PM_BETA>::TN; }
     else if (mode == PM_KING_HOMO) { *tile_r = 64 * Fp4Scheme<PM_KING_HOMO>::TM; *tile_c = 64 * Fp4Scheme<PM_KING_HOMO>::TN; }
+    else if (mode == PM_DISS) { *tile_r = 64 * Fp4Scheme<PM_DISS>::TM; *tile_c = 64 * Fp4Scheme<PM_DISS>::TN; }
     else return false;
     if (wg_per_cu) *wg_per_cu = (mode == PM_KING_ROBUST) ? Fp4Scheme<PM_KING_ROBUST>::WPS : 1;
     return true;
@@ -2872,6 +2898,10 @@ int launch_pair_i8(hipStream_t st, int mode, const int4 *work, int n_blocks, con
         return launch_i8<PM_BETA>(st, work, n_blocks, w2, ncols_pad, n_q, n_snp, acc, acc_plane, nf, 0);
     case PM_GCTA_MISS:   // only for blocks that hold missing calls
         return launch_i8<PM_GCTA_MISS>(st, work, n_blocks, w2, ncols_pad, n_q, n_snp, acc, acc_plane, d_missing, 1);
+    case PM_DISS:        // MX-fp4 only: the general kernel for blocks with missing calls, g.g' of the two-product kernel for the others
+        if (!fp4_general || !fp4_nomiss || !d_missing) { set_error("launch_pair_i8: the dissimilarity counters need the MX-fp4 kernels"); return 1; }
+        if (launch_fp4_gen<PM_DISS>(st, work, n_blocks, w2, ncols_pad, n_q / 2, acc, acc_plane, d_missing)) return 1;
+        return launch_fp4_nomiss<PM_DISS>(st, work_nm, n_blocks_nm, w2, ncols_pad, n_q / 2, n_snp, acc, acc_plane, d_missing);
     }
     set_error("launch_pair_i8: bad mode");
     return 1;

@@ -981,12 +981,13 @@ int launch_uvcorr(hipStream_t st, const uint32_t *w8, int64_t ncols_pad, int n_d
 // 1024 mantissas of u, as uv_factor_kernel) meets a term that is f^2 of the sum.  u v IS the SNP's weight in C and M as well.
 // homo_uv_tables_kernel: one wave per SNP, both weights: tables (8-byte entries {row pair, column pair}, syrk_uv_kernel's format),
 // the effective weights {w1, w2} (x 2^-16: the tables carry 2^16 c so that (p(1-p))^2 ~ 1e-10 stays in fp16's normal range) and
-// the block totals into the context's two KING-homo scalars.
+// the block totals into the context's two KING-homo scalars.  n_w = 1 (individual dissimilarity, whose weight is 8 p (1 - p)): the first
+// weight only -- no second table, its effective weight stays 0.
 __global__ __launch_bounds__(256) void homo_uv_tables_kernel(const int32_t *__restrict__ sum, const int32_t *__restrict__ num,
                                                              int64_t n_snp, int64_t n_snp_pad, uint2 *__restrict__ lut1,
                                                              uint2 *__restrict__ lut2, double2 *__restrict__ wts,
                                                              double *__restrict__ totals,
-                                                             const unsigned long long *__restrict__ d_missing, int swap_odd)
+                                                             const unsigned long long *__restrict__ d_missing, int swap_odd, int n_w)
 {
     if (*d_missing == 0ull) return;               // blocks without missing calls: every pair gets the whole sum (build_lut_kernel)
     const int lane = threadIdx.x & 63;
@@ -1000,7 +1001,7 @@ __global__ __launch_bounds__(256) void homo_uv_tables_kernel(const int32_t *__re
     }
     uint32_t uv[2] = {0u, 0u};
     double weff[2] = {0.0, 0.0};
-    for (int t = 0; t < 2; t++) {
+    for (int t = 0; t < n_w; t++) {
         const double tt = ldexp(t == 0 ? c1 : c1 * c1, 2 * H3_HOMO_SHIFT);
         if (!(tt > 0) || tt < 1e-7) continue;                  // wave-uniform (weights below 2^-16 x 1e-7 ~ 1e-12 count as zero)
         const int e = ilogb(sqrt(tt));
@@ -1033,7 +1034,7 @@ __global__ __launch_bounds__(256) void homo_uv_tables_kernel(const int32_t *__re
         const int c0 = lane & 3, c1i = lane >> 2;
         const bool odd = (k & 1);
         const bool mine3 = odd ? (c1i == 3) : (c0 == 3);
-        for (int t = 0; t < 2; t++) {
+        for (int t = 0; t < n_w; t++) {
             uint16_t *e16 = reinterpret_cast<uint16_t *>((t == 0 ? lut1 : lut2) + (k >> 1) * 16 + lane);
             const int sw = (swap_odd && ((k >> 3) & 1)) ? 2 : 0;      // odd quarters: {column pair, row pair} (syrk_uv16_kernel)
             e16[(odd ? 1 : 0) + sw] = mine3 ? (uint16_t)(uv[t] & 0xFFFFu) : (uint16_t)0;       // row value (u)
@@ -1100,13 +1101,13 @@ __global__ __launch_bounds__(256) void homo_miss_add_kernel(const double2 *__res
 
 int launch_homo_uv(hipStream_t st, const int32_t *sum, const int32_t *num, int64_t n_snp, int64_t n_snp_pad, uint2 *lut1, uint2 *lut2,
                    double2 *wts, double *totals, const uint32_t *w8, int64_t ncols_pad, double2 *tc, double *msum,
-                   const unsigned long long *d_missing, int swap_odd)
+                   const unsigned long long *d_missing, int swap_odd, int n_w)
 {
     if (n_snp_pad <= 0) return 0;
     // tables of whole 1024-slot chunks (syrk_uv_kernel copies whole chunks): zero weights beyond the block
     const int64_t n_tab = (n_snp_pad + UV_CHS - 1) / UV_CHS * UV_CHS;
     hipLaunchKernelGGL(homo_uv_tables_kernel, dim3((unsigned)((n_tab + 3) / 4)), dim3(256), 0, st, sum, num, n_snp, n_tab, lut1, lut2, wts,
-                       totals, d_missing, swap_odd);
+                       totals, d_missing, swap_odd, n_w);
     hipLaunchKernelGGL(homo_totals_kernel, dim3(1), dim3(1024), 0, st, wts, n_tab, totals, d_missing);
     const int n_d = (int)(n_snp_pad / 8);
     const int n_chunk = (n_d + H3_LUTCH / 16 - 1) / (H3_LUTCH / 16);

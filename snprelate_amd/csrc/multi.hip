@@ -125,21 +125,22 @@ int64_t panel_scratch_bytes(int kind, int64_t n, int64_t bmax, int64_t r0)
     const int64_t np = round_up(n - r0, PANEL_ALIGN), rb = round_up(n, 256) / 4, bp = round_up(bmax, 1024);
     int64_t b = bmax * rb;                                                           // packed
     const bool pc = kind != SNPGPU_PCA_COV && kind != SNPGPU_EIGMIX, mm = kind == SNPGPU_KING_HOMO || kind == SNPGPU_GRM_GCTA ||
-                    kind == SNPGPU_PCA_COV || kind == SNPGPU_EIGMIX;
+                    kind == SNPGPU_PCA_COV || kind == SNPGPU_EIGMIX || kind == SNPGPU_DISS;
     if (pc) b += 4 * (bmax / 16 + 32) * np;                                          // w2
     if (kind == SNPGPU_GRM_GCTA) b += bmax * np / 8;                                 // mm256
     if (mm) b += 4 * (bp / 8 + 96) * np + 8 * (5 * bp / 512 + 16) * np;              // wt, tcorr
     if (kind == SNPGPU_EIGMIX) b += 4 * (bp / 8 + 96) * np;                          // wt12
     if (kind == SNPGPU_KING_HOMO) b += 16 * (bp / 256 + 16) * np + 16 * np + 2 * 64 * (bp + 2048) + 16 * (bp + 2048);   // homo_tc, homo_msum, homo_lut x 2, homo_wts
-    if (mm && kind != SNPGPU_KING_HOMO)                                              // per-SNP tables of the single-product / exact-row kernels
+    if (kind == SNPGPU_DISS) b += 16 * (bp / 256 + 16) * np + 16 * np + 64 * (bp + 2048) + 16 * (bp + 2048);            // ... one table
+    if (mm && kind != SNPGPU_KING_HOMO && kind != SNPGPU_DISS)                       // per-SNP tables of the single-product / exact-row kernels
         b += (64 + 64 + 32 + 32 + 8 + 16 + 8 * UV_QMAX) * (bp + 2048) + 16 * (bmax + 2048) + 16 * np + 8 * np;     // (uvlut, uvpace, ...)
     return b;
 }
 
 int auto_panels_per_device(int kind, int64_t n, int64_t bmax, const int32_t *devices, int nd, int passes, std::string *why, int at_least = 1)
 {
-    const double per_pair[] = {12, 20, 24, 12, 8, 32, 12};      // IBS, KING-robust, KING-homo, GCTA (8 + 4), PCA, EIGMIX (2 x 8 + ...), beta
-    const double bpe = (kind >= SNPGPU_IBS && kind <= SNPGPU_INDIV_BETA) ? per_pair[kind - SNPGPU_IBS] : 8;
+    const double per_pair[] = {12, 20, 24, 12, 8, 32, 12, 12};  // IBS, KING-robust, KING-homo, GCTA (8 + 4), PCA, EIGMIX (2 x 8 + ...), beta, dissimilarity
+    const double bpe = (kind >= SNPGPU_IBS && kind <= SNPGPU_DISS) ? per_pair[kind - SNPGPU_IBS] : 8;
     const bool eig = kind == SNPGPU_GRM_GCTA || kind == SNPGPU_PCA_COV || kind == SNPGPU_EIGMIX;
     std::vector<double> budget((size_t)nd, 0.0);
     for (int d = 0; d < nd; d++) {
@@ -894,6 +895,13 @@ int snpgpu_multi_king_homo(snpgpu_multi *m, double *k0, double *k1, int mem)
     if (need(m, SNPGPU_KING_HOMO, SNPGPU_KING_HOMO, "snpgpu_multi_king_homo")) return 1;
     void *out[2] = {k0, k1};
     return gather_slabs(m, 2, sizeof(double), out, mem, [](snpgpu_ctx *c, void **p) { return snpgpu_king_homo(c, (double *)p[0], (double *)p[1], 1, SNPGPU_DEVICE); });
+}
+
+int snpgpu_multi_diss(snpgpu_multi *m, double *out_, int mem)
+{
+    if (need(m, SNPGPU_DISS, SNPGPU_DISS, "snpgpu_multi_diss")) return 1;
+    void *out[1] = {out_};
+    return gather_slabs(m, 1, sizeof(double), out, mem, [](snpgpu_ctx *c, void **p) { return snpgpu_diss(c, (double *)p[0], 1, SNPGPU_DEVICE); });
 }
 
 int snpgpu_multi_grm_gcta(snpgpu_multi *m, double *out_, int mem)

@@ -95,7 +95,8 @@ void set_error(const std::string &msg);
 // counter sets of the bit-plane pair kernel
 enum PairMode { PM_IBS = 0, PM_KING_ROBUST = 1, PM_KING_HOMO = 2, PM_GCTA_MISS = 3, PM_BETA = 4,
                 PM_IBS_NOMISS = 5 /* int8 kernel only: IBS / KING-robust for blocks without missing calls */,
-                PM_HOMO_NOMISS = 6 /* ... KING-homo for such blocks: the same two products into its two planes */ };
+                PM_HOMO_NOMISS = 6 /* ... KING-homo for such blocks: the same two products into its two planes */,
+                PM_DISS = 7 /* individual dissimilarity: one plane, sum g (2 - g') + (2 - g) g' over the SNPs both samples are called at */ };
 constexpr int pair_mode_counters(int m) { return (m == PM_IBS || m == PM_BETA) ? 3 : m == PM_KING_ROBUST ? 5 : m == PM_KING_HOMO ? 2 : 1; }
 
 // decode-table flavours of the SYRK kernel (what z(g) is)
@@ -216,7 +217,7 @@ int launch_uvcorr(hipStream_t st, const uint32_t *w8, int64_t ncols_pad, int n_d
                   int n_kpart, double2 *tc, double *uvterm, const unsigned long long *d_missing, int nibble = 0);
 int launch_homo_uv(hipStream_t st, const int32_t *sum, const int32_t *num, int64_t n_snp, int64_t n_snp_pad, uint2 *lut1, uint2 *lut2,
                    double2 *wts, double *totals, const uint32_t *w8, int64_t ncols_pad, double2 *tc, double *msum,
-                   const unsigned long long *d_missing, int swap_odd = 0);
+                   const unsigned long long *d_missing, int swap_odd = 0, int n_w = 2);
 int launch_transpose8(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t col0,
                       int64_t ncols_pad, int n_d, uint32_t *w8, const unsigned long long *d_wide16 = nullptr,
                       int always_wide = 0, const int32_t *slot_src = nullptr, int nibble_nomiss = 0);
@@ -236,6 +237,14 @@ int launch_fin_king_robust(hipStream_t st, const PanelGeom &g, const uint32_t *a
                            double *ibs0, double *kin, int packed);
 int launch_fin_king_homo(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const double *facc, double fscale,
                          double *k0, double *k1, int packed, const double *w_const = nullptr, const double *msum = nullptr);
+// individual dissimilarity: out = SumGeno / SumAFreq (x 2 on the diagonal), or (out == nullptr) the packed sums themselves
+int launch_fin_diss(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const double *facc, double fscale, const double *w_const,
+                    const double *msum, const uint32_t *called, double *out, uint32_t *geno_sum, double *wsum, int packed);
+// rank-one terms of the dissimilarity counter of blocks without missing calls: SumGeno += 2 (S_r + S_c), S = H + 2 T; then het = 0
+int launch_diss_settle(hipStream_t st, uint32_t *acc, int64_t rows_pad, int64_t ncols_pad, uint32_t *het);
+// called[j] = 1 once column sample j is called at an SNP of this block with 0 < p < 1 (packed rows [n_snp][RB])
+int launch_diss_called(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, const int32_t *sum, const int32_t *num,
+                       int64_t col0, int64_t ncols, uint32_t *called);
 int launch_fin_gcta(hipStream_t st, const PanelGeom &g, const double *num, const uint32_t *miss,
                     const uint32_t *diag, const unsigned long long *d_nlocus, double *out, int packed,
                     const double *colterm = nullptr, const double *uvterm = nullptr);
@@ -347,6 +356,7 @@ struct snpgpu_ctx {
     bool uv_eigmix = false;      // ... for the EIGMIX numerator (weight 1: exact)
     bool homo_uv = false;        // KING-homo blocks with missing calls: weight sums = totals - per-sample missing sums + ONE fp16 product each
     snpgpu::DevBuf homo_lut[2], homo_wts, homo_tc, homo_msum, homo_work;   //     ... its tables, effective weights, per-chunk partials, M[2][ncols_pad], work list
+    snpgpu::DevBuf diss_called;  // dissimilarity: per column sample, 1 once it is called at an SNP of nonzero weight (exact zero denominators)
     int homo_blocks = 0;
     bool colterm_pending = false;  //     panel once, before a result is read (settle_colterm, api.hip)
     // accumulators

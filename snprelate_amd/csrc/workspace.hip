@@ -309,6 +309,15 @@ int snpgpu_gnrIBD_KING_Homo(int, int use_matrix, int, double *k0, double *k1)
     return snpgpu_king_homo(g.c, k0, k1, use_matrix ? 1 : 0, SNPGPU_HOST);
 }
 
+// gnrDiss, src/genIBS.cpp:652-683: always the full n x n matrix
+int snpgpu_gnrDiss(int, int, double *out)
+{
+    if (need_ws("snpgpu_gnrDiss")) return 1;
+    CtxGuard g;
+    if (run_stream(SNPGPU_DISS, 0, &g.c)) return 1;
+    return snpgpu_diss(g.c, out, 0, SNPGPU_HOST);
+}
+
 // gnrGRM method switch, src/genPCA.cpp:1633-1710
 int snpgpu_gnrGRM(int, const char *method, int use_matrix, int, double *out)
 {
