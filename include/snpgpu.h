@@ -547,6 +547,46 @@ int snpgpu_gnrIBD_MLE(const double *allele_freq, int kinship_constraint, int max
 int snpgpu_gnrIBD_LogLik(const double *afreq, const double *k0, const double *k1, double *out);
 int snpgpu_gnrIBD_LogLik_k01(const double *afreq, double k0, double k1, double *out);
 
+/* ---- (1f) population statistics: snpgdsFst and the Fst scan of snpgdsSlidingWindow ---------------------------------------------
+ * Everything gnrFst (src/genFst.cpp:170-242) needs from a SNP is 2 K integers: per population the allele count ACnt (sum of the
+ * called genotypes) and Cnt (2 x called samples) of WC84 / WH02 (:56-74, :103-120).  One pass over the 2-bit rows produces them
+ * exactly (integer arithmetic: bit-identical whatever the reduction order); the rest is fp64 on the counters, with the reference's
+ * operation order inside a SNP and sums over SNPs taken sequentially in ascending order.  A SNP where a population has no called
+ * sample has a NaN ratio and enters no sum.  (n_c of W&C84 sums Cnt^2 exactly; the reference's int product overflows beyond
+ * 23 170 called samples in a population.)
+ *   geno   rows [n_snp] of `format` (SNPGPU_GENO_PACKED2 rows are read where they lie, padding codes of the last byte ignored;
+ *          SNPGPU_GENO_U8 goes through the repack) in `mem`: host, or complete device memory of `device`.  2-bit rows in device
+ *          memory are counted by one launch; host rows and one-byte genotypes are streamed through a staging buffer in SNP blocks;
+ *          the counters of all n_snp SNPs stay on the device (8 K bytes per SNP)
+ *   pop    host int32 [n_samp], 0-based population index; n_pop = K >= 2, every population with at least one sample
+ *   method SNPGPU_FST_WC84 (Weir & Cockerham 1984) or SNPGPU_FST_WH02 (Weir & Hill 2002)
+ * Argument errors (n_pop < 2, an index outside [0, K), an empty population, an unknown method, an unsorted or out-of-range
+ * window list) are refused before any device is touched. */
+enum snpgpu_fst_method { SNPGPU_FST_WC84 = 1, SNPGPU_FST_WH02 = 2 };
+/* acnt / cnt: int32 [n_snp][n_pop] in out_mem */
+int snpgpu_pop_counts(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, const int32_t *pop, int n_pop,
+                      int32_t *acnt, int32_t *cnt, int out_mem, int device);
+/* gnrFst: fst = the ratio of sums (W&C84) / 1 - H_W / H_B of the summed H (W&H02); fst_snp: host [n_snp] or NULL, the per-SNP
+ * ratios; beta: host [n_pop][n_pop] or NULL, W&H02 only (symmetric) */
+int snpgpu_fst(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, const int32_t *pop, int n_pop, int method,
+               double *fst, double *fst_snp, double *beta, int device);
+/* the same for n_win SNP sets in CSR form (host): window w = snp_index[offsets[w] ... offsets[w + 1]), 0-based rows of geno in
+ * ascending order; offsets[0] = 0.  fst_win: host [n_win] (NaN for an empty window); beta_win: host [n_win][n_pop][n_pop] or
+ * NULL; fst_snp as above.  The genotypes are read once however the windows overlap. */
+int snpgpu_fst_windows(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, const int32_t *pop, int n_pop, int method,
+                       const int64_t *offsets, const int32_t *snp_index, int64_t n_win, double *fst_win, double *beta_win,
+                       double *fst_snp, int device);
+/* of the last call above on this thread: stats[0] ms of the counter kernel (HIP events, summed over the blocks), [1] its launches,
+ * [2] ms from the first to the last Fst kernel (per-SNP terms, window sums; the device-to-host copies of the window results that
+ * lie between the launches of a W&H02 scan included), [3] genotype bytes the counter kernel read */
+int snpgpu_pop_stats(double *stats);
+/* gnrFst(Pop, nPop, Method) on the working space's selected SNPs: pop 1-based as R passes a factor, method "W&C84" / "W&H02" */
+int snpgpu_gnrFst(const int32_t *pop, int n_pop, const char *method, double *fst, double *fst_snp, double *beta);
+/* the Fst case (FunIdx 1) of gnrSlidingWindow(FUNIdx, WinSize, Shift, Unit, WinStart, AsIs, chflag, ChrPos, Param, Verbose): the
+ * windows of one chromosome in CSR form over the working space's selected SNPs (the host computes the membership) */
+int snpgpu_gnrSlidingWindowFst(const int32_t *pop, int n_pop, const char *method, const int64_t *offsets, const int32_t *snp_index,
+                               int64_t n_win, double *fst_win, double *beta_win, double *fst_snp);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------------------
  * What THIS device's matrix pipe sustains right now: a register-only stream of one MFMA instruction (never waiting on memory,
  * two waves per SIMD) run for `seconds`, rate taken over the second half.  The kernels of this library run against the socket

@@ -32,6 +32,7 @@
 //   gpu_gnrLDpruning(StartIdx, pos_bp, slide_max_bp,             src/genLD.cpp:1014-1035 (+ Perform_LD_Pruning :807-924)
 //                    slide_max_n, LD_threshold, method,
 //                    NumThread, verbose)
+//   gpu_gnrFst(Pop, nPop, Method)                               src/genFst.cpp:170-242
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -740,6 +741,33 @@ COREARRAY_DLL_EXPORT SEXP gpu_gnrLDpruning(SEXP StartIdx, SEXP pos_bp, SEXP slid
         int *p = INTEGER(rv_ans);            // a logical vector's data are ints (TRUE = 1)
         for (size_t i = 0; i < ps.n_snp; i++) p[i] = keep[i] ? TRUE : 0;
         UNPROTECT(2);
+    COREARRAY_CATCH
+}
+
+// gnrFst(Pop, nPop, Method), src/genFst.cpp:170-242: list(Fst, per-SNP ratios[, beta]).  One pass over the working space's 2-bit rows
+// gives the exact per-population allele counters on the device; the Fst terms are fp64 in the reference's order (snpgpu_fst).
+COREARRAY_DLL_EXPORT SEXP gpu_gnrFst(SEXP Pop, SEXP nPop, SEXP Method)
+{
+    const int n_pop = Rf_asInteger(nPop);
+    const char *method = CHAR(STRING_ELT(Method, 0));
+    COREARRAY_TRY
+        const bool wh02 = strcmp(method, "W&H02") == 0;
+        if (!wh02 && strcmp(method, "W&C84") != 0) throw ErrCoreArray("%s", "'method' should be \"W&C84\" or \"W&H02\"");
+        PackedSpace ps;
+        ps.read("Fst", false, 1);
+        if (Rf_xlength(Pop) != (R_xlen_t)ps.n_samp) throw ErrCoreArray("%s", "'Pop' should have one entry per sample of the working space");
+        std::vector<int32_t> pop(ps.n_samp);
+        const int *codes = INTEGER(Pop);              // a factor's codes start at 1
+        for (size_t i = 0; i < ps.n_samp; i++) pop[i] = codes[i] - 1;
+        PROTECT(rv_ans = Rf_allocVector(VECSXP, wh02 ? 3 : 2));
+        SET_VECTOR_ELT(rv_ans, 0, Rf_allocVector(REALSXP, 1));
+        SET_VECTOR_ELT(rv_ans, 1, Rf_allocVector(REALSXP, (R_xlen_t)ps.n_snp));
+        if (wh02) SET_VECTOR_ELT(rv_ans, 2, Rf_allocMatrix(REALSXP, n_pop, n_pop));      // symmetric: either storage order
+        if (snpgpu_fst(&ps.rows[0], (int64_t)ps.n_snp, (int64_t)ps.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, &pop[0], n_pop,
+                       wh02 ? SNPGPU_FST_WH02 : SNPGPU_FST_WC84, REAL(VECTOR_ELT(rv_ans, 0)), REAL(VECTOR_ELT(rv_ans, 1)),
+                       wh02 ? REAL(VECTOR_ELT(rv_ans, 2)) : nullptr, opt_int("snpgpu.device", "SNPGPU_DEVICE", 0)))
+            gpu_fail();
+        UNPROTECT(1);
     COREARRAY_CATCH
 }
 

@@ -16,6 +16,7 @@ extern SEXP gpu_gnrIBD_LogLik(SEXP, SEXP, SEXP);
 extern SEXP gpu_gnrIBD_LogLik_k01(SEXP, SEXP, SEXP);
 extern SEXP gpu_gnrLDpruning(SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP);
 extern SEXP gpu_gnrDiss(SEXP, SEXP);
+extern SEXP gpu_gnrFst(SEXP, SEXP, SEXP);
 //
 //   table entries:
 //     { "gnrGRM",             (DL_FUNC)&gpu_gnrGRM,             5 },
@@ -31,6 +32,7 @@ extern SEXP gpu_gnrDiss(SEXP, SEXP);
 //     { "gnrIBD_LogLik_k01",  (DL_FUNC)&gpu_gnrIBD_LogLik_k01,  3 },
 //     { "gnrLDpruning",       (DL_FUNC)&gpu_gnrLDpruning,       8 },
 //     { "gnrDiss",            (DL_FUNC)&gpu_gnrDiss,            2 },
+//     { "gnrFst",             (DL_FUNC)&gpu_gnrFst,             3 },
 //
 // The CPU bodies (gnrGRM ... in src/genPCA.cpp, src/genIBS.cpp, src/genKING.cpp) may stay in the package as
 // unregistered functions -- e.g. behind options(snpgpu.enable = FALSE) with a second table -- or be deleted together

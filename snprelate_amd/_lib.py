@@ -50,7 +50,10 @@ EXPORTS = [
     "snpgpu_gnrIBD_LogLik_k01", "snpgpu_diag_fp64_rate",
     "snpgpu_ld_prune", "snpgpu_ld_prune_bits", "snpgpu_gnrLDpruning",
     "snpgpu_diss", "snpgpu_diss_sums", "snpgpu_gnrDiss", "snpgpu_multi_diss",
+    "snpgpu_pop_counts", "snpgpu_fst", "snpgpu_fst_windows", "snpgpu_pop_stats", "snpgpu_gnrFst", "snpgpu_gnrSlidingWindowFst",
 ]
+FST_WC84, FST_WH02 = 1, 2
+FST_METHODS = ("W&C84", "W&H02")
 
 
 class SnpGpuError(RuntimeError):
@@ -239,6 +242,12 @@ def lib():
     L.snpgpu_ld_prune_bits.argtypes = [vp, i64, i64, c_int, c_int, i64, i64, dbl, c_int, vp, ctypes.POINTER(Opts),
                                        ctypes.POINTER(LDPruneInfo)]
     L.snpgpu_gnrLDpruning.argtypes = [i64, vp, i32, i32, dbl, c_int, c_int, c_int, vp]
+    L.snpgpu_pop_counts.argtypes = [vp, i64, i64, c_int, c_int, vp, c_int, vp, vp, c_int, c_int]
+    L.snpgpu_fst.argtypes = [vp, i64, i64, c_int, c_int, vp, c_int, c_int, vp, vp, vp, c_int]
+    L.snpgpu_fst_windows.argtypes = [vp, i64, i64, c_int, c_int, vp, c_int, c_int, vp, vp, i64, vp, vp, vp, c_int]
+    L.snpgpu_pop_stats.argtypes = [vp]
+    L.snpgpu_gnrFst.argtypes = [vp, c_int, ctypes.c_char_p, vp, vp, vp]
+    L.snpgpu_gnrSlidingWindowFst.argtypes = [vp, c_int, ctypes.c_char_p, vp, vp, i64, vp, vp, vp]
     _lib = L
     return L
 
@@ -928,6 +937,68 @@ def ibd_mle(geno, n_samp, allele_freq=None, max_niter=1000, reltol=float(np.sqrt
                                int(bool(coeff_correct)), int(rows[0]), int(rows[1]), _ptr(k0), _ptr(k1), _ptr(nit), _ptr(af),
                                HOST, int(device)))
     return k0, k1, nit, af
+
+
+def _pop_input(geno, n_samp, fmt, n_snp, pop):
+    """(pointer, n_snp, format, memory kind, keep-alive, pop int32) for host rows (numpy) or device rows (an int address)"""
+    n_samp = int(n_samp)
+    p = np.ascontiguousarray(pop, dtype=np.int32)
+    if p.shape != (n_samp,):
+        raise ValueError("pop should hold one population index per sample")
+    if isinstance(geno, int):
+        if n_snp is None:
+            raise ValueError("device rows need n_snp")
+        return ctypes.c_void_p(geno), int(n_snp), GENO_PACKED2 if fmt is None else int(fmt), DEVICE, None, p
+    g = np.ascontiguousarray(geno, dtype=np.uint8)
+    if fmt is None:
+        fmt = GENO_U8 if g.shape[1] == n_samp else GENO_PACKED2
+    exp = n_samp if fmt == GENO_U8 else (n_samp + 3) // 4
+    if g.ndim != 2 or g.shape[1] != exp:
+        raise ValueError("genotype rows have the wrong shape")
+    return _ptr(g), g.shape[0], int(fmt), HOST, g, p
+
+
+def pop_counts(geno, n_samp, pop, n_pop, fmt=None, n_snp=None, device=0):
+    """(ACnt, Cnt) int32 [n_snp][n_pop] of snpgpu_pop_counts: per SNP and population the sum of the called genotypes and twice
+    the number of called samples.  geno: host rows (numpy, U8 or PACKED2) or a device address (int) with n_snp (and fmt);
+    pop: 0-based population index per sample."""
+    ptr, n, fmt, mem, _keep, p = _pop_input(geno, n_samp, fmt, n_snp, pop)
+    a = np.empty((n, int(n_pop)), np.int32)
+    c = np.empty((n, int(n_pop)), np.int32)
+    check(lib().snpgpu_pop_counts(ptr, n, int(n_samp), fmt, mem, _ptr(p), int(n_pop), _ptr(a), _ptr(c), HOST, int(device)))
+    return a, c
+
+
+def fst(geno, n_samp, pop, n_pop, method=FST_WC84, fmt=None, n_snp=None, device=0):
+    """snpgpu_fst: (Fst, FstSNP [n_snp], Beta [n_pop][n_pop] or None)"""
+    ptr, n, fmt, mem, _keep, p = _pop_input(geno, n_samp, fmt, n_snp, pop)
+    f = ctypes.c_double(0)
+    per = np.empty(n, np.float64)
+    beta = np.empty((int(n_pop), int(n_pop)), np.float64) if int(method) == FST_WH02 else None
+    check(lib().snpgpu_fst(ptr, n, int(n_samp), fmt, mem, _ptr(p), int(n_pop), int(method), ctypes.byref(f), _ptr(per), _ptr(beta),
+                           int(device)))
+    return f.value, per, beta
+
+
+def fst_windows(geno, n_samp, pop, n_pop, offsets, snp_index, method=FST_WC84, fmt=None, n_snp=None, device=0):
+    """snpgpu_fst_windows: (Fst per window, FstSNP [n_snp], Beta [n_win][n_pop][n_pop] or None) for CSR windows"""
+    ptr, n, fmt, mem, _keep, p = _pop_input(geno, n_samp, fmt, n_snp, pop)
+    off = np.ascontiguousarray(offsets, np.int64)
+    idx = np.ascontiguousarray(snp_index, np.int32)
+    n_win = len(off) - 1
+    f = np.empty(max(n_win, 0), np.float64)
+    per = np.empty(n, np.float64)
+    beta = np.empty((max(n_win, 0), int(n_pop), int(n_pop)), np.float64) if int(method) == FST_WH02 else None
+    check(lib().snpgpu_fst_windows(ptr, n, int(n_samp), fmt, mem, _ptr(p), int(n_pop), int(method), _ptr(off), _ptr(idx), n_win,
+                                   _ptr(f), _ptr(beta), _ptr(per), int(device)))
+    return f, per, beta
+
+
+def pop_stats():
+    """(counter kernel ms, its launches, Fst kernels ms, genotype bytes read) of the last pop_counts / fst call on this thread"""
+    s = np.zeros(4, np.float64)
+    check(lib().snpgpu_pop_stats(_ptr(s)))
+    return float(s[0]), int(s[1]), float(s[2]), float(s[3])
 
 
 def ibd_mle_stats():

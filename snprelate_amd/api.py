@@ -20,6 +20,8 @@ INTEGRATION.md):
     snpgdsIBDMLELogLik            R/IBD.R:162-205
     snpgdsLDpruning               R/LD.R:100-243   (LD-based SNP pruning)
     snpgdsDiss                    R/IBD.R:432-450  (individual dissimilarity)
+    snpgdsFst                     R/IBD.R:756-830  (fixation index, W&C84 / W&H02)
+    snpgdsSlidingWindow           R/AllUtilities.R:1998-2239 (window scan of Fst / allele frequencies / a callable)
 
 All arithmetic runs on the MI355X through libsnpgpu.so (`_lib`); there is no
 CPU fallback.  R's ``NULL`` is ``None``, ``NaN`` is ``float('nan')``; R lists
@@ -850,3 +852,329 @@ def snpgdsLDpruning(gdsobj, sample_id=None, snp_id=None, autosome_only=True, rem
     if verbose:
         print("%s markers are selected in total." % _pretty(ntotal))
     return res
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# population statistics: snpgdsFst (R/IBD.R:756-830) and snpgdsSlidingWindow (R/AllUtilities.R:1998-2239)
+FST_METHODS = _lib.FST_METHODS
+SLIDE_UNITS = ("basepair", "locus")
+SLIDE_AS_IS = ("list", "numeric", "array")
+SLIDE_WITH_ID = ("snp.id", "snp.id.in.window", "none")
+SLIDE_FUNS = ("snpgdsFst", "snpgdsSNPRateFreq")
+
+
+def _match_arg(value, choices, name):
+    """match.arg: NULL or the whole default vector selects the first choice"""
+    if value is None or (isinstance(value, (tuple, list)) and tuple(value) == tuple(choices)):
+        return choices[0]
+    if isinstance(value, str) and value in choices:
+        return value
+    raise ValueError("'%s' should be one of %s" % (name, ", ".join('"%s"' % c for c in choices)))
+
+
+def _working_sample_ids(gdsobj, sample_id):
+    """ws$sample.id of .InitFile2: the file's samples that are selected, in FILE order"""
+    ids = np.asarray(gdsobj.sample_id)
+    if sample_id is None:
+        return ids
+    return ids[np.isin(ids, np.asarray(sample_id))]
+
+
+def _param_fst(sample_id, population, method, ws_sample_id):
+    """.paramFst (R/IBD.R:756-795) without its verbose lines: `population` is any sequence of labels, its levels the sorted unique
+    labels (as factor()); returns the 1-based codes in working sample order, the levels, their sizes and the method."""
+    method = _match_arg(method, FST_METHODS, "method")
+    if population is None or isinstance(population, (str, bytes)) or not hasattr(population, "__len__"):
+        raise TypeError("is.factor(population) is not TRUE")
+    labels = list(population)
+    na = [lab is None or (isinstance(lab, (float, np.floating)) and math.isnan(lab)) for lab in labels]
+    levels = sorted(set(lab for lab, m in zip(labels, na) if not m))
+    if sample_id is None:
+        if len(labels) != len(ws_sample_id):
+            raise ValueError("The length of 'population' should be the number of samples in the GDS file.")
+    else:
+        want = list(np.asarray(sample_id))
+        if len(labels) != len(want):
+            raise ValueError("The length of 'population' should be the same as the length of 'sample.id'.")
+        where = {}
+        for i, s in enumerate(want):
+            where.setdefault(s, i)                       # match(): the first occurrence
+        pos = [where[s] for s in list(ws_sample_id)]
+        labels = [labels[i] for i in pos]
+        na = [na[i] for i in pos]
+    if any(na):
+        raise ValueError("'population' should not have missing values!")
+    if len(levels) <= 1:
+        raise ValueError("There should be at least two populations!")
+    code = {lab: i + 1 for i, lab in enumerate(levels)}
+    codes = np.array([code[lab] for lab in labels], np.int32)
+    sizes = np.bincount(codes, minlength=len(levels) + 1)[1:]
+    if (sizes < 1).any():
+        raise ValueError("Each population should have at least one individual.")
+    return dict(population=codes, npop=len(levels), method=method, levels=levels, sizes=sizes)
+
+
+def _print_param_fst(v):
+    print("Method: Weir & Cockerham, 1984" if v["method"] == "W&C84" else "Method: Weir & Hill, 2002")
+    print("# of Populations: %d\n    %s" % (v["npop"], ", ".join("%s (%d)" % (lv, n) for lv, n in zip(v["levels"], v["sizes"]))))
+
+
+def snpgdsFst(gdsobj, population, method="W&C84", sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True,
+              maf=float("nan"), missing_rate=0.01, with_id=False, verbose=True, device=0):
+    """Fixation index (R/IBD.R:797-830 -> gnrFst, src/genFst.cpp:170-242): dict(Fst, MeanFst, FstSNP[, Beta, Beta_levels]
+    [, sample_id, snp_id]).  `population`: one label per sample of the file, or per entry of `sample_id` (re-ordered to the working
+    sample order as .paramFst does); its levels are the sorted unique labels.  method "W&C84" (Weir & Cockerham 1984) or "W&H02"
+    (Weir & Hill 2002, with the K x K matrix Beta whose rows / columns are Beta_levels).  The per-population allele counters are
+    exact integers from one pass over the genotypes on the GPU (snpgpu_pop_counts); the Fst terms are fp64 in the reference's
+    operation order."""
+    if not isinstance(gdsobj, GenoFile) and not hasattr(gdsobj, "packed"):
+        raise TypeError("'gdsobj' should be a SNP GDS object (snpgdsOpen / GenoFile)")
+    v = _param_fst(sample_id, population, method, _working_sample_ids(gdsobj, sample_id))
+    ws = _init_file2("Fst estimation on genotypes:", gdsobj, sample_id, snp_id, autosome_only, remove_monosnp, maf, missing_rate,
+                     1, verbose, device)
+    if verbose:
+        _print_param_fst(v)
+    k = v["npop"]
+    fst = ctypes.c_double(0)
+    per = np.empty(ws["n_snp"], np.float64)
+    beta = np.empty((k, k), np.float64) if v["method"] == "W&H02" else None
+    _lib.check(_lib.lib().snpgpu_gnrFst(_lib._ptr(v["population"]), k, v["method"].encode(), ctypes.byref(fst), _lib._ptr(per),
+                                        _lib._ptr(beta)))
+    rv = dict(sample_id=ws["sample_id"], snp_id=ws["snp_id"]) if with_id else {}
+    rv["Fst"] = fst.value
+    ok = ~np.isnan(per)
+    rv["MeanFst"] = float(per[ok].mean()) if ok.any() else float("nan")
+    rv["FstSNP"] = per
+    if beta is not None:
+        rv["Beta"] = beta
+        rv["Beta_levels"] = list(v["levels"])
+    return rv
+
+
+def sliding_num_win(start, end, winsize, shift):
+    """SlidingNumWin (src/genSlideWin.cpp:78-85): window starts start, start + shift, ... <= end - winsize, plus one"""
+    e = end - winsize
+    return (0 if start > e else (e - start) // shift + 1) + 1
+
+
+def _window_members(lo_vals, key, winsize):
+    """CSR membership of the windows lo <= key < lo + winsize in ascending SNP index order; key: one integer per SNP"""
+    order = np.argsort(key, kind="stable")
+    skey = key[order]
+    a = np.searchsorted(skey, lo_vals, side="left")
+    b = np.searchsorted(skey, lo_vals + winsize, side="left")
+    offsets = np.zeros(len(lo_vals) + 1, np.int64)
+    np.cumsum(b - a, out=offsets[1:])
+    idx = np.empty(int(offsets[-1]), np.int32)
+    in_order = bool((order[1:] > order[:-1]).all()) if len(order) > 1 else True
+    for w in range(len(lo_vals)):
+        seg = order[a[w]:b[w]]
+        idx[offsets[w]:offsets[w + 1]] = seg if in_order else np.sort(seg)
+    return offsets, idx
+
+
+def _finite_mean(x):
+    """GetMean (src/genSlideWin.cpp:61-75): the mean of the finite values, summed in order; 0 / 0 without any"""
+    f = x[np.isfinite(x)]
+    return float(np.cumsum(f)[-1]) / len(f) if len(f) else float("nan")
+
+
+def snpgdsSlidingWindow(gdsobj, sample_id=None, snp_id=None, FUN=None, winsize=100000, shift=10000, unit="basepair", winstart=None,
+                        autosome_only=False, remove_monosnp=True, maf=float("nan"), missing_rate=float("nan"), as_is="list",
+                        with_id="snp.id", num_thread=1, verbose=True, device=0, **kwargs):
+    """Sliding-window scan (R/AllUtilities.R:1998-2239, gnrSlidingWindow src/genSlideWin.cpp:101-327): a dict with sample_id,
+    (snp_id,) and per chromosome -- in order of first appearance, 0 / "" left out, SNPs with a position <= 0 dropped -- the keys
+    "chr<ch>.val", "chr<ch>.num" (SNPs per window), "chr<ch>.pos" (mean position, NaN for an empty window) and "chr<ch>.posrange".
+    Windows: SlidingNumWin of them, starting at `winstart` (None: the first position / the first SNP; a scalar; or one value per
+    chromosome) and `shift` apart, half-open x <= pos < x + winsize (unit "basepair") or index windows (unit "locus").
+
+    FUN="snpgdsFst" (population=, method= as keyword arguments): every window's Fst from ONE pass over the chromosome's genotypes
+      (snpgpu_gnrSlidingWindowFst: exact per-population counters, window sums on the device).  as_is "numeric": the window's Fst
+      (NaN for an empty window); "list": [Fst, FstSNP of the window's SNPs(, Beta)] per window, None for an empty one -- the
+      reference's unnamed gnrFst list.  as_is "array" raises NotImplementedError: the reference fills it from the per-SNP ratio
+      vector at stride npop + 1 instead of from Beta and reads past its end in small windows, so there is no defined result.
+    FUN="snpgdsSNPRateFreq": window means of the finite per-SNP allele frequency / minor allele frequency / missing rate;
+      "list": the window's three per-SNP vectors, "numeric": the mean MAF, "array": 3 x windows.
+    FUN callable: the host loop of the R function, FUN(sample_id, snp_ids, positions, **kwargs) per window, keys "chr<ch>" (values),
+      ".num", ".pos", ".posrange" and, with with_id="snp.id.in.window", ".snpid".  As in R, basepair windows then start at the first
+      position whatever `winstart` says (it only enters the window count).  One deviation: a locus window running past the last
+      SNP passes only the SNPs that exist (R passes NA ids), with .num = winsize and .pos = NaN as R's NA indexing gives.
+    shift must be positive (the reference would not terminate otherwise).  The argument checks of the R function run before the
+    device is used; of a `winstart` with one value per chromosome only "more values than the file has chromosomes" can be known
+    then -- the chromosome set is that of the SNPs the device-side filter (remove_monosnp, maf, missing_rate) keeps, so any other
+    wrong length is reported after the filter, as in R.  With FUN="snpgdsFst" keyword arguments other than population / method
+    are ignored, as R's list(...) lookup ignores them."""
+    # the R function's argument checks, before anything reaches the device
+    if not _is_number(winsize):
+        raise TypeError("is.numeric(winsize) is not TRUE")
+    if not _is_number(shift):
+        raise TypeError("is.numeric(shift) is not TRUE")
+    unit = _match_arg(unit, SLIDE_UNITS, "unit")
+    as_is = _match_arg(as_is, SLIDE_AS_IS, "as.is")
+    with_id = _match_arg(with_id, SLIDE_WITH_ID, "with.id")
+    if not (math.isfinite(winsize) and math.isfinite(shift)) or abs(winsize) >= 2 ** 31 or abs(shift) >= 2 ** 31:
+        raise ValueError("is.finite(winsize) & is.finite(shift) is not TRUE")
+    winsize, shift = int(winsize), int(shift)
+    if shift <= 0:
+        raise ValueError("'shift' should be positive")
+    if winstart is not None:
+        ok = _is_number(winstart) or (isinstance(winstart, (list, tuple, np.ndarray)) and np.ndim(winstart) == 1 and
+                                      all(_is_number(x) for x in winstart))
+        if not ok:
+            raise TypeError("is.null(winstart) | (is.numeric(winstart) & is.vector(winstart)) is not TRUE")
+        winstart = [winstart] if _is_number(winstart) else list(winstart)
+        if not all(math.isfinite(x) for x in winstart):
+            raise ValueError("all(is.finite(winstart)) is not TRUE")
+        winstart = [int(x) for x in winstart]
+    if callable(FUN):
+        if FUN is snpgdsFst:
+            raise ValueError('Please use `FUN="snpgdsFst"` instead.')
+        if FUN is snpgdsSNPRateFreq:
+            raise ValueError('Please use `FUN="snpgdsSNPRateFreq"` instead.')
+        fun_idx = 0
+    elif isinstance(FUN, str):
+        if FUN not in SLIDE_FUNS:
+            raise ValueError("'FUN' should be one of %s." % ",".join(SLIDE_FUNS))
+        fun_idx = SLIDE_FUNS.index(FUN) + 1
+    else:
+        raise TypeError("'FUN' should be a function, or a character.")
+    if not isinstance(gdsobj, GenoFile) and not hasattr(gdsobj, "packed"):
+        raise TypeError("'gdsobj' should be a SNP GDS object (snpgdsOpen / GenoFile)")
+    position = getattr(gdsobj, "snp_position", None)
+    if position is None:
+        raise ValueError("GDS node 'snp.position' not found")
+    param = None
+    if fun_idx == 1:
+        if as_is == "array":
+            raise NotImplementedError(
+                'snpgdsSlidingWindow(FUN="snpgdsFst", as.is="array") has no defined result: the reference fills the array from the '
+                "per-SNP ratio vector at stride npop + 1 (src/genSlideWin.cpp:284-292), not from Beta, and reads past its end in "
+                'small windows; use as.is="list" or "numeric"')
+        param = _param_fst(sample_id, kwargs.get("population"), kwargs.get("method"), _working_sample_ids(gdsobj, sample_id))
+    elif fun_idx == 2 and kwargs:
+        raise ValueError("Unused additional parameters '...'.")
+    total_ids = np.asarray(gdsobj.snp_id)
+    chrom = np.asarray(gdsobj.snp_chromosome)
+    numeric_chr = np.issubdtype(chrom.dtype, np.number)
+
+    def chrom_set(flag):
+        c = chrom[flag]
+        _, first = np.unique(c, return_index=True)
+        return [x for x in c[np.sort(first)] if not (x == 0 if numeric_chr else x == "")]
+
+    placed = np.asarray(position) > 0
+    if winstart is not None and len(winstart) != 1 and len(winstart) > len(chrom_set(placed)):
+        raise ValueError("'winstart' should be specified according to the chromosome set (%s)" %
+                         ",".join(str(c) for c in chrom_set(placed)))
+
+    ws = _init_file2("Sliding Window Analysis:", gdsobj, sample_id, snp_id, autosome_only, remove_monosnp, maf, missing_rate,
+                     num_thread, verbose, device)
+    if verbose:
+        print("    window size: %d, shift: %d%s" % (winsize, shift, " (basepair)" if unit == "basepair" else " (locus index)"))
+        if param is not None:
+            _print_param_fst(param)
+    ans = dict(sample_id=ws["sample_id"])
+    if with_id in ("snp.id", "snp.id.in.window"):
+        ans["snp_id"] = ws["snp_id"]
+    in_ws = np.isin(total_ids, ws["snp_id"])
+    snp_flag = in_ws & placed
+    chrset = chrom_set(snp_flag)
+    if winstart is not None and len(winstart) != 1 and len(winstart) != len(chrset):
+        raise ValueError("'winstart' should be specified according to the chromosome set (%s)" % ",".join(str(c) for c in chrset))
+    if verbose:
+        print("Chromosome Set: %s" % ",".join(str(c) for c in chrset))
+    L = _lib.lib()
+    for ci, ch in enumerate(chrset):
+        chflag = snp_flag & (chrom == ch)
+        sid = total_ids[chflag]
+        chpos = np.asarray(position)[chflag].astype(np.int64)
+        winst = None if winstart is None else winstart[0 if len(winstart) == 1 else ci]
+        n_chr = len(chpos)
+        rg = (int(chpos.min()), int(chpos.max()))
+        key = "chr%s" % ch
+        if fun_idx == 0:
+            if unit == "basepair":
+                n = sliding_num_win(rg[0] if winst is None else winst, rg[1], winsize, shift)
+            else:
+                n = sliding_num_win(1 if winst is None else winst, n_chr, winsize, shift)
+            if verbose:
+                print("%s, Chromosome %s (%d SNPs), %d windows" % (time.ctime(), ch, n_chr, n))
+            rvlist = [None] * n if as_is == "list" else np.zeros(n, np.float64)
+            nlist, poslist, sidlist = np.zeros(n, np.int32), np.zeros(n, np.float64), [None] * n
+            x = rg[0] if unit == "basepair" else 1
+            for i in range(n):
+                if unit == "basepair":
+                    k = (x <= chpos) & (chpos < x + winsize)
+                    ssid, ppos = sid[k], chpos[k]
+                    nlist[i] = len(ppos)
+                    poslist[i] = ppos.mean() if len(ppos) else float("nan")
+                else:
+                    lo, hi = max(x - 1, 0), max(min(x - 1 + winsize, n_chr), 0)
+                    ssid, ppos = sid[lo:hi], chpos[lo:hi]
+                    nlist[i] = winsize
+                    poslist[i] = ppos.mean() if (len(ppos) == winsize and x >= 1) else float("nan")
+                v = FUN(ans["sample_id"], ssid, ppos, **kwargs)
+                if as_is == "list":
+                    rvlist[i] = v
+                else:
+                    rvlist[i] = float(np.asarray(v, np.float64).reshape(-1)[0])
+                sidlist[i] = ssid
+                x += shift
+            ans[key] = rvlist
+            ans[key + ".num"] = nlist
+            ans[key + ".pos"] = poslist
+            ans[key + ".posrange"] = np.array(rg, np.int32)
+            if with_id == "snp.id.in.window":
+                ans[key + ".snpid"] = sidlist
+            continue
+
+        # gnrSlidingWindow
+        if unit == "basepair":
+            start, end, wkey = (rg[0] if winst is None else winst), rg[1], chpos
+        else:
+            start, end, wkey = (0 if winst is None else winst - 1), n_chr - 1, np.arange(n_chr, dtype=np.int64)
+        n_win = sliding_num_win(start, end, winsize, shift)
+        if verbose:
+            print("%s, Chromosome %s (%d SNPs), %d windows" % (time.ctime(), ch, n_chr, n_win))
+        offsets, idx = _window_members(start + shift * np.arange(n_win, dtype=np.int64), wkey, winsize)
+        num = np.diff(offsets).astype(np.int32)
+        psum = np.concatenate([[0.0], np.cumsum(chpos[idx].astype(np.float64))])       # integers: exact in any order
+        with np.errstate(invalid="ignore", divide="ignore"):
+            pos = np.where(num > 0, (psum[offsets[1:]] - psum[offsets[:-1]]) / np.maximum(num, 1), np.nan)
+        rows = np.ascontiguousarray(ws["packed"][chflag[in_ws]])
+        _lib.check(L.snpgpu_ws_set_geno(_lib._ptr(rows), n_chr, ws["n_samp"], _lib.GENO_PACKED2, int(device)))
+        if fun_idx == 1:
+            k = param["npop"]
+            fw = np.empty(n_win, np.float64)
+            per = np.empty(n_chr, np.float64)
+            want_beta = param["method"] == "W&H02" and as_is == "list"
+            beta = np.empty((n_win, k, k), np.float64) if want_beta else None
+            _lib.check(L.snpgpu_gnrSlidingWindowFst(_lib._ptr(param["population"]), k, param["method"].encode(), _lib._ptr(offsets),
+                                                    _lib._ptr(idx), n_win, _lib._ptr(fw), _lib._ptr(beta), _lib._ptr(per)))
+            if as_is == "numeric":
+                val = np.where(num > 0, fw, np.nan)
+            else:
+                val = [None] * n_win
+                for w in range(n_win):
+                    if num[w] > 0:
+                        val[w] = [float(fw[w]), per[idx[offsets[w]:offsets[w + 1]]]] + ([beta[w]] if want_beta else [])
+        else:
+            af, mf, mr = (np.empty(n_chr, np.float64) for _ in range(3))
+            _lib.check(L.snpgpu_ws_snp_rate_freq(_lib._ptr(af), _lib._ptr(mf), _lib._ptr(mr)))
+            seg = [idx[offsets[w]:offsets[w + 1]] for w in range(n_win)]
+            if as_is == "list":
+                val = [[af[s], mf[s], mr[s]] if len(s) else None for s in seg]
+            elif as_is == "numeric":
+                val = np.array([_finite_mean(mf[s]) if len(s) else np.nan for s in seg], np.float64)
+            else:
+                val = np.full((3, n_win), np.nan)
+                for w, s in enumerate(seg):
+                    if len(s):
+                        val[:, w] = (_finite_mean(af[s]), _finite_mean(mf[s]), _finite_mean(mr[s]))
+        ans[key + ".val"] = val
+        ans[key + ".num"] = num
+        ans[key + ".pos"] = pos
+        ans[key + ".posrange"] = np.array(rg, np.int32)
+    if verbose:
+        print("%s\tDone." % time.ctime())
+    return ans

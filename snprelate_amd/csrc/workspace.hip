@@ -1173,6 +1173,43 @@ int snpgpu_gnrIBD_LogLik(const double *afreq, const double *k0, const double *k1
                              0, 0, out, nullptr, SNPGPU_HOST, g_ws.device);
 }
 
+// gnrFst(Pop, nPop, Method), src/genFst.cpp:170-242, and the Fst case of gnrSlidingWindow, src/genSlideWin.cpp:101-327, on the
+// selected SNPs.  What does not depend on the working space is checked first, so that it is refused without a device.
+static int ws_fst(const char *fn, const int32_t *pop, int n_pop, const char *method, const int64_t *offsets, const int32_t *snp_index,
+                  int64_t n_win, double *fst_win, double *beta_win, double *fst_snp)
+{
+    if (n_pop < 2) { set_error(std::string(fn) + ": There should be at least two populations!"); return 1; }
+    if (!pop || !fst_win) { set_error(std::string(fn) + ": NULL argument"); return 1; }
+    int code = 0;
+    if (method && strcmp(method, "W&C84") == 0) code = SNPGPU_FST_WC84;
+    else if (method && strcmp(method, "W&H02") == 0) code = SNPGPU_FST_WH02;
+    else { set_error(std::string(fn) + ": 'method' should be one of \"W&C84\", \"W&H02\""); return 1; }
+    if (need_ws(fn)) return 1;
+    const int64_t L = (int64_t)g_ws.sel.size();
+    if (L < 1) { set_error(std::string(fn) + ": no SNP in the working dataset"); return 1; }
+    std::vector<int32_t> pop0((size_t)g_ws.n_samp);
+    for (int64_t i = 0; i < g_ws.n_samp; i++) pop0[(size_t)i] = pop[i] - 1;     // R's factor codes start at 1
+    std::vector<uint8_t> buf;
+    gather_block(0, L, buf);
+    if (!offsets)
+        return snpgpu_fst(buf.data(), L, g_ws.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, pop0.data(), n_pop, code, fst_win, fst_snp,
+                          beta_win, g_ws.device);
+    return snpgpu_fst_windows(buf.data(), L, g_ws.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, pop0.data(), n_pop, code, offsets, snp_index,
+                              n_win, fst_win, beta_win, fst_snp, g_ws.device);
+}
+
+int snpgpu_gnrFst(const int32_t *pop, int n_pop, const char *method, double *fst, double *fst_snp, double *beta)
+{
+    return ws_fst("snpgpu_gnrFst", pop, n_pop, method, nullptr, nullptr, 1, fst, beta, fst_snp);
+}
+
+int snpgpu_gnrSlidingWindowFst(const int32_t *pop, int n_pop, const char *method, const int64_t *offsets, const int32_t *snp_index,
+                               int64_t n_win, double *fst_win, double *beta_win, double *fst_snp)
+{
+    if (!offsets) { set_error("snpgpu_gnrSlidingWindowFst: offsets is NULL"); return 1; }
+    return ws_fst("snpgpu_gnrSlidingWindowFst", pop, n_pop, method, offsets, snp_index, n_win, fst_win, beta_win, fst_snp);
+}
+
 int snpgpu_gnrIBD_LogLik_k01(const double *afreq, double k0, double k1, double *out)
 {
     std::vector<uint8_t> buf;

@@ -57,7 +57,7 @@ class GenoFile:
     """
 
     def __init__(self, genotype=None, sample_id=None, snp_id=None, snp_chromosome=None,
-                 packed=None, n_samp=None, snp_position=None):
+                 packed=None, n_samp=None, snp_position=None, sample_annot=None):
         if packed is None:
             genotype = np.asarray(genotype, dtype=np.uint8)
             n_snp, n_samp = genotype.shape
@@ -77,6 +77,8 @@ class GenoFile:
         # snp.position (int32 base pairs), read by snpgdsLDpruning; None when the file has no such node
         self.snp_position = None if snp_position is None else np.asarray(snp_position, np.int32)
         assert self.snp_position is None or len(self.snp_position) == self.n_snp
+        # columns of the sample.annot folder this reader can decode (e.g. "pop.group"), one entry per sample
+        self.sample_annot = {} if sample_annot is None else dict(sample_annot)
         # snpgdsOption() defaults (R/AllUtilities.R:1910-1991)
         self.autosome_start, self.autosome_end = 1, 22
         assert len(self.sample_id) == self.n_samp and len(self.snp_id) == self.n_snp
@@ -176,6 +178,20 @@ def _node_coder(head):
     return text
 
 
+def _sample_annot(columns, raw):
+    """The text columns of the sample.annot folder, decoded like sample.id (NUL-separated labels); `columns`: (name, descriptor
+    stream id) pairs, raw(id) -> (dims, bytes).  Columns of another type are left out."""
+    out = {}
+    for name, sid in columns:
+        try:
+            dims, b = raw(sid)
+        except (ValueError, KeyError, IndexError, struct.error, zlib.error):
+            continue
+        if len(dims) == 1 and b.count(b"\x00") == dims[0]:
+            out[name] = np.array([x.decode("latin1") for x in b.split(b"\x00")[:dims[0]]])
+    return out
+
+
 def open_gds(path):
     """Read a SNPRelate-written SNP GDS file with an uncompressed bit2
     ``genotype`` node into a :class:`GenoFile`."""
@@ -224,7 +240,14 @@ def open_gds(path):
     else:
         # snp.order: dims = [n_samp][n_snp]
         geno = np.ascontiguousarray(g.T)
-    return GenoFile(genotype=geno, sample_id=sample_id, snp_id=snp_id, snp_chromosome=chrom, snp_position=position)
+    annot = {}
+    if "sample.annot" in entries:
+        def raw_id(sid):
+            dims, dsid, is_zip, _ = _node_info(streams[sid])
+            return dims, (zlib.decompress(streams[dsid]) if is_zip else streams[dsid])
+        annot = _sample_annot(_dir_entries(streams[entries["sample.annot"]]), raw_id)
+    return GenoFile(genotype=geno, sample_id=sample_id, snp_id=snp_id, snp_chromosome=chrom, snp_position=position,
+                    sample_annot=annot)
 
 
 # ---------------------------------------------------------------------------
@@ -316,8 +339,10 @@ class GenoStream:
 
     `blocks(block_snps, buffers=[b0, b1])` fills caller-provided (page-locked) buffers in turn instead of allocating."""
 
-    def __init__(self, path, sample_id, snp_id, snp_chromosome, dims, extents, length, zipped, sample_order):
+    def __init__(self, path, sample_id, snp_id, snp_chromosome, dims, extents, length, zipped, sample_order, snp_position=None,
+                 sample_annot=None):
         self.path, self.sample_id, self.snp_id, self.snp_chromosome = path, sample_id, snp_id, snp_chromosome
+        self.snp_position, self.sample_annot = snp_position, ({} if sample_annot is None else dict(sample_annot))
         self._dims, self._extents, self._length, self._zipped = dims, extents, length, zipped
         self.sample_order = sample_order
         self.n_snp, self.n_samp = (dims[0], dims[1]) if sample_order else (dims[1], dims[0])
@@ -473,6 +498,17 @@ def open_gds_stream(path):
         dims, b = small("snp.chromosome")
         chrom = (np.frombuffer(b, np.uint8, count=dims[0]).astype(np.int32) if len(b) == dims[0]
                  else np.frombuffer(b, "<i4", count=dims[0]).copy())
+        position = None
+        if "snp.position" in entries:
+            dims, b = small("snp.position")
+            position = np.frombuffer(b, "<i4", count=dims[0]).copy()
+        annot = {}
+        if "sample.annot" in entries:
+            def raw_id(sid):
+                dims, dsid, is_zip, _ = _node_info(load(sid))
+                b = load(dsid)
+                return dims, (zlib.decompress(b) if is_zip else b)
+            annot = _sample_annot(_dir_entries(load(entries["sample.annot"])), raw_id)
         gdesc = load(entries["genotype"])
         dims, sid, is_zip, attr = _node_info(gdesc)
         ext, slen = extents(sid)
@@ -483,7 +519,7 @@ def open_gds_stream(path):
         elif slen != (2 * dims[0] * dims[1] + 7) // 8:      # an uncompressed bit2 node is exactly its genotypes, no more, no less
             raise ValueError("the genotype node holds %d bytes where %d x %d 2-bit genotypes need %d: compressed or damaged data"
                              % (slen, dims[0], dims[1], (2 * dims[0] * dims[1] + 7) // 8))
-    return GenoStream(path, sample_id, snp_id, chrom, dims, ext, slen, is_zip, b"sample.order" in attr)
+    return GenoStream(path, sample_id, snp_id, chrom, dims, ext, slen, is_zip, b"sample.order" in attr, position, annot)
 
 
 # ---------------------------------------------------------------------------
