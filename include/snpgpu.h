@@ -587,6 +587,56 @@ int snpgpu_gnrFst(const int32_t *pop, int n_pop, const char *method, double *fst
 int snpgpu_gnrSlidingWindowFst(const int32_t *pop, int n_pop, const char *method, const int64_t *offsets, const int32_t *snp_index,
                                int64_t n_win, double *fst_win, double *beta_win, double *fst_snp);
 
+/* ---- (1g) quality-control statistics: snpgdsSampMissRate, snpgdsHWE, snpgdsIndInb ------------------------------------------------
+ * All three come from one pass over the 2-bit rows with a lane per word column of samples: the exact genotype counts of every SNP
+ * and the missing calls of every sample (integer atomics: bit-identical whatever the order), and fp64 work on them.
+ *   geno   rows [n_snp] of `format` (SNPGPU_GENO_PACKED2 rows are read where they lie, padding codes of the last byte ignored;
+ *          SNPGPU_GENO_U8 goes through the repack) in `mem`: host, or complete device memory of `device`.  2-bit rows in device
+ *          memory are read by one launch per 1 048 560 SNPs; host rows and one-byte genotypes are streamed through a staging buffer in SNP blocks
+ * Argument errors (an unknown method, a non-finite reltol, NULL outputs) are refused before any device is touched. */
+/* snp_cnt: int32 [n_snp][3], the samples with g = 0, 1, 2; samp_missing: int32 [n_samp], the SNPs with g > 2; both in out_mem,
+ * either may be NULL */
+int snpgpu_geno_counts(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, int32_t *snp_cnt,
+                       int32_t *samp_missing, int out_mem, int device);
+/* gnrHWE (src/genHWE.cpp:46-137): the p-value of the Wigginton-Cutler-Abecasis exact test on (AA = #g==2, AB = #g==1, BB = #g==0)
+ * per SNP; NaN for a SNP without a call.  One lane per SNP runs the recurrence from the midpoint down and then up in the
+ * reference's operation order (terms and normalising sum bit-identical to it) and a second time for the p-value, which adds
+ * term / sum over the terms not greater than the observed one in that generation order (the reference adds them in ascending index
+ * order: the two differ by the order of a sum of at most rare_copies / 2 + 1 non-negative terms).  SNPs are assigned to lanes in
+ * descending order of rare_copies (sorted on the host from the counters), so the lanes of a wave finish together.  The product
+ * rare_copies x (2 genotypes - rare_copies) is taken in 64 bits (the reference's int overflows beyond 32 767 samples).
+ * pvalue: host [n_snp] */
+int snpgpu_hwe(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, double *pvalue, int device);
+/* the test on given counts: snp_cnt int32 [n_snp][3] (g = 0, 1, 2) and pvalue [n_snp] both in `mem` */
+int snpgpu_hwe_counts(const int32_t *snp_cnt, int64_t n_snp, double *pvalue, int mem, int device);
+/* gnrIndInb (src/genIBD.cpp:1847-2006).  allele_freq: host [n_snp] or NULL = estimated from the counters (the moment methods:
+ * calc_afreq's sum / num * 0.5; SNPGPU_INB_MLE: GetAlleleFreqs' sum / (2 num); NaN for a SNP without a call).
+ * Moment methods: per SNP a table of the three values a genotype adds (fp64, the reference's operations in its order, no FMA
+ * contraction) and one lane per sample that walks the SNPs in ascending order, sums carried across streamed blocks: the result is
+ * the reference's sequential sum bit for bit.  Non-finite values add nothing and do not count; mom.weir adds numerator and
+ * 2 p (1 - p) for every called genotype, so a NaN frequency poisons the samples called there.
+ * SNPGPU_INB_MLE (_inb_mle, :1393-1438): rows transposed once to resident sample-major words, one wave per sample, sums over the
+ * SNPs reduced in the wave (so compared within a tolerance, not bit for bit); start value _inb_mom_ratio clamped to
+ * [0.001, 0.999], a non-finite start is returned as it is with niter -1, a sample that never meets the stop test reports 10 001.
+ *   coeff: double [n_samp], niter: int32 [n_samp] or NULL (written for SNPGPU_INB_MLE only), both in out_mem;
+ *   afreq_out: host [n_snp] or NULL, the frequencies used */
+enum snpgpu_inb_method { SNPGPU_INB_MOM_WEIR = 1, SNPGPU_INB_MOM_VISSCHER = 2, SNPGPU_INB_MLE = 3, SNPGPU_INB_GCTA1 = 4,
+                         SNPGPU_INB_GCTA2 = 5, SNPGPU_INB_GCTA3 = 6 /* = mom.visscher */ };
+int snpgpu_ind_inb(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, const double *allele_freq, int method,
+                   double reltol, double *coeff, int32_t *niter, double *afreq_out, int out_mem, int device);
+/* of the last call above on this thread (HIP events, summed over the streamed blocks): stats[0] ms of the counter kernel, [1] its
+ * launches, [2] genotype bytes it read, [3] ms of the moment kernel (table kernel included), [4] ms of the MLE kernel, [5] its
+ * lane-steps that held a genotype word, [6] lane-steps issued (the ratio is the fill of a wave's last 64-word stride: geometry), [7] ms of the HWE kernel */
+int snpgpu_qc_stats(double *stats);
+/* gnrSampFreq() (src/SNPRelate.cpp:275-283): missing rate per sample over the working space's selected SNPs; out host [n_samp] */
+int snpgpu_gnrSampFreq(double *out);
+/* gnrHWE(): pvalue host [n selected SNPs] */
+int snpgpu_gnrHWE(double *pvalue);
+/* gnrIndInb(afreq, method, reltol, num_iter, verbose): method "mom.weir", "mom.visscher", "mle", "gcta1", "gcta2", "gcta3";
+ * afreq host [n selected SNPs] or NULL; coeff host [n_samp]; niter host [n_samp], written for "mle" when out_num_iter != 0 */
+int snpgpu_gnrIndInb(const double *afreq, const char *method, double reltol, int out_num_iter, int verbose, double *coeff,
+                     int32_t *niter);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------------------
  * What THIS device's matrix pipe sustains right now: a register-only stream of one MFMA instruction (never waiting on memory,
  * two waves per SIMD) run for `seconds`, rate taken over the second half.  The kernels of this library run against the socket

@@ -33,6 +33,10 @@
 //                    slide_max_n, LD_threshold, method,
 //                    NumThread, verbose)
 //   gpu_gnrFst(Pop, nPop, Method)                               src/genFst.cpp:170-242
+//   gpu_gnrSampFreq()                                           src/SNPRelate.cpp:275-283
+//   gpu_gnrHWE()                                                src/genHWE.cpp:117-137
+//   gpu_gnrIndInb(afreq, method, reltol, num_iter, verbose)     src/genIBD.cpp:1847-2006
+//   gpu_gnrIndInbCoef(snp, afreq, reltol)                       src/genIBD.cpp:1814-1827
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -768,6 +772,95 @@ COREARRAY_DLL_EXPORT SEXP gpu_gnrFst(SEXP Pop, SEXP nPop, SEXP Method)
                        wh02 ? REAL(VECTOR_ELT(rv_ans, 2)) : nullptr, opt_int("snpgpu.device", "SNPGPU_DEVICE", 0)))
             gpu_fail();
         UNPROTECT(1);
+    COREARRAY_CATCH
+}
+
+// gnrSampFreq(), src/SNPRelate.cpp:275-283: the missing rate of every sample from the exact per-sample counters of one pass
+COREARRAY_DLL_EXPORT SEXP gpu_gnrSampFreq()
+{
+    COREARRAY_TRY
+        PackedSpace ps;
+        ps.read("Sample missing rates", false, 1);
+        std::vector<int32_t> miss(ps.n_samp);
+        if (snpgpu_geno_counts(&ps.rows[0], (int64_t)ps.n_snp, (int64_t)ps.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, nullptr, &miss[0],
+                               SNPGPU_HOST, opt_int("snpgpu.device", "SNPGPU_DEVICE", 0)))
+            gpu_fail();
+        PROTECT(rv_ans = Rf_allocVector(REALSXP, (R_xlen_t)ps.n_samp));
+        for (size_t i = 0; i < ps.n_samp; i++) REAL(rv_ans)[i] = (double)miss[i] / (double)ps.n_snp;
+        UNPROTECT(1);
+    COREARRAY_CATCH
+}
+
+// gnrHWE(), src/genHWE.cpp:117-137: the exact test per SNP on the counters of one pass (snpgpu_hwe)
+COREARRAY_DLL_EXPORT SEXP gpu_gnrHWE()
+{
+    COREARRAY_TRY
+        PackedSpace ps;
+        ps.read("HWE", false, 1);
+        PROTECT(rv_ans = Rf_allocVector(REALSXP, (R_xlen_t)ps.n_snp));
+        if (snpgpu_hwe(&ps.rows[0], (int64_t)ps.n_snp, (int64_t)ps.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, REAL(rv_ans),
+                       opt_int("snpgpu.device", "SNPGPU_DEVICE", 0)))
+            gpu_fail();
+        UNPROTECT(1);
+    COREARRAY_CATCH
+}
+
+static int inb_method_code(const char *m)
+{
+    static const char *const names[6] = {"mom.weir", "mom.visscher", "mle", "gcta1", "gcta2", "gcta3"};
+    for (int k = 0; k < 6; k++)
+        if (strcmp(m, names[k]) == 0) return k + 1;
+    return 0;
+}
+
+// gnrIndInb(afreq, method, reltol, num_iter, verbose), src/genIBD.cpp:1847-2006: list(coefficients, iteration counts or NULL)
+COREARRAY_DLL_EXPORT SEXP gpu_gnrIndInb(SEXP afreq, SEXP method, SEXP reltol, SEXP num_iter, SEXP verbose)
+{
+    const int code = inb_method_code(CHAR(STRING_ELT(method, 0)));
+    const double rtol = as_real(reltol);
+    const bool want_iter = Rf_asLogical(num_iter) == 1 && code == SNPGPU_INB_MLE;
+    COREARRAY_TRY
+        if (!code) throw ErrCoreArray("%s", "invalid 'method' of gnrIndInb");
+        PackedSpace ps;
+        ps.read("Individual inbreeding coefficients", Rf_asLogical(verbose) == 1, 1);
+        const double *af = nullptr;
+        SEXP af_real = R_NilValue;                     // the coerced copy stays protected across the allocations below
+        if (!Rf_isNull(afreq)) {
+            if (Rf_xlength(afreq) != (R_xlen_t)ps.n_snp) throw ErrCoreArray("%s", "'afreq' should have one entry per SNP of the working space");
+            af_real = Rf_coerceVector(afreq, REALSXP);
+        }
+        PROTECT(af_real);
+        if (af_real != R_NilValue) af = REAL(af_real);
+        PROTECT(rv_ans = Rf_allocVector(VECSXP, 2));
+        SET_VECTOR_ELT(rv_ans, 0, Rf_allocVector(REALSXP, (R_xlen_t)ps.n_samp));
+        if (want_iter) SET_VECTOR_ELT(rv_ans, 1, Rf_allocVector(INTSXP, (R_xlen_t)ps.n_samp));
+        if (snpgpu_ind_inb(&ps.rows[0], (int64_t)ps.n_snp, (int64_t)ps.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, af, code, rtol,
+                           REAL(VECTOR_ELT(rv_ans, 0)), want_iter ? INTEGER(VECTOR_ELT(rv_ans, 1)) : nullptr, nullptr, SNPGPU_HOST,
+                           opt_int("snpgpu.device", "SNPGPU_DEVICE", 0)))
+            gpu_fail();
+        UNPROTECT(2);
+    COREARRAY_CATCH
+}
+
+// gnrIndInbCoef(snp, afreq, reltol), src/genIBD.cpp:1814-1827: the MLE of one individual as a one-sample call of snpgpu_ind_inb
+// (one byte per genotype; anything outside 0 ... 2, NA_INTEGER included, is a missing call)
+COREARRAY_DLL_EXPORT SEXP gpu_gnrIndInbCoef(SEXP snp, SEXP afreq, SEXP reltol)
+{
+    if (Rf_xlength(reltol) != 1) Rf_error("%s", "`reltol' should a real number.");
+    const double rtol = as_real(reltol);
+    COREARRAY_TRY
+        const R_xlen_t n = Rf_xlength(snp);
+        if (Rf_xlength(afreq) != n) throw ErrCoreArray("%s", "'snp' and 'afreq' should have the same length");
+        SEXP snp_int = PROTECT(Rf_coerceVector(snp, INTSXP)), af_real = PROTECT(Rf_coerceVector(afreq, REALSXP));
+        const int *g = INTEGER(snp_int);
+        std::vector<uint8_t> rows((size_t)n);
+        for (R_xlen_t i = 0; i < n; i++) rows[(size_t)i] = (g[i] >= 0 && g[i] <= 2) ? (uint8_t)g[i] : (uint8_t)3;
+        double f = 0;
+        if (snpgpu_ind_inb(&rows[0], (int64_t)n, 1, SNPGPU_GENO_U8, SNPGPU_HOST, REAL(af_real), SNPGPU_INB_MLE,
+                           rtol, &f, nullptr, nullptr, SNPGPU_HOST, opt_int("snpgpu.device", "SNPGPU_DEVICE", 0)))
+            gpu_fail();
+        UNPROTECT(2);
+        rv_ans = Rf_ScalarReal(f);
     COREARRAY_CATCH
 }
 

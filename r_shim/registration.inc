@@ -17,6 +17,10 @@ extern SEXP gpu_gnrIBD_LogLik_k01(SEXP, SEXP, SEXP);
 extern SEXP gpu_gnrLDpruning(SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP);
 extern SEXP gpu_gnrDiss(SEXP, SEXP);
 extern SEXP gpu_gnrFst(SEXP, SEXP, SEXP);
+extern SEXP gpu_gnrSampFreq();
+extern SEXP gpu_gnrHWE();
+extern SEXP gpu_gnrIndInb(SEXP, SEXP, SEXP, SEXP, SEXP);
+extern SEXP gpu_gnrIndInbCoef(SEXP, SEXP, SEXP);
 //
 //   table entries:
 //     { "gnrGRM",             (DL_FUNC)&gpu_gnrGRM,             5 },
@@ -33,6 +37,10 @@ extern SEXP gpu_gnrFst(SEXP, SEXP, SEXP);
 //     { "gnrLDpruning",       (DL_FUNC)&gpu_gnrLDpruning,       8 },
 //     { "gnrDiss",            (DL_FUNC)&gpu_gnrDiss,            2 },
 //     { "gnrFst",             (DL_FUNC)&gpu_gnrFst,             3 },
+//     { "gnrSampFreq",        (DL_FUNC)&gpu_gnrSampFreq,        0 },
+//     { "gnrHWE",             (DL_FUNC)&gpu_gnrHWE,             0 },
+//     { "gnrIndInb",          (DL_FUNC)&gpu_gnrIndInb,          5 },
+//     { "gnrIndInbCoef",      (DL_FUNC)&gpu_gnrIndInbCoef,      3 },
 //
 // The CPU bodies (gnrGRM ... in src/genPCA.cpp, src/genIBS.cpp, src/genKING.cpp) may stay in the package as
 // unregistered functions -- e.g. behind options(snpgpu.enable = FALSE) with a second table -- or be deleted together

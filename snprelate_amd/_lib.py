@@ -51,9 +51,13 @@ EXPORTS = [
     "snpgpu_ld_prune", "snpgpu_ld_prune_bits", "snpgpu_gnrLDpruning",
     "snpgpu_diss", "snpgpu_diss_sums", "snpgpu_gnrDiss", "snpgpu_multi_diss",
     "snpgpu_pop_counts", "snpgpu_fst", "snpgpu_fst_windows", "snpgpu_pop_stats", "snpgpu_gnrFst", "snpgpu_gnrSlidingWindowFst",
+    "snpgpu_geno_counts", "snpgpu_hwe", "snpgpu_hwe_counts", "snpgpu_ind_inb", "snpgpu_qc_stats", "snpgpu_gnrSampFreq", "snpgpu_gnrHWE",
+    "snpgpu_gnrIndInb",
 ]
 FST_WC84, FST_WH02 = 1, 2
 FST_METHODS = ("W&C84", "W&H02")
+INB_METHODS = ("mom.weir", "mom.visscher", "mle", "gcta1", "gcta2", "gcta3")      # snpgpu_inb_method = index + 1
+INB_MLE = 3
 
 
 class SnpGpuError(RuntimeError):
@@ -248,6 +252,14 @@ def lib():
     L.snpgpu_pop_stats.argtypes = [vp]
     L.snpgpu_gnrFst.argtypes = [vp, c_int, ctypes.c_char_p, vp, vp, vp]
     L.snpgpu_gnrSlidingWindowFst.argtypes = [vp, c_int, ctypes.c_char_p, vp, vp, i64, vp, vp, vp]
+    L.snpgpu_geno_counts.argtypes = [vp, i64, i64, c_int, c_int, vp, vp, c_int, c_int]
+    L.snpgpu_hwe.argtypes = [vp, i64, i64, c_int, c_int, vp, c_int]
+    L.snpgpu_hwe_counts.argtypes = [vp, i64, vp, c_int, c_int]
+    L.snpgpu_ind_inb.argtypes = [vp, i64, i64, c_int, c_int, vp, c_int, dbl, vp, vp, vp, c_int, c_int]
+    L.snpgpu_qc_stats.argtypes = [vp]
+    L.snpgpu_gnrSampFreq.argtypes = [vp]
+    L.snpgpu_gnrHWE.argtypes = [vp]
+    L.snpgpu_gnrIndInb.argtypes = [vp, ctypes.c_char_p, dbl, c_int, c_int, vp, vp]
     _lib = L
     return L
 
@@ -999,6 +1011,76 @@ def pop_stats():
     s = np.zeros(4, np.float64)
     check(lib().snpgpu_pop_stats(_ptr(s)))
     return float(s[0]), int(s[1]), float(s[2]), float(s[3])
+
+
+def _qc_input(geno, n_samp, fmt, n_snp):
+    """(pointer, n_snp, format, memory kind, keep-alive) for host rows (numpy) or device rows (an int address)"""
+    n_samp = int(n_samp)
+    if isinstance(geno, int):
+        if n_snp is None:
+            raise ValueError("device rows need n_snp")
+        return ctypes.c_void_p(geno), int(n_snp), GENO_PACKED2 if fmt is None else int(fmt), DEVICE, None
+    g = np.ascontiguousarray(geno, dtype=np.uint8)
+    if fmt is None:
+        fmt = GENO_U8 if g.shape[1] == n_samp else GENO_PACKED2
+    exp = n_samp if fmt == GENO_U8 else (n_samp + 3) // 4
+    if g.ndim != 2 or g.shape[1] != exp:
+        raise ValueError("genotype rows have the wrong shape")
+    return _ptr(g), g.shape[0], int(fmt), HOST, g
+
+
+def geno_counts(geno, n_samp, fmt=None, n_snp=None, device=0, want_snp=True, want_samp=True):
+    """(snp_cnt int32 [n_snp][3] for g = 0, 1, 2; samp_missing int32 [n_samp]) of snpgpu_geno_counts; None for a part not asked
+    for.  geno: host rows (numpy, U8 or PACKED2) or a device address (int) with n_snp (and fmt)."""
+    ptr, n, fmt, mem, _keep = _qc_input(geno, n_samp, fmt, n_snp)
+    c = np.empty((n, 3), np.int32) if want_snp else None
+    m = np.empty(int(n_samp), np.int32) if want_samp else None
+    check(lib().snpgpu_geno_counts(ptr, n, int(n_samp), fmt, mem, _ptr(c), _ptr(m), HOST, int(device)))
+    return c, m
+
+
+def hwe(geno, n_samp, fmt=None, n_snp=None, device=0):
+    """snpgpu_hwe: p-value of the exact test of Hardy-Weinberg equilibrium per SNP (NaN without a call)"""
+    ptr, n, fmt, mem, _keep = _qc_input(geno, n_samp, fmt, n_snp)
+    p = np.empty(n, np.float64)
+    check(lib().snpgpu_hwe(ptr, n, int(n_samp), fmt, mem, _ptr(p), int(device)))
+    return p
+
+
+def hwe_counts(snp_cnt, device=0):
+    """snpgpu_hwe_counts on host counts int32 [n_snp][3] (g = 0, 1, 2)"""
+    c = np.ascontiguousarray(snp_cnt, np.int32)
+    if c.ndim != 2 or c.shape[1] != 3:
+        raise ValueError("snp_cnt should be [n_snp][3]")
+    p = np.empty(c.shape[0], np.float64)
+    check(lib().snpgpu_hwe_counts(_ptr(c), c.shape[0], _ptr(p), HOST, int(device)))
+    return p
+
+
+def ind_inb(geno, n_samp, method="mom.weir", allele_freq=None, reltol=float(np.finfo(float).eps ** 0.75), fmt=None, n_snp=None,
+            device=0):
+    """snpgpu_ind_inb: (coeff [n_samp], niter int32 [n_samp] or None unless "mle", afreq [n_snp] as used)"""
+    if method not in INB_METHODS:
+        raise ValueError("'method' should be one of %s" % ", ".join('"%s"' % m for m in INB_METHODS))
+    ptr, n, fmt, mem, _keep = _qc_input(geno, n_samp, fmt, n_snp)
+    af_in = None if allele_freq is None else np.ascontiguousarray(allele_freq, np.float64)
+    if af_in is not None and af_in.shape != (n,):
+        raise ValueError("allele_freq should hold one frequency per SNP")
+    code = INB_METHODS.index(method) + 1
+    coeff = np.empty(int(n_samp), np.float64)
+    nit = np.empty(int(n_samp), np.int32) if code == INB_MLE else None
+    af = np.empty(n, np.float64)
+    check(lib().snpgpu_ind_inb(ptr, n, int(n_samp), fmt, mem, _ptr(af_in), code, float(reltol), _ptr(coeff), _ptr(nit), _ptr(af),
+                               HOST, int(device)))
+    return coeff, nit, af
+
+
+def qc_stats():
+    """dict of snpgpu_qc_stats for the last geno_counts / hwe / hwe_counts / ind_inb call on this thread"""
+    s = np.zeros(8, np.float64)
+    check(lib().snpgpu_qc_stats(_ptr(s)))
+    return dict(count_ms=float(s[0]), count_launches=int(s[1]), count_bytes=float(s[2]), mom_ms=float(s[3]), mle_ms=float(s[4]),
+                mle_lane_steps_useful=int(s[5]), mle_lane_steps_issued=int(s[6]), hwe_ms=float(s[7]))
 
 
 def ibd_mle_stats():

@@ -22,9 +22,15 @@ INTEGRATION.md):
     snpgdsDiss                    R/IBD.R:432-450  (individual dissimilarity)
     snpgdsFst                     R/IBD.R:756-830  (fixation index, W&C84 / W&H02)
     snpgdsSlidingWindow           R/AllUtilities.R:1998-2239 (window scan of Fst / allele frequencies / a callable)
+    snpgdsSampMissRate            R/AllUtilities.R:230-248   (missing rate per sample)
+    snpgdsHWE                     R/AllUtilities.R:255-279   (exact test of Hardy-Weinberg equilibrium per SNP)
+    snpgdsSelectSNP               R/AllUtilities.R:286-299   (the SNPs that pass the filters)
+    snpgdsIndInbCoef              R/AllUtilities.R:312-341   (inbreeding coefficient of one individual, on the host)
+    snpgdsIndInb                  R/AllUtilities.R:349-378   (individual inbreeding coefficients, six methods)
 
-All arithmetic runs on the MI355X through libsnpgpu.so (`_lib`); there is no
-CPU fallback.  R's ``NULL`` is ``None``, ``NaN`` is ``float('nan')``; R lists
+All arithmetic on genotype matrices runs on the MI355X through libsnpgpu.so
+(`_lib`); there is no CPU fallback.  The one exception is snpgdsIndInbCoef, which
+takes one individual's vectors and, like its R original, computes on the host.  R's ``NULL`` is ``None``, ``NaN`` is ``float('nan')``; R lists
 are dicts with the same field names.
 """
 import ctypes
@@ -1178,3 +1184,139 @@ def snpgdsSlidingWindow(gdsobj, sample_id=None, snp_id=None, FUN=None, winsize=1
     if verbose:
         print("%s\tDone." % time.ctime())
     return ans
+
+
+# ---- quality-control statistics ---------------------------------------------------------------------------------------------
+INB_METHODS = _lib.INB_METHODS
+INB_COEF_METHODS = ("mom.weir", "mom.visscher", "mle")
+_RELTOL_INB = float(np.finfo(float).eps ** 0.75)
+
+
+def _scalar_reltol(reltol):
+    """stopifnot(is.numeric(reltol), length(reltol) == 1L) / gnrIndInbCoef's own check (src/genIBD.cpp:1820-1821)"""
+    if isinstance(reltol, (bool, np.bool_)) or not isinstance(reltol, (int, float, np.integer, np.floating)):
+        raise ValueError("`reltol' should a real number.")
+    return float(reltol)
+
+
+def snpgdsSampMissRate(gdsobj, sample_id=None, snp_id=None, with_id=False, device=0):
+    """Missing rate per sample (R/AllUtilities.R:230-248 -> gnrSampFreq -> GetSampMissingRates, src/dGenGWAS.cpp:207-248):
+    float64 [n_samp] = (calls > 2) / n_snp over the selected SNPs, from the exact per-sample counters of snpgpu_geno_counts.
+    with_id: R names the vector by sample; here, as snpgdsSNPRateFreq does with its ids, dict(sample_id, MissingRate)."""
+    ws = _init_file(gdsobj, sample_id, snp_id, device)
+    rv = np.empty(ws["n_samp"], np.float64)
+    _lib.check(_lib.lib().snpgpu_gnrSampFreq(_lib._ptr(rv)))
+    if with_id:
+        return dict(sample_id=ws["sample_id"], MissingRate=rv)
+    return rv
+
+
+def snpgdsHWE(gdsobj, sample_id=None, snp_id=None, with_id=False, device=0):
+    """p-value per SNP of the exact test of Hardy-Weinberg equilibrium (R/AllUtilities.R:255-279 -> gnrHWE,
+    src/genHWE.cpp:46-137; Wigginton, Cutler & Abecasis 2005) on (AA = #g==2, AB = #g==1, BB = #g==0); NaN without a call.
+    with_id: dict(pvalue, sample_id, snp_id)."""
+    if not isinstance(with_id, (bool, np.bool_)):
+        raise TypeError("is.logical(with.id) is not TRUE")
+    ws = _init_file(gdsobj, sample_id, snp_id, device)
+    rv = np.empty(ws["n_snp"], np.float64)
+    _lib.check(_lib.lib().snpgpu_gnrHWE(_lib._ptr(rv)))
+    if with_id:
+        return dict(pvalue=rv, sample_id=ws["sample_id"], snp_id=ws["snp_id"])
+    return rv
+
+
+def snpgdsSelectSNP(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True, maf=float("nan"),
+                    missing_rate=float("nan"), verbose=True, device=0):
+    """The candidate SNPs that pass the filters (R/AllUtilities.R:286-299): ws$snp.id of .InitFile2"""
+    ws = _init_file2(None, gdsobj, sample_id, snp_id, autosome_only, remove_monosnp, maf, missing_rate, 1, verbose, device)
+    return ws["snp_id"]
+
+
+def _inb_mle_host(g, p, reltol):
+    """_inb_mle<int> (src/genIBD.cpp:1393-1438) for one individual in numpy: g int (anything outside 0 ... 2 is skipped), p the
+    allele frequencies.  The sums over the SNPs are numpy's (pairwise), not the reference's sequential ones."""
+    with np.errstate(all="ignore"):
+        called = (g >= 0) & (g <= 2)
+        gc, pc = g[called].astype(np.float64), p[called]
+        F = np.float64(np.sum(gc * gc - (1 + 2 * pc) * gc + 2 * pc * pc)) / np.float64(np.sum(2 * pc * (1 - pc)))
+        if not np.isfinite(F):
+            return float(F)
+        F = min(max(F, 0.001), 1 - 0.001)
+        het, hom = gc == 1, gc != 1
+        x = np.where(gc == 0, 1 - pc, pc)
+        n_het = int(het.sum())
+
+        def loglik(F):
+            val = np.log(np.where(het, (1 - F) * 2 * pc * (1 - pc), (1 - F) * x * x + F * x))
+            return float(np.sum(val[np.isfinite(val)]))
+
+        L = loglik(F)
+        contol = abs(L) * reltol
+        for _ in range(10000):
+            old = L
+            tmp = (F / (F + x * (1 - F)))[hom]
+            ok = np.isfinite(tmp)
+            m = int(ok.sum()) + n_het
+            F = np.float64(np.sum(tmp[ok])) / np.float64(m)
+            L = loglik(F)
+            if abs(L - old) <= contol:
+                break
+        return float(F)
+
+
+def snpgdsIndInbCoef(x, p, method="mom.weir", reltol=_RELTOL_INB):
+    """Inbreeding coefficient of one individual from genotypes x and allele frequencies p (R/AllUtilities.R:312-341).  All three
+    methods run on the host in numpy: the two moment methods as the R code does, "mle" through _inb_mle_host, a numpy routine
+    that follows gnrIndInbCoef -> _inb_mle<int> (src/genIBD.cpp:1393-1438, :1814-1827) step by step."""
+    method = _match_arg(method, INB_COEF_METHODS, "method")
+    reltol = _scalar_reltol(reltol)
+    x = np.asarray(x)
+    p = np.asarray(p)
+    for name, v in (("x", x), ("p", p)):
+        if v.ndim != 1 or v.dtype.kind not in "iuf":
+            raise TypeError("is.vector(%s) & is.numeric(%s) is not TRUE" % (name, name))
+    if len(x) != len(p):
+        raise ValueError("length(x) == length(p) is not TRUE")
+    x = x.astype(np.float64)
+    p = p.astype(np.float64)
+    x[~np.isin(x, (0, 1, 2))] = np.nan
+    with np.errstate(all="ignore"):
+        if method == "mom.weir":
+            num = x * x - (1 + 2 * p) * x + 2 * p * p
+            den = 2 * p * (1 - p)
+            flag = np.isfinite(num) & np.isfinite(den)
+            return float(np.float64(np.sum(num[flag])) / np.float64(np.sum(den[flag])))
+        if method == "mom.visscher":
+            d = (x * x - (1 + 2 * p) * x + 2 * p * p) / (2 * p * (1 - p))
+            d = d[np.isfinite(d)]
+            return float(d.mean()) if len(d) else float("nan")
+    g = np.where(np.isnan(x), -1, x).astype(np.int64)
+    return _inb_mle_host(g, p, reltol)
+
+
+def snpgdsIndInb(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True, maf=float("nan"),
+                 missing_rate=float("nan"), method="mom.weir", allele_freq=None, out_num_iter=True, reltol=_RELTOL_INB,
+                 verbose=True, device=0):
+    """Individual inbreeding coefficients (R/AllUtilities.R:349-378 -> gnrIndInb, src/genIBD.cpp:1847-2006): dict(sample_id,
+    snp_id, inbreeding[, out_num_iter]).  Methods "mom.weir", "mom.visscher", "mle", "gcta1", "gcta2", "gcta3".  The moment methods
+    are the reference's sequential fp64 sums bit for bit (one lane per sample walks the SNPs in order); "mle" iterates per sample on
+    the GPU with sums reduced in a wave and also returns out_num_iter (int32) unless out_num_iter is False.  Without allele_freq
+    the frequencies come from the selected genotypes, as in the reference (gnrSNPFreq for "mle", calc_afreq otherwise)."""
+    method = _match_arg(method, INB_METHODS, "method")
+    if not isinstance(out_num_iter, (bool, np.bool_)):
+        raise TypeError("is.logical(out.num.iter) is not TRUE")
+    reltol = _scalar_reltol(reltol)
+    ws = _init_file2("Estimating individual inbreeding coefficients:", gdsobj, sample_id, snp_id, autosome_only, remove_monosnp,
+                     maf, missing_rate, 1, verbose, device, allele_freq=allele_freq)
+    n = ws["n_samp"]
+    if ws["n_snp"] < 1:
+        raise ValueError("snpgdsIndInb: no SNP in the working dataset")
+    coeff = np.empty(n, np.float64)
+    want_iter = method == "mle" and bool(out_num_iter)
+    niter = np.empty(n, np.int32) if want_iter else None
+    _lib.check(_lib.lib().snpgpu_gnrIndInb(_lib._ptr(ws["allele_freq"]), method.encode(), reltol, int(want_iter),
+                                           int(bool(verbose)), _lib._ptr(coeff), _lib._ptr(niter)))
+    rv = dict(sample_id=ws["sample_id"], snp_id=ws["snp_id"], inbreeding=coeff)
+    if want_iter:
+        rv["out_num_iter"] = niter
+    return rv

@@ -1218,4 +1218,53 @@ int snpgpu_gnrIBD_LogLik_k01(const double *afreq, double k0, double k1, double *
                              nullptr, nullptr, k0, k1, out, nullptr, SNPGPU_HOST, g_ws.device);
 }
 
+// gnrSampFreq (src/SNPRelate.cpp:275-283), gnrHWE (src/genHWE.cpp:117-137) and gnrIndInb (src/genIBD.cpp:1847-2006) on the selected
+// SNPs.  What does not depend on the working space is checked first, so that it is refused without a device.
+static int ws_qc_rows(const char *fn, std::vector<uint8_t> &buf)
+{
+    if (need_ws(fn)) return 1;
+    if ((int64_t)g_ws.sel.size() < 1) { set_error(std::string(fn) + ": no SNP in the working dataset"); return 1; }
+    gather_block(0, (int64_t)g_ws.sel.size(), buf);
+    return 0;
+}
+
+int snpgpu_gnrSampFreq(double *out)
+{
+    if (!out) { set_error("snpgpu_gnrSampFreq: out is NULL"); return 1; }
+    std::vector<uint8_t> buf;
+    if (ws_qc_rows("snpgpu_gnrSampFreq", buf)) return 1;
+    const int64_t L = (int64_t)g_ws.sel.size();
+    std::vector<int32_t> miss((size_t)g_ws.n_samp);
+    if (snpgpu_geno_counts(buf.data(), L, g_ws.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, nullptr, miss.data(), SNPGPU_HOST, g_ws.device))
+        return 1;
+    for (int64_t i = 0; i < g_ws.n_samp; i++) out[i] = (double)miss[(size_t)i] / (double)L;     // GetSampMissingRates: cnt /= fSNPNum
+    return 0;
+}
+
+int snpgpu_gnrHWE(double *pvalue)
+{
+    if (!pvalue) { set_error("snpgpu_gnrHWE: pvalue is NULL"); return 1; }
+    std::vector<uint8_t> buf;
+    if (ws_qc_rows("snpgpu_gnrHWE", buf)) return 1;
+    return snpgpu_hwe(buf.data(), (int64_t)g_ws.sel.size(), g_ws.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, pvalue, g_ws.device);
+}
+
+int snpgpu_gnrIndInb(const double *afreq, const char *method, double reltol, int out_num_iter, int, double *coeff, int32_t *niter)
+{
+    static const char *const names[6] = {"mom.weir", "mom.visscher", "mle", "gcta1", "gcta2", "gcta3"};
+    int code = 0;
+    for (int k = 0; k < 6 && method; k++)
+        if (strcmp(method, names[k]) == 0) code = k + 1;
+    if (!code) {
+        set_error("snpgpu_gnrIndInb: 'method' should be one of \"mom.weir\", \"mom.visscher\", \"mle\", \"gcta1\", \"gcta2\", \"gcta3\"");
+        return 1;
+    }
+    if (!coeff) { set_error("snpgpu_gnrIndInb: coeff is NULL"); return 1; }
+    if (code == SNPGPU_INB_MLE && !std::isfinite(reltol)) { set_error("snpgpu_gnrIndInb: `reltol' should a real number."); return 1; }
+    std::vector<uint8_t> buf;
+    if (ws_qc_rows("snpgpu_gnrIndInb", buf)) return 1;
+    return snpgpu_ind_inb(buf.data(), (int64_t)g_ws.sel.size(), g_ws.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, afreq, code, reltol, coeff,
+                          out_num_iter ? niter : nullptr, nullptr, SNPGPU_HOST, g_ws.device);
+}
+
 }  // extern "C"
