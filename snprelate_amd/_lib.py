@@ -653,19 +653,31 @@ class LDPruneInfo(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
-def _prune_input(geno, n_samp, fmt, n_snp):
-    """(pointer, n_snp, format, memory kind) of host rows (numpy) or device rows (an int address with n_snp and fmt given)"""
+def _geno_input(geno, n_samp, fmt, n_snp, *, device_fmt_default):
+    """(pointer, n_snp, format, memory kind, keep-alive) of host rows (numpy, U8 or PACKED2; fmt None: U8 when a row holds n_samp
+    bytes) or device rows (an int address with n_snp; their fmt None means device_fmt_default, which is None where it must be
+    named)"""
+    n_samp = int(n_samp)
     if isinstance(geno, int):
+        fmt = device_fmt_default if fmt is None else fmt
         if n_snp is None or fmt is None:
-            raise ValueError("device rows need n_snp and fmt")
+            raise ValueError("device rows need n_snp and fmt" if device_fmt_default is None else "device rows need n_snp")
         return ctypes.c_void_p(geno), int(n_snp), int(fmt), DEVICE, None
     g = np.ascontiguousarray(geno, dtype=np.uint8)
+    if g.ndim != 2:
+        raise ValueError("genotype rows have the wrong shape")
     if fmt is None:
         fmt = GENO_U8 if g.shape[1] == n_samp else GENO_PACKED2
-    exp = n_samp if fmt == GENO_U8 else (n_samp + 3) // 4
-    if g.ndim != 2 or g.shape[1] != exp:
+    if g.shape[1] != (n_samp if fmt == GENO_U8 else (n_samp + 3) // 4):
         raise ValueError("genotype rows have the wrong shape")
     return _ptr(g), g.shape[0], int(fmt), HOST, g
+
+
+def _pop_array(pop, n_samp):
+    p = np.ascontiguousarray(pop, dtype=np.int32)
+    if p.shape != (int(n_samp),):
+        raise ValueError("pop should hold one population index per sample")
+    return p
 
 
 def ld_prune(geno, n_samp, pos_bp, start_idx, slide_max_bp, slide_max_n, ld_threshold, method=LD_COMPOSITE, fmt=None, n_snp=None,
@@ -674,7 +686,7 @@ def ld_prune(geno, n_samp, pos_bp, start_idx, slide_max_bp, slide_max_n, ld_thre
     PACKED2; fmt None: U8 when a row holds n_samp bytes) or a device address (int) with n_snp and fmt; start_idx 0-based;
     the window limits are the reference's int32 values."""
     n_samp = int(n_samp)
-    ptr, n, fmt, mem, _keep_alive = _prune_input(geno, n_samp, fmt, n_snp)
+    ptr, n, fmt, mem, _keep_alive = _geno_input(geno, n_samp, fmt, n_snp, device_fmt_default=None)
     pos = np.ascontiguousarray(pos_bp, dtype=np.int32)
     if pos.shape != (n,):
         raise ValueError("pos_bp should hold one int32 per SNP")
@@ -691,7 +703,7 @@ def ld_prune_bits(geno, n_samp, start_idx, width, ld_threshold, method=LD_COMPOS
     """The threshold bits snpgpu_ld_prune scans for a band of `width` (snpgpu_ld_prune_bits): bool [n_snp][width], entry
     [x, k - 1] for the pair (x, x + k); and the info dict."""
     n_samp = int(n_samp)
-    ptr, n, fmt, mem, _keep_alive = _prune_input(geno, n_samp, fmt, n_snp)
+    ptr, n, fmt, mem, _keep_alive = _geno_input(geno, n_samp, fmt, n_snp, device_fmt_default=None)
     wpr = (int(width) + 63) // 64
     words = np.zeros((n, max(wpr, 1)), np.uint64)
     o = Opts(device=int(device), max_block_snps=int(max_block_snps))
@@ -934,47 +946,26 @@ def ibd_mle(geno, n_samp, allele_freq=None, max_niter=1000, reltol=float(np.sqrt
     returns (k0, k1, niter, afreq) with k0 / k1 / niter full n x n and afreq as InitAFreq leaves it (-1 = none).
     rows = (r0, r1): only the pairs of those upper-triangle rows (and their mirrors) are written, into `out` = (k0, k1, niter)
     when given."""
-    if geno_dev_ptr is None:
-        geno = np.ascontiguousarray(geno, np.uint8)
-        n_snp, ptr, mem = geno.shape[0], _ptr(geno), HOST
-    else:
-        ptr, mem = ctypes.c_void_p(int(geno_dev_ptr)), DEVICE
+    ptr, n_snp, fmt, mem, _keep = _geno_input(geno if geno_dev_ptr is None else int(geno_dev_ptr), n_samp, GENO_PACKED2, n_snp,
+                                              device_fmt_default=GENO_PACKED2)
     af_in = None if allele_freq is None else np.ascontiguousarray(allele_freq, np.float64)
     if out is None:
         out = (np.empty((n_samp, n_samp), np.float64), np.empty((n_samp, n_samp), np.float64),
                np.empty((n_samp, n_samp), np.int32))
     k0, k1, nit = out
     af = np.empty(n_snp, np.float64)
-    check(lib().snpgpu_ibd_mle(ptr, int(n_snp), int(n_samp), GENO_PACKED2, mem, _ptr(af_in), int(max_niter), float(reltol),
+    check(lib().snpgpu_ibd_mle(ptr, n_snp, int(n_samp), fmt, mem, _ptr(af_in), int(max_niter), float(reltol),
                                int(bool(coeff_correct)), int(rows[0]), int(rows[1]), _ptr(k0), _ptr(k1), _ptr(nit), _ptr(af),
                                HOST, int(device)))
     return k0, k1, nit, af
-
-
-def _pop_input(geno, n_samp, fmt, n_snp, pop):
-    """(pointer, n_snp, format, memory kind, keep-alive, pop int32) for host rows (numpy) or device rows (an int address)"""
-    n_samp = int(n_samp)
-    p = np.ascontiguousarray(pop, dtype=np.int32)
-    if p.shape != (n_samp,):
-        raise ValueError("pop should hold one population index per sample")
-    if isinstance(geno, int):
-        if n_snp is None:
-            raise ValueError("device rows need n_snp")
-        return ctypes.c_void_p(geno), int(n_snp), GENO_PACKED2 if fmt is None else int(fmt), DEVICE, None, p
-    g = np.ascontiguousarray(geno, dtype=np.uint8)
-    if fmt is None:
-        fmt = GENO_U8 if g.shape[1] == n_samp else GENO_PACKED2
-    exp = n_samp if fmt == GENO_U8 else (n_samp + 3) // 4
-    if g.ndim != 2 or g.shape[1] != exp:
-        raise ValueError("genotype rows have the wrong shape")
-    return _ptr(g), g.shape[0], int(fmt), HOST, g, p
 
 
 def pop_counts(geno, n_samp, pop, n_pop, fmt=None, n_snp=None, device=0):
     """(ACnt, Cnt) int32 [n_snp][n_pop] of snpgpu_pop_counts: per SNP and population the sum of the called genotypes and twice
     the number of called samples.  geno: host rows (numpy, U8 or PACKED2) or a device address (int) with n_snp (and fmt);
     pop: 0-based population index per sample."""
-    ptr, n, fmt, mem, _keep, p = _pop_input(geno, n_samp, fmt, n_snp, pop)
+    p = _pop_array(pop, n_samp)
+    ptr, n, fmt, mem, _keep = _geno_input(geno, n_samp, fmt, n_snp, device_fmt_default=GENO_PACKED2)
     a = np.empty((n, int(n_pop)), np.int32)
     c = np.empty((n, int(n_pop)), np.int32)
     check(lib().snpgpu_pop_counts(ptr, n, int(n_samp), fmt, mem, _ptr(p), int(n_pop), _ptr(a), _ptr(c), HOST, int(device)))
@@ -983,7 +974,8 @@ def pop_counts(geno, n_samp, pop, n_pop, fmt=None, n_snp=None, device=0):
 
 def fst(geno, n_samp, pop, n_pop, method=FST_WC84, fmt=None, n_snp=None, device=0):
     """snpgpu_fst: (Fst, FstSNP [n_snp], Beta [n_pop][n_pop] or None)"""
-    ptr, n, fmt, mem, _keep, p = _pop_input(geno, n_samp, fmt, n_snp, pop)
+    p = _pop_array(pop, n_samp)
+    ptr, n, fmt, mem, _keep = _geno_input(geno, n_samp, fmt, n_snp, device_fmt_default=GENO_PACKED2)
     f = ctypes.c_double(0)
     per = np.empty(n, np.float64)
     beta = np.empty((int(n_pop), int(n_pop)), np.float64) if int(method) == FST_WH02 else None
@@ -994,7 +986,8 @@ def fst(geno, n_samp, pop, n_pop, method=FST_WC84, fmt=None, n_snp=None, device=
 
 def fst_windows(geno, n_samp, pop, n_pop, offsets, snp_index, method=FST_WC84, fmt=None, n_snp=None, device=0):
     """snpgpu_fst_windows: (Fst per window, FstSNP [n_snp], Beta [n_win][n_pop][n_pop] or None) for CSR windows"""
-    ptr, n, fmt, mem, _keep, p = _pop_input(geno, n_samp, fmt, n_snp, pop)
+    p = _pop_array(pop, n_samp)
+    ptr, n, fmt, mem, _keep = _geno_input(geno, n_samp, fmt, n_snp, device_fmt_default=GENO_PACKED2)
     off = np.ascontiguousarray(offsets, np.int64)
     idx = np.ascontiguousarray(snp_index, np.int32)
     n_win = len(off) - 1
@@ -1013,26 +1006,10 @@ def pop_stats():
     return float(s[0]), int(s[1]), float(s[2]), float(s[3])
 
 
-def _qc_input(geno, n_samp, fmt, n_snp):
-    """(pointer, n_snp, format, memory kind, keep-alive) for host rows (numpy) or device rows (an int address)"""
-    n_samp = int(n_samp)
-    if isinstance(geno, int):
-        if n_snp is None:
-            raise ValueError("device rows need n_snp")
-        return ctypes.c_void_p(geno), int(n_snp), GENO_PACKED2 if fmt is None else int(fmt), DEVICE, None
-    g = np.ascontiguousarray(geno, dtype=np.uint8)
-    if fmt is None:
-        fmt = GENO_U8 if g.shape[1] == n_samp else GENO_PACKED2
-    exp = n_samp if fmt == GENO_U8 else (n_samp + 3) // 4
-    if g.ndim != 2 or g.shape[1] != exp:
-        raise ValueError("genotype rows have the wrong shape")
-    return _ptr(g), g.shape[0], int(fmt), HOST, g
-
-
 def geno_counts(geno, n_samp, fmt=None, n_snp=None, device=0, want_snp=True, want_samp=True):
     """(snp_cnt int32 [n_snp][3] for g = 0, 1, 2; samp_missing int32 [n_samp]) of snpgpu_geno_counts; None for a part not asked
     for.  geno: host rows (numpy, U8 or PACKED2) or a device address (int) with n_snp (and fmt)."""
-    ptr, n, fmt, mem, _keep = _qc_input(geno, n_samp, fmt, n_snp)
+    ptr, n, fmt, mem, _keep = _geno_input(geno, n_samp, fmt, n_snp, device_fmt_default=GENO_PACKED2)
     c = np.empty((n, 3), np.int32) if want_snp else None
     m = np.empty(int(n_samp), np.int32) if want_samp else None
     check(lib().snpgpu_geno_counts(ptr, n, int(n_samp), fmt, mem, _ptr(c), _ptr(m), HOST, int(device)))
@@ -1041,7 +1018,7 @@ def geno_counts(geno, n_samp, fmt=None, n_snp=None, device=0, want_snp=True, wan
 
 def hwe(geno, n_samp, fmt=None, n_snp=None, device=0):
     """snpgpu_hwe: p-value of the exact test of Hardy-Weinberg equilibrium per SNP (NaN without a call)"""
-    ptr, n, fmt, mem, _keep = _qc_input(geno, n_samp, fmt, n_snp)
+    ptr, n, fmt, mem, _keep = _geno_input(geno, n_samp, fmt, n_snp, device_fmt_default=GENO_PACKED2)
     p = np.empty(n, np.float64)
     check(lib().snpgpu_hwe(ptr, n, int(n_samp), fmt, mem, _ptr(p), int(device)))
     return p
@@ -1062,7 +1039,7 @@ def ind_inb(geno, n_samp, method="mom.weir", allele_freq=None, reltol=float(np.f
     """snpgpu_ind_inb: (coeff [n_samp], niter int32 [n_samp] or None unless "mle", afreq [n_snp] as used)"""
     if method not in INB_METHODS:
         raise ValueError("'method' should be one of %s" % ", ".join('"%s"' % m for m in INB_METHODS))
-    ptr, n, fmt, mem, _keep = _qc_input(geno, n_samp, fmt, n_snp)
+    ptr, n, fmt, mem, _keep = _geno_input(geno, n_samp, fmt, n_snp, device_fmt_default=GENO_PACKED2)
     af_in = None if allele_freq is None else np.ascontiguousarray(allele_freq, np.float64)
     if af_in is not None and af_in.shape != (n,):
         raise ValueError("allele_freq should hold one frequency per SNP")
@@ -1092,11 +1069,11 @@ def ibd_mle_stats():
 
 def ibd_loglik(geno, n_samp, allele_freq=None, k0=None, k1=None, k0_all=float("nan"), k1_all=float("nan"), device=0):
     """snpgpu_ibd_loglik: EM_LogLik of every pair at the n x n (k0, k1), or at the global pair when k0 / k1 are None"""
-    geno = np.ascontiguousarray(geno, np.uint8)
+    ptr, n_snp, fmt, mem, _keep = _geno_input(geno, n_samp, GENO_PACKED2, None, device_fmt_default=GENO_PACKED2)
     af_in = None if allele_freq is None else np.ascontiguousarray(allele_freq, np.float64)
     m0 = None if k0 is None else np.ascontiguousarray(k0, np.float64)
     m1 = None if k1 is None else np.ascontiguousarray(k1, np.float64)
     out = np.empty((n_samp, n_samp), np.float64)
-    check(lib().snpgpu_ibd_loglik(_ptr(geno), geno.shape[0], int(n_samp), GENO_PACKED2, HOST, _ptr(af_in), _ptr(m0), _ptr(m1),
+    check(lib().snpgpu_ibd_loglik(ptr, n_snp, int(n_samp), fmt, mem, _ptr(af_in), _ptr(m0), _ptr(m1),
                                   float(k0_all), float(k1_all), _ptr(out), None, HOST, int(device)))
     return out

@@ -6,7 +6,7 @@
 
 #include <rocblas/rocblas.h>
 
-#include "snpgpu_internal.h"
+#include "host_util.h"
 
 namespace snpgpu {
 
@@ -183,11 +183,7 @@ int snpgpu_create(int kind, int64_t n_samp, const snpgpu_opts *opts, snpgpu_ctx 
     if (n_samp <= 0 || n_samp > 0x7fffffffLL) { set_error("snpgpu_create: invalid number of samples"); return 1; }
     snpgpu_opts o{};
     if (opts) o = *opts;
-    int ndev = 0;
-    SNPGPU_HIP_CHECK(hipGetDeviceCount(&ndev));
-    if (ndev <= 0) { set_error("snpgpu_create: no HIP device (the GPU path has no CPU fallback)"); return 1; }
-    if (o.device < 0 || o.device >= ndev) { set_error("snpgpu_create: invalid device ordinal"); return 1; }
-    SNPGPU_HIP_CHECK(hipSetDevice(o.device));
+    if (use_device("snpgpu_create", o.device)) return 1;
     {
         // the kernels are written for gfx950 (MI355X) and nothing else: MX-fp4 matrix instructions, 160 KiB of LDS per workgroup,
         // 512 registers per lane.  A device of another architecture could not load the code objects; say so here rather than at

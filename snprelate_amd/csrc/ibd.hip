@@ -11,7 +11,7 @@
 #include <cmath>
 #include <vector>
 
-#include "snpgpu_internal.h"
+#include "host_util.h"
 
 namespace snpgpu {
 size_t ibd_snp_bytes();
@@ -38,27 +38,8 @@ namespace {
 
 thread_local double g_stats[4] = {0, 0, 0, 0};   // EM kernel ms, all kernels ms, useful / issued lane-sweeps
 
-struct Bufs {
-    std::vector<DevBuf *> all;
-    ~Bufs() { for (DevBuf *b : all) { b->release(); delete b; } }
-    DevBuf *get(size_t bytes, int &rc)
-    {
-        DevBuf *b = new DevBuf;
-        all.push_back(b);
-        if (!rc) rc = b->alloc(bytes);
-        return b;
-    }
-};
-
-struct Stream {
-    hipStream_t s = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Stream()
-    {
-        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-        if (s) (void)hipStreamDestroy(s);
-    }
-};
+constexpr GenoLimits IBD_GENO = {2, NO_LIMIT, NO_LIMIT, true, "at least two samples are needed"};
+enum { T_EM = 0, T_REST = 1 };   // snpgpu_ibd_mle's EventLog: the EM kernel; candidates and expansion, back to back with it
 
 // the genotype words and per-SNP tables both sweeps read, and the frequencies of InitAFreq
 struct Prep {
@@ -68,17 +49,7 @@ struct Prep {
     std::vector<double> af;            // MLEAlleleFreq (host)
 };
 
-int check_args(const char *fn, const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem)
-{
-    if (!geno) { set_error(std::string(fn) + ": geno is NULL"); return 1; }
-    if (n_samp < 2) { set_error(std::string(fn) + ": at least two samples are needed"); return 1; }
-    if (n_snp < 1) { set_error(std::string(fn) + ": no SNP in the working dataset"); return 1; }
-    if (format != SNPGPU_GENO_PACKED2) { set_error(std::string(fn) + ": genotypes must be SNPGPU_GENO_PACKED2 rows"); return 1; }
-    if (mem != SNPGPU_HOST && mem != SNPGPU_DEVICE) { set_error(std::string(fn) + ": invalid memory kind"); return 1; }
-    return 0;
-}
-
-int prepare(const char *fn, Stream &st, Bufs &bufs, const void *geno, int64_t n_snp, int64_t n_samp, int mem,
+int prepare(CallStream &st, DevArena &bufs, const void *geno, int64_t n_snp, int64_t n_samp, int mem,
             const double *allele_freq, Prep &P)
 {
     int rc = 0;
@@ -111,7 +82,6 @@ int prepare(const char *fn, Stream &st, Bufs &bufs, const void *geno, int64_t n_
                            (uint8_t *)usable->p, (uint32_t *)P.gt->p))
         return 1;
     SNPGPU_HIP_CHECK(hipStreamSynchronize(st.s));
-    (void)fn;
     return 0;
 }
 
@@ -123,42 +93,6 @@ std::vector<int64_t> row_offsets(int64_t n, int64_t r0, int64_t r1, bool diag)
     return off;
 }
 
-int open_stream(int device, Stream &st)
-{
-    int ndev = 0;
-    SNPGPU_HIP_CHECK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) { set_error("invalid device ordinal"); return 1; }
-    SNPGPU_HIP_CHECK(hipSetDevice(device));
-    SNPGPU_HIP_CHECK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-    for (auto &e : st.ev) SNPGPU_HIP_CHECK(hipEventCreate(&e));
-    return 0;
-}
-
-// a device view of an n x n output: the caller's buffer, or a device copy that is written back afterwards
-struct OutMat {
-    void *user = nullptr, *dev = nullptr;
-    size_t bytes = 0;
-    int mem = 0;
-    DevBuf *tmp = nullptr;
-    int open(Bufs &bufs, void *u, size_t b, int m, bool keep, hipStream_t s)
-    {
-        user = u; bytes = b; mem = m;
-        if (!u) return 0;
-        if (m == SNPGPU_DEVICE) { dev = u; return 0; }
-        int rc = 0;
-        tmp = bufs.get(b, rc);
-        if (rc) return 1;
-        dev = tmp->p;
-        if (keep) SNPGPU_HIP_CHECK(hipMemcpyAsync(dev, u, b, hipMemcpyHostToDevice, s));
-        return 0;
-    }
-    int close(hipStream_t s)
-    {
-        if (user && mem != SNPGPU_DEVICE) SNPGPU_HIP_CHECK(hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, s));
-        return 0;
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -168,7 +102,7 @@ int snpgpu_ibd_mle(const void *geno, int64_t n_snp, int64_t n_samp, int format, 
                    int32_t *niter, double *afreq_out, int out_mem, int device)
 {
     const char *fn = "snpgpu_ibd_mle";
-    if (check_args(fn, geno, n_snp, n_samp, format, mem)) return 1;
+    if (check_geno(fn, geno, n_snp, n_samp, format, mem, IBD_GENO)) return 1;
     if (!k0 || !k1) { set_error("snpgpu_ibd_mle: k0 / k1 is NULL"); return 1; }
     if (out_mem != SNPGPU_HOST && out_mem != SNPGPU_DEVICE) { set_error("snpgpu_ibd_mle: invalid out_mem"); return 1; }
     int64_t r0 = row_begin, r1 = row_end;
@@ -177,11 +111,12 @@ int snpgpu_ibd_mle(const void *geno, int64_t n_snp, int64_t n_samp, int format, 
     if (r0 < 0 || r1 > n_samp || r0 >= r1) { set_error("snpgpu_ibd_mle: invalid row range"); return 1; }
     for (double &s : g_stats) s = 0;
 
-    Stream st;
-    Bufs bufs;
-    if (open_stream(device, st)) return 1;
+    Call c;
+    if (c.open(fn, device, true)) return 1;
+    CallStream &st = c.st;
+    DevArena &bufs = c.bufs;
     Prep P;
-    if (prepare(fn, st, bufs, geno, n_snp, n_samp, mem, allele_freq, P)) return 1;
+    if (prepare(st, bufs, geno, n_snp, n_samp, mem, allele_freq, P)) return 1;
     if (afreq_out) std::copy(P.af.begin(), P.af.end(), afreq_out);
 
     // Init_EPrIBD_IBS(afreq, NULL, false), src/genIBD.cpp:253-338: plain monomials, SNPs with a finite p in [0, 1]
@@ -236,21 +171,20 @@ int snpgpu_ibd_mle(const void *geno, int64_t n_snp, int64_t n_samp, int format, 
     const int64_t want = (n_pairs + 63) / 64;
     const int n_waves = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)cus * 16));
 
-    SNPGPU_HIP_CHECK(hipEventRecord(st.ev[0], st.s));
+    if (c.log.begin(T_EM, st.s)) return 1;
     if (launch_ibd_em(st.s, n_waves, (const uint32_t *)P.gt->p, P.w4, P.tab->p, (const double *)mk0->p,
                       (const double *)mk1->p, (const int64_t *)drow->p, n_rows, r0, n_samp, n_pairs, max_niter, reltol,
                       (unsigned long long *)queue->p, (double *)pk0->p, (double *)pk1->p, (double *)pl->p,
                       (int32_t *)pn->p))
         return 1;
-    SNPGPU_HIP_CHECK(hipEventRecord(st.ev[1], st.s));
+    if (c.log.end(st.s) || c.log.begin(T_REST, st.s)) return 1;
     if (coeff_correct &&
         launch_ibd_candidates(st.s, (const uint32_t *)P.gt->p, P.w4, P.tab->p, (const int64_t *)drow->p, n_rows, r0, n_samp,
                               n_pairs, (const double *)pl->p, (double *)pk0->p, (double *)pk1->p))
         return 1;
-    SNPGPU_HIP_CHECK(hipEventRecord(st.ev[2], st.s));
 
     const size_t nn = (size_t)n_samp * (size_t)n_samp;
-    OutMat o0, o1, on;
+    HostOut o0, o1, on;
     if (o0.open(bufs, k0, nn * sizeof(double), out_mem, !whole, st.s) ||
         o1.open(bufs, k1, nn * sizeof(double), out_mem, !whole, st.s) ||
         on.open(bufs, niter, nn * sizeof(int32_t), out_mem, !whole, st.s))
@@ -259,15 +193,14 @@ int snpgpu_ibd_mle(const void *geno, int64_t n_snp, int64_t n_samp, int format, 
                           (const double *)pk1->p, (const int32_t *)pn->p, (double *)o0.dev, (double *)o1.dev,
                           (int32_t *)on.dev))
         return 1;
-    SNPGPU_HIP_CHECK(hipEventRecord(st.ev[3], st.s));
+    if (c.log.end(st.s)) return 1;
     if (o0.close(st.s) || o1.close(st.s) || on.close(st.s)) return 1;
     unsigned long long q[3] = {0, 0, 0};
     SNPGPU_HIP_CHECK(hipMemcpyAsync(q, queue->p, sizeof(q), hipMemcpyDeviceToHost, st.s));
     SNPGPU_HIP_CHECK(hipStreamSynchronize(st.s));
-    float ms_em = 0, ms_all = 0;
-    (void)hipEventElapsedTime(&ms_em, st.ev[0], st.ev[1]);
-    (void)hipEventElapsedTime(&ms_all, st.ev[0], st.ev[3]);
-    g_stats[0] = ms_em; g_stats[1] = ms_all; g_stats[2] = (double)q[1]; g_stats[3] = (double)q[2];
+    double ms_rest = 0;
+    if (c.log.sum_ms(T_EM, &g_stats[0]) || c.log.sum_ms(T_REST, &ms_rest)) return 1;
+    g_stats[1] = g_stats[0] + ms_rest; g_stats[2] = (double)q[1]; g_stats[3] = (double)q[2];
     return 0;
 }
 
@@ -276,15 +209,16 @@ int snpgpu_ibd_loglik(const void *geno, int64_t n_snp, int64_t n_samp, int forma
                       int out_mem, int device)
 {
     const char *fn = "snpgpu_ibd_loglik";
-    if (check_args(fn, geno, n_snp, n_samp, format, mem)) return 1;
+    if (check_geno(fn, geno, n_snp, n_samp, format, mem, IBD_GENO)) return 1;
     if (!out) { set_error("snpgpu_ibd_loglik: out is NULL"); return 1; }
     if ((k0 == nullptr) != (k1 == nullptr)) { set_error("snpgpu_ibd_loglik: give both k0 and k1 matrices, or neither"); return 1; }
     if (out_mem != SNPGPU_HOST && out_mem != SNPGPU_DEVICE) { set_error("snpgpu_ibd_loglik: invalid out_mem"); return 1; }
-    Stream st;
-    Bufs bufs;
-    if (open_stream(device, st)) return 1;
+    Call c;
+    if (c.open(fn, device, false)) return 1;
+    CallStream &st = c.st;
+    DevArena &bufs = c.bufs;
     Prep P;
-    if (prepare(fn, st, bufs, geno, n_snp, n_samp, mem, allele_freq, P)) return 1;
+    if (prepare(st, bufs, geno, n_snp, n_samp, mem, allele_freq, P)) return 1;
     if (afreq_out) std::copy(P.af.begin(), P.af.end(), afreq_out);
     int rc = 0;
     const std::vector<int64_t> off = row_offsets(n_samp, 0, n_samp, true);
@@ -292,7 +226,7 @@ int snpgpu_ibd_loglik(const void *geno, int64_t n_snp, int64_t n_samp, int forma
     if (rc) return 1;
     SNPGPU_HIP_CHECK(hipMemcpyAsync(drow->p, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, st.s));
     const size_t nn = (size_t)n_samp * (size_t)n_samp;
-    OutMat m0, m1, o;
+    HostOut m0, m1, o;
     if (k0) {
         if (m0.open(bufs, (void *)k0, nn * sizeof(double), out_mem, true, st.s) ||
             m1.open(bufs, (void *)k1, nn * sizeof(double), out_mem, true, st.s))

@@ -17,10 +17,9 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
-#include <string>
 #include <vector>
 
-#include "snpgpu_internal.h"
+#include "host_util.h"
 
 using namespace snpgpu;
 
@@ -29,7 +28,6 @@ namespace {
 inline int64_t pr_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 constexpr size_t PRUNE_TABLE_BUDGET = size_t(1) << 30;   // bytes of band tables per launch
 constexpr int64_t PRUNE_BLOCK_DEFAULT = 16384;          // rows per streamed block
-constexpr size_t PRUNE_RAW_BYTES = size_t(64) << 20;    // host-input staging buffer, at most
 
 // the reference's window test: kept SNP j is still listed at candidate i (position differences exact in 64 bits)
 inline bool in_window(int64_t i, int64_t j, const int32_t *pos, int32_t max_bp, int32_t max_n)
@@ -110,75 +108,6 @@ int prune_scan(int64_t M, int64_t start, const int32_t *pos, int32_t max_bp, int
     return 0;
 }
 
-// HIP events around the phases of one call
-struct PruneTimer {
-    hipStream_t st;
-    bool on;
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> ev;
-    PruneTimer(hipStream_t s, bool enable) : st(s), on(enable) {}
-    ~PruneTimer()
-    {
-        for (auto &e : ev) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
-    }
-    int begin(int phase)
-    {
-        if (!on) return 0;
-        hipEvent_t a, b;
-        SNPGPU_HIP_CHECK(hipEventCreate(&a));
-        if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); set_error("snpgpu_ld_prune: hipEventCreate failed"); return 1; }
-        ev.push_back({phase, {a, b}});
-        SNPGPU_HIP_CHECK(hipEventRecord(a, st));
-        return 0;
-    }
-    int end()
-    {
-        if (!on) return 0;
-        SNPGPU_HIP_CHECK(hipEventRecord(ev.back().second.second, st));
-        return 0;
-    }
-    int sum(double (&ms)[4])
-    {
-        for (auto &e : ev) {
-            float t = 0;
-            SNPGPU_HIP_CHECK(hipEventElapsedTime(&t, e.second.first, e.second.second));
-            ms[e.first] += t;
-        }
-        return 0;
-    }
-};
-
-struct PruneBufs {
-    DevBuf rows[2], raw, tab, bits;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    ~PruneBufs()
-    {
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (auto &b : rows) b.release();
-        raw.release(); tab.release(); bits.release();
-        if (own_stream) (void)hipStreamDestroy(stream);
-    }
-};
-
-// n caller rows -> staging rows at dst (host input through `raw`, at most PRUNE_RAW_BYTES per copy)
-int prune_stage(PruneBufs &b, const uint8_t *src, int64_t n, int64_t N, int64_t rbp, int format, int mem, uint8_t *dst)
-{
-    if (mem == SNPGPU_DEVICE) return launch_ld_stage(b.stream, src, format, n, N, rbp, dst);
-    const int64_t irb = format == SNPGPU_GENO_U8 ? N : (N + 3) / 4;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)PRUNE_RAW_BYTES / irb));
-    if (b.raw.bytes < (size_t)(chunk * irb)) {
-        SNPGPU_HIP_CHECK(hipStreamSynchronize(b.stream));
-        b.raw.release();
-        if (b.raw.alloc((size_t)(chunk * irb))) return 1;
-    }
-    for (int64_t o = 0; o < n; o += chunk) {
-        const int64_t m = std::min(chunk, n - o);
-        SNPGPU_HIP_CHECK(hipMemcpyAsync(b.raw.p, src + o * irb, (size_t)(m * irb), hipMemcpyHostToDevice, b.stream));
-        if (launch_ld_stage(b.stream, b.raw.p, format, m, N, rbp, dst + o * rbp)) return 1;
-    }
-    return 0;
-}
-
 // 64 x 64 tiles a band launch computes (ld_count_kernel<true>'s exit rule)
 int64_t band_tiles(int64_t n_i, int64_t n_b, int64_t W)
 {
@@ -191,14 +120,9 @@ int64_t band_tiles(int64_t n_i, int64_t n_b, int64_t W)
 
 int check_args(const char *fn, const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, int64_t start_idx, int method)
 {
-    const std::string f(fn);
-    if (!geno) { set_error(f + ": NULL argument"); return 1; }
-    if (n_snp <= 0 || n_snp > 0x3fffffffLL) { set_error(f + ": invalid number of SNPs"); return 1; }
-    if (n_samp <= 0 || n_samp >= (int64_t(1) << 24)) { set_error(f + ": invalid number of samples (1 ... 2^24 - 1)"); return 1; }
-    if (format != SNPGPU_GENO_U8 && format != SNPGPU_GENO_PACKED2) { set_error(f + ": invalid genotype format"); return 1; }
-    if (mem != SNPGPU_HOST && mem != SNPGPU_DEVICE) { set_error(f + ": invalid memory kind"); return 1; }
-    if (start_idx < 0 || start_idx >= n_snp) { set_error(f + ": invalid start index (0 ... n_snp - 1)"); return 1; }
-    if (method < SNPGPU_LD_COMPOSITE || method > SNPGPU_LD_CORR) { set_error(f + ": invalid LD method (1 ... 4: composite, r, dprime, corr)"); return 1; }
+    if (check_geno(fn, geno, n_snp, n_samp, format, mem, LD_GENO)) return 1;
+    if (start_idx < 0 || start_idx >= n_snp) return fail(fn, "invalid start index (0 ... n_snp - 1)");
+    if (method < SNPGPU_LD_COMPOSITE || method > SNPGPU_LD_CORR) return fail(fn, "invalid LD method (1 ... 4: composite, r, dprime, corr)");
     return 0;
 }
 
@@ -208,20 +132,15 @@ int prune_bits(const char *fn, const uint8_t *geno, int64_t M, int64_t N, int fo
 {
     snpgpu_opts o{};
     if (opts) o = *opts;
-    int ndev = 0;
-    SNPGPU_HIP_CHECK(hipGetDeviceCount(&ndev));
-    if (ndev <= 0) { set_error(std::string(fn) + ": no HIP device (the GPU path has no CPU fallback)"); return 1; }
-    if (o.device < 0 || o.device >= ndev) { set_error(std::string(fn) + ": invalid device ordinal"); return 1; }
+    Call c;
+    if (c.open(fn, o.device, info != nullptr, o.stream)) return 1;
+    hipStream_t s = c.st.s;
+    EventLog &tm = c.log;
     const int64_t wpr = (W + 63) / 64;
     try { bits.assign((size_t)(M * wpr), 0); }
-    catch (...) { set_error(std::string(fn) + ": host allocation of the bit rows failed"); return 1; }
+    catch (...) { return fail(fn, "host allocation of the bit rows failed"); }
     if (W == 0) return 0;
-    if (W > 0x3fffffffLL) { set_error(std::string(fn) + ": invalid band width"); return 1; }
-    SNPGPU_HIP_CHECK(hipSetDevice(o.device));
-    PruneBufs b;
-    if (o.stream) b.stream = (hipStream_t)o.stream;
-    else if (hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking) == hipSuccess) b.own_stream = true;
-    else { set_error(std::string(fn) + ": hipStreamCreate failed"); return 1; }
+    if (W > 0x3fffffffLL) return fail(fn, "invalid band width");
 
     const int64_t rbp = pr_up((N + 3) / 4, 32);
     const int64_t irb = format == SNPGPU_GENO_U8 ? N : (N + 3) / 4;
@@ -230,57 +149,55 @@ int prune_bits(const char *fn, const uint8_t *geno, int64_t M, int64_t N, int fo
     const int64_t P = std::max<int64_t>(64, std::min(pr_up(blk, 64), (int64_t)(PRUNE_TABLE_BUDGET / ((size_t)W * 36)) / 64 * 64));
     // the table kernel reads whole 64-row tiles, up to 63 rows past the resident ones: one spare tile
     const size_t rbytes = (size_t)(pr_up(cap, 64) + 64) * (size_t)rbp;
-    int rc = b.rows[0].alloc(rbytes);
-    if (!rc && cap < M) rc = b.rows[1].alloc(rbytes);
-    if (!rc) rc = b.tab.alloc((size_t)(P * W * 36)) | b.bits.alloc((size_t)(P * wpr * 8));
-    if (rc) { set_error(std::string(fn) + ": device allocation failed"); return 1; }
+    int rc = 0;
+    DevBuf *rows[2] = {c.bufs.get(rbytes, rc), cap < M ? c.bufs.get(rbytes, rc) : nullptr};
+    DevBuf *tab = c.bufs.get((size_t)(P * W * 36), rc), *dbits = c.bufs.get((size_t)(P * wpr * 8), rc), *raw = c.bufs.get(0, rc);
+    if (rc) return fail(fn, "device allocation failed");
     // rows past the data only meet pairs the kernel never writes; a defined content all the same, for the spare tile only
-    for (auto &r : b.rows)
-        if (r.p) SNPGPU_HIP_CHECK(hipMemsetAsync((uint8_t *)r.p + (size_t)cap * rbp, 0xFF, r.bytes - (size_t)cap * rbp, b.stream));
+    for (DevBuf *r : rows)
+        if (r) SNPGPU_HIP_CHECK(hipMemsetAsync((uint8_t *)r->p + (size_t)cap * rbp, 0xFF, r->bytes - (size_t)cap * rbp, s));
 
-    PruneTimer tm(b.stream, info != nullptr);
     enum { ST = 0, TAB = 1, BITS = 2, CPY = 3 };
     int64_t n_fed = 0, base = 0, n_res = 0, done = 0, launches = 0, tiles = 0;
     int cur = 0;
     while (n_fed < M) {
         const int64_t m = std::min(M - n_fed, cap - n_res);
-        if (tm.begin(ST) || prune_stage(b, geno + n_fed * irb, m, N, rbp, format, mem, (uint8_t *)b.rows[cur].p + n_res * rbp) ||
-            tm.end())
+        if (tm.begin(ST, s) || stage_ld_rows(s, *raw, geno + n_fed * irb, m, N, rbp, format, mem, (uint8_t *)rows[cur]->p + n_res * rbp) ||
+            tm.end(s))
             return 1;
         n_res += m; n_fed += m;
         const bool last = n_fed == M;
         const int64_t i_end = last ? M : base + n_res - W;
-        const uint8_t *rows = (const uint8_t *)b.rows[cur].p;
+        const uint8_t *res = (const uint8_t *)rows[cur]->p;
         for (int64_t i0 = done; i0 < i_end; i0 += P) {
             const int64_t n_i = std::min(P, i_end - i0);
-            if (tm.begin(TAB) ||
-                launch_ld_count_band(b.stream, rows, (int)(i0 - base), (int)n_i, (int)n_res, (int)W, rbp, (int32_t *)b.tab.p) ||
-                tm.end())
+            if (tm.begin(TAB, s) || launch_ld_count_band(s, res, (int)(i0 - base), (int)n_i, (int)n_res, (int)W, rbp, (int32_t *)tab->p) ||
+                tm.end(s))
                 return 1;
-            if (tm.begin(BITS) ||
-                launch_ld_prune_bits(b.stream, (const int32_t *)b.tab.p, n_i, (int)W, i0, M, start, method, threshold, (uint64_t *)b.bits.p) ||
-                tm.end())
+            if (tm.begin(BITS, s) ||
+                launch_ld_prune_bits(s, (const int32_t *)tab->p, n_i, (int)W, i0, M, start, method, threshold, (uint64_t *)dbits->p) ||
+                tm.end(s))
                 return 1;
-            if (tm.begin(CPY)) return 1;
-            SNPGPU_HIP_CHECK(hipMemcpyAsync(bits.data() + i0 * wpr, b.bits.p, (size_t)(n_i * wpr) * 8, hipMemcpyDeviceToHost, b.stream));
-            if (tm.end()) return 1;
+            if (tm.begin(CPY, s)) return 1;
+            SNPGPU_HIP_CHECK(hipMemcpyAsync(bits.data() + i0 * wpr, dbits->p, (size_t)(n_i * wpr) * 8, hipMemcpyDeviceToHost, s));
+            if (tm.end(s)) return 1;
             launches++;
             tiles += band_tiles(n_i, n_res - (i0 - base), W);
         }
         done = i_end;
         if (!last) {
             const int nxt = cur ^ 1;
-            if (tm.begin(ST)) return 1;
-            SNPGPU_HIP_CHECK(hipMemcpyAsync(b.rows[nxt].p, rows + (i_end - base) * rbp, (size_t)(W * rbp), hipMemcpyDeviceToDevice, b.stream));
-            if (tm.end()) return 1;
+            if (tm.begin(ST, s)) return 1;
+            SNPGPU_HIP_CHECK(hipMemcpyAsync(rows[nxt]->p, res + (i_end - base) * rbp, (size_t)(W * rbp), hipMemcpyDeviceToDevice, s));
+            if (tm.end(s)) return 1;
             cur = nxt; base = i_end; n_res = W;
         }
     }
-    if (hipStreamSynchronize(b.stream) != hipSuccess) { set_error(std::string(fn) + ": kernel failed"); return 1; }
+    if (hipStreamSynchronize(s) != hipSuccess) return fail(fn, "kernel failed");
     if (info) {
-        double ms[4] = {0, 0, 0, 0};
-        if (tm.sum(ms)) return 1;
-        info->ms_stage = ms[ST]; info->ms_tables = ms[TAB]; info->ms_bits = ms[BITS]; info->ms_copy = ms[CPY];
+        if (tm.sum_ms(ST, &info->ms_stage) || tm.sum_ms(TAB, &info->ms_tables) || tm.sum_ms(BITS, &info->ms_bits) ||
+            tm.sum_ms(CPY, &info->ms_copy))
+            return 1;
         info->table_launches = launches;
         info->table_tiles = tiles;
     }

@@ -7,12 +7,9 @@
 // sum over them.  2-bit rows are counted where they lie (no re-layout); one-byte genotypes go through the existing repack first.
 // All argument errors are found before any device is touched.
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
-#include <string>
 #include <vector>
 
-#include "snpgpu_internal.h"
+#include "host_util.h"
 
 namespace snpgpu {
 int launch_pop_mask(hipStream_t st, const int32_t *pop, int64_t n_samp, int64_t rb, int K, int n_var, int h0, int g, int64_t mbytes,
@@ -36,50 +33,8 @@ thread_local double g_stats[4] = {0, 0, 0, 0};   // counter kernel ms, its launc
 constexpr size_t POP_STAGE_BYTES = size_t(256) << 20;    // genotype bytes per streamed block
 constexpr size_t POP_SUMH_BYTES = size_t(64) << 20;      // W&H02 window sums per launch
 
-struct Bufs {
-    std::vector<DevBuf *> all;
-    ~Bufs() { for (DevBuf *b : all) { b->release(); delete b; } }
-    DevBuf *get(size_t bytes, int &rc)
-    {
-        DevBuf *b = new DevBuf;
-        all.push_back(b);
-        if (!rc) rc = b->alloc(bytes);
-        return b;
-    }
-};
-
-struct Stream {
-    hipStream_t s = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~Stream()
-    {
-        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-        if (s) (void)hipStreamDestroy(s);
-    }
-    int open(const char *fn, int device)
-    {
-        int ndev = 0;
-        SNPGPU_HIP_CHECK(hipGetDeviceCount(&ndev));
-        if (ndev <= 0) { set_error(std::string(fn) + ": no HIP device (the GPU path has no CPU fallback)"); return 1; }
-        if (device < 0 || device >= ndev) { set_error(std::string(fn) + ": invalid device ordinal"); return 1; }
-        SNPGPU_HIP_CHECK(hipSetDevice(device));
-        SNPGPU_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        for (auto &e : ev) SNPGPU_HIP_CHECK(hipEventCreate(&e));
-        return 0;
-    }
-};
-
-int fail(const char *fn, const char *msg) { set_error(std::string(fn) + ": " + msg); return 1; }
-
-int check_geno(const char *fn, const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem)
-{
-    if (!geno) return fail(fn, "geno is NULL");
-    if (n_snp < 1) return fail(fn, "no SNP in the working dataset");
-    if (n_samp < 1 || n_samp >= (int64_t(1) << 30)) return fail(fn, "invalid number of samples (1 ... 2^30 - 1)");
-    if (format != SNPGPU_GENO_U8 && format != SNPGPU_GENO_PACKED2) return fail(fn, "invalid genotype format");
-    if (mem != SNPGPU_HOST && mem != SNPGPU_DEVICE) return fail(fn, "invalid memory kind");
-    return 0;
-}
+constexpr GenoLimits POP_GENO = {1, int64_t(1) << 30, NO_LIMIT, false, "invalid number of samples (1 ... 2^30 - 1)"};
+enum { T_COUNT = 0, T_FST = 1 };   // phases of a call's EventLog (always on: snpgpu_pop_stats reports every call)
 
 int check_pop(const char *fn, const int32_t *pop, int64_t n_samp, int n_pop)
 {
@@ -118,61 +73,42 @@ int check_windows(const char *fn, const int64_t *offsets, const int32_t *snp_ind
 }
 
 // the counters of all n_snp rows into device arrays [n_snp][K]; pop: host, 0-based
-int count_all(Stream &st, Bufs &bufs, const void *geno, int64_t n_snp, int64_t N, int format, int mem, const int32_t *pop, int K,
-              int32_t *dacnt, int32_t *dcnt)
+int count_all(Call &c, const void *geno, int64_t n_snp, int64_t N, int format, int mem, const int32_t *pop, int K, int32_t *dacnt,
+              int32_t *dcnt)
 {
-    const bool repack = format == SNPGPU_GENO_U8;
-    const int64_t rb_in = repack ? N : (N + 3) / 4;
-    const int64_t rb = repack ? (N + 255) / 256 * 64 : rb_in;        // bytes per row the counter kernel reads
+    hipStream_t s = c.st.s;
     // 2-bit rows in device memory need no staging buffer: one launch over all of them.  Everything else goes through buffers of
     // the staging budget, block by block (SNPGPU_POP_BLOCK_SNPS: a block size for either case, e.g. to test the streaming)
-    int64_t B = (mem == SNPGPU_DEVICE && !repack) ? (n_snp + 15) / 16 * 16 : (int64_t)(POP_STAGE_BYTES / (size_t)rb_in);
-    if (const char *e = getenv("SNPGPU_POP_BLOCK_SNPS")) { if (atoll(e) > 0) B = atoll(e); }
-    B = std::max<int64_t>(16, B / 16 * 16);                          // whole 16-byte lines: every block starts on the same line offset
-    B = std::min(B, (n_snp + 15) / 16 * 16);
-
-    int rc = 0;
-    DevBuf *raw = mem == SNPGPU_HOST ? bufs.get((size_t)(B * rb_in) + 32, rc) : nullptr;
-    DevBuf *packed = repack ? bufs.get((size_t)(B * rb) + 32, rc) : nullptr;
-    if (rc) return 1;
-    const uint8_t *first = repack ? (const uint8_t *)packed->p : raw ? (const uint8_t *)raw->p : (const uint8_t *)geno;
-    const int h0 = (int)((uintptr_t)first & 15);
+    RowBlocks blocks;
+    if (blocks.open(c.bufs, geno, n_snp, N, format, mem, POP_STAGE_BYTES, NO_LIMIT, "SNPGPU_POP_BLOCK_SNPS")) return 1;
+    const int64_t rb = blocks.rb;                                    // bytes per row the counter kernel reads
+    const int h0 = (int)((uintptr_t)blocks.first() & 15);
     int g = 16;
     while (rb % g) g >>= 1;                                          // gcd(rb, 16)
     const int n_var = 16 / g;
     const int64_t mbytes = (rb + 15 + 15) / 16 * 16, mvec = mbytes / 16;
-    DevBuf *mask = bufs.get((size_t)n_var * (size_t)K * (size_t)mbytes, rc);
-    DevBuf *dpop = bufs.get(sizeof(int32_t) * (size_t)N, rc);
+    int rc = 0;
+    DevBuf *mask = c.bufs.get((size_t)n_var * (size_t)K * (size_t)mbytes, rc);
+    DevBuf *dpop = c.bufs.get(sizeof(int32_t) * (size_t)N, rc);
     if (rc) return 1;
-    SNPGPU_HIP_CHECK(hipMemcpyAsync(dpop->p, pop, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, st.s));
-    if (launch_pop_mask(st.s, (const int32_t *)dpop->p, N, rb, K, n_var, h0, g, mbytes, (uint8_t *)mask->p)) return 1;
+    SNPGPU_HIP_CHECK(hipMemcpyAsync(dpop->p, pop, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, s));
+    if (launch_pop_mask(s, (const int32_t *)dpop->p, N, rb, K, n_var, h0, g, mbytes, (uint8_t *)mask->p)) return 1;
 
-    for (int64_t i0 = 0; i0 < n_snp; i0 += B) {
-        const int64_t nb = std::min(B, n_snp - i0);
-        const uint8_t *src = (const uint8_t *)geno + i0 * rb_in;
-        if (raw) {
-            SNPGPU_HIP_CHECK(hipMemcpyAsync(raw->p, src, (size_t)(nb * rb_in), hipMemcpyHostToDevice, st.s));
-            src = (const uint8_t *)raw->p;
-        }
-        if (repack) {
-            if (launch_repack(st.s, src, format, nb, N, (uint8_t *)packed->p, rb)) return 1;
-            src = (const uint8_t *)packed->p;
-        }
-        SNPGPU_HIP_CHECK(hipEventRecord(st.ev[0], st.s));
-        if (launch_pop_count(st.s, src, rb, nb, K, n_var, h0, g, mvec, mask->p, dacnt + i0 * K, dcnt + i0 * K)) return 1;
-        SNPGPU_HIP_CHECK(hipEventRecord(st.ev[1], st.s));
-        SNPGPU_HIP_CHECK(hipStreamSynchronize(st.s));                // the staging buffers are reused by the next block
-        float ms = 0;
-        SNPGPU_HIP_CHECK(hipEventElapsedTime(&ms, st.ev[0], st.ev[1]));
-        g_stats[0] += ms; g_stats[1] += 1; g_stats[3] += (double)nb * (double)rb;
-    }
-    return 0;
+    return blocks.for_each(s, [&](const uint8_t *src, int64_t, int64_t i0, int64_t nb) {
+        if (c.log.begin(T_COUNT, s) ||
+            launch_pop_count(s, src, rb, nb, K, n_var, h0, g, mvec, mask->p, dacnt + i0 * K, dcnt + i0 * K) || c.log.end(s))
+            return 1;
+        g_stats[1] += 1; g_stats[3] += (double)nb * (double)rb;
+        return c.log.wait_last(&g_stats[0]);
+    });
 }
 
 // Fst of the windows (CSR, host arrays; offsets == NULL: one window of all SNPs) from the device counters
-int fst_core(Stream &st, Bufs &bufs, const int32_t *dacnt, const int32_t *dcnt, int64_t n_snp, int K, int method, const int64_t *offsets,
+int fst_core(Call &c, const int32_t *dacnt, const int32_t *dcnt, int64_t n_snp, int K, int method, const int64_t *offsets,
              const int32_t *snp_index, int64_t n_win, double *fst_win, double *beta_win, double *fst_snp)
 {
+    CallStream &st = c.st;
+    DevArena &bufs = c.bufs;
     int rc = 0;
     const int64_t whole[2] = {0, n_snp};
     if (!offsets) { offsets = whole; snp_index = nullptr; n_win = 1; }
@@ -186,7 +122,7 @@ int fst_core(Stream &st, Bufs &bufs, const int32_t *dacnt, const int32_t *dcnt, 
     if (n_idx > 0)
         SNPGPU_HIP_CHECK(hipMemcpyAsync(didx->p, snp_index, sizeof(int32_t) * (size_t)n_idx, hipMemcpyHostToDevice, st.s));
     const int32_t *idx = snp_index ? (const int32_t *)didx->p : nullptr;
-    SNPGPU_HIP_CHECK(hipEventRecord(st.ev[0], st.s));
+    if (c.log.begin(T_FST, st.s)) return 1;
     if (launch_fst_terms(st.s, method, dacnt, dcnt, n_snp, K, (double *)dnum->p, (double *)dden->p, (double *)dratio->p,
                          (uint8_t *)dvalid->p))
         return 1;
@@ -213,13 +149,10 @@ int fst_core(Stream &st, Bufs &bufs, const int32_t *dacnt, const int32_t *dcnt, 
                                                 hipMemcpyDeviceToHost, st.s));
         }
     }
-    SNPGPU_HIP_CHECK(hipEventRecord(st.ev[1], st.s));
+    if (c.log.end(st.s)) return 1;
     if (fst_snp) SNPGPU_HIP_CHECK(hipMemcpyAsync(fst_snp, dratio->p, sizeof(double) * (size_t)n_snp, hipMemcpyDeviceToHost, st.s));
     SNPGPU_HIP_CHECK(hipStreamSynchronize(st.s));
-    float ms = 0;
-    SNPGPU_HIP_CHECK(hipEventElapsedTime(&ms, st.ev[0], st.ev[1]));
-    g_stats[2] = ms;
-    return 0;
+    return c.log.sum_ms(T_FST, &g_stats[2]);
 }
 
 // counters of the whole input on the device, then the windows' Fst (offsets == NULL: all SNPs as one window)
@@ -227,15 +160,14 @@ int fst_run(const char *fn, const void *geno, int64_t n_snp, int64_t n_samp, int
             const int64_t *offsets, const int32_t *snp_index, int64_t n_win, double *fst_win, double *beta_win, double *fst_snp, int device)
 {
     for (double &s : g_stats) s = 0;
-    Stream st;
-    Bufs bufs;
-    if (st.open(fn, device)) return 1;
+    Call c;
+    if (c.open(fn, device, true)) return 1;
     int rc = 0;
     const size_t bytes = sizeof(int32_t) * (size_t)n_snp * (size_t)n_pop;
-    DevBuf *da = bufs.get(bytes, rc), *dc = bufs.get(bytes, rc);
+    DevBuf *da = c.bufs.get(bytes, rc), *dc = c.bufs.get(bytes, rc);
     if (rc) return 1;
-    if (count_all(st, bufs, geno, n_snp, n_samp, format, mem, pop, n_pop, (int32_t *)da->p, (int32_t *)dc->p)) return 1;
-    return fst_core(st, bufs, (const int32_t *)da->p, (const int32_t *)dc->p, n_snp, n_pop, method, offsets, snp_index, n_win, fst_win,
+    if (count_all(c, geno, n_snp, n_samp, format, mem, pop, n_pop, (int32_t *)da->p, (int32_t *)dc->p)) return 1;
+    return fst_core(c, (const int32_t *)da->p, (const int32_t *)dc->p, n_snp, n_pop, method, offsets, snp_index, n_win, fst_win,
                     beta_win, fst_snp);
 }
 
@@ -247,27 +179,18 @@ int snpgpu_pop_counts(const void *geno, int64_t n_snp, int64_t n_samp, int forma
                       int32_t *acnt, int32_t *cnt, int out_mem, int device)
 {
     const char *fn = "snpgpu_pop_counts";
-    if (check_geno(fn, geno, n_snp, n_samp, format, mem) || check_pop(fn, pop, n_samp, n_pop)) return 1;
+    if (check_geno(fn, geno, n_snp, n_samp, format, mem, POP_GENO) || check_pop(fn, pop, n_samp, n_pop)) return 1;
     if (!acnt || !cnt) return fail(fn, "acnt / cnt is NULL");
     if (out_mem != SNPGPU_HOST && out_mem != SNPGPU_DEVICE) return fail(fn, "invalid out_mem");
     for (double &s : g_stats) s = 0;
-    Stream st;
-    Bufs bufs;
-    if (st.open(fn, device)) return 1;
+    Call c;
+    if (c.open(fn, device, true)) return 1;
     const size_t bytes = sizeof(int32_t) * (size_t)n_snp * (size_t)n_pop;
-    int32_t *da = acnt, *dc = cnt;
-    if (out_mem == SNPGPU_HOST) {
-        int rc = 0;
-        da = (int32_t *)bufs.get(bytes, rc)->p;
-        dc = (int32_t *)bufs.get(bytes, rc)->p;
-        if (rc) return 1;
-    }
-    if (count_all(st, bufs, geno, n_snp, n_samp, format, mem, pop, n_pop, da, dc)) return 1;
-    if (out_mem == SNPGPU_HOST) {
-        SNPGPU_HIP_CHECK(hipMemcpyAsync(acnt, da, bytes, hipMemcpyDeviceToHost, st.s));
-        SNPGPU_HIP_CHECK(hipMemcpyAsync(cnt, dc, bytes, hipMemcpyDeviceToHost, st.s));
-    }
-    SNPGPU_HIP_CHECK(hipStreamSynchronize(st.s));
+    HostOut oa, oc;
+    if (oa.open(c.bufs, acnt, bytes, out_mem, false, c.st.s) || oc.open(c.bufs, cnt, bytes, out_mem, false, c.st.s)) return 1;
+    if (count_all(c, geno, n_snp, n_samp, format, mem, pop, n_pop, (int32_t *)oa.dev, (int32_t *)oc.dev)) return 1;
+    if (oa.close(c.st.s) || oc.close(c.st.s)) return 1;
+    SNPGPU_HIP_CHECK(hipStreamSynchronize(c.st.s));
     return 0;
 }
 
@@ -276,7 +199,7 @@ int snpgpu_fst_windows(const void *geno, int64_t n_snp, int64_t n_samp, int form
                        double *fst_snp, int device)
 {
     const char *fn = "snpgpu_fst_windows";
-    if (check_geno(fn, geno, n_snp, n_samp, format, mem) || check_pop(fn, pop, n_samp, n_pop) || check_method(fn, method) ||
+    if (check_geno(fn, geno, n_snp, n_samp, format, mem, POP_GENO) || check_pop(fn, pop, n_samp, n_pop) || check_method(fn, method) ||
         check_windows(fn, offsets, snp_index, n_win, n_snp))
         return 1;
     if (!fst_win) return fail(fn, "fst_win is NULL");
@@ -287,7 +210,7 @@ int snpgpu_fst(const void *geno, int64_t n_snp, int64_t n_samp, int format, int 
                double *fst, double *fst_snp, double *beta, int device)
 {
     const char *fn = "snpgpu_fst";
-    if (check_geno(fn, geno, n_snp, n_samp, format, mem) || check_pop(fn, pop, n_samp, n_pop) || check_method(fn, method)) return 1;
+    if (check_geno(fn, geno, n_snp, n_samp, format, mem, POP_GENO) || check_pop(fn, pop, n_samp, n_pop) || check_method(fn, method)) return 1;
     if (!fst) return fail(fn, "fst is NULL");
     return fst_run(fn, geno, n_snp, n_samp, format, mem, pop, n_pop, method, nullptr, nullptr, 1, fst, beta, fst_snp, device);
 }

@@ -3,7 +3,7 @@
 // (CGenoReadBySNP) stays with the caller exactly as for the pairwise accumulators.
 #include <cstring>
 
-#include "snpgpu_internal.h"
+#include "host_util.h"
 
 using namespace snpgpu;
 
@@ -83,11 +83,7 @@ int snpgpu_proj_create(int64_t n_samp, int n_eig, const snpgpu_opts *opts, snpgp
     if (n_eig <= 0 || n_eig > 4096) { set_error("snpgpu_proj_create: invalid number of eigenvectors"); return 1; }
     snpgpu_opts o{};
     if (opts) o = *opts;
-    int ndev = 0;
-    SNPGPU_HIP_CHECK(hipGetDeviceCount(&ndev));
-    if (ndev <= 0) { set_error("snpgpu_proj_create: no HIP device (the GPU path has no CPU fallback)"); return 1; }
-    if (o.device < 0 || o.device >= ndev) { set_error("snpgpu_proj_create: invalid device ordinal"); return 1; }
-    SNPGPU_HIP_CHECK(hipSetDevice(o.device));
+    if (use_device("snpgpu_proj_create", o.device)) return 1;
     snpgpu_proj *p = new snpgpu_proj();
     p->device = o.device; p->N = n_samp; p->k = n_eig; p->kp = (int)up(n_eig, 16);
     p->RB = up(n_samp, 256) / 4;

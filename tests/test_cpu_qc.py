@@ -41,6 +41,8 @@ def test_refusals_without_a_device(hapmap):
         api.snpgdsIndInbCoef([0, 1], [0.5, 0.5], method="gcta1")
     with pytest.raises(TypeError):
         api.snpgdsIndInb(hapmap, out_num_iter=1, verbose=False)
+    with pytest.raises(ValueError, match="genotype rows have the wrong shape"):
+        _lib.hwe(np.zeros(8, np.uint8), 8)                     # one row given as a 1-D array
     # the C ABI refuses before it asks for a device
     L = _lib.lib()
     g = np.zeros((4, 2), np.uint8)
