@@ -637,6 +637,49 @@ int snpgpu_gnrHWE(double *pvalue);
 int snpgpu_gnrIndInb(const double *afreq, const char *method, double reltol, int out_num_iter, int verbose, double *coeff,
                      int32_t *niter);
 
+/* ---- (1h) hierarchical clustering and the permutation test of the tree: snpgdsHCluster, snpgdsCutTree ----------------------------
+ * snpgpu_hclust_average is host code and touches no device: R's hclust(as.dist(dist), method = "average") on an n x n matrix with
+ * leading dimension ld, of which, like as.dist, only the lower triangle (dist[i * ld + j], i > j) is read.
+ *   merge   int32 [n - 1][2], R's convention: singletons negative, earlier rows positive and 1-based, a singleton before a cluster,
+ *           two singletons as (-i, -j) with i < j, two clusters with the smaller row number first
+ *   height  double [n - 1], the average (Lance-Williams) distance of each merge
+ *   order   int32 [n], 1-based: the leaves with the first column of every merge to the left
+ * Nearest-neighbour lists: every row keeps its nearest neighbour among the later rows, the globally closest pair is merged into the
+ * row of lower index by (m_i d_ik + m_j d_jk) / (m_i + m_j), the rows that pointed at either are scanned again.  Both scans compare
+ * with a strict <, so of tied distances the one of lowest index wins.  Refused: n < 2, a non-finite entry in the lower triangle. */
+int snpgpu_hclust_average(int64_t n, const double *dist, int64_t ld, int32_t *merge, double *height, int32_t *order);
+/* gnrDistPerm (src/SNPRelate.cpp:502-677).  dist: double [n][n] in `mem` (host, or device memory of `device`); merge: host int32
+ * [n - 1][2] as above.  For merge m with member list A (the n1 members of the first column, then the n2 of the second), N = n1 + n2,
+ * NSub1 = min(n1, n2), NSub2 = N - NSub1: obs = mean of dist[A[i] * n + A[j]] over i < n1 <= j; every permutation re-splits A into
+ * NSub1 and NSub2 members and takes the same mean; z = (obs - mean) / sd with sd over n_perm - 1, and z = 0 when n1 = n2 = 1 or
+ * whenever sd > 0 is false (NaN included).  group: host int32 [n], the reference's sequential pass over the merges (:628-664).
+ * Outputs on the host: z, n1, n2 [n - 1] and group [n] are required; obs, perm_mean, perm_sd [n - 1] may be NULL (perm_mean and
+ * perm_sd are NaN for a merge of two singletons).
+ * Deliberate differences from the reference, whose Mersenne-Twister stream cannot be followed in parallel:
+ *   random stream   Philox4x32-10 keyed by `seed`, counter (draw >> 2, permutation, merge, 0), word draw & 3, u = (x + 0.5) 2^-32
+ *   draw rule       the reference's: for i in 0 ... NSub1 - 1 swap slot i with slot i + min(Range - 1, (int)(u (Range - 1) + 0.5)),
+ *                   Range = N - i, the product and the sum rounded separately (no fused multiply-add)
+ *   start           every permutation starts from the merge's member order rotated by an offset of its own, floor(u N) with u from
+ *                   word 0 of the block with counter (2^32 - 1, permutation, merge, 0).  The reference carries the arrangement
+ *                   over, which mixes it; started from the plain member order every time, the draw rule (slot i stays, and the
+ *                   last slot is drawn, with half the probability of the others) would favour some re-splits of a small cluster
+ *                   and shift its z by more than the Monte-Carlo spread
+ *   result          a function of (dist, merge, n_perm, seed) alone, bit-identical from run to run: every sum has a fixed order,
+ *                   mean and sd are taken over the n_perm values in index order (two passes)
+ * The device holds the matrix gathered into leaf order (n^2 doubles), the row sums of every merge (at most n^2 / 2 + n doubles) and
+ * the n_perm (n - 1) permutation values; a call the device cannot hold is refused.  Refused before the first HIP call: n < 2,
+ * n_perm < 50, a non-finite z_threshold, NULL required arguments, and a merge whose entries are out of range, refer to a row that
+ * is not earlier, or use a sample or a row twice. */
+int snpgpu_dist_perm(const double *dist, int64_t n, int mem, const int32_t *merge, int n_perm, double z_threshold, uint64_t seed, double *z,
+                     int32_t *n1, int32_t *n2, int32_t *group, double *obs, double *perm_mean, double *perm_sd, int device);
+/* gnrDistPerm(n, dist, merge, n.perm, z.threshold): merge as R holds it, column-major int [2][n - 1]; everything in host memory */
+int snpgpu_gnrDistPerm(int n_dist, const double *dist, const int32_t *merge, int n_perm, double z_threshold, uint64_t seed, double *z,
+                       int32_t *n1, int32_t *n2, int32_t *group, int device);
+/* of the last snpgpu_dist_perm / snpgpu_gnrDistPerm on this thread (HIP events): stats[0] ms of the gather and row-sum pass, [1] ms
+ * of the permutation kernels, [2] launches timed in [0], [3] launches timed in [1], [4] matrix elements the permutations gathered,
+ * [5] permutations evaluated */
+int snpgpu_tree_stats(double *stats);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------------------
  * What THIS device's matrix pipe sustains right now: a register-only stream of one MFMA instruction (never waiting on memory,
  * two waves per SIMD) run for `seconds`, rate taken over the second half.  The kernels of this library run against the socket

@@ -37,6 +37,7 @@
 //   gpu_gnrHWE()                                                src/genHWE.cpp:117-137
 //   gpu_gnrIndInb(afreq, method, reltol, num_iter, verbose)     src/genIBD.cpp:1847-2006
 //   gpu_gnrIndInbCoef(snp, afreq, reltol)                       src/genIBD.cpp:1814-1827
+//   gpu_gnrDistPerm(n, dist, merge, n.perm, z.threshold)        src/SNPRelate.cpp:549-677
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -861,6 +862,41 @@ COREARRAY_DLL_EXPORT SEXP gpu_gnrIndInbCoef(SEXP snp, SEXP afreq, SEXP reltol)
             gpu_fail();
         UNPROTECT(2);
         rv_ans = Rf_ScalarReal(f);
+    COREARRAY_CATCH
+}
+
+// R's random number interface (<R_ext/Random.h>; the reference's gnrDistPerm uses the same three)
+void GetRNGstate(void);
+void PutRNGstate(void);
+double unif_rand(void);
+
+// gnrDistPerm(n, dist, merge, n.perm, z.threshold), src/SNPRelate.cpp:549-677: list(z, n1, n2, group).  The permutations run on
+// the device with a counter-based stream (snpgpu_dist_perm); its 64-bit seed is drawn here from R's generator, so set.seed()
+// still governs a run -- the values differ from the CPU routine's, which consumes R's stream draw by draw.
+COREARRAY_DLL_EXPORT SEXP gpu_gnrDistPerm(SEXP N_Dist, SEXP Dist, SEXP Merge, SEXP N_Perm, SEXP Z_Threshold)
+{
+    const int n = Rf_asInteger(N_Dist), n_perm = Rf_asInteger(N_Perm);
+    const double z_threshold = as_real(Z_Threshold);
+    GetRNGstate();
+    const uint64_t hi = (uint64_t)(unif_rand() * 4294967296.0), lo = (uint64_t)(unif_rand() * 4294967296.0);
+    PutRNGstate();
+    COREARRAY_TRY
+        if (n < 2) throw ErrCoreArray("%s", "gnrDistPerm: a tree has at least two samples");
+        if (Rf_xlength(Dist) != (R_xlen_t)n * n || Rf_xlength(Merge) != 2 * (R_xlen_t)(n - 1))
+            throw ErrCoreArray("%s", "gnrDistPerm: 'dist' should be n x n and 'merge' (n - 1) x 2");
+        SEXP dist = PROTECT(Rf_coerceVector(Dist, REALSXP)), merge = PROTECT(Rf_coerceVector(Merge, INTSXP));
+        PROTECT(rv_ans = Rf_allocVector(VECSXP, 4));
+        SET_VECTOR_ELT(rv_ans, 0, Rf_allocVector(REALSXP, n - 1));
+        SET_VECTOR_ELT(rv_ans, 1, Rf_allocVector(INTSXP, n - 1));
+        SET_VECTOR_ELT(rv_ans, 2, Rf_allocVector(INTSXP, n - 1));
+        SET_VECTOR_ELT(rv_ans, 3, Rf_allocVector(INTSXP, n));
+        // R's matrix is column-major: dist[A[i] + n A[j]] there is dist[A[j]][A[i]] here, the transposed matrix -- the reference
+        // indexes REAL(Dist) as dist[I[i] * n + I[j]] too, so the same buffer gives the same entries
+        if (snpgpu_gnrDistPerm(n, REAL(dist), INTEGER(merge), n_perm, z_threshold, (hi << 32) | lo, REAL(VECTOR_ELT(rv_ans, 0)),
+                               INTEGER(VECTOR_ELT(rv_ans, 1)), INTEGER(VECTOR_ELT(rv_ans, 2)), INTEGER(VECTOR_ELT(rv_ans, 3)),
+                               opt_int("snpgpu.device", "SNPGPU_DEVICE", 0)))
+            gpu_fail();
+        UNPROTECT(3);
     COREARRAY_CATCH
 }
 

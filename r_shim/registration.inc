@@ -21,6 +21,7 @@ extern SEXP gpu_gnrSampFreq();
 extern SEXP gpu_gnrHWE();
 extern SEXP gpu_gnrIndInb(SEXP, SEXP, SEXP, SEXP, SEXP);
 extern SEXP gpu_gnrIndInbCoef(SEXP, SEXP, SEXP);
+extern SEXP gpu_gnrDistPerm(SEXP, SEXP, SEXP, SEXP, SEXP);
 //
 //   table entries:
 //     { "gnrGRM",             (DL_FUNC)&gpu_gnrGRM,             5 },
@@ -41,6 +42,7 @@ extern SEXP gpu_gnrIndInbCoef(SEXP, SEXP, SEXP);
 //     { "gnrHWE",             (DL_FUNC)&gpu_gnrHWE,             0 },
 //     { "gnrIndInb",          (DL_FUNC)&gpu_gnrIndInb,          5 },
 //     { "gnrIndInbCoef",      (DL_FUNC)&gpu_gnrIndInbCoef,      3 },
+//     { "gnrDistPerm",        (DL_FUNC)&gpu_gnrDistPerm,        5 },
 //
 // The CPU bodies (gnrGRM ... in src/genPCA.cpp, src/genIBS.cpp, src/genKING.cpp) may stay in the package as
 // unregistered functions -- e.g. behind options(snpgpu.enable = FALSE) with a second table -- or be deleted together

@@ -53,6 +53,7 @@ EXPORTS = [
     "snpgpu_pop_counts", "snpgpu_fst", "snpgpu_fst_windows", "snpgpu_pop_stats", "snpgpu_gnrFst", "snpgpu_gnrSlidingWindowFst",
     "snpgpu_geno_counts", "snpgpu_hwe", "snpgpu_hwe_counts", "snpgpu_ind_inb", "snpgpu_qc_stats", "snpgpu_gnrSampFreq", "snpgpu_gnrHWE",
     "snpgpu_gnrIndInb",
+    "snpgpu_hclust_average", "snpgpu_dist_perm", "snpgpu_gnrDistPerm", "snpgpu_tree_stats",
 ]
 FST_WC84, FST_WH02 = 1, 2
 FST_METHODS = ("W&C84", "W&H02")
@@ -260,6 +261,11 @@ def lib():
     L.snpgpu_gnrSampFreq.argtypes = [vp]
     L.snpgpu_gnrHWE.argtypes = [vp]
     L.snpgpu_gnrIndInb.argtypes = [vp, ctypes.c_char_p, dbl, c_int, c_int, vp, vp]
+    u64 = ctypes.c_uint64
+    L.snpgpu_hclust_average.argtypes = [i64, vp, i64, vp, vp, vp]
+    L.snpgpu_dist_perm.argtypes = [vp, i64, c_int, vp, c_int, dbl, u64, vp, vp, vp, vp, vp, vp, vp, c_int]
+    L.snpgpu_gnrDistPerm.argtypes = [c_int, vp, vp, c_int, dbl, u64, vp, vp, vp, vp, c_int]
+    L.snpgpu_tree_stats.argtypes = [vp]
     _lib = L
     return L
 
@@ -1077,3 +1083,48 @@ def ibd_loglik(geno, n_samp, allele_freq=None, k0=None, k1=None, k0_all=float("n
     check(lib().snpgpu_ibd_loglik(ptr, n_snp, int(n_samp), fmt, mem, _ptr(af_in), _ptr(m0), _ptr(m1),
                                   float(k0_all), float(k1_all), _ptr(out), None, HOST, int(device)))
     return out
+
+
+def hclust_average(dist):
+    """snpgpu_hclust_average on a square float64 matrix (its lower triangle): (merge int32 [n - 1][2], height [n - 1],
+    order int32 [n]) as R's hclust(as.dist(dist), method = "average") returns them.  Host code, no device."""
+    d = np.ascontiguousarray(dist, np.float64)
+    if d.ndim != 2 or d.shape[0] != d.shape[1]:
+        raise ValueError("dist should be a square matrix")
+    n = d.shape[0]
+    merge = np.zeros((max(n - 1, 0), 2), np.int32)
+    height = np.zeros(max(n - 1, 0), np.float64)
+    order = np.zeros(n, np.int32)
+    check(lib().snpgpu_hclust_average(n, _ptr(d), n, _ptr(merge), _ptr(height), _ptr(order)))
+    return merge, height, order
+
+
+def dist_perm(dist, merge, n_perm=5000, z_threshold=15.0, seed=0, device=0, n=None):
+    """snpgpu_dist_perm: dict(z, n1, n2, group, obs, perm_mean, perm_sd).  dist: a square float64 numpy matrix, or a device
+    address (int) with n; merge: int32 [n - 1][2] in R's convention."""
+    if isinstance(dist, int):
+        if n is None:
+            raise ValueError("a device matrix needs n")
+        ptr, mem, n = ctypes.c_void_p(dist), DEVICE, int(n)
+    else:
+        d = np.ascontiguousarray(dist, np.float64)
+        if d.ndim != 2 or d.shape[0] != d.shape[1]:
+            raise ValueError("dist should be a square matrix")
+        ptr, mem, n = _ptr(d), HOST, d.shape[0]
+    mg = np.ascontiguousarray(merge, np.int32)
+    if mg.shape != (n - 1, 2):
+        raise ValueError("merge should be [n - 1][2]")
+    nm = max(n - 1, 0)
+    z, obs, mean, sd = (np.zeros(nm, np.float64) for _ in range(4))
+    n1, n2, group = np.zeros(nm, np.int32), np.zeros(nm, np.int32), np.zeros(n, np.int32)
+    check(lib().snpgpu_dist_perm(ptr, n, mem, _ptr(mg), int(n_perm), float(z_threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(z),
+                                 _ptr(n1), _ptr(n2), _ptr(group), _ptr(obs), _ptr(mean), _ptr(sd), int(device)))
+    return dict(z=z, n1=n1, n2=n2, group=group, obs=obs, perm_mean=mean, perm_sd=sd)
+
+
+def tree_stats():
+    """dict of snpgpu_tree_stats for the last dist_perm on this thread"""
+    s = np.zeros(6, np.float64)
+    check(lib().snpgpu_tree_stats(_ptr(s)))
+    return dict(prep_ms=float(s[0]), perm_ms=float(s[1]), prep_launches=int(s[2]), perm_launches=int(s[3]), gathered=float(s[4]),
+                permutations=float(s[5]))

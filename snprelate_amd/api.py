@@ -1320,3 +1320,140 @@ def snpgdsIndInb(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remove
     if want_iter:
         rv["out_num_iter"] = niter
     return rv
+
+
+# ---- hierarchical clustering and the permutation test of the tree ---------------------------------------------------------------------
+
+
+def snpgdsHCluster(dist, sample_id=None, need_mat=True, hang=0.25):
+    """Average-linkage clustering of a dissimilarity matrix (R/AllUtilities.R:386-424 -> hclust(as.dist(dist), "average"), here
+    snpgpu_hclust_average on the host).
+
+    Results in this mirror are dicts without classes: a dict with "diss" is taken as a snpgdsDiss result, one with "ibs" as a
+    snpgdsIBS result (1 - ibs is clustered); a square array needs sample_id.  Returns dict(sample_id, hclust=dict(merge, height,
+    order, labels, method="average"), dendrogram=None[, dist]); R's dendrogram is a plotting object and is not built, `hang` is
+    stored only."""
+    if isinstance(dist, dict):
+        if "diss" in dist:
+            sample_id, dist = dist["sample_id"], dist["diss"]
+        elif "ibs" in dist:
+            sample_id, dist = dist["sample_id"], 1 - np.asarray(dist["ibs"], np.float64)
+        else:
+            raise TypeError("is.matrix(dist) | inherits(dist, \"snpgdsDissClass\") | inherits(dist, \"snpgdsIBSClass\") is not TRUE")
+    dist = np.asarray(dist, np.float64)
+    if dist.ndim != 2:
+        raise TypeError("is.matrix(dist) | inherits(dist, \"snpgdsDissClass\") | inherits(dist, \"snpgdsIBSClass\") is not TRUE")
+    if sample_id is None:
+        if dist.shape[0] != dist.shape[1]:
+            raise ValueError("nrow(dist) == ncol(dist) is not TRUE")
+        raise ValueError("Please specify 'sample.id'.")
+    sample_id = np.asarray(sample_id)
+    if dist.shape[0] != len(sample_id):
+        raise ValueError("nrow(dist) == length(sample.id) is not TRUE")
+    if dist.shape[1] != len(sample_id):
+        raise ValueError("ncol(dist) == length(sample.id) is not TRUE")
+    merge, height, order = _lib.hclust_average(dist)
+    rv = dict(sample_id=sample_id, hclust=dict(merge=merge, height=height, order=order, labels=sample_id, method="average"),
+              dendrogram=None, hang=hang)
+    if need_mat:
+        rv["dist"] = dist
+    return rv
+
+
+def _relabel_groups(group, outlier_n):
+    """R/AllUtilities.R:485-510: names "G%03d" / "Outlier%03d" (groups of at most outlier_n members), sorted as a factor's levels
+    are, renamed in that order to G001 ..., Outlier001 ...; without outlier detection when outlier_n is not finite"""
+    group = np.asarray(group)
+    vals, counts = np.unique(group, return_counts=True)
+    if math.isfinite(outlier_n):
+        small = vals[counts <= outlier_n]
+        flag = np.isin(group, small)
+        names = np.array([("Outlier%03d" if f else "G%03d") % g for g, f in zip(group, flag)], dtype=object)
+        n_o = len(small)
+        n_g = len(vals) - n_o
+        new = ["G%03d" % k for k in range(1, n_g + 1)] + ["Outlier%03d" % k for k in range(1, n_o + 1)]
+    else:
+        names = np.array(["G%03d" % g for g in group], dtype=object)
+        new = ["G%03d" % k for k in range(1, len(vals) + 1)]
+    levels = sorted(set(names.tolist()))
+    ren = dict(zip(levels, new))
+    return np.array([ren[s] for s in names], dtype=object)
+
+
+def _group_dmat(dist, samp_group, levels):
+    k = len(levels)
+    dmat = np.zeros((k, k), np.float64)
+    sel = [samp_group == g for g in levels]
+    with np.errstate(all="ignore"), warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        for i in range(k):
+            m = dist[np.ix_(sel[i], sel[i])]
+            dmat[i, i] = np.nanmean(m[~np.eye(m.shape[0], dtype=bool)]) if m.shape[0] > 1 else np.nan
+            for j in range(i + 1, k):
+                dmat[i, j] = dmat[j, i] = np.nanmean(dist[np.ix_(sel[i], sel[j])])
+    return dmat
+
+
+def snpgdsCutTree(hc, z_threshold=15, outlier_n=5, n_perm=5000, samp_group=None, col_outlier="red", col_list=None, pch_outlier=4,
+                  pch_list=None, label_H=False, label_Z=True, verbose=True, device=0, seed=None):
+    """Groups of individuals from the tree of snpgdsHCluster by a permutation test of every merge (R/AllUtilities.R:432-623 ->
+    gnrDistPerm, src/SNPRelate.cpp:502-677, here snpgpu_dist_perm on the device).
+
+    R's checks come first and in R's order.  With samp_group given no permutation runs (merge and clust_count are None).  The
+    random stream is counter-based and keyed by `seed` (None: a fresh seed from numpy.random.default_rng()), so a result is a
+    function of (dist, merge, n_perm, seed).  The plotting arguments are accepted and stored only; R's dendrogram is not built.
+    Returns dict(sample_id, z_threshold, outlier_n, samp_order, samp_group, dmat, dendrogram=None, merge=dict(z, n1, n2),
+    clust_count); samp_group is an array of level names, `levels` their sorted list (the row / column names of dmat), clust_count a
+    list of (name, count) in order of first appearance along samp_order."""
+    if not (isinstance(hc, dict) and "hclust" in hc and "sample_id" in hc):
+        raise TypeError("inherits(hc, \"snpgdsHCClass\") is not TRUE")
+    if not (_is_number(z_threshold) and math.isfinite(z_threshold)):
+        raise ValueError("is.finite(z.threshold) is not TRUE")
+    if not _is_number(n_perm):
+        raise ValueError("is.numeric(n.perm) is not TRUE")
+    for name, v in (("label.H", label_H), ("label.Z", label_Z), ("verbose", verbose)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise TypeError("is.logical(%s) is not TRUE" % name)
+    if not n_perm >= 50:
+        raise ValueError("n.perm >= 50 is not TRUE")
+    if hc.get("dist") is None:
+        raise ValueError("`hc' should have a matrix of dissimilarity.")
+    auto = samp_group is None
+    if verbose and auto:
+        _cat(True, "Determine groups by permutation (Z threshold: %g, outlier threshold: %s):" %
+             (z_threshold, "%d" % outlier_n if math.isfinite(outlier_n) else str(outlier_n)))
+    dist = np.ascontiguousarray(hc["dist"], np.float64)
+    sample_id = hc["sample_id"]
+    order = np.asarray(hc["hclust"]["order"])
+    ans = dict(sample_id=sample_id, z_threshold=z_threshold, outlier_n=outlier_n, samp_order=order)
+    if not auto:
+        samp_group = np.asarray(samp_group, dtype=object)
+        if len(samp_group) != len(sample_id):
+            raise ValueError("length(samp.group) == length(hc$sample.id) is not TRUE")
+        merge = None
+    else:
+        if hc["hclust"].get("merge") is None:
+            raise ValueError("!is.null(hc$hclust$merge) is not TRUE")
+        if seed is None:
+            seed = int(np.random.default_rng().integers(0, 2 ** 63))
+        rv = _lib.dist_perm(dist, hc["hclust"]["merge"], n_perm=int(n_perm), z_threshold=float(z_threshold), seed=seed, device=device)
+        merge = dict(z=rv["z"], n1=rv["n1"], n2=rv["n2"])
+        samp_group = _relabel_groups(rv["group"], outlier_n)
+        ans["seed"] = seed
+    levels = sorted(set(samp_group.tolist()))
+    ans["samp_group"] = samp_group
+    ans["levels"] = levels
+    ans["dmat"] = _group_dmat(dist, samp_group, levels)
+    ans["dendrogram"] = None
+    ans["plot"] = dict(col_outlier=col_outlier, col_list=col_list, pch_outlier=pch_outlier, pch_list=pch_list, label_H=label_H,
+                       label_Z=label_Z)
+    ans["merge"] = merge
+    if merge is not None:
+        cluster = samp_group[order - 1].tolist()
+        seen = list(dict.fromkeys(cluster))
+        ans["clust_count"] = [(c, cluster.count(c)) for c in seen]
+    else:
+        ans["clust_count"] = None
+    if verbose:
+        _cat(True, "Create %d groups." % len(levels))
+    return ans
