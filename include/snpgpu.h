@@ -702,6 +702,12 @@ int snpgpu_diag_mfma_rate(int device, int mode, double seconds, double *tflops, 
 int snpgpu_diag_fp64_rate(int device, double seconds, double *tflops);
 /* PCI address "dddd:bb:dd.f" of HIP device `device` (hipDeviceGetPCIBusId): which physical GPU a rank really drives */
 int snpgpu_diag_device_pci(int device, char *buf, int len);
+/* The kernel path a context of `kind` over n_samp samples would take under the CURRENT environment, as "key=value" lines in buf
+ * (NUL-terminated; an error when len is too small): the plan snpgpu_create allocates from and snpgpu_feed reads, the names of the
+ * kernels a block with / without missing calls takes, and -- block_snps > 0 -- the fp32 run geometry of a block of that many SNPs.
+ * Makes no HIP call (opts->device is ignored, opts may be NULL): the dispatch can be checked on a host without a GPU.  Refusals of
+ * snpgpu_create that do not depend on the device (invalid panel rows, a form the dissimilarity kind lacks) are returned as such. */
+int snpgpu_diag_plan(int kind, int64_t n_samp, const snpgpu_opts *opts, int64_t block_snps, char *buf, int len);
 
 #ifdef __cplusplus
 }

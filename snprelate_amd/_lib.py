@@ -54,6 +54,7 @@ EXPORTS = [
     "snpgpu_geno_counts", "snpgpu_hwe", "snpgpu_hwe_counts", "snpgpu_ind_inb", "snpgpu_qc_stats", "snpgpu_gnrSampFreq", "snpgpu_gnrHWE",
     "snpgpu_gnrIndInb",
     "snpgpu_hclust_average", "snpgpu_dist_perm", "snpgpu_gnrDistPerm", "snpgpu_tree_stats",
+    "snpgpu_diag_plan",
 ]
 FST_WC84, FST_WH02 = 1, 2
 FST_METHODS = ("W&C84", "W&H02")
@@ -134,6 +135,7 @@ def lib():
     L.snpgpu_device_count.argtypes = [ctypes.POINTER(c_int)]
     L.snpgpu_diag_mfma_rate.argtypes = [c_int, c_int, dbl, ctypes.POINTER(dbl), ctypes.POINTER(dbl)]
     L.snpgpu_diag_device_pci.argtypes = [c_int, ctypes.c_char_p, c_int]
+    L.snpgpu_diag_plan.argtypes = [c_int, i64, ctypes.POINTER(Opts), i64, ctypes.c_char_p, c_int]
     L.snpgpu_synth_block.argtypes = [vp, i64, i64, i64, ctypes.c_uint32, dbl, c_int, c_int, c_int, vp]
     L.snpgpu_create.argtypes = [c_int, i64, ctypes.POINTER(Opts), ctypes.POINTER(vp)]
     L.snpgpu_destroy.argtypes = [vp]
@@ -298,6 +300,16 @@ def device_pci(device=0):
     buf = ctypes.create_string_buffer(64)
     check(lib().snpgpu_diag_device_pci(int(device), buf, 64))
     return buf.value.decode()
+
+
+def diag_plan(kind, n_samp, block_snps=0, bayesian=False, rows=None, max_block_snps=0):
+    """The kernel path a context would take under the current environment, as a dict of strings (snpgpu_diag_plan: the plan
+    snpgpu_create allocates from, the kernels of a block with / without missing calls and, with block_snps, its fp32 run
+    geometry).  No GPU is needed; what snpgpu_create would refuse whatever the device raises SnpGpuError with the same text."""
+    o = Opts(0, int(bool(bayesian)), int(rows[0]) if rows else 0, int(rows[1]) if rows else 0, int(max_block_snps), None)
+    buf = ctypes.create_string_buffer(8192)
+    check(lib().snpgpu_diag_plan(int(kind), int(n_samp), ctypes.byref(o), int(block_snps), buf, len(buf)))
+    return dict(line.split("=", 1) for line in buf.value.decode().splitlines())
 
 
 def synth_block(dev_ptr, n_samp, snp_begin, n_snp, seed, missing=0.0, spectrum=0, special=False, device=0, stream=None):

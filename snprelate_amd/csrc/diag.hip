@@ -5,9 +5,11 @@
 // by a few per cent from box to box.  bench.py therefore measures it in the run it reports (roofline.sustained_peak_measured)
 // instead of quoting a constant: snpgpu_diag_mfma_rate streams one MFMA instruction from registers -- 8 independent accumulators
 // per wave, 2 waves per SIMD, so the pipe never waits -- for `seconds` and returns the rate over the second half of that time.
-#include "snpgpu_internal.h"
+#include "ctx_plan.h"
 
 #include <chrono>
+#include <cstring>
+#include <sstream>
 #include <vector>
 
 namespace snpgpu {
@@ -288,4 +290,82 @@ extern "C" int snpgpu_diag_fp64_rate(int device, double seconds, double *tflops)
     if (d_src) (void)hipFree(d_src);
     if (d_out) (void)hipFree(d_out);
     return rc;
+}
+
+// ---- snpgpu_diag_plan: names of the kernels a block takes under a plan (what launch_pair_i8 / launch_syrk_h3 / launch_syrk_uv run)
+static const char *uv_form_kernel(UvForm f)
+{
+    return f == UvForm::Mfma32x32x16 ? "syrk_uv_kernel" : f == UvForm::Lookup16x16x32 ? "syrk_uv16_kernel" : "syrk_uv16c_kernel";
+}
+// the pair-counter kernel of a block with / without missing calls ("none": the block needs none)
+static const char *plan_counter_kernel(const CtxPlan &p, bool missing)
+{
+    if (!p.use_pc) return "none";
+    if (!p.pc_i8) return (p.pc_mode == PM_GCTA_MISS && !missing) ? "none" : "pair_popcount_kernel";
+    if (p.pc_mode == PM_GCTA_MISS) return !missing ? "none" : p.miss_fp4 ? "pair_mfma_fp4_miss_kernel" : "pair_mfma_i8_kernel";
+    if (!missing && p.want_het) return p.nomiss_fp4 ? "pair_mfma_fp4_nomiss_kernel" : "pair_mfma_i8_kernel";
+    return p.general_fp4 ? "pair_mfma_fp4_kernel" : "pair_mfma_i8_kernel";
+}
+// the SYRK kernel of table 0 (KING-homo / dissimilarity: of the weight sums)
+static const char *plan_syrk_kernel(const CtxPlan &p, bool missing)
+{
+    if (!p.use_mm) return "none";
+    if (p.homo_uv) return missing ? uv_form_kernel(p.homo_form) : "none";
+    const bool homo = p.lut_mode[0] == LUT_HOMO_W1;       // (with the two-product counter kernel: blocks with missing calls only)
+    if (homo && p.want_het && !missing) return "none";
+    if (!p.mm_h3) return "syrk_mfma_kernel";
+    if (p.h3_a_kind[0] > 0) return "syrk_h3_kernel<2, false>";
+    if (p.h3_a_kind[0] < 0) return "syrk_h3_kernel<3, false>";
+    if (!missing && p.uv_enabled) return uv_form_kernel(p.uv_form);
+    if (missing && !(p.h3_exact_missing || p.eigmix_x1)) return "syrk_h3_kernel<3, false>";
+    return (p.want_x1_list && (missing || !p.uv_eigmix)) ? "syrk_x1_kernel" : "syrk_h3_kernel<2, true>";
+}
+
+// the plan of a context as text: every line "key=value", keys stable (tests/test_cpu_plan.py reads them)
+extern "C" int snpgpu_diag_plan(int kind, int64_t n_samp, const snpgpu_opts *opts, int64_t block_snps, char *buf, int len)
+{
+    if (!buf || len <= 0) { set_error("snpgpu_diag_plan: no buffer"); return 1; }
+    snpgpu_opts o{};
+    if (opts) o = *opts;
+    CtxPlan p;
+    std::string why;
+    if (plan_context(kind, n_samp, o, Switches::from_env(), &p, &why)) { set_error("snpgpu_create: " + why); return 1; }
+    static const char *const pair_modes[] = {"ibs", "king_robust", "king_homo", "gcta_miss", "beta", "ibs_nomiss", "homo_nomiss", "diss"};
+    static const char *const lut_modes[] = {"gcta", "bayes", "homo_w1", "homo_w2", "eigmix_num", "eigmix_missw"};
+    static const char *const uv_forms[] = {"mfma32x32x16", "lookup16x16x32", "converted", "converted_carry"};
+    static const char *const layouts[] = {"entry8or16", "entry16", "entry12", "entry12or8", "entry12missing"};
+    std::ostringstream t;
+    t << "kind=" << p.kind << "\nbayesian=" << p.bayesian << "\nn_samp=" << p.N << "\nrow0=" << p.row0 << "\nrow1=" << p.row1
+      << "\ncol0=" << p.col0 << "\nrows_pad=" << p.rows_pad << "\nncols_pad=" << p.ncols_pad << "\nRB=" << p.RB << "\nBmax=" << p.Bmax
+      << "\nKWmax=" << p.KWmax << "\nfull=" << p.full << "\nacc_tiles_c=" << p.acc_tiles_c << "\ntail_parts=" << p.tail_parts
+      << "\ncounter_mode=" << (p.use_pc ? pair_modes[p.pc_mode] : "none") << "\nn_u32=" << p.n_u32
+      << "\ncounter_backend=" << (!p.use_pc ? "none" : p.pc_i8 ? "mfma" : "popcount");
+    if (p.use_pc && p.pc_i8)
+        t << "\nnomiss_fp4=" << p.nomiss_fp4 << "\ngeneral_fp4=" << p.general_fp4 << "\nmiss_fp4=" << p.miss_fp4
+          << "\ncounter_tile=" << p.pc_tile_r << "x" << p.pc_tile_c << "x" << p.pc_wg_per_cu << "\nwant_het=" << p.want_het
+          << "\nnomiss_tile=" << p.nm_tile_r << "x" << p.nm_tile_c << "x" << p.nm_wg_per_cu << "\ngcta_sparse=" << p.gcta_sparse
+          << "\nsp_max_rate=" << p.sp_max_rate;
+    t << "\nn_lut=" << p.n_lut;
+    for (int i = 0; i < p.n_lut; i++) t << "\nlut_mode" << i << "=" << lut_modes[p.lut_mode[i]] << "\nh3_a_kind" << i << "=" << p.h3_a_kind[i];
+    if (p.use_mm)
+        t << "\nsyrk_family=" << (p.mm_h3 ? "split_fp16" : "fp32") << "\nh3_super=" << p.h3_super << "\nx1_super=" << p.x1_super
+          << "\nh3_exact_rows=" << p.h3_exact_rows << "\nh3_exact_missing=" << p.h3_exact_missing << "\nh3_w_shift=" << p.h3_w_shift
+          << "\nh3_promote=" << p.h3_promote << "\nuv_promote=" << p.uv_promote << "\nwant_x1_list=" << p.want_x1_list
+          << "\nuv_enabled=" << p.uv_enabled << "\nuv_eigmix=" << p.uv_eigmix << "\nuv_targets=" << p.uv_targets
+          << "\nuv_form=" << uv_forms[(int)p.uv_form] << "\nuvc_pace=" << p.uvc_pace << "\neigmix_x1=" << p.eigmix_x1
+          << "\nsparse_missing=" << p.sparse_missing << "\nx1_short_runs=" << p.x1_short_runs << "\nx1_sparse_mac=" << p.x1_sparse_mac
+          << "\nwt_layout=" << layouts[(int)p.wt_layout] << "\nwt_block_flag=" << p.wt_block_flag << "\nhomo_uv=" << p.homo_uv
+          << "\nhomo_form=" << uv_forms[(int)p.homo_form] << "\nhomo_weights=" << p.homo_weights;
+    t << "\ncounter_kernel_nomiss=" << plan_counter_kernel(p, false) << "\ncounter_kernel_missing=" << plan_counter_kernel(p, true)
+      << "\nsyrk_kernel_nomiss=" << plan_syrk_kernel(p, false) << "\nsyrk_kernel_missing=" << plan_syrk_kernel(p, true);
+    if (block_snps > 0 && p.use_mm) {
+        const BlockRuns b = plan_block(p, block_snps);
+        t << "\nblock_snps=" << block_snps << "\nuv_runs=" << b.uv_runs << "\nuv_cpr=" << b.uv_cpr << "\nuv_chunks=" << b.uv_chunks
+          << "\nuv_q=" << b.uv_q << "\nn_pad=" << b.n_pad << "\nn_q=" << b.n_q;
+    }
+    t << "\n";
+    const std::string s = t.str();
+    if ((int64_t)s.size() + 1 > (int64_t)len) { set_error("snpgpu_diag_plan: buffer too small"); return 1; }
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return 0;
 }

@@ -24,6 +24,7 @@
 #include <limits>
 #include <vector>
 
+#include "ctx_plan.h"
 #include "eigen.h"
 
 namespace snpgpu {
@@ -629,12 +630,12 @@ int snpgpu_panels_topk_eigen(snpgpu_ctx *const *panels, int n_panels, double sca
 {
     if (!panels || n_panels <= 0 || !panels[0]) { set_error("snpgpu_panels_topk_eigen: no panels"); return 1; }
     const int dev = panels[0]->device;
-    const int64_t n = panels[0]->N;
+    const int64_t n = panels[0]->plan.N;
     std::vector<snpgpu_ctx *> v;
     for (int i = 0; i < n_panels; i++) {
         snpgpu_ctx *c = panels[i];
-        if (!c || c->device != dev || c->N != n) { set_error("snpgpu_panels_topk_eigen: the panels must share one device and one sample count"); return 1; }
-        if (!(c->kind == SNPGPU_PCA_COV || ((c->kind == SNPGPU_GRM_GCTA || c->kind == SNPGPU_EIGMIX) && c->frozen))) {
+        if (!c || c->device != dev || c->plan.N != n) { set_error("snpgpu_panels_topk_eigen: the panels must share one device and one sample count"); return 1; }
+        if (!(c->plan.kind == SNPGPU_PCA_COV || ((c->plan.kind == SNPGPU_GRM_GCTA || c->plan.kind == SNPGPU_EIGMIX) && c->frozen))) {
             set_error("snpgpu_panels_topk_eigen: needs PCA_COV contexts, or GRM_GCTA / EIGMIX contexts after snpgpu_finalize_inplace");
             return 1;
         }
@@ -652,3 +653,73 @@ int snpgpu_panels_topk_eigen(snpgpu_ctx *const *panels, int n_panels, double sca
 }
 
 }  // extern "C"
+
+// Y += scale * (this panel's part of the symmetric matrix) Q, enqueued on the context's stream
+int snpgpu::ctx_panel_matmul_enqueue(snpgpu_ctx *c, double scale, const double *Q, int m, double *Y, bool fp32_products)
+{
+    if (!c || !(c->plan.kind == SNPGPU_PCA_COV || ((c->plan.kind == SNPGPU_GRM_GCTA || c->plan.kind == SNPGPU_EIGMIX) && c->frozen))) {
+        set_error("snpgpu_pca_panel_matmul: needs a PCA_COV context, or a GRM_GCTA / EIGMIX context after snpgpu_finalize_inplace");
+        return 1;
+    }
+    if (!Q || !Y || m <= 0) { set_error("snpgpu_pca_panel_matmul: invalid arguments"); return 1; }
+    SNPGPU_HIP_CHECK(hipSetDevice(c->device));
+    if (snpgpu::ctx_settle(c)) return 1;
+    double *P = (double *)c->acc_f64.p;      // row-major [rows_pad][ld]  ==  column-major M (ld x rows), M[j,i] = P[i,j]
+    const int64_t n = c->plan.N, r0 = c->plan.row0, r1 = c->plan.row1, ld = c->plan.ncols_pad;
+    if (!getenv("SNPGPU_EIG_BLAS")) {
+        // one pass over the panel, every tile used for both triangles (kernels_eig.hip); below the diagonal
+        // it reads only the 64 x 64 tiles on it
+        if (c->diag_mirrored == 0) {
+            if (launch_mirror_diag_tiles(c->stream, c->geom(), P, 64)) return 1;
+            c->diag_mirrored = 1;
+        }
+        if (!c->eig_qt.p && c->eig_qt.alloc(sizeof(double) * 48 * (size_t)(n + 16))) return 1;
+        // fp32 products stream an fp32 COPY of the (settled, mirrored) plane where the device has room for it next to 8 GiB of
+        // head room: half the bytes per product, no conversions (SNPGPU_EIG_F32_PANEL=0: convert the fp64 plane on the fly)
+        const float *P32 = nullptr;
+        if (fp32_products && !(getenv("SNPGPU_EIG_F32_PANEL") && !atoi(getenv("SNPGPU_EIG_F32_PANEL")))) {
+            const size_t elems = (size_t)c->plane();
+            if (!c->acc_f32.p) {
+                size_t fr = 0, tot = 0;
+                if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr > elems * sizeof(float) + ((size_t)8 << 30)) {
+                    if (c->acc_f32.alloc(elems * sizeof(float))) return 1;
+                    c->acc_f32_valid = false;
+                }
+            }
+            if (c->acc_f32.p && !c->acc_f32_valid) {
+                if (launch_panel_to_f32(c->stream, P, (float *)c->acc_f32.p, elems)) return 1;
+                c->acc_f32_valid = true;
+            }
+            if (c->acc_f32.p) P32 = (const float *)c->acc_f32.p;
+        }
+        return launch_sym_panel_matmul(c->stream, P, ld, c->plan.acc_tiles_c, r1 - r0, n - r0, r0, n, scale, Q, m, Y, (double *)c->eig_qt.p,
+                                       fp32_products, P32);
+    }
+    if (c->plan.acc_tiles_c) { set_error("snpgpu_pca_panel_matmul: SNPGPU_EIG_BLAS must be set when the context is created (row-major panel)"); return 1; }
+    if (!c->blas) {
+        rocblas_handle hb = nullptr;
+        if (rocblas_create_handle(&hb) != rocblas_status_success) { set_error("rocblas_create_handle failed"); return 1; }
+        rocblas_set_stream(hb, c->stream);
+        rocblas_set_pointer_mode(hb, rocblas_pointer_mode_host);
+        c->blas = hb;
+    }
+    if (c->diag_mirrored != 2) {             // the dgemm form needs the whole diagonal square
+        if (launch_mirror_diag(c->stream, c->geom(), P)) return 1;
+        c->diag_mirrored = 2;
+    }
+    rocblas_handle h = (rocblas_handle)c->blas;
+    const int64_t nI = r1 - r0, nJ = n - r0, nR = n - r1;
+    const double one = 1.0;
+    // Y[I] += scale * P[I, r0:N] * Q[r0:N]        (P = M^T)
+    rocblas_status st = rocblas_dgemm(h, rocblas_operation_transpose, rocblas_operation_none, (rocblas_int)nI, m,
+                                      (rocblas_int)nJ, &scale, P, (rocblas_int)ld, Q + r0, (rocblas_int)n, &one,
+                                      Y + r0, (rocblas_int)n);
+    if (st != rocblas_status_success) { set_error("rocblas_dgemm (panel rows) failed"); return 1; }
+    if (nR > 0) {
+        // Y[r1:N] += scale * P[I, r1:N]^T * Q[I]   (= M[r1-r0 : , :] * Q[I])
+        st = rocblas_dgemm(h, rocblas_operation_none, rocblas_operation_none, (rocblas_int)nR, m, (rocblas_int)nI, &scale,
+                           P + nI, (rocblas_int)ld, Q + r0, (rocblas_int)n, &one, Y + r1, (rocblas_int)n);
+        if (st != rocblas_status_success) { set_error("rocblas_dgemm (panel columns) failed"); return 1; }
+    }
+    return 0;
+}

@@ -89,7 +89,7 @@ struct DevArena {
     DevArena() = default;
     DevArena(const DevArena &) = delete;
     DevArena &operator=(const DevArena &) = delete;
-    ~DevArena() { for (DevBuf *b : all) { b->release(); delete b; } }
+    ~DevArena() { for (DevBuf *b : all) delete b; }
     // A buffer of `bytes`, or nullptr with rc set: when this allocation fails, or when rc was set already (so a run of get()s
     // needs one test of rc after it -- and nothing of the run may be dereferenced before that test).
     DevBuf *get(size_t bytes, int &rc)

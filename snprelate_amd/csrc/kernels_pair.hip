@@ -1649,44 +1649,42 @@ static unsigned run_inner_grid(int n_blocks, int n_runs, int group)
 
 // run_chunks: table chunks per fp32 run (0: the whole block is one run); n_target > 1: run q's sums are multiplied by
 // uv_run_factor(q) at its flush (the run's SNPs were factorised for the weight target t / f_q, uv_factor_kernel)
-int launch_syrk_uv(hipStream_t st, const int4 *work_x1, int n_blocks_x1, const uint32_t *w8, int64_t ncols_pad,
-                   const uint2 *lut, int n_q, double *acc, int64_t ld, int64_t tiles_c, const unsigned long long *d_missing,
-                   int64_t n_rows_real, int run_chunks, int n_target, int run_if_missing, int64_t copy_lut_bytes, int64_t copy_acc_elems,
-                   int uv16, const void *pace_src, int pace)
+int launch_syrk_uv(hipStream_t st, const SyrkPanel &p, const SyrkUvOpts &o)
 {
-    if (n_q <= 0 || n_blocks_x1 <= 0) return 0;
-    const int n_chunk = (n_q + (UV_CHS / 16) - 1) / (UV_CHS / 16);           // table chunks of the block; one launch per fp32 run
-    const int run = run_chunks > 0 ? run_chunks : n_chunk;
+    const int run_if_missing = o.run_if_missing ? 1 : 0, pace = o.pace ? 1 : 0, uv16 = (int)o.form;    // the kernels' integer codes
+    if (o.n_q <= 0 || o.n_blocks_x1 <= 0) return 0;
+    const int n_chunk = (o.n_q + (UV_CHS / 16) - 1) / (UV_CHS / 16);           // table chunks of the block; one launch per fp32 run
+    const int run = o.run_chunks > 0 ? o.run_chunks : n_chunk;
     const int n_runs = (n_chunk + run - 1) / run;
     // (round 6: a non-atomic read-modify-write flush for tiles with one owner per launch was measured -- 465.8 against 456.8 ms per
     // step in the one-launch-per-run form, profiles/r06_flush_rmw_ab.txt -- and removed)
     // uv16: the same launch geometry and arguments, the 16x16x32 form of the kernel (its tables carry swapped odd quarters)
-    if (uv16 >= 2) {                              // syrk_uv16c_kernel: `lut` = the slots' factor arrays; pace-maker arguments instead of table copies
+    if (uv16 >= 2) {                              // syrk_uv16c_kernel: `o.lut` = the slots' factor arrays; pace-maker arguments instead of table copies
         if (uv16 == 3 && n_runs > 1)              // work items = tiles, the runs walked inside, half the sub-tiles carried in LDS
-            hipLaunchKernelGGL(syrk_uv16c_kernel, dim3((unsigned)n_blocks_x1), dim3(256), 0, st, w8, ncols_pad, lut, n_q, acc, ld, tiles_c, work_x1,
-                               d_missing, n_rows_real, 0, n_chunk, 1.0, n_runs, run, n_target, 0, 0, run_if_missing, (const char *)pace_src, pace);
+            hipLaunchKernelGGL(syrk_uv16c_kernel, dim3((unsigned)o.n_blocks_x1), dim3(256), 0, st, p.w8, p.ncols_pad, o.lut, o.n_q, p.acc, p.ld, p.tiles_c, o.work_x1,
+                               o.d_missing, p.n_rows_real, 0, n_chunk, 1.0, n_runs, run, o.n_target, 0, 0, run_if_missing, (const char *)o.pace_src, pace);
         else if (n_runs > 1 && run_inner_launch())
-            hipLaunchKernelGGL(syrk_uv16c_kernel, dim3(run_inner_grid(n_blocks_x1, n_runs, run_inner_launch())), dim3(256), 0, st, w8, ncols_pad,
-                               lut, n_q, acc, ld, tiles_c, work_x1, d_missing, n_rows_real, 0, n_chunk, 1.0, n_runs, run, n_target,
-                               run_inner_launch(), n_blocks_x1 / 8, run_if_missing, (const char *)pace_src, pace);
+            hipLaunchKernelGGL(syrk_uv16c_kernel, dim3(run_inner_grid(o.n_blocks_x1, n_runs, run_inner_launch())), dim3(256), 0, st, p.w8, p.ncols_pad,
+                               o.lut, o.n_q, p.acc, p.ld, p.tiles_c, o.work_x1, o.d_missing, p.n_rows_real, 0, n_chunk, 1.0, n_runs, run, o.n_target,
+                               run_inner_launch(), o.n_blocks_x1 / 8, run_if_missing, (const char *)o.pace_src, pace);
         else
             for (int lo = 0, q = 0; lo < n_chunk; lo += run, q++)
-                hipLaunchKernelGGL(syrk_uv16c_kernel, dim3((unsigned)n_blocks_x1), dim3(256), 0, st, w8, ncols_pad, lut, n_q, acc, ld, tiles_c,
-                                   work_x1, d_missing, n_rows_real, lo, std::min(lo + run, n_chunk),
-                                   n_target > 1 ? uv_run_factor(q % n_target) : 1.0, 1, 0, 1, 1, 0, run_if_missing, (const char *)pace_src, pace);
+                hipLaunchKernelGGL(syrk_uv16c_kernel, dim3((unsigned)o.n_blocks_x1), dim3(256), 0, st, p.w8, p.ncols_pad, o.lut, o.n_q, p.acc, p.ld, p.tiles_c,
+                                   o.work_x1, o.d_missing, p.n_rows_real, lo, std::min(lo + run, n_chunk),
+                                   o.n_target > 1 ? uv_run_factor(q % o.n_target) : 1.0, 1, 0, 1, 1, 0, run_if_missing, (const char *)o.pace_src, pace);
         SNPGPU_HIP_CHECK(hipGetLastError());
         return 0;
     }
     const auto kern = uv16 ? syrk_uv16_kernel : syrk_uv_kernel;
     if (n_runs > 1 && run_inner_launch())
-        hipLaunchKernelGGL(kern, dim3(run_inner_grid(n_blocks_x1, n_runs, run_inner_launch())), dim3(256), 0, st,
-                           w8, ncols_pad, lut, n_q, acc, ld, tiles_c, work_x1, d_missing, n_rows_real, 0, n_chunk, 1.0, n_runs, run, n_target,
-                           run_inner_launch(), n_blocks_x1 / 8, run_if_missing, copy_lut_bytes, copy_acc_elems);
+        hipLaunchKernelGGL(kern, dim3(run_inner_grid(o.n_blocks_x1, n_runs, run_inner_launch())), dim3(256), 0, st,
+                           p.w8, p.ncols_pad, o.lut, o.n_q, p.acc, p.ld, p.tiles_c, o.work_x1, o.d_missing, p.n_rows_real, 0, n_chunk, 1.0, n_runs, run, o.n_target,
+                           run_inner_launch(), o.n_blocks_x1 / 8, run_if_missing, o.copy_lut_bytes, o.copy_acc_elems);
     else
         for (int lo = 0, q = 0; lo < n_chunk; lo += run, q++)
-            hipLaunchKernelGGL(kern, dim3((unsigned)n_blocks_x1), dim3(256), 0, st, w8, ncols_pad, lut, n_q, acc, ld,
-                               tiles_c, work_x1, d_missing, n_rows_real, lo, std::min(lo + run, n_chunk),
-                               n_target > 1 ? uv_run_factor(q % n_target) : 1.0, 1, 0, 1, 1, 0, run_if_missing, copy_lut_bytes, copy_acc_elems);
+            hipLaunchKernelGGL(kern, dim3((unsigned)o.n_blocks_x1), dim3(256), 0, st, p.w8, p.ncols_pad, o.lut, o.n_q, p.acc, p.ld,
+                               p.tiles_c, o.work_x1, o.d_missing, p.n_rows_real, lo, std::min(lo + run, n_chunk),
+                               o.n_target > 1 ? uv_run_factor(q % o.n_target) : 1.0, 1, 0, 1, 1, 0, run_if_missing, o.copy_lut_bytes, o.copy_acc_elems);
     SNPGPU_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1696,45 +1694,41 @@ int launch_syrk_uv(hipStream_t st, const int4 *work_x1, int n_blocks_x1, const u
 // launches does the work (blocks with missing calls: three products), with d_missing == nullptr the exact-row kernel
 // takes every block (the row value of a missing call is the fp16 residual avg - c_s).  a_kind 1 / 2: two-product kernel
 // with a constant row table, always.  promote_snps: fp32 run length of the exact-row kernel (0 = default).
-int launch_syrk_h3(hipStream_t st, const int4 *work, int n_blocks, const uint32_t *w8, int64_t ncols_pad,
-                   const uint2 *lut, int n_q, double *acc, int64_t ld, int64_t tiles_c,
-                   const unsigned long long *d_skip_if_zero, int a_kind, const unsigned long long *d_missing, int64_t n_rows_real,
-                   int promote_snps,
-                   const int4 *work_x1, int n_blocks_x1, const unsigned long long *d_short_runs)
+int launch_syrk_h3(hipStream_t st, const SyrkPanel &p, const SyrkH3Opts &o)
 {
-    if (n_q <= 0 || n_blocks <= 0) return 0;
+    if (o.n_q <= 0 || o.n_blocks <= 0) return 0;
     const int p3 = H3_PROMOTE / H3_LUTCH;                                    // three products: 512-SNP chunks
-    const int p2e = (promote_snps > 0 ? promote_snps : H3_PROMOTE_EXACT) / (H3_LUTCH / 2);   // exact rows: 256-SNP chunks
+    const int p2e = (o.promote_snps > 0 ? o.promote_snps : H3_PROMOTE_EXACT) / (H3_LUTCH / 2);   // exact rows: 256-SNP chunks
     const int p2c = H3_PROMOTE / H3_LUTCH;                                   // constant row table: 512-SNP chunks
-    if (a_kind < 0 || (a_kind == 0 && d_missing))
-        hipLaunchKernelGGL((syrk_h3_kernel<3, false>), dim3((unsigned)n_blocks), dim3(256), 0, st, w8, ncols_pad, lut, n_q, acc, ld, tiles_c, work,
-                           d_skip_if_zero, a_kind == 0 ? d_missing : nullptr, n_rows_real, 0, p3);
-    if (a_kind == 0 && work_x1 && !d_missing) {
-        const int n_chunk = (n_q + (X1_CHS / 16) - 1) / (X1_CHS / 16);       // table chunks of the block; one launch per fp32 run
-        const int run = std::max(1, (promote_snps > 0 ? promote_snps : H3_PROMOTE_EXACT) / X1_CHS);
+    if (o.a_kind < 0 || (o.a_kind == 0 && o.d_missing))
+        hipLaunchKernelGGL((syrk_h3_kernel<3, false>), dim3((unsigned)o.n_blocks), dim3(256), 0, st, p.w8, p.ncols_pad, o.lut, o.n_q, p.acc, p.ld, p.tiles_c, o.work,
+                           o.d_skip_if_zero, o.a_kind == 0 ? o.d_missing : nullptr, p.n_rows_real, 0, p3);
+    if (o.a_kind == 0 && o.work_x1 && !o.d_missing) {
+        const int n_chunk = (o.n_q + (X1_CHS / 16) - 1) / (X1_CHS / 16);       // table chunks of the block; one launch per fp32 run
+        const int run = std::max(1, (o.promote_snps > 0 ? o.promote_snps : H3_PROMOTE_EXACT) / X1_CHS);
         // (fused launch only) blocks flagged by build_lut_kernel run as half-length fp32 runs: the grid is laid out for those
-        const int short_div = (d_short_runs && run >= 2 && (run % 2) == 0) ? 2 : 1;
+        const int short_div = (o.d_short_runs && run >= 2 && (run % 2) == 0) ? 2 : 1;
         const int n_runs = (n_chunk + run / short_div - 1) / (run / short_div);
         // (round 6: a 16x16x32 form of this kernel -- syrk_uv16_kernel's skeleton, column operands looked up just in time, a padded
         // table layout against the bank conflicts of two quarters per LDS pass -- was built, passed every parity test and ran configs[2]
         // with 2 % missing calls in 883 - 902 ms per step against 896 here, depending on the issue pattern: not kept,
         // profiles/r06_x116_patterns.txt)
         if (n_runs > 1 && run_inner_launch())
-            hipLaunchKernelGGL(syrk_x1_kernel, dim3(run_inner_grid(n_blocks_x1, n_runs, run_inner_launch())), dim3(256), 0, st, w8, ncols_pad,
-                               lut, n_q, acc, ld, tiles_c, work_x1, d_skip_if_zero, n_rows_real, 0, n_chunk, n_runs, run, run_inner_launch(),
-                               n_blocks_x1 / 8, short_div > 1 ? d_short_runs : nullptr, short_div);
+            hipLaunchKernelGGL(syrk_x1_kernel, dim3(run_inner_grid(o.n_blocks_x1, n_runs, run_inner_launch())), dim3(256), 0, st, p.w8, p.ncols_pad,
+                               o.lut, o.n_q, p.acc, p.ld, p.tiles_c, o.work_x1, o.d_skip_if_zero, p.n_rows_real, 0, n_chunk, n_runs, run, run_inner_launch(),
+                               o.n_blocks_x1 / 8, short_div > 1 ? o.d_short_runs : nullptr, short_div);
         else
             for (int lo = 0; lo < n_chunk; lo += run)
                 for (int half = 0; half < short_div; half++)      // (short_div = 2: see the kernel's one-launch-per-run branch)
-                    hipLaunchKernelGGL(syrk_x1_kernel, dim3((unsigned)n_blocks_x1), dim3(256), 0, st, w8, ncols_pad, lut, n_q, acc, ld, tiles_c,
-                                       work_x1, d_skip_if_zero, n_rows_real, lo, std::min(lo + run, n_chunk), 1, run, half, 0,
-                                       short_div > 1 ? d_short_runs : nullptr, short_div);
-    } else if (a_kind == 0)
-        hipLaunchKernelGGL((syrk_h3_kernel<2, true>), dim3((unsigned)n_blocks), dim3(256), 0, st, w8, ncols_pad, lut, n_q, acc, ld, tiles_c,
-                           work, d_skip_if_zero, d_missing, n_rows_real, a_kind, p2e > 0 ? p2e : 1);
-    else if (a_kind > 0)
-        hipLaunchKernelGGL((syrk_h3_kernel<2, false>), dim3((unsigned)n_blocks), dim3(256), 0, st, w8, ncols_pad, lut, n_q, acc, ld, tiles_c,
-                           work, d_skip_if_zero, nullptr, n_rows_real, a_kind, p2c);
+                    hipLaunchKernelGGL(syrk_x1_kernel, dim3((unsigned)o.n_blocks_x1), dim3(256), 0, st, p.w8, p.ncols_pad, o.lut, o.n_q, p.acc, p.ld, p.tiles_c,
+                                       o.work_x1, o.d_skip_if_zero, p.n_rows_real, lo, std::min(lo + run, n_chunk), 1, run, half, 0,
+                                       short_div > 1 ? o.d_short_runs : nullptr, short_div);
+    } else if (o.a_kind == 0)
+        hipLaunchKernelGGL((syrk_h3_kernel<2, true>), dim3((unsigned)o.n_blocks), dim3(256), 0, st, p.w8, p.ncols_pad, o.lut, o.n_q, p.acc, p.ld, p.tiles_c,
+                           o.work, o.d_skip_if_zero, o.d_missing, p.n_rows_real, o.a_kind, p2e > 0 ? p2e : 1);
+    else if (o.a_kind > 0)
+        hipLaunchKernelGGL((syrk_h3_kernel<2, false>), dim3((unsigned)o.n_blocks), dim3(256), 0, st, p.w8, p.ncols_pad, o.lut, o.n_q, p.acc, p.ld, p.tiles_c,
+                           o.work, o.d_skip_if_zero, nullptr, p.n_rows_real, o.a_kind, p2c);
     SNPGPU_HIP_CHECK(hipGetLastError());
     return 0;
 }

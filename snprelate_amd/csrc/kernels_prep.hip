@@ -411,16 +411,13 @@ __global__ __launch_bounds__(256) void build_lut_kernel(const int32_t *__restric
     }
 }
 
-int launch_build_lut(hipStream_t st, const int32_t *sum, const int32_t *num, int64_t n_snp, int64_t n_snp_pad,
-                     int lut_mode, int split16, float2 *lut, unsigned long long *d_nlocus, double *d_sumden,
-                     double *dvals, const unsigned long long *d_missing, double2 *ccoef, int exact_rows_always, int w_shift,
-                     int exact_with_missing, int entry12, double *homo_const, double4 *uvsp_miss, int x1_sparse_mac,
-                     unsigned long long *d_short_runs)
+int launch_build_lut(hipStream_t st, const int32_t *sum, const int32_t *num, int64_t n_snp, int64_t n_snp_pad, const BuildLutOpts &o)
 {
     if (n_snp_pad <= 0) return 0;
     hipLaunchKernelGGL(build_lut_kernel, dim3((unsigned)((n_snp_pad + 255) / 256)), dim3(256), 0, st, sum, num,
-                       n_snp, n_snp_pad, lut_mode, split16, lut, d_nlocus, d_sumden, dvals, d_missing, ccoef,
-                       exact_rows_always, w_shift, exact_with_missing, entry12, homo_const, uvsp_miss, x1_sparse_mac, d_short_runs);
+                       n_snp, n_snp_pad, o.lut_mode, o.split16 ? 1 : 0, o.lut, o.d_nlocus, o.d_sumden, o.dvals, o.d_missing, o.ccoef,
+                       o.exact_rows_always ? 1 : 0, o.w_shift, o.exact_with_missing ? 1 : 0, o.entry12 ? 1 : 0, o.homo_const, o.uvsp_miss,
+                       o.x1_sparse_mac, o.d_short_runs);
     SNPGPU_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -778,24 +775,25 @@ __global__ __launch_bounds__(256) void uv_tables_kernel(const uint32_t *__restri
 
 // n_target > 1: the block's slots are dealt to n_target runs of cpr table chunks (slot_of / slot_src are written);
 // n_target == 1: slot k = SNP k (slot_src may be null)
-int launch_build_uv(hipStream_t st, const int32_t *sum, const int32_t *num, int64_t n_snp, int64_t n_snp_pad, int lut_mode,
-                    uint2 *lut, double4 *uvcoef, double *kpart, double4 *uvsp, float *cand_err, uint32_t *cand_uv,
-                    double2 *snp_tavg, int32_t *slot_of, int32_t *slot_src, int n_target, int cpr,
-                    const unsigned long long *d_missing, int swap_odd)
+int launch_build_uv(hipStream_t st, const int32_t *sum, const int32_t *num, int64_t n_snp, int64_t n_snp_pad, const BuildUvOpts &o)
 {
     if (n_snp_pad <= 0) return 0;
+    const int n_target = o.n_target, cpr = o.cpr;
+    int32_t *slot_of = o.slot_of, *slot_src = o.slot_src;
+    // the kernel's swap_odd: 0 plain tables, 1 swapped odd quarters (lookup form), 2 factor arrays (converted forms)
+    const int swap_odd = o.form == UvForm::Mfma32x32x16 ? 0 : o.form == UvForm::Lookup16x16x32 ? 1 : 2;
     if (n_target < 1 || n_target > UV_QMAX || (n_target > 1 && ((n_snp_pad % UV_CHS) != 0 || !slot_src || !slot_of || cpr < 1))) {
         set_error("build_uv: invalid run plan");
         return 1;
     }
     const int n_chunk = (int)((n_snp_pad + UV_CHS - 1) / UV_CHS);
-    hipLaunchKernelGGL(uv_factor_kernel, dim3((unsigned)((n_snp_pad + 3) / 4)), dim3(256), 0, st, sum, num, n_snp, n_snp_pad, lut_mode,
-                       n_target, cand_err, cand_uv, snp_tavg, uvsp, d_missing);
+    hipLaunchKernelGGL(uv_factor_kernel, dim3((unsigned)((n_snp_pad + 3) / 4)), dim3(256), 0, st, sum, num, n_snp, n_snp_pad, o.lut_mode,
+                       n_target, o.cand_err, o.cand_uv, o.snp_tavg, o.uvsp, o.d_missing);
     if (n_target > 1)
-        hipLaunchKernelGGL(uv_assign_kernel, dim3(1), dim3(1024), 0, st, cand_err, snp_tavg, n_snp_pad, n_target, cpr, n_chunk, slot_of,
-                           slot_src, d_missing);
-    hipLaunchKernelGGL(uv_tables_kernel, dim3((unsigned)(n_snp_pad / 256)), dim3(256), 0, st, cand_uv, snp_tavg,
-                       n_target > 1 ? slot_src : nullptr, n_snp_pad, n_target, cpr, lut, uvcoef, kpart, d_missing, swap_odd);
+        hipLaunchKernelGGL(uv_assign_kernel, dim3(1), dim3(1024), 0, st, o.cand_err, o.snp_tavg, n_snp_pad, n_target, cpr, n_chunk, slot_of,
+                           slot_src, o.d_missing);
+    hipLaunchKernelGGL(uv_tables_kernel, dim3((unsigned)(n_snp_pad / 256)), dim3(256), 0, st, o.cand_uv, o.snp_tavg,
+                       n_target > 1 ? slot_src : nullptr, n_snp_pad, n_target, cpr, o.lut, o.uvcoef, o.kpart, o.d_missing, swap_odd);
     SNPGPU_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1314,13 +1312,12 @@ __global__ __launch_bounds__(256) void transpose8_kernel(const uint8_t *__restri
     }
 }
 
-int launch_transpose8(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t col0,
-                      int64_t ncols_pad, int n_d, uint32_t *w8, const unsigned long long *d_wide16, int always_wide,
-                      const int32_t *slot_src, int nibble_nomiss)
+int launch_transpose8(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t col0, int64_t ncols_pad,
+                      const Transpose8Opts &o)
 {
-    dim3 grid((unsigned)((ncols_pad + TR_SAMPLES - 1) / TR_SAMPLES), (unsigned)((n_d + 7) / 8));   // groups of 64 SNPs (slots)
-    hipLaunchKernelGGL(transpose8_kernel, grid, dim3(256), 0, st, packed, RB, n_snp, col0, ncols_pad, n_d, w8, d_wide16,
-                       always_wide, slot_src, nibble_nomiss);
+    dim3 grid((unsigned)((ncols_pad + TR_SAMPLES - 1) / TR_SAMPLES), (unsigned)((o.n_d + 7) / 8));   // groups of 64 SNPs (slots)
+    hipLaunchKernelGGL(transpose8_kernel, grid, dim3(256), 0, st, packed, RB, n_snp, col0, ncols_pad, o.n_d, o.w8, o.d_block_flag,
+                       (int)o.layout, o.slot_src, o.nibble_nomiss ? 1 : 0);     // (WordLayout = the kernel's always_wide codes)
     SNPGPU_HIP_CHECK(hipGetLastError());
     return 0;
 }

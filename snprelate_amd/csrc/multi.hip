@@ -25,6 +25,7 @@
 #include <thread>
 #include <vector>
 
+#include "ctx_plan.h"
 #include "eigen.h"
 
 using namespace snpgpu;
@@ -387,7 +388,7 @@ int gather_slabs(snpgpu_multi *m, int n_out, size_t esz, void *const *out, int m
         for (int i : D.panels) {
             snpgpu_ctx *c = m->ctx[(size_t)i];
             const size_t elems = (size_t)snpgpu_slab_size(c);
-            const size_t off = (size_t)tri_offset(m->N, c->row0);
+            const size_t off = (size_t)tri_offset(m->N, c->plan.row0);
             std::vector<DevBuf> tmp((size_t)n_out);
             std::vector<void *> ptr((size_t)n_out);
             const bool direct = (mem == SNPGPU_DEVICE && c->device == dev0);
@@ -751,8 +752,8 @@ int snpgpu_multi_panel(const snpgpu_multi *m, int i, snpgpu_ctx **ctx, int64_t *
 {
     if (!m || i < 0 || i >= (int)m->ctx.size()) { set_error("snpgpu_multi_panel: invalid panel"); return 1; }
     if (ctx) *ctx = m->ctx[(size_t)i];
-    if (row_begin) *row_begin = m->ctx[(size_t)i]->row0;
-    if (row_end) *row_end = m->ctx[(size_t)i]->row1;
+    if (row_begin) *row_begin = m->ctx[(size_t)i]->plan.row0;
+    if (row_end) *row_end = m->ctx[(size_t)i]->plan.row1;
     if (device) *device = m->ctx[(size_t)i]->device;
     return 0;
 }
@@ -960,10 +961,10 @@ int snpgpu_multi_topk_eigen(snpgpu_multi *m, double scale, int k, const snpgpu_e
     if (opts && opts->reduce) { set_error("snpgpu_multi_topk_eigen: the object reduces over its own devices; no callback"); return 1; }
     // the resident panels must be the whole triangle
     int64_t rows = 0;
-    for (snpgpu_ctx *c : m->ctx) rows += c->row1 - c->row0;
+    for (snpgpu_ctx *c : m->ctx) rows += c->plan.row1 - c->plan.row0;
     if (rows != m->N) { set_error("snpgpu_multi_topk_eigen: needs all panels resident (a one-pass plan)"); return 1; }
     for (snpgpu_ctx *c : m->ctx)
-        if (!(c->kind == SNPGPU_PCA_COV || c->frozen)) { set_error("snpgpu_multi_topk_eigen: call snpgpu_multi_finalize_inplace first"); return 1; }
+        if (!(c->plan.kind == SNPGPU_PCA_COV || c->frozen)) { set_error("snpgpu_multi_topk_eigen: call snpgpu_multi_finalize_inplace first"); return 1; }
     double sc = scale;
     if (m->kind == SNPGPU_PCA_COV && !(scale > 0)) {         // scale <= 0: the (n - 1) / trace factor of gnrPCA, src/genPCA.cpp:1386-1390
         double tr = 0;

@@ -109,6 +109,26 @@ enum LutMode {
     LUT_EIGMIX_MISSW = 5 // sqrt(4p(1-p)) for MISSING calls, 0 otherwise -> weighted both-missing sums
 };
 
+void pair_i8_tile(int mode, int *tile_r, int *tile_c, int *wg_per_cu = nullptr);
+bool pair_fp4_tile(int mode, int *tile_r, int *tile_c, int *wg_per_cu);
+
+// form of the single-product SYRK (syrk_uv*_kernel)
+enum class UvForm {
+    Mfma32x32x16 = 0,      // syrk_uv_kernel
+    Lookup16x16x32 = 1,    // syrk_uv16_kernel: operands looked up in LDS tables (tables with swapped odd quarters)
+    Converted = 2,         // syrk_uv16c_kernel: operands CONVERTED from nibble words (`uvlut` holds the slots' factors, `wt` bytes
+                           // c0 | c1 << 4 in blocks without missing calls); GRM / PCA contexts only
+    ConvertedCarry = 3     // ... and a work item walks its tile's runs itself, half the sub-tile sums carried in LDS as fp32
+};
+// what a byte of the pair-coded words holds (transpose8_kernel): the table offset of the pair's entry
+enum class WordLayout {
+    Entry8Or16 = 0,        // 8 * code; 16 * code in a block without missing calls when the block flag is passed
+    Entry16 = 1,           // 16 * code in every block
+    Entry12 = 2,           // 12 * code in every block
+    Entry12Or8 = 3,        // 12 * code, 8 * code in a block without missing calls (single-product kernel: 8-byte entries)
+    Entry12Missing = 4     // 12 * code, written only for a block WITH missing calls (EIGMIX: a second word array)
+};
+
 struct TileGrid {      // upper-trapezoid tile enumeration with XCD super-tiles
     int tile_r, tile_c;        // tile extents in samples
     int super;                 // super-tile edge in tiles
@@ -150,12 +170,24 @@ int launch_repack(hipStream_t st, const void *src, int format, int64_t n_snp, in
                   uint8_t *packed, int64_t RB);
 int launch_snp_stats(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t n_samp,
                      int32_t *sum, int32_t *num, unsigned long long *d_missing_cells, int32_t *nhet = nullptr);
-int launch_build_lut(hipStream_t st, const int32_t *sum, const int32_t *num, int64_t n_snp, int64_t n_snp_pad,
-                     int lut_mode, int split16, float2 *lut, unsigned long long *d_nlocus, double *d_sumden,
-                     double *dvals, const unsigned long long *d_missing = nullptr, double2 *ccoef = nullptr,
-                     int exact_rows_always = 0, int w_shift = 0, int exact_with_missing = 0, int entry12 = 0,
-                     double *homo_const = nullptr, double4 *uvsp_miss = nullptr, int x1_sparse_mac = 0,
-                     unsigned long long *d_short_runs = nullptr);
+// table pass of one SYRK table (build_lut_kernel); the named fields are the kernel's arguments of the same names
+struct BuildLutOpts {
+    int lut_mode = 0;
+    bool split16 = false;
+    float2 *lut = nullptr;
+    unsigned long long *d_nlocus = nullptr;
+    double *d_sumden = nullptr, *dvals = nullptr;
+    const unsigned long long *d_missing = nullptr;
+    double2 *ccoef = nullptr;
+    bool exact_rows_always = false;
+    int w_shift = 0;
+    bool exact_with_missing = false, entry12 = false;
+    double *homo_const = nullptr;
+    double4 *uvsp_miss = nullptr;
+    int x1_sparse_mac = 0;
+    unsigned long long *d_short_runs = nullptr;
+};
+int launch_build_lut(hipStream_t st, const int32_t *sum, const int32_t *num, int64_t n_snp, int64_t n_snp_pad, const BuildLutOpts &o);
 int launch_colcorr(hipStream_t st, const uint32_t *w8, int64_t ncols_pad, int n_d, const double2 *ccoef, double *tc,
                    double *colterm, const unsigned long long *d_missing, int always = 0, int entry12 = 0);
 int launch_colterm_settle(hipStream_t st, double *acc, int64_t ld, int64_t tiles_c, int64_t n_rows_real, int64_t ncols_pad, int64_t n_cols_real,
@@ -187,29 +219,51 @@ int launch_pair_sparse_miss(hipStream_t st, const uint4 *mm, int64_t snp_stride,
 int launch_transpose2_direct(hipStream_t st, const uint8_t *src, int64_t n_samp, int64_t n_snp, int64_t col0,
                              int64_t ncols_pad, int n_d, uint32_t *w2, uint32_t *het, uint32_t *het_blk,
                              unsigned long long *d_missing);
-void pair_i8_tile(int mode, int *tile_r, int *tile_c, int *wg_per_cu = nullptr);
 int launch_pair_fp4_miss(hipStream_t st, const int4 *work, int n_blocks, const uint32_t *w2, int64_t ncols_pad, int n_s,
                          uint32_t *acc, const unsigned long long *d_missing);
 int launch_pair_i8(hipStream_t st, int mode, const int4 *work, int n_blocks, const uint32_t *w2, int64_t ncols_pad,
                    int n_q, int n_snp, uint32_t *acc, int64_t acc_plane, const unsigned long long *d_missing,
                    const int4 *work_nm = nullptr, int n_blocks_nm = 0, bool fp4_nomiss = false, bool fp4_general = false);
-bool pair_fp4_tile(int mode, int *tile_r, int *tile_c, int *wg_per_cu);
 int launch_het_settle(hipStream_t st, uint32_t *acc, int64_t plane, int64_t rows_pad, int64_t ncols_pad, uint32_t *het,
                       int king, int plane_ibs1 = 1, int plane_ibs0x2 = 2);
-int launch_syrk_h3(hipStream_t st, const int4 *work, int n_blocks, const uint32_t *w8, int64_t ncols_pad,
-                    const uint2 *lut, int n_q, double *acc, int64_t ld, int64_t tiles_c,
-                    const unsigned long long *d_skip_if_zero = nullptr, int a_kind = -1, const unsigned long long *d_missing = nullptr, int64_t n_rows_real = 0,
-                    int promote_snps = 0, const int4 *work_x1 = nullptr, int n_blocks_x1 = 0,
-                    const unsigned long long *d_short_runs = nullptr);
-int launch_syrk_uv(hipStream_t st, const int4 *work_x1, int n_blocks_x1, const uint32_t *w8, int64_t ncols_pad,
-                   const uint2 *lut, int n_q, double *acc, int64_t ld, int64_t tiles_c, const unsigned long long *d_missing,
-                   int64_t n_rows_real, int run_chunks, int n_target, int run_if_missing = 0, int64_t copy_lut_bytes = 0,
-                   int64_t copy_acc_elems = 0, int uv16 = 0,      // uv16 = 2, 3: syrk_uv16c_kernel (lut = factor arrays)
-                   const void *pace_src = nullptr, int pace = 0);   // ... and its pace-maker (on / off; 16 x 1 KiB per wave and chunk)
-int launch_build_uv(hipStream_t st, const int32_t *sum, const int32_t *num, int64_t n_snp, int64_t n_snp_pad, int lut_mode,
-                    uint2 *lut, double4 *uvcoef, double *kpart, double4 *uvsp, float *cand_err, uint32_t *cand_uv,
-                    double2 *snp_tavg, int32_t *slot_of, int32_t *slot_src, int n_target, int cpr,
-                    const unsigned long long *d_missing, int swap_odd = 0);
+// what every SYRK launch shares: the pair-coded words and the fp64 plane they add to
+struct SyrkPanel { const uint32_t *w8; int64_t ncols_pad; double *acc; int64_t ld, tiles_c, n_rows_real; };
+struct SyrkH3Opts {
+    const int4 *work = nullptr, *work_x1 = nullptr;
+    int n_blocks = 0, n_blocks_x1 = 0;
+    const uint2 *lut = nullptr;
+    int n_q = 0, a_kind = -1, promote_snps = 0;
+    const unsigned long long *d_skip_if_zero = nullptr, *d_missing = nullptr, *d_short_runs = nullptr;
+};
+int launch_syrk_h3(hipStream_t st, const SyrkPanel &p, const SyrkH3Opts &o);
+struct SyrkUvOpts {
+    const int4 *work_x1 = nullptr;
+    int n_blocks_x1 = 0;
+    const uint2 *lut = nullptr;                  // Converted forms: the slots' factor arrays
+    int n_q = 0;
+    const unsigned long long *d_missing = nullptr;
+    int run_chunks = 0, n_target = 1;
+    bool run_if_missing = false;
+    int64_t copy_lut_bytes = 0, copy_acc_elems = 0;   // table / plane stride between the copies of a work list (KING-homo's weights)
+    UvForm form = UvForm::Mfma32x32x16;
+    const void *pace_src = nullptr;              // Converted forms: the pace-maker (16 x 1 KiB per wave and chunk) and its switch
+    bool pace = false;
+};
+int launch_syrk_uv(hipStream_t st, const SyrkPanel &p, const SyrkUvOpts &o);
+struct BuildUvOpts {
+    int lut_mode = 0;
+    uint2 *lut = nullptr;
+    double4 *uvcoef = nullptr, *uvsp = nullptr;
+    double *kpart = nullptr;
+    float *cand_err = nullptr;
+    uint32_t *cand_uv = nullptr;
+    double2 *snp_tavg = nullptr;
+    int32_t *slot_of = nullptr, *slot_src = nullptr;
+    int n_target = 1, cpr = 1;
+    const unsigned long long *d_missing = nullptr;
+    UvForm form = UvForm::Mfma32x32x16;          // table layout of the kernel that reads them
+};
+int launch_build_uv(hipStream_t st, const int32_t *sum, const int32_t *num, int64_t n_snp, int64_t n_snp_pad, const BuildUvOpts &o);
 int launch_uv_sparse(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t N, int64_t row0, int64_t row1,
                      int64_t col0, const double4 *uvsp, double *acc, int64_t ld, int64_t tiles_c, int64_t ncols_pad, double *uvterm,
                      const unsigned long long *d_missing, int missing_blocks = 0);
@@ -218,9 +272,16 @@ int launch_uvcorr(hipStream_t st, const uint32_t *w8, int64_t ncols_pad, int n_d
 int launch_homo_uv(hipStream_t st, const int32_t *sum, const int32_t *num, int64_t n_snp, int64_t n_snp_pad, uint2 *lut1, uint2 *lut2,
                    double2 *wts, double *totals, const uint32_t *w8, int64_t ncols_pad, double2 *tc, double *msum,
                    const unsigned long long *d_missing, int swap_odd = 0, int n_w = 2);
-int launch_transpose8(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t col0,
-                      int64_t ncols_pad, int n_d, uint32_t *w8, const unsigned long long *d_wide16 = nullptr,
-                      int always_wide = 0, const int32_t *slot_src = nullptr, int nibble_nomiss = 0);
+struct Transpose8Opts {
+    int n_d = 0;
+    uint32_t *w8 = nullptr;
+    const unsigned long long *d_block_flag = nullptr;   // the block's missing-call flag (the kernel's d_wide16)
+    WordLayout layout = WordLayout::Entry8Or16;
+    const int32_t *slot_src = nullptr;
+    bool nibble_nomiss = false;
+};
+int launch_transpose8(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t col0, int64_t ncols_pad,
+                      const Transpose8Opts &o);
 int launch_syrk(hipStream_t st, const TileGrid &tg, const uint32_t *w8, int64_t ncols_pad, const float2 *lut,
                 int n_q, double *acc, int64_t ld, int64_t tiles_c, const unsigned long long *d_skip_if_zero = nullptr);
 
@@ -267,9 +328,19 @@ int launch_mirror_diag_tiles(hipStream_t st, const PanelGeom &g, double *num, in
 int ctx_settle(snpgpu_ctx *c);                                   // pending column / row terms of the fp16 SYRK -> panel
 int ctx_panel_matmul_enqueue(snpgpu_ctx *c, double scale, const double *Q, int m, double *Y, bool fp32_products = false);   // no host synchronisation
 
-struct DevBuf {
+struct DevBuf {            // owns its device memory: released with the object, movable, not copyable
     void *p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     int alloc(size_t n)
     {
         if (n == 0) n = 16;
@@ -285,7 +356,6 @@ struct DevBuf {
     }
 };
 
-
 }  // namespace snpgpu
 
 struct snpgpu_proj {       // PCA projector (proj.hip)
@@ -299,111 +369,3 @@ struct snpgpu_proj {       // PCA projector (proj.hip)
     bool staged_words = false; // ... and whether w2 holds its sample-major words
     snpgpu::DevBuf raw, packed, sum, num, w2, et, eig_in, out, part, cnt, avg, scale, sl, af, sc, acc, flag;
 };
-
-struct snpgpu_ctx {
-    int kind = 0, device = 0, bayesian = 0;
-    int64_t N = 0, row0 = 0, row1 = 0, col0 = 0;
-    int64_t rows_pad = 0, ncols_pad = 0, RB = 0, Bmax = 0;
-    int KWmax = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    bool full = false;
-    int64_t n_snp_total = 0;
-    // asynchronous host feeds: second stream + double-buffered raw block + events
-    hipStream_t copy_stream = nullptr;
-    snpgpu::DevBuf raw2[2];
-    hipEvent_t ev_copied[2] = {nullptr, nullptr};    // H2D of raw2[k] finished
-    hipEvent_t ev_consumed[2] = {nullptr, nullptr};  // repack of raw2[k] finished (buffer reusable)
-    const void *host_src[2] = {nullptr, nullptr};
-    int raw_turn = 0;
-    int diag_mirrored = 0;        // eigen solver: 1 = diagonal 64 x 64 tiles mirrored, 2 = whole diagonal square
-    bool frozen = false;          // snpgpu_finalize_inplace: plane 0 of acc_f64 holds the FINAL matrix (upper trapezoid of the
-    int frozen_diagadj = 0;       //   panel rectangle); no feeds may follow, the kind's finaliser copies it out
-    double frozen_scale = 1.0;
-    void *blas = nullptr;         // rocblas_handle, created on first use
-    bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[2];  // [0] pair popcount, [1] SYRK
-
-    // feed-block scratch
-    snpgpu::DevBuf raw, packed, sum, num, nhet, lut[2], rowp, colp, wt, w2, scalars, family, miss_diag, dvals, samp_het, samp_dmiss, samp_dsq;
-    snpgpu::DevBuf eig_qt;        // eigen solver: sample-major copy of the current vector block, double [N][48]
-    snpgpu::DevBuf acc_f32;       // eigen solver: fp32 copy of plane 0 for the fp32 products (made on first use where memory allows)
-    bool acc_f32_valid = false;   //     ... and whether it still mirrors the plane (a feed invalidates it)
-    snpgpu::DevBuf het_blk;       // per-block het counts of the one-pass pre-pass (committed to `het` when the block's flag is final)
-    snpgpu::DevBuf het, i8_work_nm;   // binary pair kernel for blocks without missing calls: per-sample het counts, its work list
-    int i8_blocks_nm = 0;
-    bool het_pending = false;
-    snpgpu::DevBuf ccoef, tcorr;   // exact-row-side SYRK: per-SNP {u, v} and per-chunk column terms [Bmax / H3_LUTCH + 1][ncols_pad]
-    snpgpu::DevBuf colterm;        // ... their running total per column (fp64 [ncols_pad]), subtracted from every row of the
-    snpgpu::DevBuf wt12;           // EIGMIX: 12 * code words of a block with missing calls (exact-row kernel of the numerator)
-    bool eigmix_x1 = false;        // EIGMIX numerator of blocks with missing calls on syrk_x1_kernel (else the legacy three-product kernel)
-    snpgpu::DevBuf uvpace;         // syrk_uv16c_kernel: 64 KiB per table chunk that every workgroup fetches (zeros; see the kernel)
-    int uvc_pace = 0;              // ... pace-maker on / off (SNPGPU_UVC_PACE, default on)
-    snpgpu::DevBuf uvlut, uvslot;  // ... its own tables (8-byte entries, per SLOT) and the slot -> SNP map of the current block
-    snpgpu::DevBuf uvcand;         // ... per SNP and weight target: {relative error, u | v << 16}, {t, avg}, SNP -> slot
-    int uv_promote = 0;            // fp32 run of the single-product kernel in slots (h3_promote: of the exact-row kernel, in SNPs)
-    snpgpu::DevBuf uvcoef, uvterm, uvkpart, uvsp;   // single-product SYRK (blocks without missing calls): per-SNP {d_b uv, c_a, d_a uv, c_b},
-                                   //     the running row / column terms {R[ncols_pad], Q[ncols_pad], K} and per-chunk parts of K
-    bool uv_enabled = false;
-    bool uv16 = false;            // single-product kernel on v_mfma_f32_16x16x32_f16 (syrk_uv16_kernel; tables with swapped odd quarters)
-    bool uvc_carry = false;       // ... syrk_uv16c_kernel walks a tile's runs itself, half the sub-tile sums carried in LDS as fp32 (SNPGPU_SYRK_UV16=3)
-    bool uvc = false;             // ... with the operands CONVERTED from nibble words instead of looked up (syrk_uv16c_kernel: `uvlut` holds the
-                                  // slots' factors, `wt` bytes c0 | c1 << 4 in blocks without missing calls); GRM / PCA contexts only
-    bool uv_targets = false;       // a weight target per fp32 run (uv_factor_kernel)
-    int x1_sparse_mac = 0;
-    bool x1_short_runs = true;     // blocks with rare variants on the sparse path AND missing calls: half-length fp32 runs (device flag)
-    bool sparse_missing = false;            // rare variants of blocks with missing calls: carriers' pairs added in fp64 (uv_sparse_kernel)
-    bool uv_eigmix = false;      // ... for the EIGMIX numerator (weight 1: exact)
-    bool homo_uv = false;        // KING-homo blocks with missing calls: weight sums = totals - per-sample missing sums + ONE fp16 product each
-    snpgpu::DevBuf homo_lut[2], homo_wts, homo_tc, homo_msum, homo_work;   //     ... its tables, effective weights, per-chunk partials, M[2][ncols_pad], work list
-    snpgpu::DevBuf diss_called;  // dissimilarity: per column sample, 1 once it is called at an SNP of nonzero weight (exact zero denominators)
-    int homo_blocks = 0;
-    bool colterm_pending = false;  //     panel once, before a result is read (settle_colterm, api.hip)
-    // accumulators
-    snpgpu::DevBuf acc_u32, acc_f64;
-    int n_u32 = 0, n_f64 = 0;
-    snpgpu::TileGrid tg_pc{}, tg_mm{};
-    snpgpu::DevBuf tg_pc_tab, tg_mm_tab;
-    bool use_pc = false, use_mm = false;
-    bool pc_i8 = false;        // pair counters on int8 MFMA (w2 words) instead of bit planes
-    bool miss_fp4 = true;      // GCTA both-missing counts on the MX-fp4 MFMA (SNPGPU_GCTA_MISS_FP4=0: the int8 kernel)
-    bool nomiss_fp4 = true;    // IBS / KING blocks without missing calls on the MX-fp4 MFMA (SNPGPU_PAIR_FP4=0: the int8 two-product kernel)
-    bool general_fp4 = false;  // ... and the general IBS / KING-robust kernels (blocks with missing calls; SNPGPU_PAIR_FP4_GENERAL=0: int8)
-    int i8_blocks = 0;         // work items (= workgroups) of the int8 pair kernel, see build_worklist
-    snpgpu::DevBuf i8_work;    // int4 {tile row, tile col, K part, K parts} per workgroup, XCD-interleaved
-    snpgpu::DevBuf mm256, sp_work;   // GCTA denominators, sparse form: per (256-sample group, SNP) set of missing calls; its 256 x 256 work list
-    int sp_blocks = 0;
-    double sp_max_rate = 0.0;        // ... taken for blocks whose missing-call rate is at most this (0: never)
-    bool mm_h3 = false;        // SYRK on split-fp16 MFMAs (GCTA / Bayesian tables) instead of fp32 MFMAs
-    bool h3_exact_rows = false; // two-product kernel with the exact row operand (g - c_s) 2^shift
-    bool h3_exact_missing = false; // ... also for blocks WITH missing calls (row value of a missing call = fp16(avg - c_s)); else three products there
-    int h3_promote = 0;         // fp32 run length of the exact-row kernel in SNPs (0 = H3_PROMOTE_EXACT; SNPGPU_H3_PROMOTE)
-    int h3_a_kind[2] = {-1, -1};
-    int h3_w_shift = 0;         // exact-row tables hold w * 2^-shift, the row operand is +-2^shift (fp16 range, |w| <= 4N)
-    int h3_blocks = 0;
-    snpgpu::DevBuf h3_work;
-    int x1_blocks = 0;          // work list of syrk_x1_kernel (256 x 256 tiles, one workgroup per CU); 0: not used
-    snpgpu::DevBuf x1_work;
-    int pc_mode = 0;
-    int lut_mode[2] = {0, 0};
-    int n_lut = 0;
-
-    // scalars layout: SCALAR_SLOTS slots of 8 bytes (unsigned long long / double) -- the allocation in snpgpu_create is exactly
-    // this many, a ninth scalar needs SCALAR_SLOTS raised with it:
-    // [0] missing cells of the current block, [1] nLocus, [2] trace (double), [3] EIGMIX SumDenominator (double),
-    // [4..5] KING-homo weight sums of the blocks without missing calls, [6..7] route of this block's both-missing counts
-    // [8] this block holds rare variants on the fp64 sparse path next to missing calls: the exact-row kernel runs it as 4096-SNP fp32 runs
-    static constexpr int SCALAR_SLOTS = 16;
-    unsigned long long *d_missing() { return (unsigned long long *)scalars.p; }
-    unsigned long long *d_nlocus() { return (unsigned long long *)scalars.p + 1; }
-    double *d_trace() { return (double *)scalars.p + 2; }
-    double *d_sumden() { return (double *)scalars.p + 3; }
-    double *d_homo_w() { return (double *)scalars.p + 4; }   // [2]: sum p(1-p), sum (p(1-p))^2 over the blocks without missing calls (KING-homo)
-    unsigned long long *d_short_runs() { return (unsigned long long *)scalars.p + 8; }
-    unsigned long long *d_miss_route() { return (unsigned long long *)scalars.p + 6; }   // [2]: this block's both-missing counts take the sparse / the dense form
-
-    int64_t acc_tiles_c = 0;     // fp64 planes tile-major: ncols_pad / 256 (0 = row-major)
-    snpgpu::PanelGeom geom() const { return snpgpu::PanelGeom{N, row0, row1, col0, rows_pad, ncols_pad, acc_tiles_c}; }
-    int64_t plane() const { return rows_pad * ncols_pad; }
-};
-

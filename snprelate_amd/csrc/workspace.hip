@@ -13,7 +13,7 @@
 #include <limits>
 #include <vector>
 
-#include "snpgpu_internal.h"
+#include "ctx_plan.h"
 
 using namespace snpgpu;
 
@@ -439,14 +439,14 @@ static int krylov_scale(snpgpu_ctx *c, double *scale)
         snpgpu::set_error("LAPACK::DSPEVX error (-1), infinite or missing values in the genetic covariance matrix!");
         return 1;
     }
-    *scale = (double)(c->N - 1) / tr;
+    *scale = (double)(c->plan.N - 1) / tr;
     return 0;
 }
 
 int snpgpu_pca_eigen(snpgpu_ctx *c, int k, double *eigval, double *eigvec, int mem)
 {
-    if (!c || c->kind != SNPGPU_PCA_COV || !c->full) { set_error("snpgpu_pca_eigen: needs a full PCA_COV context"); return 1; }
-    const int64_t n = c->N;
+    if (!c || c->plan.kind != SNPGPU_PCA_COV || !c->plan.full) { set_error("snpgpu_pca_eigen: needs a full PCA_COV context"); return 1; }
+    const int64_t n = c->plan.N;
     if (k <= 0 || k > n) { set_error("Invalid 'eigen.cnt'."); return 1; }
     SNPGPU_HIP_CHECK(hipSetDevice(c->device));
     if (!dense_route(n, k)) {

@@ -141,6 +141,26 @@ def test_king_homo_blocks_without_missing_calls(missing_blocks, pair_backend):
             np.testing.assert_allclose(k1, r1, rtol=1e-5, atol=2e-5, equal_nan=True)
 
 
+def test_refused_create_leaves_the_process_usable(monkeypatch):
+    """A context that snpgpu_create refuses from its plan (the dissimilarity kind without the MX-fp4 counters) owns nothing when the
+    call returns: the refusal carries the same text as ever, and a default GRM context created next in this process matches the
+    oracle."""
+    from snprelate_amd import _lib
+    monkeypatch.setenv("SNPGPU_PAIR_FP4", "0")
+    with pytest.raises(_lib.SnpGpuError, match="snpgpu_create: the dissimilarity kind needs the MX-fp4 counter kernels and the fp16 "
+                                               "weight product"):
+        _acc(_lib.DISS, 64)
+    monkeypatch.delenv("SNPGPU_PAIR_FP4")
+    n, L = 64, 300
+    g = synth_geno(n, L, missing=0.05, seed=n + 3)
+    ref = orc.grm_gcta(g)
+    with _acc(_lib.GRM_GCTA, n) as a:
+        a.feed(g)
+        got = a.grm_gcta(packed=True)
+    assert _rel_err(got, ref) < 1e-5
+    assert np.array_equal(np.isfinite(got), np.isfinite(ref))
+
+
 @pytest.fixture(params=["f16", "f16_uvc", "f16_uv16", "f16_uv32", "f16_x1", "f16_2w", "h3", "f32"])
 def syrk_backend(request, monkeypatch):
     """The SYRK kernels behind GRM / PCA.  f16 (default): blocks without missing calls take the single-product kernel
