@@ -680,6 +680,51 @@ int snpgpu_gnrDistPerm(int n_dist, const double *dist, const int32_t *merge, int
  * [5] permutations evaluated */
 int snpgpu_tree_stats(double *stats);
 
+/* ---- (1i) genotype scores of listed sample pairs: snpgdsPairScore ------------------------------------------------------------------
+ * gnrPairScore (src/genIBS.cpp:690-891): pair j is (idx1[j], idx2[j]), 0-based sample indices in host memory; a sample may be in
+ * both lists and may be paired with itself.  A score is map[g1][g2] of the method's 4 x 4 integer map wherever g1 < 3 && g2 < 3;
+ * the two *.only maps hold -1 at some such cells, and there -1 is a score like any other (it enters Sum, SqSum and Num and is
+ * written to the matrix).  The four *.major / *.minor methods first flip a SNP (every g < 3 becomes 2 - g) when gsum < n, n the
+ * number of called genotypes over both lists and gsum their sum, a sample counting once per appearance.
+ * The device only counts, whatever the method: per SNP the table of the pairs' codes before any flip, per pair the table of the
+ * SNPs' codes after it.  snpgpu_pair_score_final turns a table into (Avg, SD, Num) on the host; all sums are integers, put
+ * through CalcAvgSD's fp64 operations (src/dGenGWAS.cpp:2365-2379), so the results are the reference's bit for bit.
+ *   geno   as in (1g); 2-bit rows in device memory are read in place, everything else is streamed in SNP blocks
+ * Refused before any device is touched: n_pair < 1, an index outside [0, n_samp), an unknown method / kind, NULL outputs. */
+enum snpgpu_pair_method { SNPGPU_PS_IBS = 1, SNPGPU_PS_GVH = 2, SNPGPU_PS_HVG = 3, SNPGPU_PS_GVH_MAJOR = 4, SNPGPU_PS_GVH_MINOR = 5,
+                          SNPGPU_PS_GVH_MAJOR_ONLY = 6, SNPGPU_PS_GVH_MINOR_ONLY = 7 };
+enum snpgpu_pair_table { SNPGPU_PS_PAIR_TABLE = 0, SNPGPU_PS_SNP_TABLE = 1 };
+enum snpgpu_pair_elem { SNPGPU_PS_ELEM_INT32 = 0, SNPGPU_PS_ELEM_BIT2 = 1 };
+/* pair_tab: int64 [n_pair][9], cell 3 a + b = the SNPs where the pair has codes (a, b), a, b < 3, counted after the flip when
+ *           need_major != 0 and as stored otherwise
+ * snp_tab:  int32 [n_snp][16], cell 4 a + b = the pairs with codes (a, b), a, b < 4 (3 = missing), as stored
+ * flip:     uint8 [n_snp], 1 where gsum < n (computed whatever need_major is)
+ * all three in out_mem; any may be NULL, not all */
+int snpgpu_pair_tables(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, const int32_t *idx1, const int32_t *idx2,
+                       int64_t n_pair, int need_major, int64_t *pair_tab, int32_t *snp_tab, uint8_t *flip, int out_mem, int device);
+/* Host code, touches no device.  table: n rows of a pair table (SNPGPU_PS_PAIR_TABLE, counted with need_major as the method needs)
+ * or of a SNP table with its flip bytes (SNPGPU_PS_SNP_TABLE; flip may be NULL for IBS / GVH / HVG).  dosage selects the 0 / 1 / 2
+ * or the 0 / 1 form of IBS, GVH and HVG and is ignored by the other methods.  out: (Avg, SD, Num) per row, laid out as the R object:
+ * pair table n x 3 column-major (out[i], out[n + i], out[2 n + i]), SNP table 3 x n (out[3 i ...]).  Num > 1: Avg = Sum / Num,
+ * SD = sqrt((SqSum - Num Avg Avg) / (Num - 1)); Num == 1: Avg = Sum, SD = NaN; Num == 0: both NaN. */
+int snpgpu_pair_score_final(int table_kind, const void *table, const uint8_t *flip, int64_t n, int method, int dosage, double *out);
+/* The score of every (SNP, pair) after the flip, out_host [n_snp][n_pair] (R's n_pair x n_snp matrix), streamed to the host in SNP
+ * blocks: SNPGPU_PS_ELEM_INT32 int32 with INT_MIN (NA_integer_) where a genotype is missing; SNPGPU_PS_ELEM_BIT2 uint8 holding the
+ * two bits a bit2 node keeps of the reference's byte: 3 for missing, and 3 for a score of -1 */
+int snpgpu_pair_score_matrix(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, const int32_t *idx1,
+                             const int32_t *idx2, int64_t n_pair, int method, int dosage, int elem_kind, void *out_host, int device);
+/* gnrPairScore(SampIdx1, SampIdx2, Method, Type, Dosage, GDSNode, Verbose) on the working space's selected SNPs.  method "IBS",
+ * "GVH", "HVG", "GVH.major", "GVH.minor", "GVH.major.only", "GVH.minor.only"; type and host `out`: "per.pair" double n_pair x 3
+ * column-major, "per.snp" double 3 x n_snp, "matrix" int32 n_pair x n_snp column-major, "gds.file" uint8 of the same shape (the
+ * bytes appended to the bit2 node) */
+int snpgpu_gnrPairScore(const int32_t *idx1, const int32_t *idx2, int64_t n_pair, const char *method, const char *type, int dosage,
+                        int verbose, void *out);
+/* of the last snpgpu_pair_tables / snpgpu_pair_score_matrix on this thread (HIP events, summed over the streamed blocks): stats[0]
+ * ms of the SNP-table kernel, [1] its launches, [2] genotype bytes it read, [3] ms of the transposition to sample-major words (flip
+ * masks included), [4] ms of the per-pair counter, [5] ms of the matrix kernel, [6] launches timed in [3] ... [5], [7] genotype bytes
+ * the transposition and the matrix kernel read */
+int snpgpu_pair_stats(double *stats);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------------------
  * What THIS device's matrix pipe sustains right now: a register-only stream of one MFMA instruction (never waiting on memory,
  * two waves per SIMD) run for `seconds`, rate taken over the second half.  The kernels of this library run against the socket

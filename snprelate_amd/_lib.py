@@ -54,12 +54,17 @@ EXPORTS = [
     "snpgpu_geno_counts", "snpgpu_hwe", "snpgpu_hwe_counts", "snpgpu_ind_inb", "snpgpu_qc_stats", "snpgpu_gnrSampFreq", "snpgpu_gnrHWE",
     "snpgpu_gnrIndInb",
     "snpgpu_hclust_average", "snpgpu_dist_perm", "snpgpu_gnrDistPerm", "snpgpu_tree_stats",
+    "snpgpu_pair_tables", "snpgpu_pair_score_final", "snpgpu_pair_score_matrix", "snpgpu_gnrPairScore", "snpgpu_pair_stats",
     "snpgpu_diag_plan",
 ]
 FST_WC84, FST_WH02 = 1, 2
 FST_METHODS = ("W&C84", "W&H02")
 INB_METHODS = ("mom.weir", "mom.visscher", "mle", "gcta1", "gcta2", "gcta3")      # snpgpu_inb_method = index + 1
 INB_MLE = 3
+PAIR_METHODS = ("IBS", "GVH", "HVG", "GVH.major", "GVH.minor", "GVH.major.only", "GVH.minor.only")      # snpgpu_pair_method = index + 1
+PAIR_TYPES = ("per.pair", "per.snp", "matrix", "gds.file")
+PAIR_TABLE, SNP_TABLE = 0, 1
+PAIR_ELEM_INT32, PAIR_ELEM_BIT2 = 0, 1
 
 
 class SnpGpuError(RuntimeError):
@@ -268,6 +273,11 @@ def lib():
     L.snpgpu_dist_perm.argtypes = [vp, i64, c_int, vp, c_int, dbl, u64, vp, vp, vp, vp, vp, vp, vp, c_int]
     L.snpgpu_gnrDistPerm.argtypes = [c_int, vp, vp, c_int, dbl, u64, vp, vp, vp, vp, c_int]
     L.snpgpu_tree_stats.argtypes = [vp]
+    L.snpgpu_pair_tables.argtypes = [vp, i64, i64, c_int, c_int, vp, vp, i64, c_int, vp, vp, vp, c_int, c_int]
+    L.snpgpu_pair_score_final.argtypes = [c_int, vp, vp, i64, c_int, c_int, vp]
+    L.snpgpu_pair_score_matrix.argtypes = [vp, i64, i64, c_int, c_int, vp, vp, i64, c_int, c_int, c_int, vp, c_int]
+    L.snpgpu_gnrPairScore.argtypes = [vp, vp, i64, ctypes.c_char_p, ctypes.c_char_p, c_int, c_int, vp]
+    L.snpgpu_pair_stats.argtypes = [vp]
     _lib = L
     return L
 
@@ -1140,3 +1150,69 @@ def tree_stats():
     check(lib().snpgpu_tree_stats(_ptr(s)))
     return dict(prep_ms=float(s[0]), perm_ms=float(s[1]), prep_launches=int(s[2]), perm_launches=int(s[3]), gathered=float(s[4]),
                 permutations=float(s[5]))
+
+
+def _pair_lists(idx1, idx2):
+    a, b = np.ascontiguousarray(idx1, np.int32), np.ascontiguousarray(idx2, np.int32)
+    if a.ndim != 1 or a.shape != b.shape:
+        raise ValueError("idx1 and idx2 should be two lists of the same length")
+    return a, b
+
+
+def _pair_method(method):
+    if method not in PAIR_METHODS:
+        raise ValueError("'method' should be one of %s" % ", ".join('"%s"' % m for m in PAIR_METHODS))
+    return PAIR_METHODS.index(method) + 1
+
+
+def pair_tables(geno, n_samp, idx1, idx2, need_major=False, fmt=None, n_snp=None, device=0, want_pair=True, want_snp=True,
+                want_flip=True):
+    """(pair_tab int64 [n_pair][3][3], snp_tab int32 [n_snp][4][4], flip uint8 [n_snp]) of snpgpu_pair_tables; None for a part
+    not asked for.  geno: host rows (numpy, U8 or PACKED2) or a device address (int) with n_snp (and fmt); idx1 / idx2: 0-based
+    sample indices of the pairs."""
+    a, b = _pair_lists(idx1, idx2)
+    ptr, n, fmt, mem, _keep = _geno_input(geno, n_samp, fmt, n_snp, device_fmt_default=GENO_PACKED2)
+    pt = np.empty((len(a), 3, 3), np.int64) if want_pair else None
+    st = np.empty((n, 4, 4), np.int32) if want_snp else None
+    fl = np.empty(n, np.uint8) if want_flip else None
+    check(lib().snpgpu_pair_tables(ptr, n, int(n_samp), fmt, mem, _ptr(a), _ptr(b), len(a), int(bool(need_major)), _ptr(pt), _ptr(st),
+                                   _ptr(fl), HOST, int(device)))
+    return pt, st, fl
+
+
+def pair_score_final(table, method="IBS", dosage=True, flip=None):
+    """snpgpu_pair_score_final (host code, no device): (Avg, SD, Num) float64 [n] each from a pair table [n][3][3] (int64, counted
+    with need_major as the method needs) or from a SNP table [n][4][4] (int32) with its flip bytes."""
+    t = np.asarray(table)
+    if t.ndim == 3 and t.shape[1:] == (3, 3):
+        t, kind = np.ascontiguousarray(t, np.int64), PAIR_TABLE
+    elif t.ndim == 3 and t.shape[1:] == (4, 4):
+        t, kind = np.ascontiguousarray(t, np.int32), SNP_TABLE
+    else:
+        raise ValueError("table should be [n][3][3] (pairs) or [n][4][4] (SNPs)")
+    f = None if flip is None else np.ascontiguousarray(flip, np.uint8)
+    if f is not None and f.shape != (t.shape[0],):
+        raise ValueError("flip should hold one byte per row of the table")
+    n = t.shape[0]
+    out = np.empty(3 * n, np.float64)
+    check(lib().snpgpu_pair_score_final(kind, _ptr(t), _ptr(f), n, _pair_method(method), int(bool(dosage)), _ptr(out)))
+    r = out.reshape(3, n) if kind == PAIR_TABLE else out.reshape(n, 3).T
+    return r[0].copy(), r[1].copy(), r[2].copy()
+
+
+def pair_score_matrix(geno, n_samp, idx1, idx2, method="IBS", dosage=True, bit2=False, fmt=None, n_snp=None, device=0):
+    """snpgpu_pair_score_matrix: [n_snp][n_pair] int32 (INT_MIN = missing), or with bit2 uint8 holding the two bits of a bit2 node"""
+    a, b = _pair_lists(idx1, idx2)
+    ptr, n, fmt, mem, _keep = _geno_input(geno, n_samp, fmt, n_snp, device_fmt_default=GENO_PACKED2)
+    out = np.empty((n, len(a)), np.uint8 if bit2 else np.int32)
+    check(lib().snpgpu_pair_score_matrix(ptr, n, int(n_samp), fmt, mem, _ptr(a), _ptr(b), len(a), _pair_method(method), int(bool(dosage)),
+                                         PAIR_ELEM_BIT2 if bit2 else PAIR_ELEM_INT32, _ptr(out), int(device)))
+    return out
+
+
+def pair_stats():
+    """dict of snpgpu_pair_stats for the last pair_tables / pair_score_matrix call on this thread"""
+    s = np.zeros(8, np.float64)
+    check(lib().snpgpu_pair_stats(_ptr(s)))
+    return dict(snp_table_ms=float(s[0]), snp_table_launches=int(s[1]), snp_table_bytes=float(s[2]), words_ms=float(s[3]),
+                pair_count_ms=float(s[4]), matrix_ms=float(s[5]), other_launches=int(s[6]), other_bytes=float(s[7]))

@@ -1322,6 +1322,116 @@ def snpgdsIndInb(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remove
     return rv
 
 
+# ---- genotype scores of listed sample pairs ---------------------------------------------------------------------------------------------
+
+PAIR_METHODS = _lib.PAIR_METHODS
+PAIR_TYPES = _lib.PAIR_TYPES
+
+
+def _any_duplicated(x):
+    x = np.asarray(x)
+    return len(np.unique(x)) != len(x)
+
+
+def _check_selection(gdsobj, sample_id, snp_id):
+    """the refusals of .InitFile (R/Internal.R:64-160) that depend on the selection alone, with its messages"""
+    if not isinstance(gdsobj, GenoFile):
+        raise TypeError("'gdsobj' should be a SNP GDS object (snpgdsOpen / GenoFile)")
+    for want, have, name, what in ((sample_id, gdsobj.sample_id, "sample.id", "sample"), (snp_id, gdsobj.snp_id, "snp.id", "SNP")):
+        if want is None:
+            continue
+        n = int(np.isin(have, np.asarray(want)).sum())
+        if n != len(want):
+            raise ValueError("Some of %s do not exist!" % name)
+        if n <= 0:
+            raise ValueError("No %s in the working dataset." % what)
+
+
+def snpgdsPairScore(gdsobj, sample1_id, sample2_id, snp_id=None, method="IBS", type="per.pair", dosage=True, with_id=True,
+                    output=None, verbose=True, device=0):
+    """Genotype scores of the pairs (sample1_id[j], sample2_id[j]) over the SNPs (R/IBS.R:81-184 -> gnrPairScore,
+    src/genIBS.cpp:690-891).  The working set is the union of the two lists with the selected SNPs, no filter.  Returns a dict:
+    sample_id, snp_id (unless with_id is False) and score --
+      type "per.pair"  dict of columns Avg, SD, Num (int32), Sample1, Sample2 (R's data.frame)
+      type "per.snp"   float64 [3][n_snp], rows Avg / SD / Num
+      type "matrix"    int32 [n_pair][n_snp], NA_integer_ (-2^31) where a genotype is missing
+      type "gds.file"  nothing in the dict: the reference writes a GDS file through gdsfmt, which is not available to this Python
+                       mirror; as snpgdsGRM(out_fn=) does, THE SAME NODES (sample.id = "id1-id2", snp.id, snp.position,
+                       snp.chromosome, genotype) are stored in a numpy archive under the name `output`.  genotype is uint8
+                       [n_pair][n_snp] holding the two bits the bit2 node keeps (3 = missing, and 3 for a score of -1); the
+                       node's "sample.order" attribute is stored as an entry of its own.
+    Avg, SD and Num come from exact integer tables counted on the GPU and equal the reference's sequential double sums bit for
+    bit, its quirks included: the *.only methods score -1 at some cells where both genotypes are called."""
+    if _any_duplicated(sample1_id):
+        raise ValueError("'sample1.id' has duplicated element(s).")
+    if _any_duplicated(sample2_id):
+        raise ValueError("'sample2.id' has duplicated element(s).")
+    s1, s2 = np.asarray(sample1_id), np.asarray(sample2_id)
+    if len(s1) != len(s2):
+        raise ValueError("length(sample1.id) == length(sample2.id) is not TRUE")
+    union = np.concatenate([s1, s2])
+    _, first = np.unique(union, return_index=True)
+    union = union[np.sort(first)]
+    # .InitFile comes here in R.  What it can refuse is checked now and the working space is set after the argument checks below,
+    # so that R's order of errors is kept and every one of them is raised before a device is touched.
+    _check_selection(gdsobj, union, snp_id)
+
+    method = _match_arg(method, PAIR_METHODS, "method")
+    type = _match_arg(type, PAIR_TYPES, "type")
+    for name, v in (("with.id", with_id), ("dosage", dosage)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise TypeError("is.logical(%s) is not TRUE" % name)
+    if not isinstance(verbose, (bool, np.bool_)):
+        raise TypeError("is.logical(verbose) is not TRUE")
+    if type == "gds.file":
+        if not isinstance(output, str):
+            raise TypeError("is.character(output) & is.vector(output) is not TRUE")
+    elif output is not None:
+        raise ValueError("'output' should be NULL, if 'type' is not \"gds.file\".")
+
+    ws = _init_file(gdsobj, union, snp_id, device)
+    if verbose:
+        print("Pair Score Calculation:")
+        print("    # of samples: %s" % _pretty(ws["n_samp"]))
+        print("    # of SNPs: %s" % _pretty(ws["n_snp"]))
+        print("Method: %s" % method)
+        if type == "gds.file":
+            print("Output: %s" % output)
+
+    # match(sampleX.id, ws$sample.id) - 1L
+    order = np.argsort(ws["sample_id"], kind="stable")
+    sorted_ids = np.asarray(ws["sample_id"])[order]
+    idx1 = np.ascontiguousarray(order[np.searchsorted(sorted_ids, s1)], np.int32)
+    idx2 = np.ascontiguousarray(order[np.searchsorted(sorted_ids, s2)], np.int32)
+    n_pair, n_snp = len(idx1), ws["n_snp"]
+    if n_snp < 1:
+        raise ValueError("snpgdsPairScore: no SNP in the working dataset")
+    if type == "per.pair":
+        out = np.empty((3, n_pair), np.float64)                       # n_pair x 3, column-major
+    elif type == "per.snp":
+        out = np.empty((n_snp, 3), np.float64)                        # 3 x n_snp, column-major
+    else:
+        out = np.empty((n_snp, n_pair), np.int32 if type == "matrix" else np.uint8)
+    _lib.check(_lib.lib().snpgpu_gnrPairScore(_lib._ptr(idx1), _lib._ptr(idx2), n_pair, method.encode(), type.encode(),
+                                              int(bool(dosage)), int(bool(verbose)), _lib._ptr(out)))
+    ans = dict(sample_id=ws["sample_id"], snp_id=ws["snp_id"]) if with_id else {}
+    if type == "per.pair":
+        ans["score"] = dict(Avg=out[0], SD=out[1], Num=out[2].astype(np.int32), Sample1=s1, Sample2=s2)
+    elif type == "per.snp":
+        ans["score"] = out.T
+    elif type == "matrix":
+        ans["score"] = out.T
+    else:
+        flag = np.isin(gdsobj.snp_id, ws["snp_id"])
+        nodes = {"sample.id": np.array(["%s-%s" % (a, b) for a, b in zip(s1, s2)]), "snp.id": ws["snp_id"],
+                 "snp.chromosome": np.asarray(gdsobj.snp_chromosome)[flag], "genotype": out.T,
+                 "genotype.attr": np.array(["sample.order"])}
+        if gdsobj.snp_position is not None:
+            nodes["snp.position"] = np.asarray(gdsobj.snp_position)[flag]
+        _gds.write_output(output, nodes)
+    return ans
+
+
 # ---- hierarchical clustering and the permutation test of the tree ---------------------------------------------------------------------
 
 

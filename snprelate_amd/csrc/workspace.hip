@@ -1267,4 +1267,44 @@ int snpgpu_gnrIndInb(const double *afreq, const char *method, double reltol, int
                           out_num_iter ? niter : nullptr, nullptr, SNPGPU_HOST, g_ws.device);
 }
 
+// gnrPairScore (src/genIBS.cpp:711-891) on the selected SNPs: the tables of snpgpu_pair_tables and the host finaliser, or the
+// score matrix.  Method and type are checked first, so that an unknown one is refused without a device.
+int snpgpu_gnrPairScore(const int32_t *idx1, const int32_t *idx2, int64_t n_pair, const char *method, const char *type, int dosage, int,
+                        void *out)
+{
+    const char *fn = "snpgpu_gnrPairScore";
+    static const char *const names[7] = {"IBS", "GVH", "HVG", "GVH.major", "GVH.minor", "GVH.major.only", "GVH.minor.only"};
+    static const char *const types[4] = {"per.pair", "per.snp", "matrix", "gds.file"};
+    int code = 0, kind = -1;
+    for (int k = 0; k < 7 && method; k++)
+        if (strcmp(method, names[k]) == 0) code = k + 1;
+    if (!code) { set_error(std::string(fn) + ": Invalid 'method'."); return 1; }
+    for (int k = 0; k < 4 && type; k++)
+        if (strcmp(type, types[k]) == 0) kind = k;
+    if (kind < 0) { set_error(std::string(fn) + ": Invalid 'type'."); return 1; }
+    if (!out) { set_error(std::string(fn) + ": out is NULL"); return 1; }
+    if (!idx1 || !idx2 || n_pair < 1) { set_error(std::string(fn) + ": no pair is given"); return 1; }
+    std::vector<uint8_t> buf;
+    if (ws_qc_rows(fn, buf)) return 1;
+    const int64_t L = (int64_t)g_ws.sel.size();
+    const int major = code >= SNPGPU_PS_GVH_MAJOR;
+    if (kind == 0) {
+        std::vector<int64_t> tab(9 * (size_t)n_pair);
+        if (snpgpu_pair_tables(buf.data(), L, g_ws.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, idx1, idx2, n_pair, major, tab.data(), nullptr,
+                               nullptr, SNPGPU_HOST, g_ws.device))
+            return 1;
+        return snpgpu_pair_score_final(SNPGPU_PS_PAIR_TABLE, tab.data(), nullptr, n_pair, code, dosage, (double *)out);
+    }
+    if (kind == 1) {
+        std::vector<int32_t> tab(16 * (size_t)L);
+        std::vector<uint8_t> flip((size_t)L);
+        if (snpgpu_pair_tables(buf.data(), L, g_ws.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, idx1, idx2, n_pair, major, nullptr, tab.data(),
+                               flip.data(), SNPGPU_HOST, g_ws.device))
+            return 1;
+        return snpgpu_pair_score_final(SNPGPU_PS_SNP_TABLE, tab.data(), flip.data(), L, code, dosage, (double *)out);
+    }
+    return snpgpu_pair_score_matrix(buf.data(), L, g_ws.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, idx1, idx2, n_pair, code, dosage,
+                                    kind == 2 ? SNPGPU_PS_ELEM_INT32 : SNPGPU_PS_ELEM_BIT2, out, g_ws.device);
+}
+
 }  // extern "C"
