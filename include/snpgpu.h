@@ -753,6 +753,10 @@ int snpgpu_diag_device_pci(int device, char *buf, int len);
  * Makes no HIP call (opts->device is ignored, opts may be NULL): the dispatch can be checked on a host without a GPU.  Refusals of
  * snpgpu_create that do not depend on the device (invalid panel rows, a form the dissimilarity kind lacks) are returned as such. */
 int snpgpu_diag_plan(int kind, int64_t n_samp, const snpgpu_opts *opts, int64_t block_snps, char *buf, int len);
+/* Work items of the GRM / PCA single-product kernel that found no free slot of its carry scratch (SNPGPU_UVC_CARRY_SLOTS) since the
+ * context was created or the count was last reset: they added their partial sums to the panel after every fp32 run instead (slower,
+ * the same result up to rounding).  0 for contexts without the scratch.  Waits for the context's stream. */
+int snpgpu_diag_carry_fallbacks(snpgpu_ctx *ctx, int64_t *count, int reset);
 
 #ifdef __cplusplus
 }

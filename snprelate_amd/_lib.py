@@ -55,7 +55,7 @@ EXPORTS = [
     "snpgpu_gnrIndInb",
     "snpgpu_hclust_average", "snpgpu_dist_perm", "snpgpu_gnrDistPerm", "snpgpu_tree_stats",
     "snpgpu_pair_tables", "snpgpu_pair_score_final", "snpgpu_pair_score_matrix", "snpgpu_gnrPairScore", "snpgpu_pair_stats",
-    "snpgpu_diag_plan",
+    "snpgpu_diag_plan", "snpgpu_diag_carry_fallbacks",
 ]
 FST_WC84, FST_WH02 = 1, 2
 FST_METHODS = ("W&C84", "W&H02")
@@ -141,6 +141,7 @@ def lib():
     L.snpgpu_diag_mfma_rate.argtypes = [c_int, c_int, dbl, ctypes.POINTER(dbl), ctypes.POINTER(dbl)]
     L.snpgpu_diag_device_pci.argtypes = [c_int, ctypes.c_char_p, c_int]
     L.snpgpu_diag_plan.argtypes = [c_int, i64, ctypes.POINTER(Opts), i64, ctypes.c_char_p, c_int]
+    L.snpgpu_diag_carry_fallbacks.argtypes = [vp, ctypes.POINTER(i64), c_int]
     L.snpgpu_synth_block.argtypes = [vp, i64, i64, i64, ctypes.c_uint32, dbl, c_int, c_int, c_int, vp]
     L.snpgpu_create.argtypes = [c_int, i64, ctypes.POINTER(Opts), ctypes.POINTER(vp)]
     L.snpgpu_destroy.argtypes = [vp]
@@ -439,6 +440,13 @@ class Accumulator:
         a, b = ctypes.c_int64(0), ctypes.c_int64(0)
         check(lib().snpgpu_counts(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    def carry_fallbacks(self, reset=True):
+        """Work items of the single-product kernel that found no free slot of the carry scratch since the last reset
+        (snpgpu_diag_carry_fallbacks; 0 for contexts without the scratch)."""
+        n = ctypes.c_int64(0)
+        check(lib().snpgpu_diag_carry_fallbacks(self._h, ctypes.byref(n), int(bool(reset))))
+        return n.value
 
     def set_timing(self, on=True):
         check(lib().snpgpu_set_timing(self._h, int(on)))

@@ -207,6 +207,10 @@ static int alloc_ctx(snpgpu_ctx *c)
     }
     // the pace-maker (see syrk_uv16c_kernel): 64 KiB per table chunk, fetched by every workgroup alongside its 8 KiB of factors
     if (p.uvc() && (c->uvpace.alloc((size_t)65536 * (Bpad / UV_CHS + 4)) || zero_now(c->uvpace))) return 1;
+    // the carry scratch beside it: nothing in a slot needs clearing (a work item's first run only writes), the flags start free
+    if (p.uvc_carry_all && (c->uvcarry.alloc(uv_carry_scratch_bytes(p.uvc_carry_slots)) ||
+                            c->uvcarry_flags.alloc(uv_carry_flag_bytes(p.uvc_carry_slots)) || zero_now(c->uvcarry_flags)))
+        return 1;
     if (p.homo_uv) {
         for (int i = 0; i < p.homo_weights; i++)
             if (c->homo_lut[i].alloc(64 * (Bpad + 2048))) return 1;
@@ -675,6 +679,7 @@ static int feed_syrk(snpgpu_ctx *c, int64_t n_snp)
             o.run_chunks = b.uv_runs > 1 ? b.uv_cpr : 0; o.n_target = b.uv_q;
             o.form = p.uv_form;
             o.pace_src = c->uvpace.p; o.pace = p.uvc_pace;
+            if (p.uvc_carry_all) { o.carry_scr = c->uvcarry.p; o.carry_flags = (unsigned int *)c->uvcarry_flags.p; o.carry_slots = p.uvc_carry_slots; }
             if (launch_syrk_uv(st, c->syrk_panel(c->wt, i), o)) return 1;
         }
     }

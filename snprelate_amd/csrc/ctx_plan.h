@@ -86,6 +86,15 @@ struct Switches {
     // the workgroups of an XCD drift apart and fetch 2.4 x the words).  Values outside 0 ... 3 are clamped.
     int syrk_uv16 = 3;
     bool uvc_pace = true;
+    // ... form 3: the sub-tile sums LDS cannot hold (29 of a wave's 64) wait in a scratch slot of device memory between runs instead of
+    // meeting the fp64 panel after every run: one panel flush per block (3.3 passes of atomics -> 1.0).  SNPGPU_UVC_CARRY_ALL=0: today's
+    // per-run atomics for those sub-tiles, exactly.  SNPGPU_UVC_CARRY_SLOTS: slots per XCD pool (0 ... 256, default 64 = twice the
+    // workgroups an XCD holds; 0: no slot, every work item takes the per-run atomics; tests).
+    // MEASURED (configs[2], one box, profiles/carry_all_ab.json): 436.6 against 439.5 ms per step in alternating rounds of one process (-0.7 %, every
+    // round below every round of the old form), 437.4 against 441.6 with bench.py alternated; WRITE_SIZE 133 -> 87.5 GB per step (40 of panel
+    // atomics + 47 of scratch stores, which the L2 writes through), FETCH_SIZE raw 173.5 -> 202 GB; no work item without a slot.
+    bool uvc_carry_all = true;
+    int uvc_carry_slots = UV_CARRY_SLOTS;
     int i8_tail_parts = 0;           // SNPGPU_I8_TAIL_PARTS 1 ... 64: K parts of the last round of a work list (0: chosen per list)
 
     static Switches from_env()
@@ -117,6 +126,8 @@ struct Switches {
         s.homo_uv = env_nonzero("SNPGPU_HOMO_UV", true);
         if ((e = getenv("SNPGPU_SYRK_UV16"))) s.syrk_uv16 = std::max(0, std::min(atoi(e), 3));
         s.uvc_pace = env_nonzero("SNPGPU_UVC_PACE", true);
+        s.uvc_carry_all = env_nonzero("SNPGPU_UVC_CARRY_ALL", true);
+        s.uvc_carry_slots = env_int_in("SNPGPU_UVC_CARRY_SLOTS", 0, UV_CARRY_SLOTS_MAX, s.uvc_carry_slots);
         s.i8_tail_parts = env_int_in("SNPGPU_I8_TAIL_PARTS", 1, 64, 0);
         return s;
     }
@@ -160,6 +171,8 @@ struct CtxPlan {
     bool uv_targets = false;     // a weight target per fp32 run (uv_factor_kernel)
     UvForm uv_form = UvForm::Mfma32x32x16;
     bool uvc_pace = false;       // Converted forms: pace-maker fetches on
+    bool uvc_carry_all = false;  // ConvertedCarry: every sub-tile sum carried between runs, those beyond LDS in scratch slots ...
+    int uvc_carry_slots = 0;     // ... of which each XCD's pool has this many
     bool eigmix_x1 = false;      // EIGMIX numerator of blocks with missing calls on syrk_x1_kernel, from its own 12 * code words
     bool sparse_missing = false; // rare variants of blocks with missing calls: carriers' pairs added in fp64 (uv_sparse_kernel)
     bool x1_short_runs = true;   // ... and such blocks as half-length fp32 runs (device flag)
@@ -310,6 +323,8 @@ inline int plan_context(int kind, int64_t n_samp, const snpgpu_opts &o, const Sw
     p.uv_form = !conv ? lookup : sw.syrk_uv16 == 3 ? UvForm::ConvertedCarry : UvForm::Converted;
     p.homo_form = lookup;
     p.uvc_pace = conv && sw.uvc_pace;       // on / off (the size is fixed: 16 KiB per wave)
+    p.uvc_carry_all = p.uv_form == UvForm::ConvertedCarry && sw.uvc_carry_all;
+    p.uvc_carry_slots = p.uvc_carry_all ? sw.uvc_carry_slots : 0;
     *out = p;
     return 0;
 }
@@ -386,6 +401,7 @@ struct snpgpu_ctx {
     bool colterm_pending = false;  //     panel once, before a result is read (ctx_settle, api.hip)
     snpgpu::DevBuf wt12;           // EIGMIX: 12 * code words of a block with missing calls (exact-row kernel of the numerator)
     snpgpu::DevBuf uvpace;         // syrk_uv16c_kernel: 64 KiB per table chunk that every workgroup fetches (zeros; see the kernel)
+    snpgpu::DevBuf uvcarry, uvcarry_flags;   // ... its carry scratch (plan.uvc_carry_all: slots of 116 KiB) and the slots' flag words
     snpgpu::DevBuf uvlut, uvslot;  // single-product SYRK: its own tables (8-byte entries, per SLOT) and the slot -> SNP map of the current block
     snpgpu::DevBuf uvcand;         // ... per SNP and weight target: {relative error, u | v << 16}, {t, avg}, SNP -> slot
     snpgpu::DevBuf uvcoef, uvterm, uvkpart, uvsp;   // ... (blocks without missing calls): per-SNP {d_b uv, c_a, d_a uv, c_b},

@@ -292,6 +292,22 @@ extern "C" int snpgpu_diag_fp64_rate(int device, double seconds, double *tflops)
     return rc;
 }
 
+// work items of syrk_uv16c_kernel that found no free slot of the carry scratch since the context was created or the count was last
+// reset (they took the per-run atomics instead: slower, never wrong)
+extern "C" int snpgpu_diag_carry_fallbacks(snpgpu_ctx *c, int64_t *count, int reset)
+{
+    if (!c || !count) { set_error("snpgpu_diag_carry_fallbacks: invalid arguments"); return 1; }
+    *count = 0;
+    if (!c->uvcarry_flags.p) return 0;
+    unsigned int n = 0;
+    SNPGPU_HIP_CHECK(hipSetDevice(c->device));
+    SNPGPU_HIP_CHECK(hipStreamSynchronize(c->stream));
+    SNPGPU_HIP_CHECK(hipMemcpy(&n, c->uvcarry_flags.p, sizeof(n), hipMemcpyDeviceToHost));
+    if (reset) SNPGPU_HIP_CHECK(hipMemset(c->uvcarry_flags.p, 0, sizeof(n)));
+    *count = (int64_t)n;
+    return 0;
+}
+
 // ---- snpgpu_diag_plan: names of the kernels a block takes under a plan (what launch_pair_i8 / launch_syrk_h3 / launch_syrk_uv run)
 static const char *uv_form_kernel(UvForm f)
 {
@@ -352,7 +368,8 @@ extern "C" int snpgpu_diag_plan(int kind, int64_t n_samp, const snpgpu_opts *opt
           << "\nh3_exact_rows=" << p.h3_exact_rows << "\nh3_exact_missing=" << p.h3_exact_missing << "\nh3_w_shift=" << p.h3_w_shift
           << "\nh3_promote=" << p.h3_promote << "\nuv_promote=" << p.uv_promote << "\nwant_x1_list=" << p.want_x1_list
           << "\nuv_enabled=" << p.uv_enabled << "\nuv_eigmix=" << p.uv_eigmix << "\nuv_targets=" << p.uv_targets
-          << "\nuv_form=" << uv_forms[(int)p.uv_form] << "\nuvc_pace=" << p.uvc_pace << "\neigmix_x1=" << p.eigmix_x1
+          << "\nuv_form=" << uv_forms[(int)p.uv_form]  << "\nuvc_pace=" << p.uvc_pace << "\nuvc_carry_all=" << p.uvc_carry_all
+          << "\nuvc_carry_slots=" << p.uvc_carry_slots << "\neigmix_x1=" << p.eigmix_x1
           << "\nsparse_missing=" << p.sparse_missing << "\nx1_short_runs=" << p.x1_short_runs << "\nx1_sparse_mac=" << p.x1_sparse_mac
           << "\nwt_layout=" << layouts[(int)p.wt_layout] << "\nwt_block_flag=" << p.wt_block_flag << "\nhomo_uv=" << p.homo_uv
           << "\nhomo_form=" << uv_forms[(int)p.homo_form] << "\nhomo_weights=" << p.homo_weights;

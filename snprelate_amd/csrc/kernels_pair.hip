@@ -1350,7 +1350,8 @@ __global__ __launch_bounds__(256, 1) void syrk_uv16c_kernel(
     const uint32_t *__restrict__ w8, int64_t ncols_pad, const uint2 *__restrict__ lut, int n_q,
     double *__restrict__ acc, int64_t ld, int64_t tiles_c, const int4 *__restrict__ work,
     const unsigned long long *__restrict__ d_missing, int64_t n_rows_real, int chunk_lo, int chunk_hi, double fscale,
-    int n_runs, int run_chunks, int n_target, int run_group, int n_items8, int run_if_missing, const char *__restrict__ pace_src, int pace)
+    int n_runs, int run_chunks, int n_target, int run_group, int n_items8, int run_if_missing, const char *__restrict__ pace_src, int pace,
+    f32x4 *__restrict__ carry_scr, unsigned int *__restrict__ carry_flags, int carry_slots)
 {
     if ((*d_missing != 0ull) != (run_if_missing != 0)) return;
     constexpr int TS = 8, D = 4;
@@ -1366,6 +1367,17 @@ __global__ __launch_bounds__(256, 1) void syrk_uv16c_kernel(
     // the other sub-tiles flush after every run as before.  Half the fp64 read-modify-writes of the 40 GB panel per run go away.
     constexpr int CARRY_SUB = 35;                  // sub-tiles 0 .. 34 in (i, j) order: 35 KiB per wave = all the LDS there is (16 + 4 + 140 KiB)
     __shared__ f32x4 scar[4][CARRY_SUB * 64];
+    // THE CARRY SCRATCH (carry_scr != nullptr): the other UV_CARRY_REST sub-tiles are carried the same way, their sums waiting in a SLOT of
+    // device memory (116 KiB per workgroup: [wave][sub-tile - CARRY_SUB][lane] f32x4, 1 KiB contiguous per wave instruction) instead of
+    // meeting the panel after every run.  After a run's K loop the operand, word and factor registers are dead: all 29 loads of a wave go
+    // out first, then the LDS part, then the adds and stores -- ONE round trip per run boundary, to lines this workgroup wrote a run
+    // earlier.  Slots come from a pool PER XCD (the hardware XCC id, never blockIdx): a slot is only ever read and written through one
+    // L2, so no dirty line of an earlier owner in another L2 can be written back over newer sums.  One lane takes a slot with a single
+    // pass of compare-and-swap over the pool's flags and frees it once every wave's last read has returned; the first run only writes,
+    // so nothing is cleared between owners.  A pass that finds no free slot waits for nothing: the item flushes sub-tiles >= CARRY_SUB
+    // after every run as before (the two schemes differ only in where the partial sums wait) and counts itself in carry_flags[0].
+    constexpr int CARRY_REST = UV_CARRY_REST;
+    static_assert(CARRY_SUB + CARRY_REST == TS * TS, "every sub-tile is carried in LDS or in the slot");
     __shared__ u32x4 space[4][64];                 // 1 KiB per wave: where the pace-maker fetches land (never read)
     const bool inner = (n_runs > 1 && run_group == 0);
 
@@ -1392,6 +1404,31 @@ __global__ __launch_bounds__(256, 1) void syrk_uv16c_kernel(
     const int la = (int)((int64_t)kq * ncols_pad + row_w + l16), lb = (int)((int64_t)kq * ncols_pad + col_w + l16);
     double *__restrict__ pacc = acc + acc_off(ld, tiles_c, row_w + 4 * kq, col_w + l16);
     const int64_t rs = tiles_c ? ACC_TILE : ld;
+
+    // a slot of the carry scratch for this work item (see above); the id travels through the pace-maker's landing area, which no
+    // fetch of this workgroup has touched yet (all of the LDS is spoken for)
+    int slot = -1;
+    unsigned int *slot_flag = nullptr;
+    if (carry_on && carry_scr) {                   // (uniform over the workgroup)
+        volatile int *mail = reinterpret_cast<volatile int *>(&space[0][0]);
+        if (tid == 0) {
+            const int xcd = (int)(__builtin_amdgcn_s_getreg(UV_GETREG_XCC_ID) & 7u);
+            unsigned int *fl = carry_flags + UV_CARRY_FLAG0 + xcd * carry_slots;
+            int got = -1, s = carry_slots > 0 ? (int)((blockIdx.x >> 3) % (unsigned)carry_slots) : 0;
+            for (int k = 0; k < carry_slots && got < 0; k++, s = (s + 1 < carry_slots) ? s + 1 : 0) {   // ONE pass, no waiting
+                unsigned int free_ = 0u;
+                if (__hip_atomic_compare_exchange_strong(fl + s, &free_, 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                    got = xcd * carry_slots + s;
+            }
+            if (got < 0) (void)__hip_atomic_fetch_add(carry_flags, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            *mail = got;
+        }
+        __syncthreads();
+        slot = __builtin_amdgcn_readfirstlane(*mail);
+        __syncthreads();                           // (wave 0's first pace-maker fetch lands where the id was)
+        if (slot >= 0) slot_flag = carry_flags + UV_CARRY_FLAG0 + slot;
+    }
+    f32x4 *scr = carry_scr + ((int64_t)(slot < 0 ? 0 : slot) * 4 + wave) * (CARRY_REST * 64) + lane;
 
     f32x4 c16[TS][TS];
 #pragma unroll
@@ -1572,18 +1609,64 @@ __global__ __launch_bounds__(256, 1) void syrk_uv16c_kernel(
         const int64_t rows_left = (n_rows_real > 0 ? n_rows_real : ((int64_t)1 << 40)) - (row_w + 4 * kq);
         const bool first_run = (run == 0), last_run = (run + 1 == runs_here);
         const float fs32 = (float)fscale;          // 1 - q / 4096: exact in fp32
+        // carried sub-tile (i, j) of the LDS part: fp32 sums in LDS until the block's last run
+#define C16_LDS_CARRY(i, j)                                                                                        \
+        do {                                                                                                       \
+            f32x4 *cp = &scar[wave][((i) * TS + (j)) * 64 + lane];                                                 \
+            f32x4 t = c16[i][j] * fs32;                                                                            \
+            if (!first_run) t += *cp;                                                                              \
+            if (!last_run) *cp = t;                                                                                \
+            c16[i][j] = t;                 /* (what the last run flushes below; every other run clears it) */      \
+        } while (0)
+        if (slot >= 0) {
+            // every sub-tile carried: 0 .. CARRY_SUB - 1 in LDS, the others in the slot.  The slot's loads first, all of them, into
+            // the registers the K loop has left; the LDS part runs while they are under way.
+            f32x4 sv[CARRY_REST];
+            f32x4 *sp_ = scr;                      // (opaque, as pflush: 29 addresses kept across the K loop would be spilled)
+            asm volatile("" : "+v"(sp_));
+            __attribute__((address_space(1))) f32x4 *sp = (__attribute__((address_space(1))) f32x4 *)sp_;
+            if (first_run) {
+#pragma unroll
+                for (int k = 0; k < CARRY_REST; k++) sv[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+            } else {
+#pragma unroll
+                for (int k = 0; k < CARRY_REST; k++) sv[k] = sp[k * 64];
+            }
+#pragma unroll
+            for (int s = 0; s < CARRY_SUB; s++) C16_LDS_CARRY(s / TS, s % TS);
+#pragma unroll
+            for (int k = 0; k < CARRY_REST; k++) {
+                const int i = (CARRY_SUB + k) / TS, j = (CARRY_SUB + k) % TS;
+                const f32x4 t = c16[i][j] * fs32 + sv[k];
+                if (!last_run) sp[k * 64] = t;
+                c16[i][j] = t;
+            }
+            if (last_run) {
+                // the slot is free once the last reads of all four waves have returned (they have: the sums above used them)
+                __syncthreads();
+                if (tid == 0) __hip_atomic_store(slot_flag, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+                for (int i = 0; i < TS; i++)
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const int row = i * 16 + r;
+                        double *__restrict__ pr = pflush + (int64_t)row * rs;
+                        if (row < rows_left) {
+#pragma unroll
+                            for (int j = 0; j < TS; j++)      // (the sums carry their factors already)
+                                (void)__builtin_amdgcn_global_atomic_fadd_f64((__attribute__((address_space(1))) double *)(pr + 16 * j),
+                                                                              (double)c16[i][j][r]);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+            }
+        } else {
 #pragma unroll
         for (int i = 0; i < TS; i++) {
             const int nc = carry_on ? ((CARRY_SUB - i * TS) < 0 ? 0 : (CARRY_SUB - i * TS) > TS ? TS : (CARRY_SUB - i * TS)) : 0;   // carried: j < nc
 #pragma unroll
             for (int j = 0; j < TS; j++)
-                if (j < nc) {                      // carried sub-tiles: fp32 sums in LDS until the block's last run
-                    f32x4 *cp = &scar[wave][(i * TS + j) * 64 + lane];
-                    f32x4 t = c16[i][j] * fs32;
-                    if (!first_run) t += *cp;
-                    if (!last_run) *cp = t;
-                    c16[i][j] = t;                 // (what the last run flushes below; every other run clears it)
-                }
+                if (j < nc) C16_LDS_CARRY(i, j);
             if (nc == TS && !last_run) continue;
 #pragma unroll
             for (int r = 0; r < 4; r++) {
@@ -1599,6 +1682,8 @@ __global__ __launch_bounds__(256, 1) void syrk_uv16c_kernel(
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
+        }
+#undef C16_LDS_CARRY
 #pragma unroll
         for (int i = 0; i < TS; i++)
 #pragma unroll
@@ -1662,16 +1747,18 @@ int launch_syrk_uv(hipStream_t st, const SyrkPanel &p, const SyrkUvOpts &o)
     if (uv16 >= 2) {                              // syrk_uv16c_kernel: `o.lut` = the slots' factor arrays; pace-maker arguments instead of table copies
         if (uv16 == 3 && n_runs > 1)              // work items = tiles, the runs walked inside, half the sub-tiles carried in LDS
             hipLaunchKernelGGL(syrk_uv16c_kernel, dim3((unsigned)o.n_blocks_x1), dim3(256), 0, st, p.w8, p.ncols_pad, o.lut, o.n_q, p.acc, p.ld, p.tiles_c, o.work_x1,
-                               o.d_missing, p.n_rows_real, 0, n_chunk, 1.0, n_runs, run, o.n_target, 0, 0, run_if_missing, (const char *)o.pace_src, pace);
+                               o.d_missing, p.n_rows_real, 0, n_chunk, 1.0, n_runs, run, o.n_target, 0, 0, run_if_missing, (const char *)o.pace_src, pace,
+                               (f32x4 *)o.carry_scr, o.carry_flags, o.carry_scr ? o.carry_slots : 0);
         else if (n_runs > 1 && run_inner_launch())
             hipLaunchKernelGGL(syrk_uv16c_kernel, dim3(run_inner_grid(o.n_blocks_x1, n_runs, run_inner_launch())), dim3(256), 0, st, p.w8, p.ncols_pad,
                                o.lut, o.n_q, p.acc, p.ld, p.tiles_c, o.work_x1, o.d_missing, p.n_rows_real, 0, n_chunk, 1.0, n_runs, run, o.n_target,
-                               run_inner_launch(), o.n_blocks_x1 / 8, run_if_missing, (const char *)o.pace_src, pace);
+                               run_inner_launch(), o.n_blocks_x1 / 8, run_if_missing, (const char *)o.pace_src, pace, (f32x4 *)nullptr, (unsigned int *)nullptr, 0);
         else
             for (int lo = 0, q = 0; lo < n_chunk; lo += run, q++)
                 hipLaunchKernelGGL(syrk_uv16c_kernel, dim3((unsigned)o.n_blocks_x1), dim3(256), 0, st, p.w8, p.ncols_pad, o.lut, o.n_q, p.acc, p.ld, p.tiles_c,
                                    o.work_x1, o.d_missing, p.n_rows_real, lo, std::min(lo + run, n_chunk),
-                                   o.n_target > 1 ? uv_run_factor(q % o.n_target) : 1.0, 1, 0, 1, 1, 0, run_if_missing, (const char *)o.pace_src, pace);
+                                   o.n_target > 1 ? uv_run_factor(q % o.n_target) : 1.0, 1, 0, 1, 1, 0, run_if_missing, (const char *)o.pace_src, pace,
+                                   (f32x4 *)nullptr, (unsigned int *)nullptr, 0);
         SNPGPU_HIP_CHECK(hipGetLastError());
         return 0;
     }

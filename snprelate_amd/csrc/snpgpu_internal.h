@@ -76,6 +76,19 @@ constexpr int H3_PROMOTE_EXACT = 8192;          // (16 384: 29 of 3.7e8 entries 
 constexpr int H3_PROMOTE_UV = 11264;            // slots per run of the single-product kernel (11 table chunks)
 constexpr int H3_PROMOTE_FAST = 32768;
 constexpr int UV_QMAX = 8;                      // runs of a block that may carry their own weight target (more runs: one target)
+// carry scratch of syrk_uv16c_kernel (ConvertedCarry): the sub-tiles of a wave that LDS cannot hold between runs (64 - 35), as f32x4 per
+// lane; a slot serves the four waves of a workgroup (116 KiB).  Flag words: [0] work items that found no free slot (diagnostic),
+// [UV_CARRY_FLAG0 + xcd * slots + s] 1 while slot s of XCD xcd's pool is taken.  UV_GETREG_XCC_ID: s_getreg operand of bits 3:0 of
+// hardware register 20 (XCC_ID)
+constexpr int UV_CARRY_REST = 29;
+constexpr int UV_CARRY_SLOT_BYTES = 4 * UV_CARRY_REST * 64 * 16;
+constexpr int UV_CARRY_FLAG0 = 16;
+constexpr int UV_CARRY_XCDS = 8;
+constexpr int UV_CARRY_SLOTS = 64;              // per XCD: twice the 32 workgroups an XCD holds at one per CU (58 MiB in all)
+constexpr int UV_CARRY_SLOTS_MAX = 256;
+constexpr int UV_GETREG_XCC_ID = ((4 - 1) << 11) | 20;
+inline size_t uv_carry_flag_bytes(int slots) { return sizeof(unsigned int) * (size_t)(UV_CARRY_FLAG0 + UV_CARRY_XCDS * slots); }
+inline size_t uv_carry_scratch_bytes(int slots) { return (size_t)UV_CARRY_XCDS * (size_t)slots * (size_t)UV_CARRY_SLOT_BYTES; }
 __host__ __device__ __forceinline__ double uv_run_factor(int q) { return 1.0 - (double)q * (1.0 / 4096.0); }   // flush factor of run q
 constexpr int H3_HOMO_SHIFT = 8;                          // KING-homo tables are multiplied by 2^8 for the fp16 split
 constexpr int H3_LUTCH = 512;                            // SNPs per LDS table chunk of the split-fp16 SYRK (2 x 32 KiB)
@@ -248,6 +261,9 @@ struct SyrkUvOpts {
     UvForm form = UvForm::Mfma32x32x16;
     const void *pace_src = nullptr;              // Converted forms: the pace-maker (16 x 1 KiB per wave and chunk) and its switch
     bool pace = false;
+    void *carry_scr = nullptr;                   // ConvertedCarry: the carry scratch (nullptr: off), its flag words, slots per XCD
+    unsigned int *carry_flags = nullptr;
+    int carry_slots = 0;
 };
 int launch_syrk_uv(hipStream_t st, const SyrkPanel &p, const SyrkUvOpts &o);
 struct BuildUvOpts {
