@@ -707,6 +707,7 @@ static int feed_impl(snpgpu_ctx *c, const void *geno, int64_t n_snp, int format,
     if (c->plan.use_mm && feed_syrk(c, n_snp)) return 1;
     c->n_snp_total += n_snp;
     c->acc_f32_valid = false;       // (the eigen solver's fp32 copy of the sums is stale now)
+    c->diag_mirrored = 0;           // (... and so are the lower triangles it mirrored: the feed kernels add no transposes below the diagonal)
     if (mem == SNPGPU_HOST) SNPGPU_HIP_CHECK(hipStreamSynchronize(c->stream));  // caller may reuse its buffer
     return 0;
 }

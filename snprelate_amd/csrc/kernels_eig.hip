@@ -346,7 +346,10 @@ int launch_sym_panel_matmul(hipStream_t st, const double *P, int64_t ld, int64_t
             const int64_t n_gb = (N + 15) / 16;
             hipLaunchKernelGGL(eig_qt4_kernel, dim3((unsigned)((n_gb + 3) / 4)), dim3(256), 0, st, Q + (int64_t)v0 * N, mc, N,
                                (f32x4 *)qt_scratch);
-            const int chunk = EG_CHUNK;
+            // panels too small to fill the device with EG_CHUNK columns per workgroup take shorter chunks: more workgroups, and
+            // shorter fp32 sums of product (1)
+            int chunk = EG_CHUNK;
+            while (chunk > 128 && ((nJ + chunk - 1) / chunk) * ((nI + EG_ROWS - 1) / EG_ROWS) < 256) chunk >>= 1;
             const dim3 grid((unsigned)((nJ + chunk - 1) / chunk), (unsigned)((nI + EG_ROWS - 1) / EG_ROWS));
             if (P32)
                 hipLaunchKernelGGL(sym_panel_matmul_f32_kernel<float>, grid, dim3(256), 0, st, P32, ld, tiles_c, nI, nJ, col0, N, scale, mc,
