@@ -19,8 +19,11 @@
  * Conventions
  *   genotypes : SNP-major blocks, sample fastest (what CGenoReadBySNP::Read
  *               returns): SNPGPU_GENO_U8      uint8 [n_snp][n_samp], >2 = missing
+ *                           (every byte 3..255 is a missing call, none is an error)
  *                         SNPGPU_GENO_PACKED2 uint8 [n_snp][ceil(n_samp/4)],
- *                           4 genotypes/byte LSB first, 3 = missing (GDS bit2)
+ *                           4 genotypes/byte LSB first, 3 = missing (GDS bit2);
+ *                           the unused codes of a row's last byte (n_samp % 4
+ *                           != 0) are ignored, whatever they hold
  *   triangles : packed upper, row-major with diagonal (CdMatTri,
  *               src/dGenGWAS.h:511-583): idx(i,j) = j + i(2N-i-1)/2, i <= j
  *   matrices  : full symmetric n x n, column-major == row-major

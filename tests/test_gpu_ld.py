@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import ld_ref
+from input_forms import scramble_padding as _scramble_padding
 from oracle.synth import synth_hash_block_packed
 from snprelate_amd import _lib, api
 from snprelate_amd.gds import unpack_2bit_rows
@@ -17,17 +18,6 @@ CODES = {m: i + 1 for i, m in enumerate(ld_ref.METHODS)}
 def _synth(n_samp, n_snp, missing, spectrum=0, special=False, seed=7):
     p = synth_hash_block_packed(n_samp, 0, n_snp, seed, missing, spectrum, special)
     return p, unpack_2bit_rows(p, n_samp)
-
-
-def _scramble_padding(p, n_samp, seed=3):
-    """random bits in the codes of samples >= n_samp of the last byte: they must count as absent whatever they hold"""
-    p = p.copy()
-    tail = (n_samp + 3) // 4 * 4 - n_samp
-    if tail:
-        keep = (1 << (2 * (4 - tail))) - 1
-        r = np.random.default_rng(seed).integers(0, 256, p.shape[0]).astype(np.uint8)
-        p[:, -1] = (p[:, -1] & keep) | (r & ~np.uint8(keep))
-    return p
 
 
 def _run(rows, n_samp, method, slide, trim, blocks=None, max_block=0):

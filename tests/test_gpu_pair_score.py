@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import pair_score_ref as P
+from input_forms import scramble_padding as _scramble_padding
 from oracle.synth import synth_hash_block_packed
 from snprelate_amd import _lib, api, gds
 from snprelate_amd.gds import pack_2bit_rows, unpack_2bit_rows
@@ -16,17 +17,6 @@ CASES = [(m, d) for m in P.METHODS for d in (True, False)]
 
 def _same(a, b):
     return np.array_equal(np.asarray(a), np.asarray(b), equal_nan=True)
-
-
-def _scramble_padding(p, n_samp, seed=3):
-    """random bits in the codes of samples >= n_samp of the last byte: they must not count whatever they hold"""
-    p = p.copy()
-    tail = (n_samp + 3) // 4 * 4 - n_samp
-    if tail:
-        keep = (1 << (2 * (4 - tail))) - 1
-        r = np.random.default_rng(seed).integers(0, 256, p.shape[0]).astype(np.uint8)
-        p[:, -1] = (p[:, -1] & keep) | (r & ~np.uint8(keep))
-    return p
 
 
 def _pairs(n_samp, n_pair, seed):

@@ -662,7 +662,8 @@ def test_grm_gcta_denominators_sparse_and_dense_routes(missing, sparse, monkeypa
 @pytest.mark.parametrize("n", [1008, 1030, 2048])
 @pytest.mark.parametrize("missing", [0.0, 0.03])
 def test_counters_from_2bit_rows_one_pass_prepass(n, missing, monkeypatch):
-    """IBS / KING-robust fed with GDS-style 2-bit rows: the one-pass pre-pass (transpose2_direct_kernel: n % 16 == 0; a
+    """IBS / KING-robust fed with GDS-style 2-bit rows: the one-pass pre-pass (transpose2_direct_kernel: rows of whole dwords,
+    ceil(n / 4) % 4 == 0, i.e. n % 16 in {13, 14, 15, 0} -- here n % 16 == 0 only, tests/test_gpu_input_forms.py has the others; a
     partial last 64-sample chunk at n = 1008) and the two-kernel form (n = 1030, or SNPGPU_PREP_TWO_PASS=1) must give the
     oracle's counters bit for bit, for blocks with and without missing calls and a ragged last block."""
     from snprelate_amd import _lib

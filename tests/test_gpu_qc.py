@@ -15,22 +15,12 @@ import pytest
 import hwe_ref as H
 import inb_ref as R
 import qc_fixtures as Q
+from input_forms import scramble_padding as _scramble_padding
 from snprelate_amd import _lib, api
 from snprelate_amd.gds import pack_2bit_rows, unpack_2bit_rows
 
 pytestmark = pytest.mark.gpu
 MOMENTS = ("mom.weir", "mom.visscher", "gcta1", "gcta2", "gcta3")
-
-
-def _scramble_padding(p, n_samp, seed=3):
-    """random bits in the codes of samples >= n_samp of the last byte: they must not count whatever they hold"""
-    p = p.copy()
-    tail = (n_samp + 3) // 4 * 4 - n_samp
-    if tail:
-        keep = (1 << (2 * (4 - tail))) - 1
-        r = np.random.default_rng(seed).integers(0, 256, p.shape[0]).astype(np.uint8)
-        p[:, -1] = (p[:, -1] & keep) | (r & ~np.uint8(keep))
-    return p
 
 
 def _geno(n, m, missing, seed):
