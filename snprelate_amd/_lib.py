@@ -863,6 +863,21 @@ class MultiAccumulator:
         check(lib().snpgpu_multi_king_robust_counts(self._h, _ptr(o), HOST))
         return o
 
+    def king_homo(self, out=None):
+        a, b = out or (self._tri(np.float64), self._tri(np.float64))
+        check(lib().snpgpu_multi_king_homo(self._h, _ptr(a), _ptr(b), HOST))
+        return a, b
+
+    def ibs_ave(self, out=None):
+        o = out if out is not None else self._tri(np.float64)
+        check(lib().snpgpu_multi_ibs_ave(self._h, _ptr(o), HOST))
+        return o
+
+    def eigmix(self, diagadj=True, scale=1.0, out=None):
+        o = out if out is not None else self._tri(np.float64)
+        check(lib().snpgpu_multi_eigmix(self._h, int(bool(diagadj)), float(scale), _ptr(o), HOST))
+        return o
+
     def diss(self, out=None):
         o = out if out is not None else self._tri(np.float64)
         check(lib().snpgpu_multi_diss(self._h, _ptr(o), HOST))
@@ -875,6 +890,12 @@ class MultiAccumulator:
         o = out if out is not None else self._tri(np.float64)
         check(lib().snpgpu_multi_grm_gcta(self._h, _ptr(o), HOST))
         return o
+
+    def pca_trace(self):
+        """TraceXTX: the sum of the resident panels' diagonal parts (snpgpu_multi_pca_trace)"""
+        tr = ctypes.c_double(0)
+        check(lib().snpgpu_multi_pca_trace(self._h, ctypes.byref(tr)))
+        return tr.value
 
     def pca_cov(self, normalize=True, want_matrix=True):
         tr = ctypes.c_double(0)

@@ -220,7 +220,9 @@ static int alloc_ctx(snpgpu_ctx *c)
             return 1;
         // every weight in one launch: work items (tile, weight)
         if (build_worklist(c, X1_TILE, X1_TILE, H3_SUPER / 2, c->homo_work, c->homo_blocks, 1, p.homo_weights)) return 1;
-        if (p.kind == SNPGPU_DISS && (c->diss_called.alloc(sizeof(uint32_t) * nc) || zero_now(c->diss_called))) return 1;
+        // (KING-homo divides by the same kind of sum: 0 / 0 = NaN for a sample without a call, as the dissimilarity)
+        if (c->diss_called.alloc(sizeof(uint32_t) * nc) || zero_now(c->diss_called)) return 1;
+        if (c->nosh.alloc(sizeof(uint32_t) * (size_t)nosh_words((int64_t)nc)) || zero_now(c->nosh)) return 1;
     }
     return 0;
 }
@@ -635,7 +637,9 @@ static int feed_syrk(snpgpu_ctx *c, int64_t n_snp)
             // KING-homo block with missing calls: tables, effective weights, totals and per-sample missing sums of BOTH weights
             // once (i == 0), then ONE single-product launch: work items (tile, weight), the copy index picks table and plane
             const bool one_w = p.homo_weights == 1;      // dissimilarity: the first weight only
-            if (i == 0 && one_w && launch_diss_called(st, packed, p.RB, n_snp, sum, num, p.col0, p.N - p.col0, (uint32_t *)c->diss_called.p))
+            if (i == 0 && launch_diss_called(st, packed, p.RB, n_snp, sum, num, p.col0, p.N - p.col0, (uint32_t *)c->diss_called.p))
+                return 1;
+            if (i == 0 && launch_nosh_block(st, packed, p.RB, n_snp, sum, num, p.col0, p.N - p.col0, p.ncols_pad, (uint32_t *)c->nosh.p))
                 return 1;
             if (i == 0 && launch_homo_uv(st, sum, num, n_snp, n_pad, (uint2 *)c->homo_lut[0].p, (uint2 *)c->homo_lut[1].p,
                                          (double2 *)c->homo_wts.p, c->d_homo_w(), wt, p.ncols_pad, (double2 *)c->homo_tc.p,
@@ -912,7 +916,9 @@ int snpgpu_king_homo(snpgpu_ctx *c, double *k0, double *k1, int packed, int mem)
     const double fscale = c->plan.mm_h3 ? std::ldexp(1.0, -2 * H3_HOMO_SHIFT) : 1.0;
     if (launch_fin_king_homo(c->stream, c->geom(), (const uint32_t *)c->acc_u32.p, (const double *)c->acc_f64.p, fscale,
                              (double *)b0.dev, (double *)b1.dev, packed, c->plan.want_het ? c->d_homo_w() : nullptr,
-                             c->plan.homo_uv ? (const double *)c->homo_msum.p : nullptr))
+                             c->plan.homo_uv ? (const double *)c->homo_msum.p : nullptr,
+                             c->plan.homo_uv ? (const uint32_t *)c->diss_called.p : nullptr,
+                             c->plan.homo_uv ? (const uint32_t *)c->nosh.p : nullptr))
         return 1;
     if (b0.commit() || b1.commit()) return 1;
     return finish(c);
@@ -925,7 +931,7 @@ int snpgpu_diss(snpgpu_ctx *c, double *out, int packed, int mem)
     if (b.prepare()) return 1;
     if (launch_fin_diss(c->stream, c->geom(), (const uint32_t *)c->acc_u32.p, (const double *)c->acc_f64.p,
                         std::ldexp(1.0, -2 * H3_HOMO_SHIFT), c->d_homo_w(), (const double *)c->homo_msum.p,
-                        (const uint32_t *)c->diss_called.p, (double *)b.dev, nullptr, nullptr, packed))
+                        (const uint32_t *)c->diss_called.p, (double *)b.dev, nullptr, nullptr, packed, (const uint32_t *)c->nosh.p))
         return 1;
     if (b.commit()) return 1;
     return finish(c);
@@ -940,7 +946,7 @@ int snpgpu_diss_sums(snpgpu_ctx *c, uint32_t *geno_sum, double *wsum, int mem)
     if (b0.prepare() || b1.prepare()) return 1;
     if (launch_fin_diss(c->stream, c->geom(), (const uint32_t *)c->acc_u32.p, (const double *)c->acc_f64.p,
                         std::ldexp(1.0, -2 * H3_HOMO_SHIFT), c->d_homo_w(), (const double *)c->homo_msum.p,
-                        (const uint32_t *)c->diss_called.p, nullptr, (uint32_t *)b0.dev, (double *)b1.dev, 1))
+                        (const uint32_t *)c->diss_called.p, nullptr, (uint32_t *)b0.dev, (double *)b1.dev, 1, (const uint32_t *)c->nosh.p))
         return 1;
     if (b0.commit() || b1.commit()) return 1;
     return finish(c);

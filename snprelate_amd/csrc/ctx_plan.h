@@ -408,7 +408,8 @@ struct snpgpu_ctx {
                                    //     the running row / column terms {R[ncols_pad], Q[ncols_pad], K} and per-chunk parts of K
     snpgpu::DevBuf homo_lut[2], homo_wts, homo_tc, homo_msum, homo_work;   // KING-homo blocks with missing calls: tables, effective weights, per-chunk partials, M[2][ncols_pad], work list
     int homo_blocks = 0;
-    snpgpu::DevBuf diss_called;  // dissimilarity: per column sample, 1 once it is called at an SNP of nonzero weight (exact zero denominators)
+    snpgpu::DevBuf nosh;         // dissimilarity, KING-homo: which pairs share no call at an SNP of nonzero weight (kernels_final.hip, nosh_*)
+    snpgpu::DevBuf diss_called;  // dissimilarity, KING-homo: per column sample, 1 once it is called at an SNP of nonzero weight (exact zero denominators)
     // accumulators
     snpgpu::DevBuf acc_u32, acc_f64;
     snpgpu::TileGrid tg_pc{}, tg_mm{};

@@ -140,12 +140,119 @@ int launch_fin_king_robust(hipStream_t st, const PanelGeom &g, const uint32_t *a
     return run_fin(st, g, packed, f);
 }
 
+// ---- pairs without a shared call (KING-homo, dissimilarity) ---------------------------------------------------------------------------
+// Both finalisers divide by weight sums over the SNPs a pair is called at TOGETHER, formed as C - M_i - M_j + B_ij: not exactly 0
+// where the true sum is, and the reference has 0 / 0 = NaN there.  Which pairs share no call at an SNP of nonzero weight (0 < p < 1) is
+// decided exactly, in integers, block by block.  In a block with Lw such SNPs a pair shares none only if the two samples' missing counts
+// there add up to Lw or more, so at least one of them is HEAVY in that block (2 x missing >= Lw).  Per sample: hb = the number of blocks
+// it was heavy in, and a slot once it was heavy.  Per slot h and column sample j one word: bit 31 = h and j shared a call in a block
+// where h was heavy, bits 0..30 = the number of blocks BOTH were heavy in.  With nb the number of blocks (Lw > 0), the pair (i, j) never
+// shared a call  <=>  hb_i + hb_j - both_ij == nb (one of them heavy in every block) and neither word has bit 31.  Ordinary data has no
+// heavy sample: one pass over the block counts the missing calls, nothing else runs.  More than NOSH_HEAVY heavy samples: the flag in
+// word 2 is set and the finalisers go without (a rounding residue decides those pairs then, as before this existed).
+// words: {nb, slots, overflow, heavy in this block, Lw of this block, -, -, -}, cnt[nc], hb[nc], slot[nc] (0: none), list[NOSH_HEAVY], T[NOSH_HEAVY][nc]
+__device__ __forceinline__ bool nosh_weighted(const int32_t *sum, const int32_t *num, int64_t k) { return sum[k] > 0 && sum[k] < 2 * num[k]; }
+
+__global__ __launch_bounds__(256) void nosh_count_kernel(const uint8_t *__restrict__ packed, int64_t RB, int64_t n_snp, const int32_t *__restrict__ sum,
+                                                         const int32_t *__restrict__ num, int64_t col0, int64_t ncols, uint32_t *__restrict__ ns)
+{
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t k0 = (int64_t)blockIdx.y * 256, k1 = (k0 + 256 < n_snp) ? (k0 + 256) : n_snp;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        uint32_t lw = 0;
+        for (int64_t k = k0; k < k1; k++) lw += nosh_weighted(sum, num, k) ? 1u : 0u;
+        if (lw) atomicAdd(&ns[4], lw);
+    }
+    if (j >= ncols) return;
+    const int64_t s = col0 + j, b = s >> 2;
+    const int sh = 2 * (int)(s & 3);
+    uint32_t c = 0;
+    for (int64_t k = k0; k < k1; k++)
+        if (((packed[k * RB + b] >> sh) & 3) == 3 && nosh_weighted(sum, num, k)) c++;
+    if (c) atomicAdd(&ns[8 + j], c);
+}
+
+__global__ __launch_bounds__(256) void nosh_classify_kernel(int64_t ncols, int64_t nc, uint32_t *__restrict__ ns)
+{
+    const uint32_t lw = ns[4];
+    if (lw == 0) return;
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j == 0) ns[0] += 1;                                    // (nobody reads it in this launch)
+    if (j >= ncols || 2u * ns[8 + j] < lw) return;
+    ns[8 + nc + j] += 1;
+    if (!ns[8 + 2 * nc + j]) {
+        const uint32_t sl = atomicAdd(&ns[1], 1u);
+        if (sl < (uint32_t)NOSH_HEAVY) ns[8 + 2 * nc + j] = sl + 1;
+        else ns[2] = 1;
+    }
+    const uint32_t pos = atomicAdd(&ns[3], 1u);
+    if (pos < (uint32_t)NOSH_HEAVY) ns[8 + 3 * nc + pos] = (uint32_t)j;
+    else ns[2] = 1;
+}
+
+// grid.y = NOSH_HEAVY: the heavy samples of this block, each against every column sample
+__global__ __launch_bounds__(256) void nosh_update_kernel(const uint8_t *__restrict__ packed, int64_t RB, int64_t n_snp, const int32_t *__restrict__ sum,
+                                                          const int32_t *__restrict__ num, int64_t col0, int64_t ncols, int64_t nc, uint32_t *__restrict__ ns)
+{
+    const uint32_t lw = ns[4], nh = ns[3] < (uint32_t)NOSH_HEAVY ? ns[3] : (uint32_t)NOSH_HEAVY;
+    if (lw == 0 || blockIdx.y >= nh) return;
+    const int64_t h = ns[8 + 3 * nc + blockIdx.y];
+    const uint32_t sl = ns[8 + 2 * nc + h];
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (sl == 0 || j >= ncols) return;                         // (no slot: more heavy samples than slots, the flag is set)
+    uint32_t *w = ns + 8 + 3 * nc + NOSH_HEAVY + (int64_t)(sl - 1) * nc + j;
+    uint32_t v = *w;
+    if (2u * ns[8 + j] >= lw) v += 1;
+    if (!(v >> 31)) {
+        const int64_t sh_ = col0 + h, sj = col0 + j;
+        const int64_t bh = sh_ >> 2, bj = sj >> 2;
+        const int th = 2 * (int)(sh_ & 3), tj = 2 * (int)(sj & 3);
+        for (int64_t k = 0; k < n_snp; k++)
+            if (((packed[k * RB + bh] >> th) & 3) != 3 && ((packed[k * RB + bj] >> tj) & 3) != 3 && nosh_weighted(sum, num, k)) { v |= 0x80000000u; break; }
+    }
+    *w = v;
+}
+
+int launch_nosh_block(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, const int32_t *sum, const int32_t *num,
+                      int64_t col0, int64_t ncols, int64_t ncols_pad, uint32_t *nosh)
+{
+    if (n_snp <= 0 || ncols <= 0) return 0;
+    const unsigned gx = (unsigned)((ncols + 255) / 256);
+    hipLaunchKernelGGL(nosh_count_kernel, dim3(gx, (unsigned)((n_snp + 255) / 256)), dim3(256), 0, st, packed, RB, n_snp, sum, num, col0, ncols, nosh);
+    hipLaunchKernelGGL(nosh_classify_kernel, dim3(gx), dim3(256), 0, st, ncols, ncols_pad, nosh);
+    hipLaunchKernelGGL(nosh_update_kernel, dim3(gx, NOSH_HEAVY), dim3(256), 0, st, packed, RB, n_snp, sum, num, col0, ncols, ncols_pad, nosh);
+    SNPGPU_HIP_CHECK(hipGetLastError());
+    SNPGPU_HIP_CHECK(hipMemsetAsync(nosh + 3, 0, sizeof(uint32_t) * 2, st));                       // this block's heavy count and Lw
+    SNPGPU_HIP_CHECK(hipMemsetAsync(nosh + 8, 0, sizeof(uint32_t) * (size_t)ncols_pad, st));       // and its missing counts
+    return 0;
+}
+
+// ri, rj: the samples relative to the panel's first column
+__device__ __forceinline__ bool nosh_never_shared(const uint32_t *ns, int64_t nc, int64_t ri, int64_t rj)
+{
+    const uint32_t nb = ns[0];
+    if (nb == 0 || ns[2]) return false;
+    const uint32_t hi = ns[8 + nc + ri], hj = ns[8 + nc + rj];
+    if (hi + hj < nb) return false;
+    const uint32_t si = ns[8 + 2 * nc + ri], sj = ns[8 + 2 * nc + rj];
+    const uint32_t *T = ns + 8 + 3 * nc + NOSH_HEAVY;
+    const uint32_t wi = si ? T[(int64_t)(si - 1) * nc + rj] : 0u, wj = sj ? T[(int64_t)(sj - 1) * nc + ri] : 0u;
+    if ((wi | wj) >> 31) return false;
+    const uint32_t both = (si ? wi : wj) & 0x7fffffffu;
+    return hi + hj - both == nb;
+}
+
 // ---- KING homo ---------------------------------------------------------------
 struct FinKingHomo {
     const uint32_t *acc; const double *facc; int64_t plane; double fscale; double *k0, *k1; const double *wc;
     // round 5: blocks with missing calls leave B_ij = sum c mu_i mu_j in the planes and per-sample sums M in msum[2][ncols_pad]:
     // masked sum = C - M_i - M_j + B_ij with C in wc (the totals of ALL blocks then); msum == nullptr: the planes hold the masked sums
     const double *msum; int64_t col0, ncols_pad;
+    // that difference of sums is not exactly 0 where the true sum is: a sample never called at an SNP of nonzero weight (called[] == 0, as
+    // FinDiss) has both weight sums 0 exactly with every sample, so 0 / 0 = NaN as in the reference.  Two samples that are both
+    // called somewhere and share no call: nosh (above), here and in FinDiss
+    const uint32_t *called;
+    const uint32_t *nosh;
     __device__ void apply(int64_t rel, int64_t relf, int64_t i, int64_t j, OutPos p) const
     {
         double a = 0, b = 0;
@@ -158,6 +265,8 @@ struct FinKingHomo {
                 saf -= msum[i - col0] + msum[j - col0];
                 saf2 -= msum[ncols_pad + i - col0] + msum[ncols_pad + j - col0];
             }
+            if (called && (!called[i - col0] || !called[j - col0])) saf = saf2 = 0.0;
+            if (nosh && nosh_never_shared(nosh, ncols_pad, i - col0, j - col0)) saf = saf2 = 0.0;
             const double theta = 0.5 - sumsq / (8 * saf);
             const double v0 = c0 / (2 * saf2);
             const double v1 = 2 - 2 * v0 - 4 * theta;
@@ -169,9 +278,9 @@ struct FinKingHomo {
     }
 };
 int launch_fin_king_homo(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const double *facc, double fscale,
-                         double *k0, double *k1, int packed, const double *w_const, const double *msum)
+                         double *k0, double *k1, int packed, const double *w_const, const double *msum, const uint32_t *called, const uint32_t *nosh)
 {
-    FinKingHomo f{acc, facc, g.rows_pad * g.ncols_pad, fscale, k0, k1, w_const, msum, g.col0, g.ncols_pad};
+    FinKingHomo f{acc, facc, g.rows_pad * g.ncols_pad, fscale, k0, k1, w_const, msum, g.col0, g.ncols_pad, called, nosh};
     return run_fin(st, g, packed, f);
 }
 
@@ -184,7 +293,7 @@ int launch_fin_king_homo(hipStream_t st, const PanelGeom &g, const uint32_t *acc
 // out == nullptr: the packed sums {SumGeno, SumAFreq} (diagnostics).
 struct FinDiss {
     const uint32_t *acc; const double *facc; double fscale; const double *wc, *msum; const uint32_t *called; int64_t col0;
-    double *out; uint32_t *gsum; double *wsum;
+    double *out; uint32_t *gsum; double *wsum; const uint32_t *nosh; int64_t ncols_pad;
     __device__ void apply(int64_t rel, int64_t relf, int64_t i, int64_t j, OutPos p) const
     {
         const uint32_t sg = acc[rel];
@@ -192,6 +301,7 @@ struct FinDiss {
         if (msum) saf -= msum[i - col0] + msum[j - col0];
         saf *= 8.0;                                                     // exact: a power of two
         if (!called[i - col0] || !called[j - col0]) saf = 0.0;
+        if (nosh && nosh_never_shared(nosh, ncols_pad, i - col0, j - col0)) saf = 0.0;
         if (!out) { gsum[p.a] = sg; wsum[p.a] = saf; return; }
         const double v = (i == j) ? 2 * ((double)sg / saf) : (double)sg / saf;
         out[p.a] = v;
@@ -199,9 +309,9 @@ struct FinDiss {
     }
 };
 int launch_fin_diss(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const double *facc, double fscale, const double *w_const,
-                    const double *msum, const uint32_t *called, double *out, uint32_t *geno_sum, double *wsum, int packed)
+                    const double *msum, const uint32_t *called, double *out, uint32_t *geno_sum, double *wsum, int packed, const uint32_t *nosh)
 {
-    FinDiss f{acc, facc, fscale, w_const, msum, called, g.col0, out, geno_sum, wsum};
+    FinDiss f{acc, facc, fscale, w_const, msum, called, g.col0, out, geno_sum, wsum, nosh, g.ncols_pad};
     return run_fin(st, g, out ? packed : 1, f);
 }
 

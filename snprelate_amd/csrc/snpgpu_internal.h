@@ -313,15 +313,23 @@ int launch_fin_king_counts(hipStream_t st, const PanelGeom &g, const uint32_t *a
 int launch_fin_king_robust(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const int32_t *family,
                            double *ibs0, double *kin, int packed);
 int launch_fin_king_homo(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const double *facc, double fscale,
-                         double *k0, double *k1, int packed, const double *w_const = nullptr, const double *msum = nullptr);
+                         double *k0, double *k1, int packed, const double *w_const = nullptr, const double *msum = nullptr,
+                         const uint32_t *called = nullptr, const uint32_t *nosh = nullptr);
 // individual dissimilarity: out = SumGeno / SumAFreq (x 2 on the diagonal), or (out == nullptr) the packed sums themselves
 int launch_fin_diss(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const double *facc, double fscale, const double *w_const,
-                    const double *msum, const uint32_t *called, double *out, uint32_t *geno_sum, double *wsum, int packed);
+                    const double *msum, const uint32_t *called, double *out, uint32_t *geno_sum, double *wsum, int packed,
+                    const uint32_t *nosh = nullptr);
 // rank-one terms of the dissimilarity counter of blocks without missing calls: SumGeno += 2 (S_r + S_c), S = H + 2 T; then het = 0
 int launch_diss_settle(hipStream_t st, uint32_t *acc, int64_t rows_pad, int64_t ncols_pad, uint32_t *het);
 // called[j] = 1 once column sample j is called at an SNP of this block with 0 < p < 1 (packed rows [n_snp][RB])
 int launch_diss_called(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, const int32_t *sum, const int32_t *num,
                        int64_t col0, int64_t ncols, uint32_t *called);
+// Pairs without a shared call (KING-homo, dissimilarity; see kernels_final.hip): the words of the tracking buffer for ncols_pad columns,
+// and the per-block update (packed rows [n_snp][RB], the block's per-SNP sum / num)
+constexpr int NOSH_HEAVY = 64;         // samples that may be missing at half the SNPs of a block or more, over the whole stream
+constexpr int64_t nosh_words(int64_t ncols_pad) { return 8 + 3 * ncols_pad + NOSH_HEAVY + (int64_t)NOSH_HEAVY * ncols_pad; }
+int launch_nosh_block(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, const int32_t *sum, const int32_t *num,
+                      int64_t col0, int64_t ncols, int64_t ncols_pad, uint32_t *nosh);
 int launch_fin_gcta(hipStream_t st, const PanelGeom &g, const double *num, const uint32_t *miss,
                     const uint32_t *diag, const unsigned long long *d_nlocus, double *out, int packed,
                     const double *colterm = nullptr, const double *uvterm = nullptr);
