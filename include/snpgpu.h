@@ -213,6 +213,37 @@ int snpgpu_finalize_inplace(snpgpu_ctx *ctx, int diagadj, double scale);
  * 500 000-sample job recomputed in fp64 on the host); no reference counterpart. */
 int snpgpu_panel_entries(snpgpu_ctx *ctx, const int64_t *rows, const int64_t *cols, int64_t n_entries, double *out);
 
+/* Related pairs straight from the resident counters: the table snpgdsIBDSelection(ibdobj, kinship.cutoff, samp.sel)
+ * (R/IBD.R:463-531) would cut out of the n x n matrices of snpgdsIBDKING / snpgdsIBDMoM, without those matrices -- only the selected
+ * pairs leave the device.  Selected: the pairs idx1 < idx2 of the panel (row_begin <= idx1 < row_end) with samp_sel[idx1] &&
+ * samp_sel[idx2] and kinship >= kinship_cutoff (R/IBD.R:500-506: a NaN kinship is never selected; a non-finite cutoff -- NaN, +-Inf,
+ * is.finite() is FALSE for all three -- selects every pair, NaN pairs included).  Order: idx1 ascending, then idx2 ascending =
+ * which(lower.tri & flag, arr.ind = TRUE) with ID1 = sample[col], ID2 = sample[row] (R/IBD.R:520-526); the same call gives the same
+ * arrays.  The values are those of the kind's finaliser, bit for bit:
+ *   SNPGPU_SEL_KING_ROBUST  KING_ROBUST context: IBS0 and kinship of snpgpu_king_robust (family as there)
+ *   SNPGPU_SEL_KING_HOMO    KING_HOMO context:   k0, k1 of snpgpu_king_homo, kinship = (1 - k0 - k1) * 0.5 + k1 * 0.25 (R/IBD.R:487)
+ *   SNPGPU_SEL_MOM          IBS context:         k0, k1 of snpgpu_ibd_mom(e, kinship_constraint), the same kinship
+ * This direct route has no reference counterpart (the reference selects from matrices it has already built). */
+enum snpgpu_sel_kind { SNPGPU_SEL_KING_ROBUST = 1, SNPGPU_SEL_KING_HOMO = 2, SNPGPU_SEL_MOM = 3 };
+typedef struct snpgpu_sel_opts {
+    int32_t        what;                /* snpgpu_sel_kind; must match the context's kind                    */
+    int32_t        kinship_constraint;  /* MOM only                                                          */
+    const int32_t *family;              /* KING_ROBUST: host int32 [n_samp], negative = NA; NULL = all NA    */
+    const double  *e;                   /* MOM: host double [5], as snpgpu_ibd_mom                           */
+    double         kinship_cutoff;      /* non-finite: every pair                                            */
+    const uint8_t *samp_sel;            /* host uint8 [n_samp], nonzero = selected; NULL = all               */
+} snpgpu_sel_opts;
+/* idx1 < idx2: 0-based sample indices; v0 / v1: IBS0 / (not written) for KING_ROBUST, k0 / k1 otherwise; any output may be
+ * NULL (capacity 0 with all NULL = count only).  Outputs in `mem` (host or the context's device), `capacity` elements each: the first
+ * `capacity` pairs of the order above are stored, nothing is written behind them, and *n_found is always the number of ALL selected
+ * pairs.  Refused: a NULL context or NULL opts, a `what` that does not match the context kind, MOM without e, a negative capacity,
+ * a non-NULL output with capacity 0. */
+int snpgpu_select_pairs(snpgpu_ctx *ctx, const snpgpu_sel_opts *o, int64_t capacity, int32_t *idx1, int32_t *idx2,
+                        double *v0, double *v1, double *kinship, int mem, int64_t *n_found);
+/* diagnostics (tools/ibd_select_bench.py): milliseconds of the last snpgpu_select_pairs on this thread, double [4] = {count pass,
+ * scan, write pass} on the device and the whole call on the host clock; no reference counterpart */
+int snpgpu_select_stats(double *ms4);
+
 /* Top-k eigenpairs of the symmetric matrix held as row panels: replaces CalcEigen / LAPACK dspevx for ANY n
  * (src/genPCA.cpp:1262-1346; the same call behind gnrEigMix, src/genEIGMIX.cpp:700-702).  Thick-restarted block Krylov +
  * Rayleigh-Ritz in C++ / HIP (csrc/eigen.hip): the O(n^2) product runs on the panels, the tall-skinny algebra on their
@@ -308,6 +339,11 @@ int snpgpu_multi_king_homo(snpgpu_multi *m, double *k0, double *k1, int mem);
 int snpgpu_multi_diss(snpgpu_multi *m, double *out, int mem);
 int snpgpu_multi_grm_gcta(snpgpu_multi *m, double *out, int mem);
 int snpgpu_multi_eigmix(snpgpu_multi *m, int diagadj, double scale, double *out, int mem);
+/* snpgpu_select_pairs over the resident panels in order of row_begin, results concatenated: the global order (idx1, then idx2) of
+ * snpgdsIBDSelection, R/IBD.R:463-531; a pass of an n_passes > 1 object returns its own panels' pairs.  `capacity` and *n_found refer
+ * to the concatenation.  Host outputs only.  No reference counterpart, as snpgpu_select_pairs. */
+int snpgpu_multi_select_pairs(snpgpu_multi *m, const snpgpu_sel_opts *o, int64_t capacity, int32_t *idx1, int32_t *idx2,
+                              double *v0, double *v1, double *kinship, int mem /* host */, int64_t *n_found);
 int snpgpu_multi_pca_trace(snpgpu_multi *m, double *trace);
 /* out may be NULL (trace only); normalize != 0: C *= (n-1)/trace with the trace of ALL panels */
 int snpgpu_multi_pca_cov(snpgpu_multi *m, double *out, int normalize, double *trace_xtx, int mem);
@@ -403,6 +439,15 @@ int snpgpu_gnrGRMMerge(int n_grm, int64_t N, const double *const *grm, const cha
  * afreq_out: double [n_snp] */
 int snpgpu_gnrIBD_PLINK(int num_thread, const double *allele_freq, int kinship_constraint, int use_matrix,
                         int verbose, double *k0, double *k1, double *afreq_out);
+/* Related pairs of the working space without any n x n matrix: accumulate once (as snpgpu_gnrIBD_KING_Robust / _KING_Homo / _PLINK
+ * do, `what` = snpgpu_sel_kind; MOM: the expectations of snpgpu_gnrIBD_PLINK from allele_freq or, NULL, the allele counts), select with
+ * snpgpu_select_pairs, keep the selection in the working space until the next call or snpgpu_ws_clear.  Equals snpgdsIBDSelection
+ * (R/IBD.R:463-531) of the corresponding snpgdsIBDKING / snpgdsIBDMoM result; the route itself has no reference counterpart.
+ * samp_sel: host uint8 [n_samp] or NULL. */
+int snpgpu_gnrIBDPairs(int what, const int32_t *family, const double *allele_freq, int kinship_constraint, double kinship_cutoff,
+                       const uint8_t *samp_sel, int num_thread, int verbose, int64_t *n_found);
+/* the kept selection: host arrays of n_found elements each, any may be NULL (v1 is 0 for KING_ROBUST) */
+int snpgpu_gnrIBDPairs_get(int32_t *idx1, int32_t *idx2, double *v0, double *v1, double *kinship);
 /* gnrIBD_Beta(Inbreeding, NumThread, useMatrix, Verbose), src/genBeta.cpp:361-460 */
 int snpgpu_gnrIBD_Beta(int inbreeding, int num_thread, int use_matrix, int verbose, double *out, double *avg_val);
 /* gnrGRM_avg_val(), src/genPCA.cpp:1605-1611 */

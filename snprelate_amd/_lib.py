@@ -56,6 +56,7 @@ EXPORTS = [
     "snpgpu_hclust_average", "snpgpu_dist_perm", "snpgpu_gnrDistPerm", "snpgpu_tree_stats",
     "snpgpu_pair_tables", "snpgpu_pair_score_final", "snpgpu_pair_score_matrix", "snpgpu_gnrPairScore", "snpgpu_pair_stats",
     "snpgpu_diag_plan", "snpgpu_diag_carry_fallbacks",
+    "snpgpu_select_pairs", "snpgpu_multi_select_pairs", "snpgpu_gnrIBDPairs", "snpgpu_gnrIBDPairs_get", "snpgpu_select_stats",
 ]
 FST_WC84, FST_WH02 = 1, 2
 FST_METHODS = ("W&C84", "W&H02")
@@ -65,6 +66,7 @@ PAIR_METHODS = ("IBS", "GVH", "HVG", "GVH.major", "GVH.minor", "GVH.major.only",
 PAIR_TYPES = ("per.pair", "per.snp", "matrix", "gds.file")
 PAIR_TABLE, SNP_TABLE = 0, 1
 PAIR_ELEM_INT32, PAIR_ELEM_BIT2 = 0, 1
+SEL_KING_ROBUST, SEL_KING_HOMO, SEL_MOM = 1, 2, 3
 
 
 class SnpGpuError(RuntimeError):
@@ -95,6 +97,11 @@ class MultiStatus(ctypes.Structure):   # snpgpu_multi_status
     _fields_ = [(k, ctypes.c_int32) for k in ("n_devices", "n_distinct_devices", "n_panels", "panels_per_device", "uses_rccl", "peer_pairs",
                                               "peer_pairs_enabled", "selftest_comm", "selftest_feed", "selftest_gather")] + \
                [("reserved", ctypes.c_int32 * 6)]
+
+
+class SelOpts(ctypes.Structure):       # snpgpu_sel_opts
+    _fields_ = [("what", ctypes.c_int32), ("kinship_constraint", ctypes.c_int32), ("family", ctypes.c_void_p), ("e", ctypes.c_void_p),
+                ("kinship_cutoff", ctypes.c_double), ("samp_sel", ctypes.c_void_p)]
 
 
 class EigInfo(ctypes.Structure):       # snpgpu_eig_info
@@ -279,6 +286,11 @@ def lib():
     L.snpgpu_pair_score_matrix.argtypes = [vp, i64, i64, c_int, c_int, vp, vp, i64, c_int, c_int, c_int, vp, c_int]
     L.snpgpu_gnrPairScore.argtypes = [vp, vp, i64, ctypes.c_char_p, ctypes.c_char_p, c_int, c_int, vp]
     L.snpgpu_pair_stats.argtypes = [vp]
+    L.snpgpu_select_pairs.argtypes = [vp, ctypes.POINTER(SelOpts), i64, vp, vp, vp, vp, vp, c_int, ctypes.POINTER(i64)]
+    L.snpgpu_multi_select_pairs.argtypes = [vp, ctypes.POINTER(SelOpts), i64, vp, vp, vp, vp, vp, c_int, ctypes.POINTER(i64)]
+    L.snpgpu_gnrIBDPairs.argtypes = [c_int, vp, vp, c_int, dbl, vp, c_int, c_int, ctypes.POINTER(i64)]
+    L.snpgpu_gnrIBDPairs_get.argtypes = [vp, vp, vp, vp, vp]
+    L.snpgpu_select_stats.argtypes = [vp]
     _lib = L
     return L
 
@@ -369,6 +381,36 @@ class PinnedBuffer:
 
 def tri_size(n):
     return n * (n + 1) // 2
+
+
+def _select_pairs(fn, handle, n, what, cutoff, family, e, constraint, samp_sel, capacity, out_ptrs):
+    """snpgpu_select_pairs / snpgpu_multi_select_pairs behind Accumulator.select_pairs and MultiAccumulator.select_pairs"""
+    fam = None if family is None else np.ascontiguousarray(family, np.int32)
+    ev = None if e is None else np.ascontiguousarray(e, np.float64)
+    sel = None if samp_sel is None else np.ascontiguousarray(np.asarray(samp_sel) != 0, np.uint8)
+    for name, a, size in (("family", fam, n), ("e", ev, 5), ("samp_sel", sel, n)):
+        if a is not None and a.shape != (size,):
+            raise ValueError("'%s' should have %d entries" % (name, size))
+    o = SelOpts(int(what), int(bool(constraint)), _ptr(fam), _ptr(ev), float(cutoff), _ptr(sel))      # (fam, ev, sel stay alive to the end)
+    found = ctypes.c_int64(0)
+    if out_ptrs is not None:
+        if capacity is None:
+            raise ValueError("device outputs need a capacity")
+        check(fn(handle, ctypes.byref(o), int(capacity), *[ctypes.c_void_p(int(x)) if x else None for x in out_ptrs], DEVICE,
+                 ctypes.byref(found)))
+        return None, None, None, None, None, found.value
+    count_only = capacity is None or int(capacity) == 0
+    if count_only:                         # capacity=None: count, then fetch everything
+        check(fn(handle, ctypes.byref(o), 0, None, None, None, None, None, HOST, ctypes.byref(found)))
+    capacity = found.value if capacity is None else int(capacity)
+    out = [np.empty(capacity, np.int32), np.empty(capacity, np.int32)] + [np.empty(capacity, np.float64) for _ in range(3)]
+    if capacity > 0:
+        check(fn(handle, ctypes.byref(o), capacity, *[_ptr(a) for a in out], HOST, ctypes.byref(found)))
+    m = min(capacity, found.value)
+    out = [a[:m] for a in out]
+    if int(what) == SEL_KING_ROBUST:
+        out[3] = None                      # (not written for this kind)
+    return out[0], out[1], out[2], out[3], out[4], found.value
 
 
 class Accumulator:
@@ -544,6 +586,14 @@ class Accumulator:
         b = np.empty(self._shape(packed), np.float64)
         check(lib().snpgpu_ibd_mom(self._h, _ptr(e), int(bool(constraint)), _ptr(a), _ptr(b), int(packed), HOST))
         return a, b
+
+    def select_pairs(self, what, cutoff=float("nan"), family=None, e=None, constraint=False, samp_sel=None, capacity=None, out_ptrs=None):
+        """The pairs idx1 < idx2 of this panel with kinship >= cutoff (non-finite: every pair) among the samples of samp_sel, in the order
+        of snpgdsIBDSelection (snpgpu_select_pairs): (idx1, idx2, v0, v1, kinship, n_found) -- v0 / v1 = IBS0 / None for SEL_KING_ROBUST,
+        k0 / k1 for SEL_KING_HOMO and SEL_MOM (needs e[5]); the arrays hold min(capacity, n_found) pairs, n_found counts all.
+        capacity=None: counts first, then fetches all.  out_ptrs: five DEVICE pointers (0 / None = absent) of `capacity` elements
+        each; then only n_found is returned."""
+        return _select_pairs(lib().snpgpu_select_pairs, self._h, self.n, what, cutoff, family, e, constraint, samp_sel, capacity, out_ptrs)
 
     def eigmix(self, diagadj=True, scale=1.0, packed=False):
         o = np.empty(self._shape(packed), np.float64)
@@ -891,6 +941,13 @@ class MultiAccumulator:
         check(lib().snpgpu_multi_grm_gcta(self._h, _ptr(o), HOST))
         return o
 
+    def select_pairs(self, what, cutoff=float("nan"), family=None, e=None, constraint=False, samp_sel=None, capacity=None, out_ptrs=None):
+        """Accumulator.select_pairs over the resident panels in order of row_begin, concatenated (snpgpu_multi_select_pairs); host
+        outputs only."""
+        if out_ptrs is not None:
+            raise ValueError("MultiAccumulator.select_pairs returns host arrays (out_ptrs is for Accumulator.select_pairs)")
+        return _select_pairs(lib().snpgpu_multi_select_pairs, self._h, self.n, what, cutoff, family, e, constraint, samp_sel, capacity, None)
+
     def pca_trace(self):
         """TraceXTX: the sum of the resident panels' diagonal parts (snpgpu_multi_pca_trace)"""
         tr = ctypes.c_double(0)
@@ -1237,6 +1294,13 @@ def pair_score_matrix(geno, n_samp, idx1, idx2, method="IBS", dosage=True, bit2=
     check(lib().snpgpu_pair_score_matrix(ptr, n, int(n_samp), fmt, mem, _ptr(a), _ptr(b), len(a), _pair_method(method), int(bool(dosage)),
                                          PAIR_ELEM_BIT2 if bit2 else PAIR_ELEM_INT32, _ptr(out), int(device)))
     return out
+
+
+def select_stats():
+    """ms of the last select_pairs call on this thread: count pass, scan, write pass (device) and the whole call (host clock)"""
+    s = np.zeros(4, np.float64)
+    check(lib().snpgpu_select_stats(_ptr(s)))
+    return dict(count_ms=s[0], scan_ms=s[1], write_ms=s[2], call_ms=s[3])
 
 
 def pair_stats():

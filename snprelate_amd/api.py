@@ -27,6 +27,8 @@ INTEGRATION.md):
     snpgdsSelectSNP               R/AllUtilities.R:286-299   (the SNPs that pass the filters)
     snpgdsIndInbCoef              R/AllUtilities.R:312-341   (inbreeding coefficient of one individual, on the host)
     snpgdsIndInb                  R/AllUtilities.R:349-378   (individual inbreeding coefficients, six methods)
+    snpgdsIBDSelection            R/IBD.R:463-531  (table of pairs at or above a kinship cutoff, on the host)
+    snpgdsIBDPairs                no reference counterpart: the same table straight from the GPU counters
 
 All arithmetic on genotype matrices runs on the MI355X through libsnpgpu.so
 (`_lib`); there is no CPU fallback.  The one exception is snpgdsIndInbCoef, which
@@ -213,6 +215,41 @@ def snpgdsIBSNum(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remove
     return dict(sample_id=ws["sample_id"], snp_id=ws["snp_id"], ibs0=o[0], ibs1=o[1], ibs2=o[2])
 
 
+def _family_codes(family_id, sample_id, ws, verbose):
+    """family.id of snpgdsIBDKING (R/IBD.R:350-372) -> int32 codes for the ABI (-1 = NA), or None when no family is given"""
+    n = ws["n_samp"]
+    if family_id is None:
+        if verbose:
+            print("No family is specified, and all individuals are treated as singletons.")
+        return None
+    family_id = np.asarray(family_id)
+    if n != len(family_id):
+        raise ValueError("'length(family.id)' should be the number of samples.")
+    if sample_id is not None:
+        # family.id[match(sample.id, ws$sample.id)] (R/IBD.R:356-357), reproduced as it stands: the vector is
+        # re-indexed by the position of each requested sample in the dataset-ordered working set
+        ws_ids = np.asarray(ws["sample_id"])
+        order = np.argsort(ws_ids, kind="stable")
+        family_id = family_id[order[np.searchsorted(ws_ids[order], np.asarray(sample_id))]]
+    # as.integer(as.factor(family.id)): every non-NA value is a level (negative integers too); "" and NA -> NA
+    # (R/IBD.R:359-364).  -1 is only the ABI's code for NA after the factorisation.
+    fam = np.full(n, -1, np.int32)
+    if family_id.dtype.kind in "fc":
+        good = ~np.isnan(family_id.astype(float))
+    elif family_id.dtype.kind in "US":
+        good = family_id != ""
+    elif family_id.dtype.kind == "O":
+        good = np.array([x is not None and x != "" for x in family_id])
+    else:
+        good = np.ones(n, bool)
+    if good.any():
+        _, codes = np.unique(family_id[good], return_inverse=True)
+        fam[good] = codes.astype(np.int32) + 1
+    _cat(verbose, "# of families: %d, and within- and between-family "
+         "relationship are estimated differently." % len(np.unique(fam[fam >= 0])))
+    return fam
+
+
 def snpgdsIBDKING(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True,
                   maf=float("nan"), missing_rate=0.01, type="KING-robust", family_id=None,
                   num_thread=1, useMatrix=False, verbose=True, device=0):
@@ -221,35 +258,7 @@ def snpgdsIBDKING(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remov
     if type not in ("KING-robust", "KING-homo"):
         raise ValueError("'arg' should be one of 'KING-robust', 'KING-homo'")   # match.arg
     n = ws["n_samp"]
-    fam = None
-    if family_id is not None:
-        family_id = np.asarray(family_id)
-        if n != len(family_id):
-            raise ValueError("'length(family.id)' should be the number of samples.")
-        if sample_id is not None:
-            # family.id[match(sample.id, ws$sample.id)] (R/IBD.R:356-357), reproduced as it stands: the vector is
-            # re-indexed by the position of each requested sample in the dataset-ordered working set
-            ws_ids = np.asarray(ws["sample_id"])
-            order = np.argsort(ws_ids, kind="stable")
-            family_id = family_id[order[np.searchsorted(ws_ids[order], np.asarray(sample_id))]]
-        # as.integer(as.factor(family.id)): every non-NA value is a level (negative integers too); "" and NA -> NA
-        # (R/IBD.R:359-364).  -1 is only the ABI's code for NA after the factorisation.
-        fam = np.full(n, -1, np.int32)
-        if family_id.dtype.kind in "fc":
-            good = ~np.isnan(family_id.astype(float))
-        elif family_id.dtype.kind in "US":
-            good = family_id != ""
-        elif family_id.dtype.kind == "O":
-            good = np.array([x is not None and x != "" for x in family_id])
-        else:
-            good = np.ones(n, bool)
-        if good.any():
-            _, codes = np.unique(family_id[good], return_inverse=True)
-            fam[good] = codes.astype(np.int32) + 1
-        _cat(verbose and type == "KING-robust", "# of families: %d, and within- and between-family "
-             "relationship are estimated differently." % len(np.unique(fam[fam >= 0])))
-    elif verbose and type == "KING-robust":
-        print("No family is specified, and all individuals are treated as singletons.")
+    fam = _family_codes(family_id, sample_id, ws, verbose and type == "KING-robust")
     a, b = _tri_or_full(n, useMatrix), _tri_or_full(n, useMatrix)
     rv = dict(sample_id=ws["sample_id"], snp_id=ws["snp_id"], afreq=None)
     if type == "KING-homo":
@@ -725,6 +734,141 @@ def snpgdsIBDMLELogLik(gdsobj, ibdobj, k0=float("nan"), k1=float("nan"), related
             raise ValueError("'ibdobj$k0' and 'ibdobj$k1' should be %d x %d matrices, not %s and %s" % (n, n, m0.shape, m1.shape))
         _lib.check(_lib.lib().snpgpu_gnrIBD_LogLik(_lib._ptr(afreq), _lib._ptr(m0), _lib._ptr(m1), _lib._ptr(out)))
     return out
+
+
+_IBD_NOT_PER_PAIR = ("sample_id", "snp_id", "afreq")
+
+
+def _full_matrix(x, n, name):
+    """a per-pair entry of an IBD object as an n x n matrix: full, or the packed upper triangle of useMatrix=True (symmetric)"""
+    x = np.asarray(x)
+    if x.shape == (n, n):
+        return x
+    if x.shape == (_lib.tri_size(n),):
+        m = np.empty((n, n), x.dtype)
+        i, j = np.triu_indices(n)
+        m[i, j] = x
+        m[j, i] = x
+        return m
+    raise ValueError("'ibdobj$%s' should be a %d x %d matrix or its packed triangle, not %s" % (name, n, n, x.shape))
+
+
+def snpgdsIBDSelection(ibdobj, kinship_cutoff=float("nan"), samp_sel=None):
+    """Table of the pairs of an IBD object (R/IBD.R:463-531): dict of columns ID1, ID2, every per-pair entry of `ibdobj` in its
+    order and -- derived from k0 / k1 or D1..D8 when the object has none -- kinship, for the pairs with kinship >= kinship_cutoff
+    (a non-finite cutoff: every pair).  Rows follow which(lower.tri & flag, arr.ind=TRUE): ID1 = the earlier sample, ascending, then
+    ID2 ascending.  samp_sel: None, a logical vector over the samples, or numeric 0-based indices (which may permute, as R's
+    indexing does).  Works on the dicts of snpgdsIBDKING / snpgdsIBDMoM / snpgdsIBDMLE, full matrices or useMatrix triangles."""
+    if not isinstance(ibdobj, dict) or "sample_id" not in ibdobj:
+        raise TypeError("inherits(ibdobj, \"snpgdsIBDClass\") is not TRUE")
+    if isinstance(kinship_cutoff, (bool, np.bool_)) or not isinstance(kinship_cutoff, (int, float, np.integer, np.floating)):
+        raise TypeError("is.numeric(kinship.cutoff) is not TRUE")
+    ids = np.asarray(ibdobj["sample_id"])
+    n = len(ids)
+    sel = None
+    if samp_sel is not None:
+        sel = np.asarray(samp_sel)
+        if sel.dtype.kind == "b":
+            if sel.shape != (n,):
+                raise ValueError("length(samp.sel) == length(ibdobj$sample.id) is not TRUE")
+            sel = np.flatnonzero(sel)
+        elif sel.dtype.kind in "iuf" and sel.ndim == 1:
+            if sel.dtype.kind == "f":
+                if not np.all(np.isfinite(sel)):
+                    raise ValueError("'samp.sel' should not hold NA")
+                sel = sel.astype(np.int64)                       # truncation, as R's numeric subscripts
+            if sel.size and (sel.min() < 0 or sel.max() >= n):
+                raise IndexError("subscript out of bounds")
+        else:
+            raise TypeError("is.null(samp.sel) | is.logical(samp.sel) | is.numeric(samp.sel) is not TRUE")
+    # the variables in the output
+    ns = [k for k in ibdobj if k not in _IBD_NOT_PER_PAIR and ibdobj[k] is not None]
+    mats = {k: _full_matrix(ibdobj[k], n, k) for k in ns}
+    if sel is not None:
+        ids = ids[sel]
+        mats = {k: m[np.ix_(sel, sel)] for k, m in mats.items()}
+        n = len(ids)
+    if "kinship" not in mats:
+        if "k0" in mats and "k1" in mats:
+            mats["kinship"] = (1 - mats["k0"] - mats["k1"]) * 0.5 + mats["k1"] * 0.25
+            ns.append("kinship")
+        elif "D1" in mats:
+            mats["kinship"] = mats["D1"] + 0.5 * (mats["D3"] + mats["D5"] + mats["D7"]) + 0.25 * mats["D8"]
+            ns.append("kinship")
+        elif np.isfinite(kinship_cutoff):
+            raise ValueError("There is no kinship coefficient.")
+    flag = np.tril(np.ones((n, n), bool), -1)
+    if np.isfinite(kinship_cutoff):
+        with np.errstate(invalid="ignore"):
+            flag &= mats["kinship"] >= kinship_cutoff           # (NaN compares FALSE: flag[is.na(flag)] <- FALSE)
+    col, row = np.nonzero(flag.T)                                # column-major walk of flag: which(flag, arr.ind=TRUE)
+    ans = dict(ID1=ids[col], ID2=ids[row])
+    for k in ns:
+        ans[k] = mats[k][row, col]
+    return ans
+
+
+_IBD_PAIR_METHODS = {"KING-robust": _lib.SEL_KING_ROBUST, "KING-homo": _lib.SEL_KING_HOMO, "MoM": _lib.SEL_MOM}
+
+
+def snpgdsIBDPairs(gdsobj, method="KING-robust", kinship_cutoff=float("nan"), samp_sel=None, family_id=None, allele_freq=None,
+                   kinship_constraint=False, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True, maf=float("nan"),
+                   missing_rate=0.01, num_thread=1, verbose=True, device=0):
+    """The related pairs of a KING or MoM run without its n x n matrices.  No reference counterpart; the result equals
+        snpgdsIBDSelection(snpgdsIBDKING(gdsobj, type=method, family_id=...), kinship_cutoff, samp_sel)      "KING-robust", "KING-homo"
+        snpgdsIBDSelection(snpgdsIBDMoM(gdsobj, allele_freq=..., kinship_constraint=...), kinship_cutoff, samp_sel)      "MoM"
+    column for column and bit for bit (ID1, ID2, IBS0 / k0, k1, kinship), plus sample_id, snp_id and, for MoM, afreq.  The counters are
+    accumulated once on the GPU and only the selected pairs come back (snpgpu_gnrIBDPairs): host memory is proportional to their
+    number.  Here samp_sel is a logical vector over the working samples or strictly increasing 0-based indices -- a selection, not a
+    permutation; for anything else build the matrices and use snpgdsIBDSelection."""
+    if method not in _IBD_PAIR_METHODS:
+        raise ValueError("'arg' should be one of %s" % ", ".join("'%s'" % m for m in _IBD_PAIR_METHODS))
+    if isinstance(kinship_cutoff, (bool, np.bool_)) or not isinstance(kinship_cutoff, (int, float, np.integer, np.floating)):
+        raise TypeError("is.numeric(kinship.cutoff) is not TRUE")
+    mom = method == "MoM"
+    ws = _init_file2("IBD analysis (%s) on genotypes, related pairs only:" % ("PLINK method of moment" if mom else "KING method of moment"),
+                     gdsobj, sample_id, snp_id, autosome_only, remove_monosnp, maf, missing_rate, num_thread, verbose, device,
+                     allele_freq=allele_freq if mom else None)
+    n = ws["n_samp"]
+    mask = None
+    if samp_sel is not None:
+        sel = np.asarray(samp_sel)
+        if sel.dtype.kind == "b" and sel.shape == (n,):
+            mask = sel
+        elif sel.dtype.kind in "iu" and sel.ndim == 1 and (sel.size == 0 or (sel.min() >= 0 and sel.max() < n and np.all(np.diff(sel) > 0))):
+            mask = np.zeros(n, bool)
+            mask[sel] = True
+        else:
+            raise ValueError("snpgdsIBDPairs: 'samp.sel' should be a logical vector over the %d samples or strictly increasing indices; "
+                             "for a permuting or repeating selection use snpgdsIBDSelection on the matrices of snpgdsIBDKING / snpgdsIBDMoM" % n)
+        mask = np.ascontiguousarray(mask, np.uint8)
+    fam = _family_codes(family_id, sample_id, ws, verbose and method == "KING-robust") if method == "KING-robust" else None
+    af_in = ws["allele_freq"] if mom else None
+    L = _lib.lib()
+    found = ctypes.c_int64(0)
+    _lib.check(L.snpgpu_gnrIBDPairs(_IBD_PAIR_METHODS[method], _lib._ptr(fam), _lib._ptr(af_in), int(bool(kinship_constraint)),
+                                    float(kinship_cutoff), _lib._ptr(mask), ws["num_thread"], int(bool(verbose)), ctypes.byref(found)))
+    m = found.value
+    i1, i2 = np.empty(m, np.int32), np.empty(m, np.int32)
+    v0, v1, kin = np.empty(m, np.float64), np.empty(m, np.float64), np.empty(m, np.float64)
+    _lib.check(L.snpgpu_gnrIBDPairs_get(_lib._ptr(i1), _lib._ptr(i2), _lib._ptr(v0), _lib._ptr(v1), _lib._ptr(kin)))
+    ids = np.asarray(ws["sample_id"])
+    ans = dict(ID1=ids[i1], ID2=ids[i2])
+    if method == "KING-robust":
+        ans.update(IBS0=v0, kinship=kin)
+    else:
+        ans.update(k0=v0, k1=v1, kinship=kin)
+    ans.update(sample_id=ws["sample_id"], snp_id=ws["snp_id"])
+    if mom:
+        if af_in is None:                  # the frequencies snpgpu_gnrIBD_PLINK reports: allele counts of the working samples
+            af = np.empty(ws["n_snp"], np.float64)
+            _lib.check(L.snpgpu_ws_snp_rate_freq(_lib._ptr(af), None, None))
+        else:
+            af = np.array(af_in, np.float64)
+            af[np.isfinite(af) & ((af < 0) | (af > 1))] = np.nan
+        ans["afreq"] = af
+    _cat(verbose, "%d pair%s selected" % (m, "" if m == 1 else "s"))
+    return ans
 
 
 LD_PRUNE_METHODS = ("composite", "r", "dprime", "corr")

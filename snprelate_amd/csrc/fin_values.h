@@ -1,0 +1,107 @@
+// The VALUE part of the relatedness finalisers, shared by the finaliser functors (kernels_final.hip), which write every pair of a panel,
+// and the selection kernels (kernels_select.hip), which write the pairs at or above a kinship cutoff: one source of each expression,
+// so that a selected pair carries the bits the finaliser would have written for it.
+// Index conventions, as in the functors: `rel` / `relf` are element offsets in the uint32 / fp64 accumulator planes (panel-relative),
+// msum, called and nosh are indexed relative to the panel's first column (i - col0), fam by ABSOLUTE sample.
+#pragma once
+#include "snpgpu_internal.h"
+
+#include <math.h>
+
+namespace snpgpu {
+
+// ri, rj: the samples relative to the panel's first column (see "pairs without a shared call", kernels_final.hip)
+__device__ __forceinline__ bool nosh_never_shared(const uint32_t *ns, int64_t nc, int64_t ri, int64_t rj)
+{
+    const uint32_t nb = ns[0];
+    if (nb == 0 || ns[2]) return false;
+    const uint32_t hi = ns[8 + nc + ri], hj = ns[8 + nc + rj];
+    if (hi + hj < nb) return false;
+    const uint32_t si = ns[8 + 2 * nc + ri], sj = ns[8 + 2 * nc + rj];
+    const uint32_t *T = ns + 8 + 3 * nc + NOSH_HEAVY;
+    const uint32_t wi = si ? T[(int64_t)(si - 1) * nc + rj] : 0u, wj = sj ? T[(int64_t)(sj - 1) * nc + ri] : 0u;
+    if ((wi | wj) >> 31) return false;
+    const uint32_t both = (si ? wi : wj) & 0x7fffffffu;
+    return hi + hj - both == nb;
+}
+
+// ---- KING robust: off-diagonal pair (i != j); kernel counters {nLoci, ibs1, 2 ibs0, N1, N2}, genKING.cpp:604-650 -----------------------
+struct KingRobustArgs {
+    const uint32_t *acc; int64_t plane; const int32_t *fam;
+};
+__device__ __forceinline__ void king_robust_value(const KingRobustArgs &a, int64_t rel, int64_t i, int64_t j, double &vi, double &vk)
+{
+    const uint32_t n = a.acc[rel], c1 = a.acc[a.plane + rel], c0 = a.acc[2 * a.plane + rel] >> 1;   // the plane holds 2 ibs0
+    const uint32_t n1 = a.acc[3 * a.plane + rel], n2 = a.acc[4 * a.plane + rel];
+    const uint32_t sumsq = c1 + 4u * c0;
+    vi = (n > 0) ? ((double)c0 / n) : (double)NAN;
+    const int f1 = a.fam ? a.fam[i] : -1, f2 = a.fam ? a.fam[j] : -1;
+    double v = (f1 == f2 && f1 >= 0) ? (0.5 - sumsq / (2.0 * (uint32_t)(n1 + n2)))
+                                     : (0.5 - sumsq / (4.0 * (n1 < n2 ? n1 : n2)));
+    if (!isfinite(v)) v = (double)NAN;
+    vk = v;
+}
+
+// ---- KING homo: off-diagonal pair, genKING.cpp:526-537 ------------------------------------------------------------------------------------
+struct KingHomoArgs {
+    const uint32_t *acc; const double *facc; int64_t plane; double fscale; const double *wc;
+    // round 5: blocks with missing calls leave B_ij = sum c mu_i mu_j in the planes and per-sample sums M in msum[2][ncols_pad]:
+    // masked sum = C - M_i - M_j + B_ij with C in wc (the totals of ALL blocks then); msum == nullptr: the planes hold the masked sums
+    const double *msum; int64_t col0, ncols_pad;
+    // that difference of sums is not exactly 0 where the true sum is: a sample never called at an SNP of nonzero weight (called[] == 0, as
+    // FinDiss) has both weight sums 0 exactly with every sample, so 0 / 0 = NaN as in the reference.  Two samples that are both
+    // called somewhere and share no call: nosh (kernels_final.hip), here and in FinDiss
+    const uint32_t *called;
+    const uint32_t *nosh;
+};
+__device__ __forceinline__ void king_homo_value(const KingHomoArgs &h, int64_t rel, int64_t relf, int64_t i, int64_t j, double &a, double &b)
+{
+    const uint32_t c1 = h.acc[rel], c0 = h.acc[h.plane + rel] >> 1;   // the plane holds 2 ibs0
+    const uint32_t sumsq = c1 + 4u * c0;
+    // tables may be pre-scaled; blocks without missing calls contribute the same sum to every pair (wc)
+    double saf = h.facc[relf] * h.fscale + (h.wc ? h.wc[0] : 0.0), saf2 = h.facc[h.plane + relf] * h.fscale + (h.wc ? h.wc[1] : 0.0);
+    if (h.msum) {
+        saf -= h.msum[i - h.col0] + h.msum[j - h.col0];
+        saf2 -= h.msum[h.ncols_pad + i - h.col0] + h.msum[h.ncols_pad + j - h.col0];
+    }
+    if (h.called && (!h.called[i - h.col0] || !h.called[j - h.col0])) saf = saf2 = 0.0;
+    if (h.nosh && nosh_never_shared(h.nosh, h.ncols_pad, i - h.col0, j - h.col0)) saf = saf2 = 0.0;
+    const double theta = 0.5 - sumsq / (8 * saf);
+    const double v0 = c0 / (2 * saf2);
+    const double v1 = 2 - 2 * v0 - 4 * theta;
+    a = isfinite(v0) ? v0 : (double)NAN;
+    b = isfinite(v1) ? v1 : (double)NAN;
+}
+
+// ---- PLINK method of moments: off-diagonal pair; Est_PLINK_Kinship, src/genIBD.cpp:341-390; kernel counters {n, ibs1, 2 ibs0} -------------
+struct MomArgs {
+    const uint32_t *acc; int64_t plane; double e00, e01, e02, e11, e12; int constraint;
+};
+__device__ __forceinline__ void mom_value(const MomArgs &m, int64_t rel, double &a, double &b)
+{
+    const int n012 = (int)m.acc[rel], IBS1 = (int)m.acc[m.plane + rel], IBS0 = (int)(m.acc[2 * m.plane + rel] >> 1);
+    const int IBS2 = n012 - IBS0 - IBS1;
+    const double f00 = m.e00 * n012, f01 = m.e01 * n012, f11 = m.e11 * n012, f02 = m.e02 * n012, f12 = m.e12 * n012,
+                 f22 = 1.0 * n012;
+    double v0 = IBS0 / f00;
+    double v1 = (IBS1 - v0 * f01) / f11;
+    double v2 = (IBS2 - v0 * f02 - v1 * f12) / f22;
+    if (v0 > 1) { v0 = 1; v1 = v2 = 0; }
+    if (v1 > 1) { v1 = 1; v0 = v2 = 0; }
+    if (v2 > 1) { v2 = 1; v0 = v1 = 0; }
+    if (v0 < 0) { const double S = v1 + v2; v1 /= S; v2 /= S; v0 = 0; }
+    if (v1 < 0) { const double S = v0 + v2; v0 /= S; v2 /= S; v1 = 0; }
+    if (v2 < 0) { const double S = v0 + v1; v0 /= S; v1 /= S; v2 = 0; }
+    if (m.constraint) {
+        v2 = 1 - v0 - v1;
+        const double pihat = v1 / 2 + v2;
+        if (pihat * pihat < v2) { v0 = (1 - pihat) * (1 - pihat); v1 = 2 * pihat * (1 - pihat); }
+    }
+    a = v0; b = v1;
+}
+
+// kinship of a pair from its k0 / k1 (snpgdsIBDSelection, R/IBD.R:487).  0.5 and 0.25 are powers of two: both products are exact, the
+// sum rounds once with or without a fused multiply-add
+__device__ __forceinline__ double kinship_k0k1(double k0, double k1) { return (1 - k0 - k1) * 0.5 + k1 * 0.25; }
+
+}  // namespace snpgpu

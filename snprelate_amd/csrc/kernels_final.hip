@@ -1,7 +1,7 @@
 // Finalisers: rectangular panel accumulators -> the reference's output layouts
 // (packed upper triangle slab, CdMatTri src/dGenGWAS.h:511-583, or the full symmetric matrix that
 // gnrIBSNum / gnrIBSAve / grm_output build, src/genIBS.cpp:463-543, src/genPCA.cpp:1586-1602).
-#include "snpgpu_internal.h"
+#include "fin_values.h"
 
 #include <math.h>
 
@@ -112,22 +112,14 @@ int launch_fin_king_counts(hipStream_t st, const PanelGeom &g, const uint32_t *a
 }
 
 struct FinKingRobust {
-    const uint32_t *acc; int64_t plane; const int32_t *fam; double *ibs0, *kin;
+    KingRobustArgs v; double *ibs0, *kin;
     __device__ void apply(int64_t rel, int64_t relf, int64_t i, int64_t j, OutPos p) const
     {
         double vi, vk;
         if (i == j) {           // genKING.cpp:623
             vi = 0; vk = 0.5;
         } else {
-            const uint32_t n = acc[rel], c1 = acc[plane + rel], c0 = acc[2 * plane + rel] >> 1;   // the plane holds 2 ibs0
-            const uint32_t n1 = acc[3 * plane + rel], n2 = acc[4 * plane + rel];
-            const uint32_t sumsq = c1 + 4u * c0;
-            vi = (n > 0) ? ((double)c0 / n) : (double)NAN;
-            const int f1 = fam ? fam[i] : -1, f2 = fam ? fam[j] : -1;
-            double v = (f1 == f2 && f1 >= 0) ? (0.5 - sumsq / (2.0 * (uint32_t)(n1 + n2)))
-                                             : (0.5 - sumsq / (4.0 * (n1 < n2 ? n1 : n2)));
-            if (!isfinite(v)) v = (double)NAN;
-            vk = v;
+            king_robust_value(v, rel, i, j, vi, vk);
         }
         ibs0[p.a] = vi; kin[p.a] = vk;
         if (p.b >= 0) { ibs0[p.b] = vi; kin[p.b] = vk; }
@@ -136,7 +128,7 @@ struct FinKingRobust {
 int launch_fin_king_robust(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const int32_t *family,
                            double *ibs0, double *kin, int packed)
 {
-    FinKingRobust f{acc, g.rows_pad * g.ncols_pad, family, ibs0, kin};
+    FinKingRobust f{KingRobustArgs{acc, g.rows_pad * g.ncols_pad, family}, ibs0, kin};
     return run_fin(st, g, packed, f);
 }
 
@@ -227,52 +219,15 @@ int launch_nosh_block(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t
     return 0;
 }
 
-// ri, rj: the samples relative to the panel's first column
-__device__ __forceinline__ bool nosh_never_shared(const uint32_t *ns, int64_t nc, int64_t ri, int64_t rj)
-{
-    const uint32_t nb = ns[0];
-    if (nb == 0 || ns[2]) return false;
-    const uint32_t hi = ns[8 + nc + ri], hj = ns[8 + nc + rj];
-    if (hi + hj < nb) return false;
-    const uint32_t si = ns[8 + 2 * nc + ri], sj = ns[8 + 2 * nc + rj];
-    const uint32_t *T = ns + 8 + 3 * nc + NOSH_HEAVY;
-    const uint32_t wi = si ? T[(int64_t)(si - 1) * nc + rj] : 0u, wj = sj ? T[(int64_t)(sj - 1) * nc + ri] : 0u;
-    if ((wi | wj) >> 31) return false;
-    const uint32_t both = (si ? wi : wj) & 0x7fffffffu;
-    return hi + hj - both == nb;
-}
+// nosh_never_shared(words, ncols_pad, ri, rj), the read side of these words, is in fin_values.h (the selection kernels share it)
 
 // ---- KING homo ---------------------------------------------------------------
 struct FinKingHomo {
-    const uint32_t *acc; const double *facc; int64_t plane; double fscale; double *k0, *k1; const double *wc;
-    // round 5: blocks with missing calls leave B_ij = sum c mu_i mu_j in the planes and per-sample sums M in msum[2][ncols_pad]:
-    // masked sum = C - M_i - M_j + B_ij with C in wc (the totals of ALL blocks then); msum == nullptr: the planes hold the masked sums
-    const double *msum; int64_t col0, ncols_pad;
-    // that difference of sums is not exactly 0 where the true sum is: a sample never called at an SNP of nonzero weight (called[] == 0, as
-    // FinDiss) has both weight sums 0 exactly with every sample, so 0 / 0 = NaN as in the reference.  Two samples that are both
-    // called somewhere and share no call: nosh (above), here and in FinDiss
-    const uint32_t *called;
-    const uint32_t *nosh;
+    KingHomoArgs v; double *k0, *k1;       // (what the arguments are: fin_values.h)
     __device__ void apply(int64_t rel, int64_t relf, int64_t i, int64_t j, OutPos p) const
     {
         double a = 0, b = 0;
-        if (i != j) {           // genKING.cpp:526-537
-            const uint32_t c1 = acc[rel], c0 = acc[plane + rel] >> 1;   // the plane holds 2 ibs0
-            const uint32_t sumsq = c1 + 4u * c0;
-            // tables may be pre-scaled; blocks without missing calls contribute the same sum to every pair (wc)
-            double saf = facc[relf] * fscale + (wc ? wc[0] : 0.0), saf2 = facc[plane + relf] * fscale + (wc ? wc[1] : 0.0);
-            if (msum) {
-                saf -= msum[i - col0] + msum[j - col0];
-                saf2 -= msum[ncols_pad + i - col0] + msum[ncols_pad + j - col0];
-            }
-            if (called && (!called[i - col0] || !called[j - col0])) saf = saf2 = 0.0;
-            if (nosh && nosh_never_shared(nosh, ncols_pad, i - col0, j - col0)) saf = saf2 = 0.0;
-            const double theta = 0.5 - sumsq / (8 * saf);
-            const double v0 = c0 / (2 * saf2);
-            const double v1 = 2 - 2 * v0 - 4 * theta;
-            a = isfinite(v0) ? v0 : (double)NAN;
-            b = isfinite(v1) ? v1 : (double)NAN;
-        }
+        if (i != j) king_homo_value(v, rel, relf, i, j, a, b);           // genKING.cpp:526-537
         k0[p.a] = a; k1[p.a] = b;
         if (p.b >= 0) { k0[p.b] = a; k1[p.b] = b; }
     }
@@ -280,7 +235,7 @@ struct FinKingHomo {
 int launch_fin_king_homo(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const double *facc, double fscale,
                          double *k0, double *k1, int packed, const double *w_const, const double *msum, const uint32_t *called, const uint32_t *nosh)
 {
-    FinKingHomo f{acc, facc, g.rows_pad * g.ncols_pad, fscale, k0, k1, w_const, msum, g.col0, g.ncols_pad, called, nosh};
+    FinKingHomo f{KingHomoArgs{acc, facc, g.rows_pad * g.ncols_pad, fscale, w_const, msum, g.col0, g.ncols_pad, called, nosh}, k0, k1};
     return run_fin(st, g, packed, f);
 }
 
@@ -358,31 +313,11 @@ int launch_fin_cov(hipStream_t st, const PanelGeom &g, const double *num, double
 // ---- PLINK method of moments ------------------------------------------------------
 // Est_PLINK_Kinship, src/genIBD.cpp:341-390; kernel counters {n, ibs1, ibs0}
 struct FinMom {
-    const uint32_t *acc; int64_t plane; double e00, e01, e02, e11, e12; int constraint; double *k0, *k1;
+    MomArgs v; double *k0, *k1;
     __device__ void apply(int64_t rel, int64_t relf, int64_t i, int64_t j, OutPos p) const
     {
         double a = 0, b = 0;
-        if (i != j) {
-            const int n012 = (int)acc[rel], IBS1 = (int)acc[plane + rel], IBS0 = (int)(acc[2 * plane + rel] >> 1);
-            const int IBS2 = n012 - IBS0 - IBS1;
-            const double f00 = e00 * n012, f01 = e01 * n012, f11 = e11 * n012, f02 = e02 * n012, f12 = e12 * n012,
-                         f22 = 1.0 * n012;
-            double v0 = IBS0 / f00;
-            double v1 = (IBS1 - v0 * f01) / f11;
-            double v2 = (IBS2 - v0 * f02 - v1 * f12) / f22;
-            if (v0 > 1) { v0 = 1; v1 = v2 = 0; }
-            if (v1 > 1) { v1 = 1; v0 = v2 = 0; }
-            if (v2 > 1) { v2 = 1; v0 = v1 = 0; }
-            if (v0 < 0) { const double S = v1 + v2; v1 /= S; v2 /= S; v0 = 0; }
-            if (v1 < 0) { const double S = v0 + v2; v0 /= S; v2 /= S; v1 = 0; }
-            if (v2 < 0) { const double S = v0 + v1; v0 /= S; v1 /= S; v2 = 0; }
-            if (constraint) {
-                v2 = 1 - v0 - v1;
-                const double pihat = v1 / 2 + v2;
-                if (pihat * pihat < v2) { v0 = (1 - pihat) * (1 - pihat); v1 = 2 * pihat * (1 - pihat); }
-            }
-            a = v0; b = v1;
-        }
+        if (i != j) mom_value(v, rel, a, b);
         k0[p.a] = a; k1[p.a] = b;
         if (p.b >= 0) { k0[p.b] = a; k1[p.b] = b; }
     }
@@ -390,7 +325,7 @@ struct FinMom {
 int launch_fin_mom(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const double *e, int constraint,
                    double *k0, double *k1, int packed)
 {
-    FinMom f{acc, g.rows_pad * g.ncols_pad, e[0], e[1], e[2], e[3], e[4], constraint, k0, k1};
+    FinMom f{MomArgs{acc, g.rows_pad * g.ncols_pad, e[0], e[1], e[2], e[3], e[4], constraint}, k0, k1};
     return run_fin(st, g, packed, f);
 }
 

@@ -922,6 +922,39 @@ int snpgpu_multi_eigmix(snpgpu_multi *m, int diagadj, double scale, double *out_
     return gather_slabs(m, 1, sizeof(double), out, mem, [=](snpgpu_ctx *c, void **p) { return snpgpu_eigmix(c, diagadj, scale, (double *)p[0], 1, SNPGPU_DEVICE); });
 }
 
+// the resident panels in order of row_begin, each one's selection behind the previous one's: the global order.  The panels run one
+// after the other (a panel's position in the output is known only once the panels before it are counted)
+int snpgpu_multi_select_pairs(snpgpu_multi *m, const snpgpu_sel_opts *o, int64_t capacity, int32_t *idx1, int32_t *idx2, double *v0, double *v1,
+                              double *kinship, int mem, int64_t *n_found)
+{
+    const char *fn = "snpgpu_multi_select_pairs";
+    // what needs no device first, with this call's name (snpgpu_select_pairs repeats the checks per panel)
+    if (!o) { set_error(std::string(fn) + ": NULL opts"); return 1; }
+    if (o->what != SNPGPU_SEL_KING_ROBUST && o->what != SNPGPU_SEL_KING_HOMO && o->what != SNPGPU_SEL_MOM) { set_error(std::string(fn) + ": invalid 'what'"); return 1; }
+    if (o->what == SNPGPU_SEL_MOM && !o->e) { set_error(std::string(fn) + ": e is NULL (SNPGPU_SEL_MOM needs the five expectations)"); return 1; }
+    if (capacity < 0) { set_error(std::string(fn) + ": negative capacity"); return 1; }
+    if (capacity == 0 && (idx1 || idx2 || v0 || v1 || kinship)) { set_error(std::string(fn) + ": capacity 0 with a non-NULL output (count only: every output NULL)"); return 1; }
+    if (!m) { set_error(std::string(fn) + ": NULL object"); return 1; }
+    const int kind = o->what == SNPGPU_SEL_KING_ROBUST ? SNPGPU_KING_ROBUST : o->what == SNPGPU_SEL_KING_HOMO ? SNPGPU_KING_HOMO : SNPGPU_IBS;
+    if (m->kind != kind) { set_error(std::string(fn) + ": 'what' does not match the object's kind"); return 1; }
+    if (mem != SNPGPU_HOST) { set_error(std::string(fn) + ": results go to host memory"); return 1; }
+    std::vector<size_t> order(m->ctx.size());
+    for (size_t i = 0; i < order.size(); i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return m->ctx[a]->plan.row0 < m->ctx[b]->plan.row0; });
+    int64_t total = 0, stored = 0;
+    for (size_t i : order) {
+        const int64_t room = capacity - stored;
+        int64_t found = 0;
+        auto at = [&](auto *p) -> decltype(p) { return (p && room > 0) ? p + stored : nullptr; };
+        if (snpgpu_select_pairs(m->ctx[i], o, room, at(idx1), at(idx2), at(v0), at(v1), at(kinship), SNPGPU_HOST, &found)) return 1;
+        total += found;
+        stored += std::min(room, found);
+    }
+    (void)hipSetDevice(m->dev[0].device);
+    if (n_found) *n_found = total;
+    return 0;
+}
+
 // trace of the whole matrix: the sum of the resident panels' diagonal parts (all panels of a one-pass plan)
 int snpgpu_multi_pca_trace(snpgpu_multi *m, double *trace)
 {

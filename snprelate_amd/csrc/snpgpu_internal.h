@@ -346,6 +346,23 @@ int launch_beta_reduce(hipStream_t st, const PanelGeom &g, const uint32_t *acc, 
 int launch_fin_beta(hipStream_t st, const PanelGeom &g, const uint32_t *acc, int mode, double avg, double mn, double *out,
                     int packed);
 int launch_mirror_diag(hipStream_t st, const PanelGeom &g, double *num);
+
+// selection of related pairs (kernels_select.hip): the pairs row0 <= i < row1, i < j < N of the panel with sel[i] && sel[j] (absolute
+// samples; nullptr: all) and kinship >= cutoff (non-finite cutoff: every pair), in the order i ascending, j ascending.  write == false
+// fills counts[select_segments(g)]; launch_select_scan turns them into offsets[segments + 1] (the last one = the total); write == true
+// stores the first `capacity` pairs (any output may be nullptr).  The kinds take the arguments of their finalisers.
+constexpr int64_t SELECT_MAX_GRID = 1 << 20;   // workgroups of a pass (one row each, stride loop beyond)
+struct SelectArgs {
+    const uint8_t *sel; double cutoff;
+    uint32_t *counts; int64_t *offsets;
+    int64_t capacity; int32_t *idx1, *idx2; double *v0, *v1, *kin;
+};
+int64_t select_segments(const PanelGeom &g);
+int launch_select_scan(hipStream_t st, const uint32_t *counts, int64_t n_seg, int64_t *offsets);
+int launch_select_king_robust(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const int32_t *family, const SelectArgs &s, bool write);
+int launch_select_king_homo(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const double *facc, double fscale, const double *w_const,
+                            const double *msum, const uint32_t *called, const uint32_t *nosh, const SelectArgs &s, bool write);
+int launch_select_mom(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const double *e, int constraint, const SelectArgs &s, bool write);
 int launch_mirror_diag_tiles(hipStream_t st, const PanelGeom &g, double *num, int T);
 
 // context-level pieces shared between api.hip and eigen.hip / multi.hip

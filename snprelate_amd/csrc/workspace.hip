@@ -25,6 +25,9 @@ struct WorkSpace {
     int64_t n_snp_all = 0, n_samp = 0, rb = 0;  // rb = ceil(n_samp/4) bytes per SNP row
     std::vector<uint8_t> packed;                // [n_snp_all][rb] 2-bit rows
     std::vector<int64_t> sel;                   // indices of the currently selected SNPs
+    // the selection kept by snpgpu_gnrIBDPairs for snpgpu_gnrIBDPairs_get
+    std::vector<int32_t> pair_idx1, pair_idx2;
+    std::vector<double> pair_v0, pair_v1, pair_kin;
 };
 WorkSpace g_ws;
 double g_grm_avg_value = 0;   // grm_avg_value, src/genPCA.cpp:1605
@@ -649,11 +652,9 @@ int snpgpu_gnrGRM_avg_val(double *avg_val)
     return 0;
 }
 
-// gnrIBD_PLINK, src/genIBS.cpp:558-639 with Init_EPrIBD_IBS, src/genIBD.cpp:253-338
-int snpgpu_gnrIBD_PLINK(int, const double *allele_freq, int kinship_constraint, int use_matrix, int, double *k0,
-                        double *k1, double *afreq_out)
+// the expectations e[5] of gnrIBD_PLINK (Init_EPrIBD_IBS, src/genIBD.cpp:253-338) over the selected SNPs; afreq_out: double [n_snp] or NULL
+static int ws_mom_expect(const double *allele_freq, double *afreq_out, double e[5])
 {
-    if (need_ws("snpgpu_gnrIBD_PLINK")) return 1;
     std::vector<int32_t> sum, num, het;
     if (ws_stats(sum, num, &het)) return 1;
     // E[IBS state | IBD state] per SNP as polynomials in the allele frequencies p, q = 1 - p (PLINK's method of moments;
@@ -697,10 +698,73 @@ int snpgpu_gnrIBD_PLINK(int, const double *allele_freq, int kinship_constraint, 
         if (finite) { for (int k = 0; k < 5; k++) tot[k] += val[k]; nValid++; }      // SNPs with a non-finite term are skipped
     }
     const double s00 = tot[0], s01 = tot[1], s02 = tot[2], s11 = tot[3], s12 = tot[4];
-    const double e[5] = {s00 / nValid, s01 / nValid, s02 / nValid, s11 / nValid, s12 / nValid};
+    e[0] = s00 / nValid; e[1] = s01 / nValid; e[2] = s02 / nValid; e[3] = s11 / nValid; e[4] = s12 / nValid;
+    return 0;
+}
+
+// gnrIBD_PLINK, src/genIBS.cpp:558-639 with Init_EPrIBD_IBS, src/genIBD.cpp:253-338
+int snpgpu_gnrIBD_PLINK(int, const double *allele_freq, int kinship_constraint, int use_matrix, int, double *k0,
+                        double *k1, double *afreq_out)
+{
+    if (need_ws("snpgpu_gnrIBD_PLINK")) return 1;
+    double e[5];
+    if (ws_mom_expect(allele_freq, afreq_out, e)) return 1;
     CtxGuard g;
     if (run_stream(SNPGPU_IBS, 0, &g.c)) return 1;
     return snpgpu_ibd_mom(g.c, e, kinship_constraint, k0, k1, use_matrix ? 1 : 0, SNPGPU_HOST);
+}
+
+// Related pairs of the working space (include/snpgpu.h): one accumulation, a count, then the selection itself -- host memory
+// proportional to the number of selected pairs, no n x n matrix
+int snpgpu_gnrIBDPairs(int what, const int32_t *family, const double *allele_freq, int kinship_constraint, double kinship_cutoff,
+                       const uint8_t *samp_sel, int, int, int64_t *n_found)
+{
+    if (what != SNPGPU_SEL_KING_ROBUST && what != SNPGPU_SEL_KING_HOMO && what != SNPGPU_SEL_MOM) {
+        set_error("snpgpu_gnrIBDPairs: invalid 'what' (SNPGPU_SEL_KING_ROBUST, SNPGPU_SEL_KING_HOMO or SNPGPU_SEL_MOM)");
+        return 1;
+    }
+    if (need_ws("snpgpu_gnrIBDPairs")) return 1;
+    if (what == SNPGPU_SEL_KING_ROBUST && (int64_t)g_ws.sel.size() >= 1073741824LL) {  // src/genKING.cpp:598-602
+        set_error("The number of SNPs should be less than 1,073,741,824.");
+        return 1;
+    }
+    g_ws.pair_idx1.clear(); g_ws.pair_idx2.clear(); g_ws.pair_v0.clear(); g_ws.pair_v1.clear(); g_ws.pair_kin.clear();
+    double e[5] = {0, 0, 0, 0, 0};
+    if (what == SNPGPU_SEL_MOM && ws_mom_expect(allele_freq, nullptr, e)) return 1;
+    snpgpu_sel_opts o{};
+    o.what = what;
+    o.kinship_constraint = kinship_constraint;
+    o.family = family;
+    o.e = what == SNPGPU_SEL_MOM ? e : nullptr;
+    o.kinship_cutoff = kinship_cutoff;
+    o.samp_sel = samp_sel;
+    CtxGuard g;
+    if (run_stream(what == SNPGPU_SEL_KING_ROBUST ? SNPGPU_KING_ROBUST : what == SNPGPU_SEL_KING_HOMO ? SNPGPU_KING_HOMO : SNPGPU_IBS, 0, &g.c)) return 1;
+    int64_t n = 0;
+    if (snpgpu_select_pairs(g.c, &o, 0, nullptr, nullptr, nullptr, nullptr, nullptr, SNPGPU_HOST, &n)) return 1;
+    if (n > 0) {
+        g_ws.pair_idx1.resize((size_t)n); g_ws.pair_idx2.resize((size_t)n);
+        g_ws.pair_v0.resize((size_t)n); g_ws.pair_v1.assign((size_t)n, 0.0); g_ws.pair_kin.resize((size_t)n);
+        int64_t again = 0;
+        if (snpgpu_select_pairs(g.c, &o, n, g_ws.pair_idx1.data(), g_ws.pair_idx2.data(), g_ws.pair_v0.data(), g_ws.pair_v1.data(),
+                                g_ws.pair_kin.data(), SNPGPU_HOST, &again))
+            return 1;
+        if (again != n) { set_error("snpgpu_gnrIBDPairs: the selection changed between the count and the fetch"); return 1; }
+    }
+    if (n_found) *n_found = n;
+    return 0;
+}
+
+int snpgpu_gnrIBDPairs_get(int32_t *idx1, int32_t *idx2, double *v0, double *v1, double *kinship)
+{
+    const size_t n = g_ws.pair_idx1.size();
+    if (n == 0) return 0;
+    if (idx1) memcpy(idx1, g_ws.pair_idx1.data(), sizeof(int32_t) * n);
+    if (idx2) memcpy(idx2, g_ws.pair_idx2.data(), sizeof(int32_t) * n);
+    if (v0) memcpy(v0, g_ws.pair_v0.data(), sizeof(double) * n);
+    if (v1) memcpy(v1, g_ws.pair_v1.data(), sizeof(double) * n);
+    if (kinship) memcpy(kinship, g_ws.pair_kin.data(), sizeof(double) * n);
+    return 0;
 }
 
 int snpgpu_gnrIBD_Beta(int inbreeding, int, int use_matrix, int, double *out, double *avg_val)
