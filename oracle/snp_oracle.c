@@ -654,7 +654,7 @@ void orc_tri_to_full_f64(const double *tri, i64 N, double *full)
 
 /* ---------------------------------------------------------------------------
  * Counter-based synthetic genotypes: C twin of oracle/synth.py:synth_hash_geno for spectra 0, 1, 2 (test / bench utility, no
- * reference counterpart; the generator itself is snpgpu_synth_block, kernels_prep.hip).  The numpy twin defines it and
+ * reference counterpart; the generator itself is snpgpu_synth_block, kernels_synth.hip).  The numpy twin defines it and
  * tests/test_cpu_host.py compares the two cell by cell; this form only makes the fp64 anchors of the full-size checks
  * (tests/fp64_anchor.py: ~650 samples x 1e6 SNPs) a matter of seconds.  out: uint8 [n_snp][n_samples].  */
 static inline uint32_t orc_mix32(uint32_t x)

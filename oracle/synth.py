@@ -26,7 +26,7 @@ def synth_geno(n_samp, n_snp, missing=0.02, seed=1, special=True):
 
 
 # ---------------------------------------------------------------------------
-# Counter-based generator: the numpy twin of snpgpu_synth_block (kernels_prep.hip: synth_block_kernel).
+# Counter-based generator: the numpy twin of snpgpu_synth_block (kernels_synth.hip: synth_block_kernel).
 # Every cell is a pure integer function of (seed, snp, sample): full-size GPU runs (N = 100 000 .. 500 000,
 # L = 1 000 000) are checked by recomputing a handful of samples here.
 _M32 = np.uint32(0xFFFFFFFF)

@@ -509,7 +509,7 @@ static int feed_counters(snpgpu_ctx *c, const Block &b)
         if (p.gcta_sparse) {      // the block's route (device side): sparse sets up to sp_max_rate missing calls, the dense product beyond
             const unsigned long long max_cells = (unsigned long long)(p.sp_max_rate * (double)p.N * (double)n_snp);
             if (launch_missmask256(st, packed, p.RB, n_snp, p.N, sum, num, p.col0, (int)(p.ncols_pad / 256), mm_stride, (uint4 *)c->mm256.p,
-                                   c->d_missing(), max_cells, c->d_miss_route()))
+                                   max_cells, c->d_miss_route()))
                 return 1;
         }
         EvScope ev(c, 0);
@@ -611,7 +611,9 @@ static int feed_syrk(snpgpu_ctx *c, int64_t n_snp)
         }
         // (EIGMIX with the single-product kernel: its exact-row kernel never runs, no column term)
         if (exact_rows && !p.uv_eigmix && launch_colcorr(st, wt, p.ncols_pad, (int)(n_pad / 8), (const double2 *)c->ccoef.p, (double *)c->tcorr.p,
-                                                         (double *)c->colterm.p, c->d_missing(), uv ? 2 : p.h3_exact_missing, entry12 ? 1 : 0))
+                                                         (double *)c->colterm.p, c->d_missing(),
+                                                         uv ? ColcorrBlocks::WithMissing : p.h3_exact_missing ? ColcorrBlocks::Every : ColcorrBlocks::WithoutMissing,
+                                                         entry12 ? 1 : 0))
             return 1;
         if (uv) {     // a block without missing calls: rare variants in fp64, row / column terms of every slot
             if (launch_uv_sparse(st, packed, p.RB, n_snp, p.N, p.row0, p.row1, p.col0, (const double4 *)c->uvsp.p, c->plane_f64(i), p.ncols_pad,
@@ -627,7 +629,7 @@ static int feed_syrk(snpgpu_ctx *c, int64_t n_snp)
             return 1;
         // EIGMIX numerator of a block with missing calls: the exact-row kernel's column term from the 12 * code words
         if (exact_rows && p.eigmix_x1 && launch_colcorr(st, (const uint32_t *)c->wt12.p, p.ncols_pad, (int)(n_pad / 8), (const double2 *)c->ccoef.p,
-                                                        (double *)c->tcorr.p, (double *)c->colterm.p, c->d_missing(), 2, 1))
+                                                        (double *)c->tcorr.p, (double *)c->colterm.p, c->d_missing(), ColcorrBlocks::WithMissing, 1))
             return 1;
         if (exact_rows) c->colterm_pending = true;
         if (eig0 && launch_eigmix_samples(st, wt, (int)(n_pad / 8), p.ncols_pad, p.col0, (const double *)c->dvals.p, (uint32_t *)c->samp_het.p,
@@ -643,9 +645,11 @@ static int feed_syrk(snpgpu_ctx *c, int64_t n_snp)
                 return 1;
             if (i == 0 && launch_nosh_block(st, packed, p.RB, n_snp, sum, num, p.col0, p.N - p.col0, p.ncols_pad, (uint32_t *)c->nosh.p))
                 return 1;
-            if (i == 0 && launch_homo_uv(st, sum, num, n_snp, n_pad, (uint2 *)c->homo_lut[0].p, (uint2 *)c->homo_lut[1].p,
-                                         (double2 *)c->homo_wts.p, c->d_homo_w(), wt, p.ncols_pad, (double2 *)c->homo_tc.p,
-                                         (double *)c->homo_msum.p, c->d_missing(), p.homo_form == UvForm::Lookup16x16x32 ? 1 : 0, p.homo_weights))
+            if (i == 0 && (launch_homo_tables(st, sum, num, n_snp, n_pad, (uint2 *)c->homo_lut[0].p, (uint2 *)c->homo_lut[1].p,
+                                              (double2 *)c->homo_wts.p, c->d_homo_w(), c->d_missing(),
+                                              p.homo_form == UvForm::Lookup16x16x32 ? 1 : 0, p.homo_weights) ||
+                           launch_homo_miss_sums(st, wt, p.ncols_pad, (int)(n_pad / 8), (const double2 *)c->homo_wts.p, (double2 *)c->homo_tc.p,
+                                                 (double *)c->homo_msum.p, c->d_missing())))
                 return 1;
             SyrkUvOpts o;
             o.work_x1 = (const int4 *)c->homo_work.p; o.n_blocks_x1 = c->homo_blocks;

@@ -11,6 +11,7 @@
 // from one row first stages that row in LDS when it fits (PS_LDS_ROW_BYTES), word by word from the aligned words that hold it.
 // Only listed sample indices are looked up, so the padding codes of a row's last byte are never read as genotypes.
 #include "snpgpu_internal.h"
+#include "prep_device.h"
 
 #include <climits>
 
@@ -170,7 +171,7 @@ __global__ __launch_bounds__(PS_THREADS) void pair_count_kernel(const uint32_t *
     if (p >= n_pair) return;
     const int64_t w0 = (int64_t)blockIdx.y * PS_WORD_CHUNK;
     const int64_t w1 = w0 + PS_WORD_CHUNK < nw ? w0 + PS_WORD_CHUNK : nw;
-    const uint32_t m55 = 0x55555555u;
+    const uint32_t m55 = GENO_LO_BITS;
     int c[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) c[k] = 0;
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(PS_THREADS) void pair_count_kernel(const uint32_t *
             x ^= f & ~((x & m55) << 1);
             y ^= f & ~((y & m55) << 1);
         }
-        const uint32_t xl = x & m55, xh = (x >> 1) & m55, yl = y & m55, yh = (y >> 1) & m55;
+        const uint32_t xl = x & m55, xh = (x >> 1) & m55, yl = y & m55, yh = (y >> 1) & m55;   // (geno_lo / geno_hi as calls change this kernel)
         const uint32_t xe[3] = {~(xl | xh) & m55, xl & ~xh, xh & ~xl};
         const uint32_t ye[3] = {~(yl | yh) & m55, yl & ~yh, yh & ~yl};
 #pragma unroll

@@ -10,6 +10,7 @@
 // once per distinct offset h of a row's first byte inside its line (16 / gcd(rb, 16) variants, zero outside the row), so
 // neither the neighbours nor the padding codes of the last byte count.
 #include "snpgpu_internal.h"
+#include "prep_device.h"
 
 namespace snpgpu {
 
@@ -34,12 +35,12 @@ __global__ __launch_bounds__(256) void pop_mask_kernel(const int32_t *__restrict
     mask[((int64_t)s * K + k) * mbytes + j] = (uint8_t)out;
 }
 
-// plane algebra of count_word (kernels_prep.hip) under a population mask
+// plane algebra of count_word (prep_device.h) under a population mask
 template <int KG>
 __device__ __forceinline__ void pop_word(uint32_t w, const uint32_t (&m)[KG], int (&n1)[KG], int (&n2)[KG], int (&nc)[KG])
 {
-    const uint32_t lo = w & 0x55555555u, hi = (w >> 1) & 0x55555555u;
-    const uint32_t one = lo & ~hi, two = hi & ~lo, called = 0x55555555u & ~(lo & hi);
+    const uint32_t lo = w & GENO_LO_BITS, hi = (w >> 1) & GENO_LO_BITS;   // (geno_lo / geno_hi as calls change pop_count_kernel: inline copy)
+    const uint32_t one = lo & ~hi, two = hi & ~lo, called = GENO_LO_BITS & ~(lo & hi);
 #pragma unroll
     for (int k = 0; k < KG; k++) {
         n1[k] += __popc(one & m[k]);

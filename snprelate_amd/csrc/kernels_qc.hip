@@ -10,6 +10,7 @@
 // Rows are read where the caller put them (rb bytes per SNP, any byte address): a lane owns the 16 samples of one 32-bit word
 // column of the row and assembles that word from the one or two aligned words that hold it.
 #include "snpgpu_internal.h"
+#include "prep_device.h"
 
 #include <cmath>
 
@@ -43,14 +44,14 @@ __global__ __launch_bounds__(256) void qc_count_kernel(const uint8_t *__restrict
     const bool live = j < n_words;
     int nv = 0;
     if (live) nv = n_samp - 16 * j < 16 ? (int)(n_samp - 16 * j) : 16;          // samples of this word: the rest is padding
-    const uint32_t m55 = nv >= 16 ? 0x55555555u : (0x55555555u & ((1u << (2 * nv)) - 1u));
+    const uint32_t m55 = nv >= 16 ? GENO_LO_BITS : (GENO_LO_BITS & ((1u << (2 * nv)) - 1u));
     const int64_t s0 = (int64_t)blockIdx.y * QC_CHUNK;
     const int64_t s1 = s0 + QC_CHUNK < n_snp ? s0 + QC_CHUNK : n_snp;
     const int lane = threadIdx.x & 63;
     uint32_t acc[4] = {0, 0, 0, 0};                 // byte t + 4 b of the lane: missing calls of sample 16 j + t + 4 b
     for (int64_t s = s0; s < s1; s++) {
         const uint32_t w = live ? qc_row_word(geno + s * rb, rb, j) : 0u;
-        const uint32_t lo = w & 0x55555555u, hi = (w >> 1) & 0x55555555u;
+        const uint32_t lo = geno_lo(w), hi = geno_hi(w);
         const uint32_t miss = lo & hi & m55;
         if (snp_cnt) {
             const uint32_t zero = ~(lo | hi) & m55, one = lo & ~hi & m55, two = hi & ~lo & m55;

@@ -69,7 +69,7 @@ constexpr int H3_PROMOTE = 4096;                          // SNPs accumulated in
 // order of the 256 instructions of a wave make no difference, tools/scratch A/B of round 4).  The accumulation error grows with
 // sqrt(run): measured over ALL 3.7e8 entries of an 8192-row panel at configs[2]'s size 32 768-SNP runs put the maximum of the
 // off-diagonal figure at 1.2e-5 (exact-row) / 1.6e-5 (single product, one weight target), 16 384 at 7e-6 / 1.2e-5 -- hence 8192 SNPs
-// for the exact-row kernel.  The single-product kernel's runs also set its number of weight targets (kernels_prep.hip,
+// for the exact-row kernel.  The single-product kernel's runs also set its number of weight targets (kernels_tables.hip,
 // uv_factor_kernel): a 32 768-SNP block = 3 runs of <= 11 264 slots, weight error 0.37e-6 rms, no refinement slots.
 // SNPGPU_H3_PROMOTE overrides both; SNPGPU_SYRK_FAST=1 restores one 32 768-SNP run (one target).
 constexpr int H3_PROMOTE_EXACT = 8192;          // (16 384: 29 of 3.7e8 entries above 1e-5, maximum 1.17e-5, on GCTA with 2 % missing calls)
@@ -142,6 +142,9 @@ enum class WordLayout {
     Entry12Missing = 4     // 12 * code, written only for a block WITH missing calls (EIGMIX: a second word array)
 };
 
+// which blocks a launch of colcorr_kernel / colterm_add_kernel serves, by the block's missing-call flag
+enum class ColcorrBlocks { WithoutMissing = 0, Every = 1, WithMissing = 2 };
+
 struct TileGrid {      // upper-trapezoid tile enumeration with XCD super-tiles
     int tile_r, tile_c;        // tile extents in samples
     int super;                 // super-tile edge in tiles
@@ -167,22 +170,14 @@ int launch_ld_final_rect(hipStream_t st, const int32_t *tab, int64_t n_i, int64_
 // LD pruning: threshold bits of band tables [n_i][w][9] -> uint64 [n_i][ceil(w / 64)] (pairs with i0 + t < start transposed)
 int launch_ld_prune_bits(hipStream_t st, const int32_t *tab, int64_t n_i, int w, int64_t i0, int64_t n_snp, int64_t start, int method,
                          double threshold, uint64_t *bits);
-// PCA projections (kernels_proj.hip)
-int launch_proj_snp(hipStream_t st, int corr, const uint32_t *w2, int64_t ncols_pad, int64_t N, int64_t n_snp,
-                    const double *et, int kp, int k, const int32_t *sum, const int32_t *num, int bayesian, double *out,
-                    double *part, int *cnt, double *out_avg, double *out_scale, const double *ext_avg = nullptr,
-                    const double *ext_scale = nullptr);
-int launch_proj_samp(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t N, int64_t n_snp, const double *sl,
-                     int kp, int k, const double *af, const double *sc, double *out);
-int launch_proj_transpose(hipStream_t st, const double *src, int64_t N, int k, double *dst, int64_t n_pad, int kp);
-int launch_synth_block(hipStream_t st, uint8_t *dst, int64_t n_samp, int64_t snp_begin, int64_t n_snp, uint32_t seed,
-                       uint32_t miss32, int spectrum, int special);
+// staging a feed block (kernels_prep.hip)
 int launch_repack_stats(hipStream_t st, const void *src, int format, int64_t n_snp, int64_t n_samp, uint8_t *packed,
                         int64_t RB, int32_t *sum, int32_t *num, unsigned long long *d_missing);
 int launch_repack(hipStream_t st, const void *src, int format, int64_t n_snp, int64_t n_samp,
                   uint8_t *packed, int64_t RB);
 int launch_snp_stats(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t n_samp,
                      int32_t *sum, int32_t *num, unsigned long long *d_missing_cells, int32_t *nhet = nullptr);
+// per-SNP tables (kernels_tables.hip)
 // table pass of one SYRK table (build_lut_kernel); the named fields are the kernel's arguments of the same names
 struct BuildLutOpts {
     int lut_mode = 0;
@@ -201,23 +196,48 @@ struct BuildLutOpts {
     unsigned long long *d_short_runs = nullptr;
 };
 int launch_build_lut(hipStream_t st, const int32_t *sum, const int32_t *num, int64_t n_snp, int64_t n_snp_pad, const BuildLutOpts &o);
+struct BuildUvOpts {
+    int lut_mode = 0;
+    uint2 *lut = nullptr;
+    double4 *uvcoef = nullptr, *uvsp = nullptr;
+    double *kpart = nullptr;
+    float *cand_err = nullptr;
+    uint32_t *cand_uv = nullptr;
+    double2 *snp_tavg = nullptr;
+    int32_t *slot_of = nullptr, *slot_src = nullptr;
+    int n_target = 1, cpr = 1;
+    const unsigned long long *d_missing = nullptr;
+    UvForm form = UvForm::Mfma32x32x16;          // table layout of the kernel that reads them
+};
+int launch_build_uv(hipStream_t st, const int32_t *sum, const int32_t *num, int64_t n_snp, int64_t n_snp_pad, const BuildUvOpts &o);
+int launch_homo_tables(hipStream_t st, const int32_t *sum, const int32_t *num, int64_t n_snp, int64_t n_snp_pad, uint2 *lut1, uint2 *lut2,
+                       double2 *wts, double *totals, const unsigned long long *d_missing, int swap_odd = 0, int n_w = 2);
+// per-sample terms beside the SYRKs (kernels_terms.hip)
 int launch_colcorr(hipStream_t st, const uint32_t *w8, int64_t ncols_pad, int n_d, const double2 *ccoef, double *tc,
-                   double *colterm, const unsigned long long *d_missing, int always = 0, int entry12 = 0);
-int launch_colterm_settle(hipStream_t st, double *acc, int64_t ld, int64_t tiles_c, int64_t n_rows_real, int64_t ncols_pad, int64_t n_cols_real,
-                          double *colterm, double *uvterm = nullptr);
+                   double *colterm, const unsigned long long *d_missing, ColcorrBlocks blocks = ColcorrBlocks::WithoutMissing,
+                   int entry12 = 0);
+int launch_uvcorr(hipStream_t st, const uint32_t *w8, int64_t ncols_pad, int n_d, const double4 *uvcoef, const double *kpart,
+                  int n_kpart, double2 *tc, double *uvterm, const unsigned long long *d_missing, int nibble = 0);
+int launch_uv_sparse(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t N, int64_t row0, int64_t row1,
+                     int64_t col0, const double4 *uvsp, double *acc, int64_t ld, int64_t tiles_c, int64_t ncols_pad, double *uvterm,
+                     const unsigned long long *d_missing, int missing_blocks = 0);
+int launch_homo_miss_sums(hipStream_t st, const uint32_t *w8, int64_t ncols_pad, int n_d, const double2 *wts, double2 *tc, double *msum,
+                          const unsigned long long *d_missing);
 int launch_eigmix_samples(hipStream_t st, const uint32_t *w8, int n_d, int64_t ncols_pad, int64_t col0,
                           const double *dvals, uint32_t *het, double *dmiss, double *dsq,
                           const unsigned long long *d_wide16 = nullptr);
-int launch_bitplanes4(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t n_samp,
-                      int64_t col0, int64_t ncols_pad, int64_t rows_pad, int KW, uint4 *rowp, uint4 *colp);
-int launch_bitplanes_miss(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t n_samp,
-                          const int32_t *sum, const int32_t *num, int64_t col0, int64_t ncols_pad,
-                          int64_t rows_pad, int KW, uint2 *rowp, uint2 *colp,
-                          const unsigned long long *d_missing_cells);
-int launch_pair_popcount(hipStream_t st, int mode, const TileGrid &tg, const void *rowp, const void *colp,
-                         int KW, int64_t ncols_pad, uint32_t *acc, int64_t acc_plane,
-                         const unsigned long long *d_skip_if_zero);
-// int8-MFMA form of the pair counters (IBS / KING / beta): sample-major 2-bit words + kernel
+// SNP-major to sample-major words (kernels_transpose.hip)
+struct Transpose8Opts {
+    int n_d = 0;
+    uint32_t *w8 = nullptr;
+    const unsigned long long *d_block_flag = nullptr;   // the block's missing-call flag (the kernel's d_wide16)
+    WordLayout layout = WordLayout::Entry8Or16;
+    const int32_t *slot_src = nullptr;
+    bool nibble_nomiss = false;
+};
+int launch_transpose8(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t col0, int64_t ncols_pad,
+                      const Transpose8Opts &o);
+// (sample-major 2-bit words of the MFMA pair counters: IBS / KING / beta)
 int launch_transpose2(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t col0,
                       int64_t ncols_pad, int n_d, uint32_t *w2, uint32_t *het = nullptr,
                       const unsigned long long *d_missing = nullptr, bool classic = false);
@@ -226,12 +246,35 @@ int launch_transpose2_missmask(hipStream_t st, const uint8_t *packed, int64_t RB
                                uint32_t *w2, uint32_t *diag, const unsigned long long *d_skip_if_zero);
 int launch_missmask256(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t N, const int32_t *sum,
                        const int32_t *num, int64_t col0, int n_groups, int64_t snp_stride, uint4 *mm,
-                       const unsigned long long *d_missing, unsigned long long max_cells, unsigned long long *flags);
-int launch_pair_sparse_miss(hipStream_t st, const uint4 *mm, int64_t snp_stride, int n_snp, uint32_t *acc, int64_t ncols_pad,
-                            const int4 *work, int n_blocks, const unsigned long long *d_run);
+                       unsigned long long max_cells, unsigned long long *flags);
 int launch_transpose2_direct(hipStream_t st, const uint8_t *src, int64_t n_samp, int64_t n_snp, int64_t col0,
                              int64_t ncols_pad, int n_d, uint32_t *w2, uint32_t *het, uint32_t *het_blk,
                              unsigned long long *d_missing);
+int launch_bitplanes4(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t n_samp,
+                      int64_t col0, int64_t ncols_pad, int64_t rows_pad, int KW, uint4 *rowp, uint4 *colp);
+int launch_bitplanes_miss(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t n_samp,
+                          const int32_t *sum, const int32_t *num, int64_t col0, int64_t ncols_pad,
+                          int64_t rows_pad, int KW, uint2 *rowp, uint2 *colp,
+                          const unsigned long long *d_missing_cells);
+// synthetic genotypes (kernels_synth.hip)
+int launch_synth_block(hipStream_t st, uint8_t *dst, int64_t n_samp, int64_t snp_begin, int64_t n_snp, uint32_t seed,
+                       uint32_t miss32, int spectrum, int special);
+// PCA projections (kernels_proj.hip)
+int launch_proj_snp(hipStream_t st, int corr, const uint32_t *w2, int64_t ncols_pad, int64_t N, int64_t n_snp,
+                    const double *et, int kp, int k, const int32_t *sum, const int32_t *num, int bayesian, double *out,
+                    double *part, int *cnt, double *out_avg, double *out_scale, const double *ext_avg = nullptr,
+                    const double *ext_scale = nullptr);
+int launch_proj_samp(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t N, int64_t n_snp, const double *sl,
+                     int kp, int k, const double *af, const double *sc, double *out);
+int launch_proj_transpose(hipStream_t st, const double *src, int64_t N, int k, double *dst, int64_t n_pad, int kp);
+// settling the per-sample terms into the panel (kernels_final.hip), pair counters (kernels_pair.hip)
+int launch_colterm_settle(hipStream_t st, double *acc, int64_t ld, int64_t tiles_c, int64_t n_rows_real, int64_t ncols_pad, int64_t n_cols_real,
+                          double *colterm, double *uvterm = nullptr);
+int launch_pair_popcount(hipStream_t st, int mode, const TileGrid &tg, const void *rowp, const void *colp,
+                         int KW, int64_t ncols_pad, uint32_t *acc, int64_t acc_plane,
+                         const unsigned long long *d_skip_if_zero);
+int launch_pair_sparse_miss(hipStream_t st, const uint4 *mm, int64_t snp_stride, int n_snp, uint32_t *acc, int64_t ncols_pad,
+                            const int4 *work, int n_blocks, const unsigned long long *d_run);
 int launch_pair_fp4_miss(hipStream_t st, const int4 *work, int n_blocks, const uint32_t *w2, int64_t ncols_pad, int n_s,
                          uint32_t *acc, const unsigned long long *d_missing);
 int launch_pair_i8(hipStream_t st, int mode, const int4 *work, int n_blocks, const uint32_t *w2, int64_t ncols_pad,
@@ -266,38 +309,6 @@ struct SyrkUvOpts {
     int carry_slots = 0;
 };
 int launch_syrk_uv(hipStream_t st, const SyrkPanel &p, const SyrkUvOpts &o);
-struct BuildUvOpts {
-    int lut_mode = 0;
-    uint2 *lut = nullptr;
-    double4 *uvcoef = nullptr, *uvsp = nullptr;
-    double *kpart = nullptr;
-    float *cand_err = nullptr;
-    uint32_t *cand_uv = nullptr;
-    double2 *snp_tavg = nullptr;
-    int32_t *slot_of = nullptr, *slot_src = nullptr;
-    int n_target = 1, cpr = 1;
-    const unsigned long long *d_missing = nullptr;
-    UvForm form = UvForm::Mfma32x32x16;          // table layout of the kernel that reads them
-};
-int launch_build_uv(hipStream_t st, const int32_t *sum, const int32_t *num, int64_t n_snp, int64_t n_snp_pad, const BuildUvOpts &o);
-int launch_uv_sparse(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t N, int64_t row0, int64_t row1,
-                     int64_t col0, const double4 *uvsp, double *acc, int64_t ld, int64_t tiles_c, int64_t ncols_pad, double *uvterm,
-                     const unsigned long long *d_missing, int missing_blocks = 0);
-int launch_uvcorr(hipStream_t st, const uint32_t *w8, int64_t ncols_pad, int n_d, const double4 *uvcoef, const double *kpart,
-                  int n_kpart, double2 *tc, double *uvterm, const unsigned long long *d_missing, int nibble = 0);
-int launch_homo_uv(hipStream_t st, const int32_t *sum, const int32_t *num, int64_t n_snp, int64_t n_snp_pad, uint2 *lut1, uint2 *lut2,
-                   double2 *wts, double *totals, const uint32_t *w8, int64_t ncols_pad, double2 *tc, double *msum,
-                   const unsigned long long *d_missing, int swap_odd = 0, int n_w = 2);
-struct Transpose8Opts {
-    int n_d = 0;
-    uint32_t *w8 = nullptr;
-    const unsigned long long *d_block_flag = nullptr;   // the block's missing-call flag (the kernel's d_wide16)
-    WordLayout layout = WordLayout::Entry8Or16;
-    const int32_t *slot_src = nullptr;
-    bool nibble_nomiss = false;
-};
-int launch_transpose8(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t n_snp, int64_t col0, int64_t ncols_pad,
-                      const Transpose8Opts &o);
 int launch_syrk(hipStream_t st, const TileGrid &tg, const uint32_t *w8, int64_t ncols_pad, const float2 *lut,
                 int n_q, double *acc, int64_t ld, int64_t tiles_c, const unsigned long long *d_skip_if_zero = nullptr);
 

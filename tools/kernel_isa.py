@@ -9,8 +9,14 @@ A translation unit is compiled device-only to assembly with the Makefile's flags
 (demangled name, made file-safe) holds its `.amdhsa_*` block (registers, LDS, scratch) and its instruction stream with everything
 removed that changes when a kernel only moves to another file: comments, `.file` / `.ident` / section / debug lines, and the function
 index k of the local labels `.LBB<k>_<n>`.  `--table` prints VGPR / AGPR / LDS / scratch per kernel as markdown rows.
+
+    python tools/kernel_isa.py --compare OUT_OLD OUT_NEW     # the class of every kernel, from two such directories
+
+identical: the files are equal.  reordered: the `.amdhsa_*` block is equal (registers, LDS, scratch) and the instruction stream has
+the same number of every mnemonic -- only order, register numbers and label numbers differ.  differs: anything else.
 The tool compares; it does not look for any instruction."""
 import argparse
+import collections
 import concurrent.futures
 import glob
 import os
@@ -107,8 +113,36 @@ def compile_unit(args):
         return src, kernels_of(open(out).read())
 
 
+def split_kernel_file(path):
+    """(amdhsa lines, mnemonic histogram) of one kernel file written by main()"""
+    lines = open(path).read().split("\n")[1:]
+    end = lines.index(".end_amdhsa_kernel") + 1 if ".end_amdhsa_kernel" in lines else 0
+    code = [ln.split() for ln in lines[end:] if ln.startswith("\t") and not ln.lstrip().startswith(".")]
+    return lines[:end], collections.Counter(t[0] for t in code if t)
+
+
+def compare(old, new):
+    """print `class<TAB>kernel` for every kernel file of the two directories; returns the number of kernels that differ"""
+    names = lambda d: {f for f in os.listdir(d) if f.endswith(".txt")}
+    a, b = names(old), names(new)
+    count = collections.Counter()
+    for f in sorted(a | b):
+        if f not in a or f not in b:
+            cls = "only in " + (old if f in a else new)
+        elif open(os.path.join(old, f)).read() == open(os.path.join(new, f)).read():
+            cls = "identical"
+        else:
+            cls = "reordered" if split_kernel_file(os.path.join(old, f)) == split_kernel_file(os.path.join(new, f)) else "differs"
+        count[cls] += 1
+        print("%s\t%s" % (cls, f[:-4]))
+    print(", ".join("%d %s" % (n, c) for c, n in sorted(count.items())), file=sys.stderr)
+    return sum(n for c, n in count.items() if c not in ("identical", "reordered"))
+
+
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    if len(sys.argv) == 4 and sys.argv[1] == "--compare":
+        sys.exit(1 if compare(sys.argv[2], sys.argv[3]) else 0)
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0], epilog="or: --compare OLD_DIR NEW_DIR")
     ap.add_argument("--all", action="store_true", help="every *.hip of the source directory")
     ap.add_argument("--csrc", default=os.path.join(ROOT, "snprelate_amd", "csrc"), help="source directory (default: this tree's)")
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))

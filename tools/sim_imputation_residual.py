@@ -43,7 +43,7 @@ def f16(x):
     return np.float16(x).astype(np.float64)
 
 
-# the weight as a product of two fp16 numbers, six targets t / f_q (kernels_prep.hip: uv_factor_kernel)
+# the weight as a product of two fp16 numbers, six targets t / f_q (kernels_tables.hip: uv_factor_kernel)
 best_err = np.full(L, 1e9)
 U = np.zeros(L)
 V = np.zeros(L)
