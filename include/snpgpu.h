@@ -591,6 +591,26 @@ int snpgpu_ibd_mle_stats(double *stats);
 int snpgpu_gnrIBD_MLE(const double *allele_freq, int kinship_constraint, int max_niter, double reltol, int coeff_correct,
                       int method, int out_num_iter, int num_thread, int verbose, double *k0, double *k1, double *afreq,
                       int32_t *niter);
+/* The same estimates for a LIST of pairs (snpgdsIBDMLEPairs, snpgdsPairIBD): no n x n object is built, only the distinct listed
+ * samples are transposed, and one wave per pair runs the IBS counts, Est_PLINK_Kinship (kinship_constraint is its last argument),
+ * the 0.005 clamp, EMAlg and LOGLIK_ADJUST.  idx1 / idx2: host [n_pairs], 0-based samples in any order, repeats and idx1 == idx2
+ * allowed; an index outside 0 ... n_samp - 1 or n_pairs < 1 is an error.  Frequencies come from all n_samp rows, or from
+ * allele_freq.  mode 0: EM; mode 1: the start values only (the method of moments, before the clamp), loglik NaN, niter 0.
+ * Outputs in out_mem, [n_pairs]: k0, k1, loglik (the log-likelihood of the returned coefficients, after LOGLIK_ADJUST; may be NULL),
+ * int32 niter (may be NULL); afreq_out as in snpgpu_ibd_mle.  A pair's result depends on its two samples only: listed twice, or in
+ * a second call, it has the same bits. */
+int snpgpu_ibd_mle_pairs(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, const double *allele_freq,
+                         const int32_t *idx1, const int32_t *idx2, int64_t n_pairs, int mode, int kinship_constraint, int max_niter,
+                         double reltol, int coeff_correct, double *k0, double *k1, double *loglik, int32_t *niter,
+                         double *afreq_out, int out_mem, int device);
+/* of the last snpgpu_ibd_mle_pairs on this thread: stats[0] EM kernel ms, [1] ms of all its kernels, [2] wave-sweeps (EM and
+ * candidate sweeps of one pair by one wave), [3] pairs */
+int snpgpu_ibd_mle_pairs_stats(double *stats);
+/* snpgpu_ibd_mle_pairs (mode 0, no constraint) on the working space's selected SNPs and samples; idx1 / idx2 index the selected
+ * samples.  Host outputs [n_pairs]; loglik, niter and afreq may be NULL */
+int snpgpu_gnrIBD_MLE_Pairs(const double *allele_freq, const int32_t *idx1, const int32_t *idx2, int64_t n_pairs, int max_niter,
+                            double reltol, int coeff_correct, int num_thread, int verbose, double *k0, double *k1, double *loglik,
+                            int32_t *niter, double *afreq);
 /* gnrIBD_LogLik(AFreq, k0, k1) / gnrIBD_LogLik_k01(AFreq, k0, k1): out host n x n; afreq may be NULL (estimated) */
 int snpgpu_gnrIBD_LogLik(const double *afreq, const double *k0, const double *k1, double *out);
 int snpgpu_gnrIBD_LogLik_k01(const double *afreq, double k0, double k1, double *out);

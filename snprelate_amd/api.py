@@ -736,6 +736,150 @@ def snpgdsIBDMLELogLik(gdsobj, ibdobj, k0=float("nan"), k1=float("nan"), related
     return out
 
 
+def _check_mle_args(logical, numeric):
+    for name, v in logical:
+        if not isinstance(v, (bool, np.bool_)):
+            raise TypeError("is.logical(%s) is not TRUE" % name)
+    for name, v in numeric:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise TypeError("is.numeric(%s) is not TRUE" % name)
+
+
+def snpgdsIBDMLEPairs(gdsobj, sample1_id, sample2_id, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True,
+                      maf=float("nan"), missing_rate=0.01, kinship=False, kinship_constraint=False, allele_freq=None,
+                      max_niter=1000, reltol=math.sqrt(np.finfo(float).eps), coeff_correct=True, out_num_iter=True, num_thread=1,
+                      verbose=True, device=0):
+    """IBD coefficients by maximum likelihood (EM) of the listed pairs (sample1_id[t], sample2_id[t]) only.  No reference
+    counterpart: each pair's k0 / k1 / niter is what snpgdsIBDMLE puts at that matrix entry, but no n x n matrix is built and one
+    wave works on each pair (snpgpu_gnrIBD_MLE_Pairs), so a few hundred pairs out of 100 000 samples -- the table of
+    snpgdsIBDPairs -- are refined directly.  sample_id is the population: it defines the allele frequencies and the SNP filters as
+    in snpgdsIBDMLE, and both ID lists must lie in it.  Returns dict(sample_id, snp_id, afreq, ID1, ID2, k0, k1, loglik, niter
+    [, kinship]); loglik is the log-likelihood of the returned coefficients (after coeff_correct); niter is None when
+    out_num_iter is False.  kinship_constraint is accepted and has no effect, as in snpgdsIBDMLE."""
+    _check_mle_args((("kinship", kinship), ("kinship.constraint", kinship_constraint), ("coeff.correct", coeff_correct),
+                     ("out.num.iter", out_num_iter)), (("max.niter", max_niter), ("reltol", reltol)))
+    id1, id2 = np.asarray(sample1_id).ravel(), np.asarray(sample2_id).ravel()
+    if id1.shape != id2.shape:
+        raise ValueError("snpgdsIBDMLEPairs: 'sample1.id' and 'sample2.id' should have the same length (%d and %d)"
+                         % (id1.size, id2.size))
+    if id1.size < 1:
+        raise ValueError("snpgdsIBDMLEPairs: no pair is listed")
+    ws = _init_file2("Identity-By-Descent analysis (MLE) on genotypes, listed pairs only:", gdsobj, sample_id, snp_id,
+                     autosome_only, remove_monosnp, maf, missing_rate, num_thread, verbose, device, allele_freq=allele_freq)
+    n, L = ws["n_samp"], ws["n_snp"]
+    if n < 2:
+        raise ValueError("snpgdsIBDMLEPairs: at least two samples are needed")
+    if L < 1:
+        raise ValueError("snpgdsIBDMLEPairs: no SNP in the working dataset")
+    ids = np.asarray(ws["sample_id"])
+    order = np.argsort(ids, kind="stable")
+    idx = []
+    for name, v in (("sample1.id", id1), ("sample2.id", id2)):
+        pos = np.clip(np.searchsorted(ids[order], v), 0, n - 1)
+        hit = ids[order][pos] == v
+        if not hit.all():
+            raise ValueError("snpgdsIBDMLEPairs: '%s' has a sample that is not in the working samples: %r"
+                             % (name, v[np.argmin(hit)].item()))
+        idx.append(np.ascontiguousarray(order[pos], np.int32))
+    af_in = ws["allele_freq"]
+    P = id1.size
+    k0, k1, ll = np.empty(P, np.float64), np.empty(P, np.float64), np.empty(P, np.float64)
+    niter = np.empty(P, np.int32) if out_num_iter else None
+    af = np.empty(L, np.float64)
+    _lib.check(_lib.lib().snpgpu_gnrIBD_MLE_Pairs(_lib._ptr(af_in), _lib._ptr(idx[0]), _lib._ptr(idx[1]), P, int(max_niter),
+                                                  float(reltol), int(bool(coeff_correct)), ws["num_thread"], int(bool(verbose)),
+                                                  _lib._ptr(k0), _lib._ptr(k1), _lib._ptr(ll), _lib._ptr(niter), _lib._ptr(af)))
+    af[af < 0] = np.nan
+    ans = dict(sample_id=ws["sample_id"], snp_id=ws["snp_id"], afreq=af, ID1=id1, ID2=id2, k0=k0, k1=k1, loglik=ll, niter=niter)
+    if kinship:
+        ans["kinship"] = 0.5 * (1 - k0 - k1) + 0.25 * k1
+    return ans
+
+
+PAIRIBD_METHODS = ("EM", "downhill.simplex", "MoM", "Jacquard")
+
+
+def _pair_vectors(geno1, geno2, allele_freq, verbose):
+    """the argument checks of snpgdsPairIBD / snpgdsPairIBDMLELogLik (R/IBD.R:216-241) and the SNPs they keep: integer codes with
+    3 = missing and the frequencies, for the loci with a finite frequency in [0, 1]"""
+    vec = []
+    for name, v in (("geno1", geno1), ("geno2", geno2), ("allele.freq", allele_freq)):
+        a = np.asarray(v)
+        if a.ndim != 1 or a.dtype.kind not in "iuf":
+            raise TypeError("is.vector(%s) & is.numeric(%s) is not TRUE" % (name, name))
+        vec.append(a)
+    g1, g2, af = vec
+    if len(g1) != len(g2):
+        raise ValueError("length(geno1) == length(geno2) is not TRUE")
+    if len(g1) != len(af):
+        raise ValueError("length(geno1) == length(allele.freq) is not TRUE")
+    af = np.array(af, np.float64)
+    af[~np.isfinite(af)] = -1
+    flag = (0 <= af) & (af <= 1)
+    if flag.sum() < len(g1):
+        _cat(verbose, "IBD MLE for %d SNPs in total, after removing loci with invalid allele frequencies." % flag.sum())
+
+    def codes(g):
+        g = np.asarray(g, np.float64)[flag]
+        ok = np.isfinite(g)
+        t = np.trunc(np.where(ok, g, 3))                       # as.integer
+        return np.where(ok & (t >= 0) & (t <= 2), t, 3).astype(np.uint8)
+    return codes(g1), codes(g2), np.ascontiguousarray(af[flag])
+
+
+def snpgdsPairIBD(geno1, geno2, allele_freq, method="EM", kinship_constraint=False, max_niter=1000,
+                  reltol=math.sqrt(np.finfo(float).eps), coeff_correct=True, out_num_iter=True, verbose=True, device=0):
+    """IBD coefficients of one pair of genotype vectors (R/IBD.R:210-259 -> gnrPairIBD, src/genIBD.cpp:1646-1719): "EM" and "MoM"
+    on the GPU (snpgpu_ibd_mle_pairs with two samples and the caller's frequencies).  Codes outside 0..2 are missing; SNPs whose
+    frequency is not a finite value in [0, 1] are dropped.  kinship_constraint acts on the start values, as in the reference.
+    Returns dict(k0, k1, loglik[, niter])."""
+    c1, c2, af = _pair_vectors(geno1, geno2, allele_freq, verbose)
+    _check_mle_args((("kinship.constraint", kinship_constraint), ("coeff.correct", coeff_correct)), ())
+    if method not in PAIRIBD_METHODS:
+        raise ValueError("'arg' should be one of %s" % ", ".join('"%s"' % m for m in PAIRIBD_METHODS))
+    if method in ("downhill.simplex", "Jacquard"):
+        raise NotImplementedError('snpgdsPairIBD: method "%s" is not built on the GPU path (only "EM" and "MoM")' % method)
+    from .gds import pack_2bit_rows
+    rows = pack_2bit_rows(np.stack([c1, c2], 1))
+    k0, k1, ll, nit, _ = _lib.ibd_mle_pairs(rows, 2, [0], [1], af, 0 if method == "EM" else 1, kinship_constraint, max_niter,
+                                            reltol, coeff_correct, device)
+    ans = dict(k0=float(k0[0]), k1=float(k1[0]), loglik=float(ll[0]))
+    if out_num_iter:
+        ans["niter"] = int(nit[0])
+    return ans
+
+
+def snpgdsPairIBDMLELogLik(geno1, geno2, allele_freq, k0=float("nan"), k1=float("nan"), relatedness="", verbose=True):
+    """Log-likelihood of one pair at (k0, k1) or a relatedness preset (R/IBD.R:267-321 -> gnrPairIBDLogLik,
+    src/genIBD.cpp:1771-1808), on the host in fp64 and in SNP order.  Non-positive sums are skipped (never -Inf)."""
+    c1, c2, af = _pair_vectors(geno1, geno2, allele_freq, verbose)
+    for name, v in (("k0", k0), ("k1", k1)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise TypeError("is.numeric(%s) is not TRUE" % name)
+    if not isinstance(relatedness, str):
+        raise TypeError("is.character(relatedness) is not TRUE")
+    if RELATEDNESS.get(relatedness) is not None:
+        k0, k1 = RELATEDNESS[relatedness]
+    k0, k1 = float(k0), float(k1)
+    k2 = 1 - k0 - k1
+    # PrIBDTable (:454-510) with its own products
+    p, q = af, 1 - af
+    a, b = np.minimum(c1, c2).astype(np.int64), np.maximum(c1, c2).astype(np.int64)
+    t0, t1, t2 = np.zeros(len(af)), np.zeros(len(af)), np.zeros(len(af))
+    ok = (0 < p) & (p < 1)
+    for ga, gb, v0, v1, v2 in ((0, 0, q * q * q * q, q * q * q, q * q), (0, 1, 2 * (p * q * q) * q, p * q * q, 0 * p),
+                               (0, 2, p * p * q * q, 0 * p, 0 * p), (1, 1, 4 * (p * q) * (p * q), p * q, 2 * (p * q)),
+                               (1, 2, 2 * p * (p * p * q), p * p * q, 0 * p), (2, 2, p * p * p * p, p * p * p, p * p)):
+        m = ok & (a == ga) & (b == gb)
+        t0[m], t1[m], t2[m] = v0[m], v1[m], v2[m]
+    with np.errstate(invalid="ignore"):
+        s = t0 * k0 + t1 * k1 + t2 * k2
+    ll = 0.0
+    for v in s[s > 0]:
+        ll += math.log(v)
+    return ll
+
+
 _IBD_NOT_PER_PAIR = ("sample_id", "snp_id", "afreq")
 
 

@@ -77,11 +77,12 @@ __device__ __forceinline__ void king_homo_value(const KingHomoArgs &h, int64_t r
 struct MomArgs {
     const uint32_t *acc; int64_t plane; double e00, e01, e02, e11, e12; int constraint;
 };
-__device__ __forceinline__ void mom_value(const MomArgs &m, int64_t rel, double &a, double &b)
+// the same from the three counts of a pair (the listed-pairs EM of kernels_ibd.hip counts them itself)
+__device__ __forceinline__ void mom_from_counts(double e00, double e01, double e02, double e11, double e12, int constraint, int n012,
+                                                int IBS1, int IBS0, double &a, double &b)
 {
-    const int n012 = (int)m.acc[rel], IBS1 = (int)m.acc[m.plane + rel], IBS0 = (int)(m.acc[2 * m.plane + rel] >> 1);
     const int IBS2 = n012 - IBS0 - IBS1;
-    const double f00 = m.e00 * n012, f01 = m.e01 * n012, f11 = m.e11 * n012, f02 = m.e02 * n012, f12 = m.e12 * n012,
+    const double f00 = e00 * n012, f01 = e01 * n012, f11 = e11 * n012, f02 = e02 * n012, f12 = e12 * n012,
                  f22 = 1.0 * n012;
     double v0 = IBS0 / f00;
     double v1 = (IBS1 - v0 * f01) / f11;
@@ -92,12 +93,17 @@ __device__ __forceinline__ void mom_value(const MomArgs &m, int64_t rel, double 
     if (v0 < 0) { const double S = v1 + v2; v1 /= S; v2 /= S; v0 = 0; }
     if (v1 < 0) { const double S = v0 + v2; v0 /= S; v2 /= S; v1 = 0; }
     if (v2 < 0) { const double S = v0 + v1; v0 /= S; v1 /= S; v2 = 0; }
-    if (m.constraint) {
+    if (constraint) {
         v2 = 1 - v0 - v1;
         const double pihat = v1 / 2 + v2;
         if (pihat * pihat < v2) { v0 = (1 - pihat) * (1 - pihat); v1 = 2 * pihat * (1 - pihat); }
     }
     a = v0; b = v1;
+}
+__device__ __forceinline__ void mom_value(const MomArgs &m, int64_t rel, double &a, double &b)
+{
+    const int n012 = (int)m.acc[rel], IBS1 = (int)m.acc[m.plane + rel], IBS0 = (int)(m.acc[2 * m.plane + rel] >> 1);
+    mom_from_counts(m.e00, m.e01, m.e02, m.e11, m.e12, m.constraint, n012, IBS1, IBS0, a, b);
 }
 
 // kinship of a pair from its k0 / k1 (snpgdsIBDSelection, R/IBD.R:487).  0.5 and 0.25 are powers of two: both products are exact, the

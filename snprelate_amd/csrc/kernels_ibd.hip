@@ -16,7 +16,10 @@
 // log-likelihood sum of log(c s) is kept as a running product renormalised by exponent every 4 (EM) or 8 (log-likelihood
 // sweep) SNPs and turned into a log once
 // per sweep.  SNPs that are not usable are written as missing codes when the words are built, so they contribute nothing.
+//
+// Listed pairs (snpgdsIBDMLEPairs): the second half of this file maps one pair to a WAVE, see "one wave per pair" below.
 #include "snpgpu_internal.h"
+#include "fin_values.h"
 
 #include <cmath>
 
@@ -314,6 +317,231 @@ __global__ void ibd_expand_kernel(const int64_t *__restrict__ rowoff, int64_t n_
     if (on) on[i * n_samp + j] = on[j * n_samp + i] = nit[idx];
 }
 
+// ---- one wave per pair (snpgpu_ibd_mle_pairs) ------------------------------------------------------------------------------------
+// A short list of pairs leaves most lanes of the lane-per-pair kernel idle and every wave waiting for its slowest pair.  Here a
+// wave owns one pair at a time and its 64 lanes split the SNPs: lane l sweeps the 16-SNP words w = 64 b + l of both samples
+// (one coalesced 256-byte load per sample and step b).  Nothing is wave-uniform per SNP, so the constants are vector loads: p
+// alone (8 bytes per SNP; q, pq and 4pq are three register operations, against 32 bytes of IbdSnp), stored transposed so that
+// the 64 lanes' values of SNP m of their words are one 512-byte line: pt[(16 b + m) * 64 + l] = p of SNP 16 (64 b + l) + m.
+// The words hold the samples' codes as they are; SNPs without 0 < p < 1 are masked by OR-ing um[w] (11 at their positions),
+// while the start values' IBS counts use the unmasked words, as the IBS context of the matrix path counts every SNP.
+// After each sweep S0, S1, the log-likelihood and the usable-SNP count are summed over the lanes by an xor butterfly
+// (32, 16, .. 1): every lane ends with the same bits, so the stop decision is wave-uniform, and a pair's result depends on
+// nothing but its own words.  When its pair stops, lane 0 takes the next one from the queue.
+struct IbdE { double e00, e01, e02, e11, e12; };
+
+__device__ inline double wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ inline int wave_sum(int v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__device__ inline IbdSnp snp_of_p(double p)
+{
+    IbdSnp t;
+    const double q = 1 - p;
+    t.q = q; t.p = p; t.pq = p * q; t.pq4 = 4 * p * q;
+    return t;
+}
+
+// this lane's share of one EM sweep; nb steps of 64 words
+__device__ inline void em_sweep_lane(const uint32_t *__restrict__ ga, const uint32_t *__restrict__ gb,
+                                     const uint32_t *__restrict__ um, const double *__restrict__ pt, int64_t nb, int lane,
+                                     double k0, double k1, double k2, double &S0, double &S1, int &nS, double &L)
+{
+    double prod = 1;
+    int ex = 0;
+    S0 = 0; S1 = 0; nS = 0;
+    for (int64_t b = 0; b < nb; b++) {
+        const int64_t w = b * 64 + lane;
+        const uint32_t wa = ga[w] | um[w], wb = gb[w];
+        const double *pp = pt + b * 1024 + lane;
+#pragma unroll 1
+        for (int h = 0; h < 16; h += 4) {
+#pragma unroll
+            for (int m = 0; m < 4; m++) {
+                const unsigned a = (wa >> (2 * (h + m))) & 3u, bb = (wb >> (2 * (h + m))) & 3u;
+                const bool use = (a != 3u) & (bb != 3u);
+                double c, a0, a1, a2;
+                ibd_terms(a, bb, snp_of_p(pp[(h + m) * 64]), c, a0, a1, a2);
+                const double m0 = a0 * k0, m1 = a1 * k1;
+                double s = m0 + m1 + a2 * k2;
+                s = use ? s : 1.0;
+                const double r = recip(s);
+                S0 = use ? fma(m0, r, S0) : S0;
+                S1 = use ? fma(m1, r, S1) : S1;
+                prod *= use ? c * s : 1.0;
+                nS += use ? 1 : 0;
+            }
+            renorm(prod, ex);
+        }
+    }
+    L = log(prod) + ex * LN2;
+}
+
+// queue: [0] next pair, [1] wave-sweeps (EM and candidate sweeps; the integer pre-sweep is not counted)
+__global__ __launch_bounds__(256) void ibd_em_pairs_kernel(const uint32_t *__restrict__ gt, int64_t wpad,
+                                                           const uint32_t *__restrict__ um, const double *__restrict__ pt,
+                                                           const int32_t *__restrict__ slot1, const int32_t *__restrict__ slot2,
+                                                           int64_t n_pairs, IbdE e, int constraint, int mode, int max_niter,
+                                                           double reltol, int coeff_correct, unsigned long long *__restrict__ queue,
+                                                           double *__restrict__ ok0, double *__restrict__ ok1,
+                                                           double *__restrict__ oll, int32_t *__restrict__ onit)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t nb = wpad / 64;
+    unsigned long long sweeps = 0;
+    while (true) {
+        unsigned long long next = 0;
+        if (lane == 0) next = atomicAdd(queue, 1ull);
+        const int64_t pair = (int64_t)__shfl(next, 0);
+        if (pair >= n_pairs) break;
+        const uint32_t *ga = gt + (int64_t)slot1[pair] * wpad, *gb = gt + (int64_t)slot2[pair] * wpad;
+
+        // start values: the pair's IBS counts from the unmasked codes (exact), then Est_PLINK_Kinship
+        int cn = 0, c1 = 0, c0 = 0;
+        for (int64_t b = 0; b < nb; b++) {
+            const uint32_t wa = ga[b * 64 + lane], wb = gb[b * 64 + lane];
+            const uint32_t both = ~(wa & (wa >> 1)) & ~(wb & (wb >> 1)) & 0x55555555u;
+            const uint32_t x = wa ^ wb, lo = x & both, hi = (x >> 1) & both;     // |a - b| = 1: x = 01 or 11; 2: x = 10
+            cn += __popc(both); c1 += __popc(lo); c0 += __popc(hi & ~lo);
+        }
+        cn = wave_sum(cn); c1 = wave_sum(c1); c0 = wave_sum(c0);
+        double a, b;
+        mom_from_counts(e.e00, e.e01, e.e02, e.e11, e.e12, constraint, cn, c1, c0, a, b);
+        if (mode == 1) {
+            if (lane == 0) {
+                ok0[pair] = a; ok1[pair] = b;
+                if (oll) oll[pair] = (double)NAN;
+                if (onit) onit[pair] = 0;
+            }
+            continue;
+        }
+        // each of k0, k1, k2 >= 0.005 and renormalised (:824-832)
+        double c = 1 - a - b;
+        if (a < 0.005) a = 0.005;
+        if (b < 0.005) b = 0.005;
+        if (c < 0.005) c = 0.005;
+        const double s = a + b + c;
+        double k0 = a / s, k1 = b / s, k2 = 1 - k0 - k1, old = 0, tol = 0;
+        double fk0, fk1, fL;
+        int it = 0, fit;
+        while (true) {                                        // the decisions of ibd_em_kernel, wave-uniform here
+            double S0, S1, L;
+            int nS;
+            em_sweep_lane(ga, gb, um, pt, nb, lane, k0, k1, k2, S0, S1, nS, L);
+            S0 = wave_sum(S0); S1 = wave_sum(S1); L = wave_sum(L); nS = wave_sum(nS);
+            sweeps++;
+            bool done = false;
+            fk0 = k0; fk1 = k1; fL = L; fit = it;
+            if (it == 0) {
+                tol = isfinite(L) ? reltol * (fabs(L) + fabs(reltol)) : reltol;
+                if (tol < 0) tol = 0;
+                if (max_niter < 0) { done = true; fit = max_niter; fL = isfinite(L) ? L : 1e8; }
+            }
+            if (!done) {
+                const double n0 = S0 / nS, n1 = S1 / nS;
+                if (fabs(L - old) <= tol) {
+                    done = true;
+                } else {
+                    old = L;
+                    k0 = n0; k1 = n1; k2 = 1 - n0 - n1;
+                    if (it >= max_niter) { done = true; fk0 = k0; fk1 = k1; fit = max_niter; }
+                    else it++;
+                }
+            }
+            if (done) break;
+        }
+        if (coeff_correct) {
+            // LOGLIK_ADJUST: the six candidates in one more sweep, in the reference's order against the final log-likelihood
+            const double c0k[6] = {0, 0.25, 0, 0.5, 0.75, 1}, c1k[6] = {0, 0.5, 1, 0.5, 0.25, 0};
+            double prod[6];
+            int ex[6];
+            bool bad[6];
+#pragma unroll
+            for (int q = 0; q < 6; q++) { prod[q] = 1; ex[q] = 0; bad[q] = false; }
+            for (int64_t bk = 0; bk < nb; bk++) {
+                const int64_t w = bk * 64 + lane;
+                const uint32_t wa = ga[w] | um[w], wb = gb[w];
+                const double *pp = pt + bk * 1024 + lane;
+#pragma unroll 1
+                for (int h = 0; h < 16; h += 8) {
+#pragma unroll
+                    for (int m = 0; m < 8; m++) {
+                        const unsigned ca = (wa >> (2 * (h + m))) & 3u, cb = (wb >> (2 * (h + m))) & 3u;
+                        const bool use = (ca != 3u) & (cb != 3u);
+                        double cf, a0, a1, a2;
+                        ibd_terms(ca, cb, snp_of_p(pp[(h + m) * 64]), cf, a0, a1, a2);
+#pragma unroll
+                        for (int q = 0; q < 6; q++) {
+                            const double sq = a0 * c0k[q] + a1 * c1k[q] + a2 * (1 - c0k[q] - c1k[q]);
+                            bad[q] = bad[q] | (use & !(sq > 0));
+                            prod[q] *= (use & (sq > 0)) ? cf * sq : 1.0;
+                        }
+                    }
+#pragma unroll
+                    for (int q = 0; q < 6; q++) renorm(prod[q], ex[q]);
+                }
+            }
+            sweeps++;
+#pragma unroll
+            for (int q = 0; q < 6; q++) {
+                const double Lq = wave_sum(log(prod[q]) + ex[q] * LN2);
+                const bool any_bad = __ballot(bad[q]) != 0ull;
+                if (!any_bad && isfinite(Lq) && fL < Lq) { fL = Lq; fk0 = c0k[q]; fk1 = c1k[q]; }
+            }
+        }
+        if (lane == 0) {
+            ok0[pair] = fk0; ok1[pair] = fk1;
+            if (oll) oll[pair] = fL;
+            if (onit) onit[pair] = fit;
+        }
+    }
+    if (lane == 0) atomicAdd(queue + 1, sweeps);
+}
+
+// words of the listed samples only: word w of slot t holds the codes of sample list[t] as they are (3 past n_snp)
+__global__ void ibd_words_listed_kernel(const uint8_t *__restrict__ rows, int64_t rb, int64_t n_snp,
+                                        const int32_t *__restrict__ list, int64_t n_list, int64_t wpad, uint32_t *__restrict__ gt)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x, w = blockIdx.y;
+    if (t >= n_list) return;
+    const int64_t s = list[t];
+    uint32_t v = 0;
+    for (int m = 0; m < 16; m++) {
+        const int64_t l = 16 * w + m;
+        unsigned code = 3u;
+        if (l < n_snp) code = (rows[l * rb + (s >> 2)] >> (2 * (s & 3))) & 3u;
+        v |= code << (2 * m);
+    }
+    gt[t * wpad + w] = v;
+}
+
+// per word: the transposed p of its 16 SNPs (0.5 where the SNP is not usable or past n_snp) and the mask of those SNPs
+__global__ void ibd_pairs_table_kernel(const double *__restrict__ af, int64_t n_snp, int64_t wpad, double *__restrict__ pt,
+                                       uint32_t *__restrict__ um)
+{
+    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= wpad) return;
+    const int64_t b = w >> 6, lane = w & 63;
+    uint32_t mask = 0;
+    for (int m = 0; m < 16; m++) {
+        const int64_t l = 16 * w + m;
+        const double p = l < n_snp ? af[l] : -1.0;
+        const bool ok = (0 < p) && (p < 1);
+        pt[(b * 16 + m) * 64 + lane] = ok ? p : 0.5;
+        if (!ok) mask |= 3u << (2 * m);
+    }
+    um[w] = mask;
+}
+
 inline unsigned grid_of(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -372,6 +600,33 @@ int launch_ibd_loglik(hipStream_t st, const uint32_t *gt, int64_t w4, const void
     hipLaunchKernelGGL(ibd_loglik_kernel<1>, dim3(grid_of(n_pairs)), dim3(256), 0, st, gt, w4 * 4, (const IbdSnp *)tab, rowoff,
                        n_rows, (int64_t)0, n_samp, n_pairs, 1, km0, km1, ks0, ks1, out, (double *)nullptr, (double *)nullptr,
                        (const double *)nullptr);
+    SNPGPU_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// wpad: words per sample, a multiple of 64; pt: wpad * 16 doubles; um: wpad words; gt: n_list * wpad words
+int launch_ibd_pairs_prepare(hipStream_t st, const uint8_t *rows, int64_t rb, int64_t n_snp, const double *af, const int32_t *list,
+                             int64_t n_list, int64_t wpad, double *pt, uint32_t *um, uint32_t *gt)
+{
+    hipLaunchKernelGGL(ibd_pairs_table_kernel, dim3(grid_of(wpad)), dim3(256), 0, st, af, n_snp, wpad, pt, um);
+    SNPGPU_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(ibd_words_listed_kernel, dim3(grid_of(n_list), (unsigned)wpad), dim3(256), 0, st, rows, rb, n_snp, list,
+                       n_list, wpad, gt);
+    SNPGPU_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// n_waves <= n_pairs; whole blocks of 4 waves (fewer than 4 waves: one smaller block), so never more waves than asked for
+int launch_ibd_em_pairs(hipStream_t st, int n_waves, const uint32_t *gt, int64_t wpad, const uint32_t *um, const double *pt,
+                        const int32_t *slot1, const int32_t *slot2, int64_t n_pairs, const double *e, int constraint, int mode,
+                        int max_niter, double reltol, int coeff_correct, unsigned long long *queue, double *k0, double *k1,
+                        double *loglik, int32_t *niter)
+{
+    if (n_pairs <= 0 || n_waves <= 0) return 0;
+    const int per = std::min(n_waves, 4);
+    const IbdE ee = {e[0], e[1], e[2], e[3], e[4]};
+    hipLaunchKernelGGL(ibd_em_pairs_kernel, dim3((unsigned)(n_waves / per)), dim3(64 * per), 0, st, gt, wpad, um, pt, slot1, slot2,
+                       n_pairs, ee, constraint, mode, max_niter, reltol, coeff_correct, queue, k0, k1, loglik, niter);
     SNPGPU_HIP_CHECK(hipGetLastError());
     return 0;
 }

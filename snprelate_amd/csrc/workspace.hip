@@ -1227,6 +1227,19 @@ int snpgpu_gnrIBD_MLE(const double *allele_freq, int, int max_niter, double relt
                           g_ws.device);
 }
 
+// the listed pairs of the selected samples (snpgdsIBDMLEPairs): EM, Est_PLINK_Kinship without the constraint as gnrIBD_MLE
+int snpgpu_gnrIBD_MLE_Pairs(const double *allele_freq, const int32_t *idx1, const int32_t *idx2, int64_t n_pairs, int max_niter,
+                            double reltol, int coeff_correct, int num_thread, int, double *k0, double *k1, double *loglik,
+                            int32_t *niter, double *afreq)
+{
+    if (num_thread <= 0) { set_error("Invalid 'num.thread'."); return 1; }
+    std::vector<uint8_t> buf;
+    if (ws_rows("snpgpu_gnrIBD_MLE_Pairs", buf)) return 1;
+    return snpgpu_ibd_mle_pairs(buf.data(), (int64_t)g_ws.sel.size(), g_ws.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, allele_freq,
+                                idx1, idx2, n_pairs, 0, 0, max_niter, reltol, coeff_correct, k0, k1, loglik, niter, afreq,
+                                SNPGPU_HOST, g_ws.device);
+}
+
 // gnrIBD_LogLik(AFreq, k0, k1) and gnrIBD_LogLik_k01(AFreq, k0, k1), src/genIBD.cpp:1289-1330 and their .Call wrappers
 int snpgpu_gnrIBD_LogLik(const double *afreq, const double *k0, const double *k1, double *out)
 {
