@@ -595,7 +595,10 @@ int snpgpu_gnrIBD_MLE(const double *allele_freq, int kinship_constraint, int max
  * samples are transposed, and one wave per pair runs the IBS counts, Est_PLINK_Kinship (kinship_constraint is its last argument),
  * the 0.005 clamp, EMAlg and LOGLIK_ADJUST.  idx1 / idx2: host [n_pairs], 0-based samples in any order, repeats and idx1 == idx2
  * allowed; an index outside 0 ... n_samp - 1 or n_pairs < 1 is an error.  Frequencies come from all n_samp rows, or from
- * allele_freq.  mode 0: EM; mode 1: the start values only (the method of moments, before the clamp), loglik NaN, niter 0.
+ * allele_freq.  mode 0: EM; mode 1: the start values only (the method of moments, before the clamp), loglik NaN, niter 0;
+ * mode 2: the downhill simplex (Simplex / SimplexMin<double, 2> / NM_LogLik, src/genIBD.cpp:60-189, :661-779) from the same
+ * clamped start values, niter = the routine's count of function evaluations (nfunk, 2 when it stops at once), coefficients NaN
+ * and loglik 0 for a pair without a shared call; any other mode is an error that names it.
  * Outputs in out_mem, [n_pairs]: k0, k1, loglik (the log-likelihood of the returned coefficients, after LOGLIK_ADJUST; may be NULL),
  * int32 niter (may be NULL); afreq_out as in snpgpu_ibd_mle.  A pair's result depends on its two samples only: listed twice, or in
  * a second call, it has the same bits. */
@@ -603,14 +606,31 @@ int snpgpu_ibd_mle_pairs(const void *geno, int64_t n_snp, int64_t n_samp, int fo
                          const int32_t *idx1, const int32_t *idx2, int64_t n_pairs, int mode, int kinship_constraint, int max_niter,
                          double reltol, int coeff_correct, double *k0, double *k1, double *loglik, int32_t *niter,
                          double *afreq_out, int out_mem, int device);
-/* of the last snpgpu_ibd_mle_pairs on this thread: stats[0] EM kernel ms, [1] ms of all its kernels, [2] wave-sweeps (EM and
- * candidate sweeps of one pair by one wave), [3] pairs */
+/* Jacquard's nine condensed coefficients of the listed pairs (snpgdsIBDMLEPairs, method "Jacquard"): PrIBDTabJacq + EM_Jacq_Alg
+ * (src/genIBD.cpp:864-1072) per pair from D1 ... D8 = 0.01, with EMAlg's stop rule (max_niter, reltol).  There are no IBS counts and
+ * no coeff_correct in this method.  The table is not symmetric in the two samples: (idx2, idx1) exchanges D3 with D5 and D4 with D6.
+ * As in the reference, an SNP at which BOTH samples are MM (code 2) enters nothing: its `case 2` / `case 2` entry has no `break`
+ * and falls through to `default`, which zeroes all nine probabilities, and the EM skips such SNPs.  That quirk is reproduced.
+ * d: eight planes [8][n_pairs] (D1 ... D8; D9 = 1 - their sum), required; loglik, niter and afreq_out may be NULL.  Inputs, index
+ * checks and out_mem as snpgpu_ibd_mle_pairs. */
+int snpgpu_ibd_jacquard_pairs(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, const double *allele_freq,
+                              const int32_t *idx1, const int32_t *idx2, int64_t n_pairs, int max_niter, double reltol, double *d,
+                              double *loglik, int32_t *niter, double *afreq_out, int out_mem, int device);
+/* of the last snpgpu_ibd_mle_pairs or snpgpu_ibd_jacquard_pairs on this thread: stats[0] ms of its one-wave-per-pair kernel, [1] ms
+ * of all its kernels, [2] wave-sweeps (sweeps of one pair's SNPs by one wave: EM iterations, candidate sweeps, function-evaluation
+ * sweeps of the simplex), [3] pairs */
 int snpgpu_ibd_mle_pairs_stats(double *stats);
 /* snpgpu_ibd_mle_pairs (mode 0, no constraint) on the working space's selected SNPs and samples; idx1 / idx2 index the selected
  * samples.  Host outputs [n_pairs]; loglik, niter and afreq may be NULL */
 int snpgpu_gnrIBD_MLE_Pairs(const double *allele_freq, const int32_t *idx1, const int32_t *idx2, int64_t n_pairs, int max_niter,
                             double reltol, int coeff_correct, int num_thread, int verbose, double *k0, double *k1, double *loglik,
                             int32_t *niter, double *afreq);
+/* The listed pairs by `method` on the working space: 0 EM (as snpgpu_gnrIBD_MLE_Pairs), 1 downhill simplex (coef: host
+ * [2][n_pairs], k0 then k1), 2 Jacquard (coef: host [8][n_pairs], D1 ... D8; coeff_correct has no effect); any other method is an
+ * error.  loglik, niter and afreq may be NULL */
+int snpgpu_gnrIBD_MLE_PairsMethod(const double *allele_freq, const int32_t *idx1, const int32_t *idx2, int64_t n_pairs, int method,
+                                  int max_niter, double reltol, int coeff_correct, int num_thread, int verbose, double *coef,
+                                  double *loglik, int32_t *niter, double *afreq);
 /* gnrIBD_LogLik(AFreq, k0, k1) / gnrIBD_LogLik_k01(AFreq, k0, k1): out host n x n; afreq may be NULL (estimated) */
 int snpgpu_gnrIBD_LogLik(const double *afreq, const double *k0, const double *k1, double *out);
 int snpgpu_gnrIBD_LogLik_k01(const double *afreq, double k0, double k1, double *out);

@@ -49,6 +49,7 @@ EXPORTS = [
     "snpgpu_ibd_mle", "snpgpu_ibd_loglik", "snpgpu_ibd_mle_stats", "snpgpu_gnrIBD_MLE", "snpgpu_gnrIBD_LogLik",
     "snpgpu_gnrIBD_LogLik_k01", "snpgpu_diag_fp64_rate",
     "snpgpu_ibd_mle_pairs", "snpgpu_ibd_mle_pairs_stats", "snpgpu_gnrIBD_MLE_Pairs",
+    "snpgpu_ibd_jacquard_pairs", "snpgpu_gnrIBD_MLE_PairsMethod",
     "snpgpu_ld_prune", "snpgpu_ld_prune_bits", "snpgpu_gnrLDpruning",
     "snpgpu_diss", "snpgpu_diss_sums", "snpgpu_gnrDiss", "snpgpu_multi_diss",
     "snpgpu_pop_counts", "snpgpu_fst", "snpgpu_fst_windows", "snpgpu_pop_stats", "snpgpu_gnrFst", "snpgpu_gnrSlidingWindowFst",
@@ -258,6 +259,8 @@ def lib():
                                        c_int, c_int]
     L.snpgpu_ibd_mle_pairs_stats.argtypes = [vp]
     L.snpgpu_gnrIBD_MLE_Pairs.argtypes = [vp, vp, vp, i64, c_int, dbl, c_int, c_int, c_int, vp, vp, vp, vp, vp]
+    L.snpgpu_ibd_jacquard_pairs.argtypes = [vp, i64, i64, c_int, c_int, vp, vp, vp, i64, c_int, dbl, vp, vp, vp, vp, c_int, c_int]
+    L.snpgpu_gnrIBD_MLE_PairsMethod.argtypes = [vp, vp, vp, i64, c_int, c_int, dbl, c_int, c_int, c_int, vp, vp, vp, vp]
     L.snpgpu_gnrIBD_LogLik.argtypes = [vp, vp, vp, vp]
     L.snpgpu_gnrIBD_LogLik_k01.argtypes = [vp, dbl, dbl, vp]
     L.snpgpu_diag_fp64_rate.argtypes = [c_int, dbl, ctypes.POINTER(dbl)]
@@ -1083,7 +1086,8 @@ def ibd_mle_pairs(geno, n_samp, idx1, idx2, allele_freq=None, mode=0, kinship_co
                   reltol=float(np.sqrt(np.finfo(float).eps)), coeff_correct=True, device=0, geno_dev_ptr=None, n_snp=None):
     """snpgpu_ibd_mle_pairs on 2-bit rows [n_snp][ceil(n_samp/4)] (numpy, or device memory via geno_dev_ptr + n_snp) for the
     pairs (idx1[t], idx2[t]), 0-based: returns (k0, k1, loglik, niter, afreq), the first four of one entry per pair.
-    mode 0: EM; mode 1: the start values (method of moments), loglik NaN and niter 0."""
+    mode 0: EM; mode 1: the start values (method of moments), loglik NaN and niter 0; mode 2: the downhill simplex, niter =
+    its count of function evaluations."""
     ptr, n_snp, fmt, mem, _keep = _geno_input(geno if geno_dev_ptr is None else int(geno_dev_ptr), n_samp, GENO_PACKED2, n_snp,
                                               device_fmt_default=GENO_PACKED2)
     af_in = None if allele_freq is None else np.ascontiguousarray(allele_freq, np.float64)
@@ -1099,8 +1103,26 @@ def ibd_mle_pairs(geno, n_samp, idx1, idx2, allele_freq=None, mode=0, kinship_co
     return k0, k1, ll, nit, af
 
 
+def ibd_jacquard_pairs(geno, n_samp, idx1, idx2, allele_freq=None, max_niter=1000, reltol=float(np.sqrt(np.finfo(float).eps)),
+                       device=0, geno_dev_ptr=None, n_snp=None):
+    """snpgpu_ibd_jacquard_pairs on 2-bit rows (as ibd_mle_pairs) for the pairs (idx1[t], idx2[t]): returns (D, loglik, niter,
+    afreq) with D [8][n_pairs] = D1 ... D8.  SNPs at which both samples carry code 2 are skipped, as in the reference."""
+    ptr, n_snp, fmt, mem, _keep = _geno_input(geno if geno_dev_ptr is None else int(geno_dev_ptr), n_samp, GENO_PACKED2, n_snp,
+                                              device_fmt_default=GENO_PACKED2)
+    af_in = None if allele_freq is None else np.ascontiguousarray(allele_freq, np.float64)
+    i1, i2 = np.ascontiguousarray(idx1, np.int32), np.ascontiguousarray(idx2, np.int32)
+    if i1.ndim != 1 or i1.shape != i2.shape:
+        raise ValueError("idx1 and idx2 should be vectors of one length")
+    P = i1.shape[0]
+    d, ll, nit = np.empty((8, P), np.float64), np.empty(P, np.float64), np.empty(P, np.int32)
+    af = np.empty(n_snp, np.float64)
+    check(lib().snpgpu_ibd_jacquard_pairs(ptr, n_snp, int(n_samp), fmt, mem, _ptr(af_in), _ptr(i1), _ptr(i2), P, int(max_niter),
+                                          float(reltol), _ptr(d), _ptr(ll), _ptr(nit), _ptr(af), HOST, int(device)))
+    return d, ll, nit, af
+
+
 def ibd_mle_pairs_stats():
-    """(EM kernel ms, all kernels ms, wave-sweeps, pairs) of the last ibd_mle_pairs on this thread"""
+    """(kernel ms, all kernels ms, wave-sweeps, pairs) of the last ibd_mle_pairs / ibd_jacquard_pairs on this thread"""
     s = np.zeros(4, np.float64)
     check(lib().snpgpu_ibd_mle_pairs_stats(_ptr(s)))
     return float(s[0]), float(s[1]), int(s[2]), int(s[3])

@@ -748,16 +748,26 @@ def _check_mle_args(logical, numeric):
 def snpgdsIBDMLEPairs(gdsobj, sample1_id, sample2_id, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True,
                       maf=float("nan"), missing_rate=0.01, kinship=False, kinship_constraint=False, allele_freq=None,
                       max_niter=1000, reltol=math.sqrt(np.finfo(float).eps), coeff_correct=True, out_num_iter=True, num_thread=1,
-                      verbose=True, device=0):
-    """IBD coefficients by maximum likelihood (EM) of the listed pairs (sample1_id[t], sample2_id[t]) only.  No reference
+                      verbose=True, device=0, method="EM"):
+    """IBD coefficients by maximum likelihood of the listed pairs (sample1_id[t], sample2_id[t]) only.  No reference
     counterpart: each pair's k0 / k1 / niter is what snpgdsIBDMLE puts at that matrix entry, but no n x n matrix is built and one
     wave works on each pair (snpgpu_gnrIBD_MLE_Pairs), so a few hundred pairs out of 100 000 samples -- the table of
     snpgdsIBDPairs -- are refined directly.  sample_id is the population: it defines the allele frequencies and the SNP filters as
     in snpgdsIBDMLE, and both ID lists must lie in it.  Returns dict(sample_id, snp_id, afreq, ID1, ID2, k0, k1, loglik, niter
     [, kinship]); loglik is the log-likelihood of the returned coefficients (after coeff_correct); niter is None when
-    out_num_iter is False.  kinship_constraint is accepted and has no effect, as in snpgdsIBDMLE."""
+    out_num_iter is False.  kinship_constraint is accepted and has no effect, as in snpgdsIBDMLE.
+
+    method: "EM" (the default), "downhill.simplex" or "Jacquard", the three of the reference's snpgdsIBDMLE.
+    "downhill.simplex" runs the reference's Nelder-Mead walk from EM's start values and returns the same dictionary; niter is
+    then the walk's count of function evaluations.  "Jacquard" estimates the nine condensed identity coefficients by EM from
+    D1 ... D8 = 0.01: the result has D1 ... D8 (D9 = 1 - their sum), loglik and niter, no k0 / k1, and with kinship=True
+    kinship = D1 + 0.5 (D3 + D5 + D7) + 0.25 D8; coeff_correct has no effect.  Jacquard's likelihood table is not symmetric in the
+    two samples, and, as the reference's table does (its MM / MM entry falls through to the default and is zeroed), it leaves out
+    every SNP at which both samples are homozygous for the A allele."""
     _check_mle_args((("kinship", kinship), ("kinship.constraint", kinship_constraint), ("coeff.correct", coeff_correct),
                      ("out.num.iter", out_num_iter)), (("max.niter", max_niter), ("reltol", reltol)))
+    if method not in IBDMLE_METHODS:
+        raise ValueError("'arg' should be one of %s" % ", ".join('"%s"' % m for m in IBDMLE_METHODS))
     id1, id2 = np.asarray(sample1_id).ravel(), np.asarray(sample2_id).ravel()
     if id1.shape != id2.shape:
         raise ValueError("snpgdsIBDMLEPairs: 'sample1.id' and 'sample2.id' should have the same length (%d and %d)"
@@ -783,14 +793,30 @@ def snpgdsIBDMLEPairs(gdsobj, sample1_id, sample2_id, sample_id=None, snp_id=Non
         idx.append(np.ascontiguousarray(order[pos], np.int32))
     af_in = ws["allele_freq"]
     P = id1.size
-    k0, k1, ll = np.empty(P, np.float64), np.empty(P, np.float64), np.empty(P, np.float64)
+    ll = np.empty(P, np.float64)
     niter = np.empty(P, np.int32) if out_num_iter else None
     af = np.empty(L, np.float64)
-    _lib.check(_lib.lib().snpgpu_gnrIBD_MLE_Pairs(_lib._ptr(af_in), _lib._ptr(idx[0]), _lib._ptr(idx[1]), P, int(max_niter),
-                                                  float(reltol), int(bool(coeff_correct)), ws["num_thread"], int(bool(verbose)),
-                                                  _lib._ptr(k0), _lib._ptr(k1), _lib._ptr(ll), _lib._ptr(niter), _lib._ptr(af)))
+    ans = dict(sample_id=ws["sample_id"], snp_id=ws["snp_id"], afreq=af, ID1=id1, ID2=id2)
+    if method == "EM":
+        k0, k1 = np.empty(P, np.float64), np.empty(P, np.float64)
+        _lib.check(_lib.lib().snpgpu_gnrIBD_MLE_Pairs(_lib._ptr(af_in), _lib._ptr(idx[0]), _lib._ptr(idx[1]), P, int(max_niter),
+                                                      float(reltol), int(bool(coeff_correct)), ws["num_thread"], int(bool(verbose)),
+                                                      _lib._ptr(k0), _lib._ptr(k1), _lib._ptr(ll), _lib._ptr(niter), _lib._ptr(af)))
+    else:
+        coef = np.empty((8 if method == "Jacquard" else 2, P), np.float64)
+        _lib.check(_lib.lib().snpgpu_gnrIBD_MLE_PairsMethod(_lib._ptr(af_in), _lib._ptr(idx[0]), _lib._ptr(idx[1]), P,
+                                                            IBDMLE_METHODS.index(method), int(max_niter), float(reltol),
+                                                            int(bool(coeff_correct)), ws["num_thread"], int(bool(verbose)),
+                                                            _lib._ptr(coef), _lib._ptr(ll), _lib._ptr(niter), _lib._ptr(af)))
+        k0, k1 = coef[0], coef[1]
     af[af < 0] = np.nan
-    ans = dict(sample_id=ws["sample_id"], snp_id=ws["snp_id"], afreq=af, ID1=id1, ID2=id2, k0=k0, k1=k1, loglik=ll, niter=niter)
+    if method == "Jacquard":
+        ans.update(("D%d" % (t + 1), coef[t]) for t in range(8))
+        ans.update(loglik=ll, niter=niter)
+        if kinship:
+            ans["kinship"] = coef[0] + 0.5 * (coef[2] + coef[4] + coef[6]) + 0.25 * coef[7]
+        return ans
+    ans.update(k0=k0, k1=k1, loglik=ll, niter=niter)
     if kinship:
         ans["kinship"] = 0.5 * (1 - k0 - k1) + 0.25 * k1
     return ans

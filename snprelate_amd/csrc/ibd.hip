@@ -10,7 +10,9 @@
 //
 // snpgpu_ibd_mle_pairs does the same for a list of pairs without any n x n object: only the listed samples are transposed to
 // words, and ibd_em_pairs_kernel (one wave per pair) counts the IBS states, applies Est_PLINK_Kinship, runs the EM and the
-// candidates, and reports the log-likelihood after LOGLIK_ADJUST (gnrPairIBD's third output).
+// candidates, and reports the log-likelihood after LOGLIK_ADJUST (gnrPairIBD's third output).  Its mode 2 runs the downhill simplex
+// (ibd_nm_pairs_kernel) and snpgpu_ibd_jacquard_pairs Jacquard's nine coefficients (ibd_jacq_pairs_kernel) on the same words and
+// tables with the same grid rule; both kernels are in kernels_ibd_methods.hip.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -41,6 +43,13 @@ int launch_ibd_em_pairs(hipStream_t st, int n_waves, const uint32_t *gt, int64_t
                         double *loglik, int32_t *niter);
 int launch_ibd_expand(hipStream_t st, const int64_t *rowoff, int64_t n_rows, int64_t r0, int64_t n_samp, int64_t n_pairs,
                       const double *k0, const double *k1, const int32_t *niter, double *o0, double *o1, int32_t *on);
+int launch_ibd_nm_pairs(hipStream_t st, int n_waves, const uint32_t *gt, int64_t wpad, const uint32_t *um, const double *pt,
+                        const int32_t *slot1, const int32_t *slot2, int64_t n_pairs, const double *e, int constraint, int max_niter,
+                        double reltol, int coeff_correct, unsigned long long *queue, double *k0, double *k1, double *loglik,
+                        int32_t *niter);
+int launch_ibd_jacq_pairs(hipStream_t st, int n_waves, const uint32_t *gt, int64_t wpad, const uint32_t *um, const double *pt,
+                          const int32_t *slot1, const int32_t *slot2, int64_t n_pairs, int max_niter, double reltol,
+                          unsigned long long *queue, double *d, double *loglik, int32_t *niter);
 }  // namespace snpgpu
 
 using namespace snpgpu;
@@ -48,7 +57,7 @@ using namespace snpgpu;
 namespace {
 
 thread_local double g_stats[4] = {0, 0, 0, 0};   // EM kernel ms, all kernels ms, useful / issued lane-sweeps
-thread_local double g_pair_stats[4] = {0, 0, 0, 0};   // snpgpu_ibd_mle_pairs: EM kernel ms, all kernels ms, wave-sweeps, pairs
+thread_local double g_pair_stats[4] = {0, 0, 0, 0};   // the last listed-pairs call: its kernel's ms, all kernels ms, wave-sweeps, pairs
 
 constexpr GenoLimits IBD_GENO = {2, NO_LIMIT, NO_LIMIT, true, "at least two samples are needed"};
 enum { T_EM = 0, T_REST = 1 };   // snpgpu_ibd_mle's EventLog: the EM kernel; candidates and expansion, back to back with it
@@ -132,6 +141,105 @@ std::vector<int64_t> row_offsets(int64_t n, int64_t r0, int64_t r1, bool diag)
     std::vector<int64_t> off((size_t)(r1 - r0 + 1), 0);
     for (int64_t r = r0; r < r1; r++) off[(size_t)(r - r0 + 1)] = off[(size_t)(r - r0)] + (n - r - (diag ? 0 : 1));
     return off;
+}
+
+// the argument checks every listed-pairs call makes before a device is touched, after its own NULL checks
+int check_pairs(const char *fn, const int32_t *idx1, const int32_t *idx2, int64_t n_pairs, int64_t n_snp, int64_t n_samp, int out_mem)
+{
+    if (!idx1 || !idx2) return fail(fn, "idx1 / idx2 is NULL");
+    if (out_mem != SNPGPU_HOST && out_mem != SNPGPU_DEVICE) return fail(fn, "invalid out_mem");
+    for (int64_t t = 0; t < n_pairs; t++)
+        for (const int32_t v : {idx1[t], idx2[t]})
+            if (v < 0 || v >= n_samp)
+                return fail(fn, "sample index " + std::to_string(v) + " of pair " + std::to_string(t) + " is out of range (0 ... " +
+                                    std::to_string(n_samp - 1) + ")");
+    if (n_snp > int64_t(65535) * 16) return fail(fn, "invalid number of SNPs: too many SNPs (<= 1 048 560)");    // grid.y = words per sample
+    return 0;
+}
+
+enum { K_EM = 0, K_NM = 1, K_JACQ = 2 };   // the kernel of a listed-pairs call
+
+// The listed-pairs call after its checks: words of the distinct listed samples, the p table, then one wave per pair in `kernel`.
+// o0 / o1: k0 / k1 [n_pairs], or for K_JACQ o0 = the eight planes [8][n_pairs] and o1 unused.
+int run_pairs(const char *fn, const void *geno, int64_t n_snp, int64_t n_samp, int mem, const double *allele_freq, const int32_t *idx1,
+              const int32_t *idx2, int64_t n_pairs, int kernel, int mode, int kinship_constraint, int max_niter, double reltol,
+              int coeff_correct, double *k0, double *k1, double *loglik, int32_t *niter, double *afreq_out, int out_mem, int device)
+{
+    for (double &s : g_pair_stats) s = 0;
+
+    // the distinct listed samples in ascending order, and each pair's two slots among them
+    std::vector<int32_t> list(idx1, idx1 + n_pairs);
+    list.insert(list.end(), idx2, idx2 + n_pairs);
+    std::sort(list.begin(), list.end());
+    list.erase(std::unique(list.begin(), list.end()), list.end());
+    std::vector<int32_t> slots((size_t)(2 * n_pairs));
+    for (int64_t t = 0; t < n_pairs; t++) {
+        slots[(size_t)t] = (int32_t)(std::lower_bound(list.begin(), list.end(), idx1[t]) - list.begin());
+        slots[(size_t)(n_pairs + t)] = (int32_t)(std::lower_bound(list.begin(), list.end(), idx2[t]) - list.begin());
+    }
+    const int64_t n_list = (int64_t)list.size(), wpad = (n_snp + 1023) / 1024 * 64;
+
+    Call c;
+    if (c.open(fn, device, true)) return 1;
+    CallStream &st = c.st;
+    DevBuf *daf = nullptr;
+    Prep P;
+    if (rows_and_freq(st, c.bufs, geno, n_snp, n_samp, mem, allele_freq, P, daf)) return 1;
+    int rc = 0;
+    DevBuf *dlist = c.bufs.get(sizeof(int32_t) * list.size(), rc), *dslot = c.bufs.get(sizeof(int32_t) * slots.size(), rc);
+    DevBuf *pt = c.bufs.get(sizeof(double) * (size_t)wpad * 16, rc), *um = c.bufs.get(sizeof(uint32_t) * (size_t)wpad, rc);
+    DevBuf *gt = c.bufs.get(sizeof(uint32_t) * (size_t)n_list * (size_t)wpad, rc);
+    DevBuf *queue = c.bufs.get(2 * sizeof(unsigned long long), rc);
+    if (rc) return 1;
+    SNPGPU_HIP_CHECK(hipMemcpyAsync(dlist->p, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, st.s));
+    SNPGPU_HIP_CHECK(hipMemcpyAsync(dslot->p, slots.data(), sizeof(int32_t) * slots.size(), hipMemcpyHostToDevice, st.s));
+    SNPGPU_HIP_CHECK(hipMemsetAsync(queue->p, 0, 2 * sizeof(unsigned long long), st.s));
+    if (c.log.begin(T_REST, st.s)) return 1;
+    if (launch_ibd_pairs_prepare(st.s, P.rows, P.rb, n_snp, (const double *)daf->p, (const int32_t *)dlist->p, n_list, wpad,
+                                 (double *)pt->p, (uint32_t *)um->p, (uint32_t *)gt->p))
+        return 1;
+    if (c.log.end(st.s)) return 1;
+    SNPGPU_HIP_CHECK(hipStreamSynchronize(st.s));          // P.af is complete
+    if (afreq_out) std::copy(P.af.begin(), P.af.end(), afreq_out);
+    double e[5];
+    e_prib(P.af, e);
+
+    hipDeviceProp_t prop;
+    int cus = 256;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+    const int n_waves = (int)std::min<int64_t>(n_pairs, (int64_t)cus * 16);
+
+    HostOut o0, o1, ol, on;
+    if (o0.open(c.bufs, k0, sizeof(double) * n_pairs * (kernel == K_JACQ ? 8 : 1), out_mem, false, st.s) ||
+        (kernel != K_JACQ && o1.open(c.bufs, k1, sizeof(double) * n_pairs, out_mem, false, st.s)) ||
+        ol.open(c.bufs, loglik, sizeof(double) * n_pairs, out_mem, false, st.s) ||
+        on.open(c.bufs, niter, sizeof(int32_t) * n_pairs, out_mem, false, st.s))
+        return 1;
+    if (c.log.begin(T_EM, st.s)) return 1;
+    const uint32_t *dgt = (const uint32_t *)gt->p, *dum = (const uint32_t *)um->p;
+    const int32_t *s1 = (const int32_t *)dslot->p, *s2 = s1 + n_pairs;
+    unsigned long long *dq = (unsigned long long *)queue->p;
+    if (kernel == K_EM)
+        rc = launch_ibd_em_pairs(st.s, n_waves, dgt, wpad, dum, (const double *)pt->p, s1, s2, n_pairs, e, kinship_constraint ? 1 : 0,
+                                 mode, max_niter, reltol, coeff_correct ? 1 : 0, dq, (double *)o0.dev, (double *)o1.dev,
+                                 (double *)ol.dev, (int32_t *)on.dev);
+    else if (kernel == K_NM)
+        rc = launch_ibd_nm_pairs(st.s, n_waves, dgt, wpad, dum, (const double *)pt->p, s1, s2, n_pairs, e, kinship_constraint ? 1 : 0,
+                                 max_niter, reltol, coeff_correct ? 1 : 0, dq, (double *)o0.dev, (double *)o1.dev, (double *)ol.dev,
+                                 (int32_t *)on.dev);
+    else
+        rc = launch_ibd_jacq_pairs(st.s, n_waves, dgt, wpad, dum, (const double *)pt->p, s1, s2, n_pairs, max_niter, reltol, dq,
+                                   (double *)o0.dev, (double *)ol.dev, (int32_t *)on.dev);
+    if (rc) return 1;
+    if (c.log.end(st.s)) return 1;
+    if (o0.close(st.s) || (kernel != K_JACQ && o1.close(st.s)) || ol.close(st.s) || on.close(st.s)) return 1;
+    unsigned long long q[2] = {0, 0};
+    SNPGPU_HIP_CHECK(hipMemcpyAsync(q, queue->p, sizeof(q), hipMemcpyDeviceToHost, st.s));
+    SNPGPU_HIP_CHECK(hipStreamSynchronize(st.s));
+    double ms_rest = 0;
+    if (c.log.sum_ms(T_EM, &g_pair_stats[0]) || c.log.sum_ms(T_REST, &ms_rest)) return 1;
+    g_pair_stats[1] = g_pair_stats[0] + ms_rest; g_pair_stats[2] = (double)q[1]; g_pair_stats[3] = (double)n_pairs;
+    return 0;
 }
 
 }  // namespace
@@ -241,80 +349,24 @@ int snpgpu_ibd_mle_pairs(const void *geno, int64_t n_snp, int64_t n_samp, int fo
     if (check_geno(fn, geno, n_snp, n_samp, format, mem, IBD_GENO)) return 1;
     if (n_pairs < 1) return fail(fn, "no pair is listed (n_pairs < 1)");
     if (!k0 || !k1) return fail(fn, "k0 / k1 is NULL");
-    if (!idx1 || !idx2) return fail(fn, "idx1 / idx2 is NULL");
-    if (mode != 0 && mode != 1) return fail(fn, "invalid mode (0 = EM, 1 = start values)");
-    if (out_mem != SNPGPU_HOST && out_mem != SNPGPU_DEVICE) return fail(fn, "invalid out_mem");
-    for (int64_t t = 0; t < n_pairs; t++)
-        for (const int32_t v : {idx1[t], idx2[t]})
-            if (v < 0 || v >= n_samp)
-                return fail(fn, "sample index " + std::to_string(v) + " of pair " + std::to_string(t) + " is out of range (0 ... " +
-                                    std::to_string(n_samp - 1) + ")");
-    if (n_snp > int64_t(65535) * 16) return fail(fn, "invalid number of SNPs: too many SNPs (<= 1 048 560)");    // grid.y = words per sample
-    for (double &s : g_pair_stats) s = 0;
+    if (mode != 0 && mode != 1 && mode != 2)
+        return fail(fn, "invalid mode " + std::to_string(mode) + " (0 = EM, 1 = start values, 2 = downhill simplex)");
+    if (check_pairs(fn, idx1, idx2, n_pairs, n_snp, n_samp, out_mem)) return 1;
+    return run_pairs(fn, geno, n_snp, n_samp, mem, allele_freq, idx1, idx2, n_pairs, mode == 2 ? K_NM : K_EM, mode,
+                     kinship_constraint, max_niter, reltol, coeff_correct, k0, k1, loglik, niter, afreq_out, out_mem, device);
+}
 
-    // the distinct listed samples in ascending order, and each pair's two slots among them
-    std::vector<int32_t> list(idx1, idx1 + n_pairs);
-    list.insert(list.end(), idx2, idx2 + n_pairs);
-    std::sort(list.begin(), list.end());
-    list.erase(std::unique(list.begin(), list.end()), list.end());
-    std::vector<int32_t> slots((size_t)(2 * n_pairs));
-    for (int64_t t = 0; t < n_pairs; t++) {
-        slots[(size_t)t] = (int32_t)(std::lower_bound(list.begin(), list.end(), idx1[t]) - list.begin());
-        slots[(size_t)(n_pairs + t)] = (int32_t)(std::lower_bound(list.begin(), list.end(), idx2[t]) - list.begin());
-    }
-    const int64_t n_list = (int64_t)list.size(), wpad = (n_snp + 1023) / 1024 * 64;
-
-    Call c;
-    if (c.open(fn, device, true)) return 1;
-    CallStream &st = c.st;
-    DevBuf *daf = nullptr;
-    Prep P;
-    if (rows_and_freq(st, c.bufs, geno, n_snp, n_samp, mem, allele_freq, P, daf)) return 1;
-    int rc = 0;
-    DevBuf *dlist = c.bufs.get(sizeof(int32_t) * list.size(), rc), *dslot = c.bufs.get(sizeof(int32_t) * slots.size(), rc);
-    DevBuf *pt = c.bufs.get(sizeof(double) * (size_t)wpad * 16, rc), *um = c.bufs.get(sizeof(uint32_t) * (size_t)wpad, rc);
-    DevBuf *gt = c.bufs.get(sizeof(uint32_t) * (size_t)n_list * (size_t)wpad, rc);
-    DevBuf *queue = c.bufs.get(2 * sizeof(unsigned long long), rc);
-    if (rc) return 1;
-    SNPGPU_HIP_CHECK(hipMemcpyAsync(dlist->p, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, st.s));
-    SNPGPU_HIP_CHECK(hipMemcpyAsync(dslot->p, slots.data(), sizeof(int32_t) * slots.size(), hipMemcpyHostToDevice, st.s));
-    SNPGPU_HIP_CHECK(hipMemsetAsync(queue->p, 0, 2 * sizeof(unsigned long long), st.s));
-    if (c.log.begin(T_REST, st.s)) return 1;
-    if (launch_ibd_pairs_prepare(st.s, P.rows, P.rb, n_snp, (const double *)daf->p, (const int32_t *)dlist->p, n_list, wpad,
-                                 (double *)pt->p, (uint32_t *)um->p, (uint32_t *)gt->p))
-        return 1;
-    if (c.log.end(st.s)) return 1;
-    SNPGPU_HIP_CHECK(hipStreamSynchronize(st.s));          // P.af is complete
-    if (afreq_out) std::copy(P.af.begin(), P.af.end(), afreq_out);
-    double e[5];
-    e_prib(P.af, e);
-
-    hipDeviceProp_t prop;
-    int cus = 256;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    const int n_waves = (int)std::min<int64_t>(n_pairs, (int64_t)cus * 16);
-
-    HostOut o0, o1, ol, on;
-    if (o0.open(c.bufs, k0, sizeof(double) * n_pairs, out_mem, false, st.s) ||
-        o1.open(c.bufs, k1, sizeof(double) * n_pairs, out_mem, false, st.s) ||
-        ol.open(c.bufs, loglik, sizeof(double) * n_pairs, out_mem, false, st.s) ||
-        on.open(c.bufs, niter, sizeof(int32_t) * n_pairs, out_mem, false, st.s))
-        return 1;
-    if (c.log.begin(T_EM, st.s)) return 1;
-    if (launch_ibd_em_pairs(st.s, n_waves, (const uint32_t *)gt->p, wpad, (const uint32_t *)um->p, (const double *)pt->p,
-                            (const int32_t *)dslot->p, (const int32_t *)dslot->p + n_pairs, n_pairs, e, kinship_constraint ? 1 : 0,
-                            mode, max_niter, reltol, coeff_correct ? 1 : 0, (unsigned long long *)queue->p, (double *)o0.dev,
-                            (double *)o1.dev, (double *)ol.dev, (int32_t *)on.dev))
-        return 1;
-    if (c.log.end(st.s)) return 1;
-    if (o0.close(st.s) || o1.close(st.s) || ol.close(st.s) || on.close(st.s)) return 1;
-    unsigned long long q[2] = {0, 0};
-    SNPGPU_HIP_CHECK(hipMemcpyAsync(q, queue->p, sizeof(q), hipMemcpyDeviceToHost, st.s));
-    SNPGPU_HIP_CHECK(hipStreamSynchronize(st.s));
-    double ms_rest = 0;
-    if (c.log.sum_ms(T_EM, &g_pair_stats[0]) || c.log.sum_ms(T_REST, &ms_rest)) return 1;
-    g_pair_stats[1] = g_pair_stats[0] + ms_rest; g_pair_stats[2] = (double)q[1]; g_pair_stats[3] = (double)n_pairs;
-    return 0;
+int snpgpu_ibd_jacquard_pairs(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, const double *allele_freq,
+                              const int32_t *idx1, const int32_t *idx2, int64_t n_pairs, int max_niter, double reltol, double *d,
+                              double *loglik, int32_t *niter, double *afreq_out, int out_mem, int device)
+{
+    const char *fn = "snpgpu_ibd_jacquard_pairs";
+    if (check_geno(fn, geno, n_snp, n_samp, format, mem, IBD_GENO)) return 1;
+    if (n_pairs < 1) return fail(fn, "no pair is listed (n_pairs < 1)");
+    if (!d) return fail(fn, "d is NULL");
+    if (check_pairs(fn, idx1, idx2, n_pairs, n_snp, n_samp, out_mem)) return 1;
+    return run_pairs(fn, geno, n_snp, n_samp, mem, allele_freq, idx1, idx2, n_pairs, K_JACQ, 0, 0, max_niter, reltol, 0, d, nullptr,
+                     loglik, niter, afreq_out, out_mem, device);
 }
 
 int snpgpu_ibd_mle_pairs_stats(double *stats)

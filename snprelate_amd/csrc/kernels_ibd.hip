@@ -18,19 +18,11 @@
 // per sweep.  SNPs that are not usable are written as missing codes when the words are built, so they contribute nothing.
 //
 // Listed pairs (snpgdsIBDMLEPairs): the second half of this file maps one pair to a WAVE, see "one wave per pair" below.
-#include "snpgpu_internal.h"
-#include "fin_values.h"
-
-#include <cmath>
+#include "ibd_device.h"
 
 namespace snpgpu {
 
 namespace {
-
-constexpr double LN2 = 0.69314718055994530942;
-
-// per-SNP constants (wave-uniform): {q, p, p q, 4 p q}
-struct IbdSnp { double q, p, pq, pq4; };
 
 __device__ inline void row_of_pair(const int64_t *__restrict__ rowoff, int64_t n_rows, int64_t r0, int64_t idx, int diag,
                                    int64_t &i, int64_t &j)
@@ -42,37 +34,6 @@ __device__ inline void row_of_pair(const int64_t *__restrict__ rowoff, int64_t n
     }
     i = r0 + lo;
     j = i + (diag ? 0 : 1) + (idx - rowoff[lo]);
-}
-
-// The usable-SNP table of codes (a, b) for allele frequency (q, p): factor c and the three coefficients.
-__device__ inline void ibd_terms(unsigned a, unsigned b, const IbdSnp &s, double &c, double &a0, double &a1, double &a2)
-{
-    const bool same = a == b, hh = (a & b) == 1u && same, het = (a == 1u) | (b == 1u);
-    const unsigned hom = same ? a : a + b - 1u;          // the homozygote of a hom/het pair
-    const double x = hom == 0u ? s.q : s.p;
-    const double xx = x * x;
-    // selects, not branches: the lanes of a wave hold different classes
-    const double pqx = s.pq * x, pq2 = s.pq * s.pq, x2 = x + x;
-    a0 = hh ? s.pq4 : same ? xx : het ? x2 : 1.0;
-    a1 = hh ? 1.0 : same ? x : het ? 1.0 : 0.0;
-    a2 = hh ? 2.0 : same ? 1.0 : 0.0;
-    c = hh ? s.pq : same ? xx : het ? pqx : pq2;
-}
-
-__device__ inline void renorm(double &prod, int &ex)
-{
-    int e;
-    prod = frexp(prod, &e);
-    ex += e;
-}
-
-__device__ inline double recip(double s)
-{
-    double r = __builtin_amdgcn_rcp(s);
-    double e = fma(-s, r, 1.0);
-    r = fma(r, e, r);
-    e = fma(-s, r, 1.0);
-    return fma(r, e, r);
 }
 
 // One sweep over the SNPs for one pair (codes from words ga / gb) at (k0, k1, k2): the posterior sums, the number of usable
@@ -328,29 +289,6 @@ __global__ void ibd_expand_kernel(const int64_t *__restrict__ rowoff, int64_t n_
 // After each sweep S0, S1, the log-likelihood and the usable-SNP count are summed over the lanes by an xor butterfly
 // (32, 16, .. 1): every lane ends with the same bits, so the stop decision is wave-uniform, and a pair's result depends on
 // nothing but its own words.  When its pair stops, lane 0 takes the next one from the queue.
-struct IbdE { double e00, e01, e02, e11, e12; };
-
-__device__ inline double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ inline int wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ inline IbdSnp snp_of_p(double p)
-{
-    IbdSnp t;
-    const double q = 1 - p;
-    t.q = q; t.p = p; t.pq = p * q; t.pq4 = 4 * p * q;
-    return t;
-}
-
 // this lane's share of one EM sweep; nb steps of 64 words
 __device__ inline void em_sweep_lane(const uint32_t *__restrict__ ga, const uint32_t *__restrict__ gb,
                                      const uint32_t *__restrict__ um, const double *__restrict__ pt, int64_t nb, int lane,
@@ -399,23 +337,13 @@ __global__ __launch_bounds__(256) void ibd_em_pairs_kernel(const uint32_t *__res
     const int64_t nb = wpad / 64;
     unsigned long long sweeps = 0;
     while (true) {
-        unsigned long long next = 0;
-        if (lane == 0) next = atomicAdd(queue, 1ull);
-        const int64_t pair = (int64_t)__shfl(next, 0);
+        const int64_t pair = take_pair(queue, lane);
         if (pair >= n_pairs) break;
         const uint32_t *ga = gt + (int64_t)slot1[pair] * wpad, *gb = gt + (int64_t)slot2[pair] * wpad;
 
         // start values: the pair's IBS counts from the unmasked codes (exact), then Est_PLINK_Kinship
-        int cn = 0, c1 = 0, c0 = 0;
-        for (int64_t b = 0; b < nb; b++) {
-            const uint32_t wa = ga[b * 64 + lane], wb = gb[b * 64 + lane];
-            const uint32_t both = ~(wa & (wa >> 1)) & ~(wb & (wb >> 1)) & 0x55555555u;
-            const uint32_t x = wa ^ wb, lo = x & both, hi = (x >> 1) & both;     // |a - b| = 1: x = 01 or 11; 2: x = 10
-            cn += __popc(both); c1 += __popc(lo); c0 += __popc(hi & ~lo);
-        }
-        cn = wave_sum(cn); c1 = wave_sum(c1); c0 = wave_sum(c0);
         double a, b;
-        mom_from_counts(e.e00, e.e01, e.e02, e.e11, e.e12, constraint, cn, c1, c0, a, b);
+        pair_mom_start(ga, gb, nb, lane, e, constraint, a, b);
         if (mode == 1) {
             if (lane == 0) {
                 ok0[pair] = a; ok1[pair] = b;
@@ -424,13 +352,9 @@ __global__ __launch_bounds__(256) void ibd_em_pairs_kernel(const uint32_t *__res
             }
             continue;
         }
-        // each of k0, k1, k2 >= 0.005 and renormalised (:824-832)
-        double c = 1 - a - b;
-        if (a < 0.005) a = 0.005;
-        if (b < 0.005) b = 0.005;
-        if (c < 0.005) c = 0.005;
-        const double s = a + b + c;
-        double k0 = a / s, k1 = b / s, k2 = 1 - k0 - k1, old = 0, tol = 0;
+        double k0, k1;
+        clamp_start(a, b, k0, k1);
+        double k2 = 1 - k0 - k1, old = 0, tol = 0;
         double fk0, fk1, fL;
         int it = 0, fit;
         while (true) {                                        // the decisions of ibd_em_kernel, wave-uniform here

@@ -1240,6 +1240,30 @@ int snpgpu_gnrIBD_MLE_Pairs(const double *allele_freq, const int32_t *idx1, cons
                                 SNPGPU_HOST, g_ws.device);
 }
 
+// the listed pairs by method: 0 EM, 1 downhill simplex (coef = k0 then k1), 2 Jacquard (coef = D1 ... D8)
+int snpgpu_gnrIBD_MLE_PairsMethod(const double *allele_freq, const int32_t *idx1, const int32_t *idx2, int64_t n_pairs, int method,
+                                  int max_niter, double reltol, int coeff_correct, int num_thread, int, double *coef, double *loglik,
+                                  int32_t *niter, double *afreq)
+{
+    if (method < 0 || method > 2) {
+        set_error("snpgpu_gnrIBD_MLE_PairsMethod: invalid method " + std::to_string(method) +
+                  " (0 = EM, 1 = downhill simplex, 2 = Jacquard)");
+        return 1;
+    }
+    if (num_thread <= 0) { set_error("Invalid 'num.thread'."); return 1; }
+    if (!coef) { set_error("snpgpu_gnrIBD_MLE_PairsMethod: coef is NULL"); return 1; }
+    if (n_pairs < 1) { set_error("snpgpu_gnrIBD_MLE_PairsMethod: no pair is listed (n_pairs < 1)"); return 1; }
+    std::vector<uint8_t> buf;
+    if (ws_rows("snpgpu_gnrIBD_MLE_PairsMethod", buf)) return 1;
+    const int64_t L = (int64_t)g_ws.sel.size();
+    if (method == 2)
+        return snpgpu_ibd_jacquard_pairs(buf.data(), L, g_ws.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, allele_freq, idx1, idx2, n_pairs,
+                                         max_niter, reltol, coef, loglik, niter, afreq, SNPGPU_HOST, g_ws.device);
+    return snpgpu_ibd_mle_pairs(buf.data(), L, g_ws.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, allele_freq, idx1, idx2, n_pairs,
+                                method == 1 ? 2 : 0, 0, max_niter, reltol, coeff_correct, coef, coef + n_pairs, loglik, niter, afreq,
+                                SNPGPU_HOST, g_ws.device);
+}
+
 // gnrIBD_LogLik(AFreq, k0, k1) and gnrIBD_LogLik_k01(AFreq, k0, k1), src/genIBD.cpp:1289-1330 and their .Call wrappers
 int snpgpu_gnrIBD_LogLik(const double *afreq, const double *k0, const double *k1, double *out)
 {

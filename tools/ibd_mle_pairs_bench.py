@@ -11,7 +11,15 @@ register-only v_fma_f64 stream sustains in the same run (snpgpu_diag_fp64_rate),
 fetches.  FP64_INSTR_PER_LANE_SNP is a FIXED count, not read from the build: the fp64 VALU instructions per lane and SNP of the EM
 sweep's inner loop in the gfx950 code object of csrc/kernels_ibd.hip as committed (84 per 4-SNP step: 37 mul, 32 fma, 8 add, 4 rcp,
 the frexp pair of the renormalisation and one conversion).  Recount it with `hipcc --cuda-device-only -S` when the kernel or the
-compiler changes.  The share counts the padded SNP slots a sweep really issues (the words are padded to 1 024 SNPs)."""
+compiler changes.  The share counts the padded SNP slots a sweep really issues (the words are padded to 1 024 SNPs).
+
+--method simplex | jacquard | all runs case (a) only, for the named method(s) of snpgdsIBDMLEPairs ("all": EM, downhill simplex and
+Jacquard in one run), and writes profiles/ibd_methods_bench.json: per method the HIP-event time of its one-wave-per-pair kernel,
+its wave-sweeps (EM iterations; function-evaluation sweeps of the simplex; the candidate sweep counts as one), SNP-evaluations per
+second (wave-sweeps x M / kernel time), the fp64 instruction count per lane-SNP of its sweep loops (FP64_INSTR_METHODS, counted in
+the gfx950 code object of csrc/kernels_ibd_methods.hip as committed, fp64 compares included), mean and 99th percentile of niter
+(the simplex's niter is its count of function evaluations), and the kernel-time ratios simplex / EM and Jacquard / EM.  The
+default --method em is everything above, unchanged."""
 import argparse
 import json
 import os
@@ -24,6 +32,10 @@ if ROOT not in sys.path:
 
 FP64_INSTR_PER_LANE_SNP = 84 / 4
 FP64_INSTR_PER_LANE_SNP_MATRIX = 66 / 4          # tools/ibd_mle_bench.py
+# per lane-SNP, from the inner loops of ibd_nm_pairs_kernel (per 8-SNP step: 140 with one point, 196 with two, 246 with three, 404 with
+# the six candidates) and ibd_jacq_pairs_kernel (84 per 2-SNP step: 31 mul, 42 fma, 6 add, 2 rcp, the frexp pair, one conversion)
+FP64_INSTR_METHODS = dict(em=FP64_INSTR_PER_LANE_SNP, simplex=140 / 8, simplex_2_points=196 / 8, simplex_3_points=246 / 8,
+                          simplex_6_candidates=404 / 8, jacquard=84 / 2)
 
 
 def median(xs):
@@ -42,8 +54,12 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--probe-seconds", type=float, default=2.0)
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ibd_mle_pairs_bench.json"))
+    ap.add_argument("--method", default="em", choices=("em", "simplex", "jacquard", "all"),
+                    help="em: the cases above (default); another value: case (a) for that method, or for all three")
+    ap.add_argument("--out", default=None, help="default: profiles/ibd_mle_pairs_bench.json, or ibd_methods_bench.json with --method")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "ibd_mle_pairs_bench.json" if a.method == "em" else "ibd_methods_bench.json")
 
     import numpy as np
     import torch
@@ -85,6 +101,49 @@ def main():
                     snp_iterations_per_s=float(sweeps) * M / (ms_em * 1e-3), niter_mean=round(float(nit.mean()), 2),
                     niter_frac_at_max=float((nit >= a.max_niter).mean()), nan_pairs=int(np.isnan(k0).sum()),
                     fp64_fraction_of_fma_stream=round(slots * FP64_INSTR_PER_LANE_SNP / (ms_em * 1e-3) / peak_instr, 4)), (k0, k1, nit)
+
+    def method_case(geno, N, i1, i2, method):
+        runs = []
+        for rep in range(a.reps + 1):
+            t0 = time.perf_counter()
+            if method == "jacquard":
+                nit = _lib.ibd_jacquard_pairs(None, N, i1, i2, max_niter=a.max_niter, device=a.device, geno_dev_ptr=geno.data_ptr(),
+                                              n_snp=M)[2]
+            else:
+                nit = _lib.ibd_mle_pairs(None, N, i1, i2, mode=2 if method == "simplex" else 0, max_niter=a.max_niter,
+                                         device=a.device, geno_dev_ptr=geno.data_ptr(), n_snp=M)[3]
+            wall = time.perf_counter() - t0
+            if rep:
+                runs.append((wall,) + _lib.ibd_mle_pairs_stats())
+        wall, ms_k, ms_all, sweeps, P = median(runs)
+        slots = float(sweeps) * wpad * 16
+        return dict(n_samp=N, pairs=int(P), kernel_ms=round(ms_k, 3), kernels_ms=round(ms_all, 3), call_ms=round(wall * 1e3, 3),
+                    wave_sweeps=int(sweeps), sweeps_per_pair=round(float(sweeps) / P, 2),
+                    snp_evaluations_per_s=float(sweeps) * M / (ms_k * 1e-3), fp64_instr_per_lane_snp=FP64_INSTR_METHODS[method],
+                    fp64_fraction_of_fma_stream=round(slots * FP64_INSTR_METHODS[method] / (ms_k * 1e-3) / peak_instr, 4),
+                    niter_mean=round(float(nit.mean()), 2), niter_p99=float(np.percentile(nit, 99)),
+                    niter_frac_at_max=float((nit >= a.max_niter).mean()))
+
+    if a.method != "em":
+        N = a.small
+        geno = synth(N, 2024)
+        i1, i2 = np.triu_indices(N, 1)
+        out = dict(tool="ibd_mle_pairs_bench --method " + a.method, source_stamp=out["source_stamp"], n_snp=M, n_samp=N,
+                   missing=a.missing, max_niter=a.max_niter, reps=a.reps, fma_stream_tflops=out["fma_stream_tflops"],
+                   fp64_instr_per_lane_snp=FP64_INSTR_METHODS, methods={})
+        for method in (("em", "simplex", "jacquard") if a.method == "all" else (a.method,)):
+            out["methods"][method] = method_case(geno, N, i1, i2, method)
+        if a.method == "all":
+            em_ms = out["methods"]["em"]["kernel_ms"]
+            out["kernel_ms_ratio_simplex_over_em"] = round(out["methods"]["simplex"]["kernel_ms"] / em_ms, 3)
+            out["kernel_ms_ratio_jacquard_over_em"] = round(out["methods"]["jacquard"]["kernel_ms"] / em_ms, 3)
+        out["fma_stream_tflops_after"] = round(_lib.diag_fp64_rate(a.probe_seconds, a.device), 2)
+        line = json.dumps(out)
+        print(line)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+        return
 
     # (a) every pair of a small N, beside the matrix path
     N = a.small
