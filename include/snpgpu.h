@@ -564,6 +564,43 @@ int snpgpu_ld_prune_bits(const void *geno, int64_t n_snp, int64_t n_samp, int fo
 int snpgpu_gnrLDpruning(int64_t start_idx, const int32_t *pos_bp, int32_t slide_max_bp, int32_t slide_max_n, double ld_threshold,
                         int method, int num_thread, int verbose, uint8_t *keep);
 
+/* LD scores of one chromosome: score[i] = sum over the window partners j of i of the squared LD value of the pair.  The SNPs
+ * are in file order with non-decreasing positions.  Pair (i, j), i != j, is in the window iff |i - j| <= slide_max_n and
+ * |pos[i] - pos[j]| <= slide_max_bp (differences exact in 64 bits; pos_bp NULL: the SNP count alone decides); the partners of i
+ * are then one range [lo, hi], and slide_max_n <= 0 or slide_max_bp < 0 leaves no pair.  Each unordered pair is evaluated once
+ * with the lower index as the first SNP (the orientation of snpgdsLDMat's band): v = the LD value of `method` (1 ... 4: composite,
+ * r, dprime, corr), t = v * v, and with SNPGPU_LDSCORE_ADJUST t = t - (1 - t) / (n - 2), n = the samples called at both SNPs.
+ * The pair is valid iff v is not NaN and, when adjusting, n > 2.  score[i] starts at 1.0 with SNPGPU_LDSCORE_SELF, else 0.0, and
+ * adds t of the valid partners lo ... hi in ascending order, one left fold in fp64 without contraction: a plain loop over
+ * snpgdsLDMat's values gives the same bits, whatever max_block_snps.  The tables are counted as for snpgpu_ld_prune (streamed row
+ * blocks, one block plus a halo of W = max (hi - i) rows resident); the terms and the fold run on the device, and only the
+ * three result vectors come back.
+ *   geno: SNPGPU_GENO_PACKED2 or SNPGPU_GENO_U8 rows [n_snp] in `mem` (host, or complete device memory as for snpgpu_ld_feed)
+ *   score: host double [n_snp]; n_valid (valid partners) and n_window (hi - lo, partners in the window): host int32 [n_snp] or NULL
+ *   opts: device, stream and max_block_snps (rows per streamed block, 0 = 16384) are used; info: may be NULL.  n_samp < 2^24.
+ * NULL geno / score, a method outside 1 ... 4, unknown flag bits and decreasing positions are refused before any device call. */
+typedef struct snpgpu_ld_score_info {
+    int64_t width;          /* W: largest distance hi - i of a pair in a window                                                  */
+    int64_t band_pairs;     /* pairs (x, x + k), k = 1 ... W, x + k < n_snp: tables counted                                      */
+    int64_t window_pairs;   /* unordered pairs inside a window: evaluated                                                        */
+    int64_t valid_pairs;    /* of those, valid ones (counted by the terms kernel)                                                */
+    int64_t table_launches; /* band table launches (each followed by one terms and one fold launch)                              */
+    int64_t table_tiles;    /* 64 x 64 pair tiles those launches computed                                                        */
+    double ms_stage;        /* HIP events: rows into the staging layout, halo copies, window upload                              */
+    double ms_tables;       /*   band table kernel                                                                               */
+    double ms_values;       /*   terms kernel                                                                                    */
+    double ms_fold;         /*   fold kernel                                                                                     */
+    double ms_copy;         /*   results device -> host                                                                          */
+} snpgpu_ld_score_info;
+enum { SNPGPU_LDSCORE_ADJUST = 1, SNPGPU_LDSCORE_SELF = 2 };
+int snpgpu_ld_score(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, const int32_t *pos_bp,
+                    int32_t slide_max_bp, int32_t slide_max_n, int method, int flags,
+                    double *score, int32_t *n_valid, int32_t *n_window,
+                    const snpgpu_opts *opts, snpgpu_ld_score_info *info);
+/* snpgpu_ld_score on the working space's selected SNPs (one chromosome, as the caller sets them): the entry an R wrapper calls */
+int snpgpu_gnrLDScore(const int32_t *pos_bp, int32_t slide_max_bp, int32_t slide_max_n, int method, int flags, int num_thread,
+                      int verbose, double *score, int32_t *n_valid, int32_t *n_window);
+
 /* ---- (1e) IBD by maximum likelihood: snpgdsIBDMLE (method "EM") and snpgdsIBDMLELogLik -----------------------------------------
  * gnrIBD_MLE (src/genIBD.cpp:1465-1548) on resident rows: allele frequencies as InitAFreq (:1122-1165; allele_freq: host
  * [n_snp] or NULL = sum / 2n over the calls, non-finite -> -1), start values from the IBS counters and Est_PLINK_Kinship with

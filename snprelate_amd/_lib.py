@@ -51,6 +51,7 @@ EXPORTS = [
     "snpgpu_ibd_mle_pairs", "snpgpu_ibd_mle_pairs_stats", "snpgpu_gnrIBD_MLE_Pairs",
     "snpgpu_ibd_jacquard_pairs", "snpgpu_gnrIBD_MLE_PairsMethod",
     "snpgpu_ld_prune", "snpgpu_ld_prune_bits", "snpgpu_gnrLDpruning",
+    "snpgpu_ld_score", "snpgpu_gnrLDScore",
     "snpgpu_diss", "snpgpu_diss_sums", "snpgpu_gnrDiss", "snpgpu_multi_diss",
     "snpgpu_pop_counts", "snpgpu_fst", "snpgpu_fst_windows", "snpgpu_pop_stats", "snpgpu_gnrFst", "snpgpu_gnrSlidingWindowFst",
     "snpgpu_geno_counts", "snpgpu_hwe", "snpgpu_hwe_counts", "snpgpu_ind_inb", "snpgpu_qc_stats", "snpgpu_gnrSampFreq", "snpgpu_gnrHWE",
@@ -69,6 +70,7 @@ PAIR_TYPES = ("per.pair", "per.snp", "matrix", "gds.file")
 PAIR_TABLE, SNP_TABLE = 0, 1
 PAIR_ELEM_INT32, PAIR_ELEM_BIT2 = 0, 1
 SEL_KING_ROBUST, SEL_KING_HOMO, SEL_MOM = 1, 2, 3
+LDSCORE_ADJUST, LDSCORE_SELF = 1, 2
 
 
 class SnpGpuError(RuntimeError):
@@ -270,6 +272,9 @@ def lib():
     L.snpgpu_ld_prune_bits.argtypes = [vp, i64, i64, c_int, c_int, i64, i64, dbl, c_int, vp, ctypes.POINTER(Opts),
                                        ctypes.POINTER(LDPruneInfo)]
     L.snpgpu_gnrLDpruning.argtypes = [i64, vp, i32, i32, dbl, c_int, c_int, c_int, vp]
+    L.snpgpu_ld_score.argtypes = [vp, i64, i64, c_int, c_int, vp, i32, i32, c_int, c_int, vp, vp, vp, ctypes.POINTER(Opts),
+                                  ctypes.POINTER(LDScoreInfo)]
+    L.snpgpu_gnrLDScore.argtypes = [vp, i32, i32, c_int, c_int, c_int, c_int, vp, vp, vp]
     L.snpgpu_pop_counts.argtypes = [vp, i64, i64, c_int, c_int, vp, c_int, vp, vp, c_int, c_int]
     L.snpgpu_fst.argtypes = [vp, i64, i64, c_int, c_int, vp, c_int, c_int, vp, vp, vp, c_int]
     L.snpgpu_fst_windows.argtypes = [vp, i64, i64, c_int, c_int, vp, c_int, c_int, vp, vp, i64, vp, vp, vp, c_int]
@@ -806,6 +811,37 @@ def ld_prune_bits(geno, n_samp, start_idx, width, ld_threshold, method=LD_COMPOS
                                      _ptr(words), ctypes.byref(o), ctypes.byref(info)))
     bits = np.unpackbits(words[:, :wpr].view(np.uint8).reshape(n, -1), axis=1, bitorder="little").astype(bool)
     return bits[:, :int(width)], info.as_dict()
+
+
+class LDScoreInfo(ctypes.Structure):
+    """snpgpu_ld_score_info (include/snpgpu.h section 1d)"""
+    _fields_ = [(k, ctypes.c_int64) for k in ("width", "band_pairs", "window_pairs", "valid_pairs", "table_launches", "table_tiles")] + \
+               [(k, ctypes.c_double) for k in ("ms_stage", "ms_tables", "ms_values", "ms_fold", "ms_copy")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def ld_score(geno, n_samp, pos_bp, slide_max_bp, slide_max_n, method=LD_CORR, adjust=True, include_self=True, fmt=None, n_snp=None,
+             device=0, max_block_snps=0, stream=None):
+    """LD scores of one chromosome (snpgpu_ld_score): (float64 score, int32 n_valid, int32 n_window, info dict), each [n_snp].
+    geno: host rows (numpy, U8 or PACKED2; fmt None: U8 when a row holds n_samp bytes) or a device address (int) with n_snp and
+    fmt; pos_bp: non-decreasing int32 positions, or None for a window in SNPs alone; the window limits are int32 values."""
+    n_samp = int(n_samp)
+    ptr, n, fmt, mem, _keep_alive = _geno_input(geno, n_samp, fmt, n_snp, device_fmt_default=None)
+    pos = None
+    if pos_bp is not None:
+        pos = np.ascontiguousarray(pos_bp, dtype=np.int32)
+        if pos.shape != (n,):
+            raise ValueError("pos_bp should hold one int32 per SNP")
+    score = np.empty(n, np.float64)
+    n_valid, n_window = np.empty(n, np.int32), np.empty(n, np.int32)
+    o = Opts(device=int(device), max_block_snps=int(max_block_snps), stream=stream)
+    info = LDScoreInfo()
+    flags = (LDSCORE_ADJUST if adjust else 0) | (LDSCORE_SELF if include_self else 0)
+    check(lib().snpgpu_ld_score(ptr, n, n_samp, fmt, mem, _ptr(pos), int(slide_max_bp), int(slide_max_n), int(method), flags,
+                                _ptr(score), _ptr(n_valid), _ptr(n_window), ctypes.byref(o), ctypes.byref(info)))
+    return score, n_valid, n_window, info.as_dict()
 
 
 class MultiAccumulator:

@@ -29,6 +29,7 @@ INTEGRATION.md):
     snpgdsIndInb                  R/AllUtilities.R:349-378   (individual inbreeding coefficients, six methods)
     snpgdsIBDSelection            R/IBD.R:463-531  (table of pairs at or above a kinship cutoff, on the host)
     snpgdsIBDPairs                no reference counterpart: the same table straight from the GPU counters
+    snpgdsLDScore                 no reference counterpart: per-SNP sums of squared LD over a window, folded on the GPU
 
 All arithmetic on genotype matrices runs on the MI355X through libsnpgpu.so
 (`_lib`); there is no CPU fallback.  The one exception is snpgdsIndInbCoef, which
@@ -1172,6 +1173,86 @@ def snpgdsLDpruning(gdsobj, sample_id=None, snp_id=None, autosome_only=True, rem
     if verbose:
         print("%s markers are selected in total." % _pretty(ntotal))
     return res
+
+
+def snpgdsLDScore(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True, maf=float("nan"),
+                  missing_rate=float("nan"), method="corr", slide_max_bp=1000000, slide_max_n=float("nan"), adjust=True,
+                  include_self=True, with_id=True, num_thread=1, verbose=True, device=0):
+    """LD score of every selected SNP: score[i] = sum of the squared LD values of the pairs (i, j) over the partners j of i on the
+    same chromosome with |i - j| <= slide_max_n (in selected SNPs) and |pos[i] - pos[j]| <= slide_max_bp.  Not a function of the
+    reference: what snpgdsLDMat's users reduce its band to, computed on the GPU without the slide x n_snp matrix (one
+    snpgpu_gnrLDScore call per chromosome over its selected SNPs in file order, include/snpgpu.h section 1d).
+
+    method: "composite", "r", "dprime" or "corr".  adjust: each squared value t becomes t - (1 - t) / (n - 2), n = the samples
+    called at both SNPs (pairs with n <= 2 are then not valid); pairs whose LD value is NaN are never valid.  include_self adds
+    the SNP's own term 1.  The window limits are coerced as in snpgdsLDpruning (NA / Inf slide_max_n becomes
+    .Machine$integer.max, finite values go through Rf_asInteger), except that a NA / Inf slide_max_bp means no limit in base
+    pairs: the positions are then not needed.  A chromosome's selected positions must not decrease.
+
+    Returns dict(sample_id, snp_id, chromosome, position, score, n_valid, n_window) in the order of the selected SNPs (n_valid:
+    valid partners, n_window: partners in the window), or the bare score with with_id=False."""
+    # the argument checks, R style, before anything reaches the device
+    if not (_is_na(slide_max_bp) or _is_number(slide_max_bp)):
+        raise TypeError("is.na(slide.max.bp) | is.numeric(slide.max.bp) is not TRUE")
+    if not (_is_na(slide_max_n) or _is_number(slide_max_n)):
+        raise TypeError("is.na(slide.max.n) | is.numeric(slide.max.n) is not TRUE")
+    if not _is_number(num_thread):
+        raise TypeError("is.numeric(num.thread) is not TRUE")
+    if not num_thread > 0:
+        raise ValueError("num.thread > 0L is not TRUE")
+    for name, v in (("adjust", adjust), ("include.self", include_self), ("with.id", with_id), ("verbose", verbose)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise TypeError("is.logical(%s) is not TRUE" % name)
+    if method not in LD_PRUNE_METHODS:
+        raise ValueError('method should be one of "composite", "r", "dprime" and "corr"')
+    if not isinstance(gdsobj, GenoFile):
+        raise TypeError("'gdsobj' should be a SNP GDS object (snpgdsOpen / GenoFile)")
+    bp_limit = not _is_na(slide_max_bp) and math.isfinite(slide_max_bp)
+    if bp_limit and gdsobj.snp_position is None:
+        raise ValueError("GDS node 'snp.position' not found (needed for a finite slide.max.bp)")
+    code = LD_PRUNE_METHODS.index(method) + 1
+
+    ws = _init_file2("LD scores:", gdsobj, sample_id, snp_id, autosome_only, remove_monosnp, maf, missing_rate, num_thread, verbose,
+                     device)
+    bp, mn = slide_max_bp, slide_max_n
+    if verbose:
+        print("    sliding window: %s basepairs, %s SNPs" % (_pretty(bp if bp_limit else math.inf),
+                                                              _pretty(mn if not _is_na(mn) and math.isfinite(mn) else math.inf)))
+        print("    method: %s" % ("composite", "R", "D'", "correlation")[code - 1])
+        print("    adjusted: %s, self term: %s" % (str(bool(adjust)).upper(), str(bool(include_self)).upper()))
+    bp = _as_integer(bp) if bp_limit else _INT_MAX
+    mn = _as_integer(_INT_MAX if _is_na(mn) or not math.isfinite(mn) else mn)
+    flags = (_lib.LDSCORE_ADJUST if adjust else 0) | (_lib.LDSCORE_SELF if include_self else 0)
+
+    snp_flag = np.isin(gdsobj.snp_id, ws["snp_id"])
+    ws_chrom = np.asarray(gdsobj.snp_chromosome)[snp_flag]           # of each working-space SNP (file order)
+    ws_pos = None if gdsobj.snp_position is None else np.ascontiguousarray(gdsobj.snp_position[snp_flag], np.int32)
+    _, first = np.unique(ws_chrom, return_index=True)
+    groups = [(ch, np.nonzero(ws_chrom == ch)[0]) for ch in ws_chrom[np.sort(first)]]
+    if bp_limit:
+        for ch, idx in groups:
+            if np.any(np.diff(ws_pos[idx].astype(np.int64)) < 0):
+                raise ValueError("snp.position decreases on chromosome %s: the SNPs of a chromosome should be sorted by position" % ch)
+    n = ws["n_snp"]
+    score = np.empty(n, np.float64)
+    n_valid, n_window = np.empty(n, np.int32), np.empty(n, np.int32)
+    L = _lib.lib()
+    for ch, idx in groups:
+        rows = np.ascontiguousarray(ws["packed"][idx])
+        _lib.check(L.snpgpu_ws_set_geno(_lib._ptr(rows), len(idx), ws["n_samp"], _lib.GENO_PACKED2, int(device)))
+        pos = np.ascontiguousarray(ws_pos[idx]) if bp_limit else None
+        s = np.empty(len(idx), np.float64)
+        nv, nw = np.empty(len(idx), np.int32), np.empty(len(idx), np.int32)
+        _lib.check(L.snpgpu_gnrLDScore(_lib._ptr(pos), bp, mn, code, flags, int(num_thread), int(bool(verbose)), _lib._ptr(s),
+                                       _lib._ptr(nv), _lib._ptr(nw)))
+        score[idx], n_valid[idx], n_window[idx] = s, nv, nw
+        if verbose:
+            print("Chrom %s: %s SNPs, %s pairs in the window, mean LD score %.6g" % (ch, _pretty(len(idx)), _pretty(int(nw.sum()) // 2),
+                                                                                    float(s.mean())))
+    if not with_id:
+        return score
+    return dict(sample_id=ws["sample_id"], snp_id=ws["snp_id"], chromosome=ws_chrom, position=ws_pos, score=score, n_valid=n_valid,
+                n_window=n_window)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

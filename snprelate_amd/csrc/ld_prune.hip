@@ -10,35 +10,22 @@
 // "|LD| > threshold" of such pairs: one bit per pair of the band (x, x + k), k = 1 ... W, computed on the device and scanned on
 // the host with the reference's list rules.
 //
-// Device side, per call (nothing is sized by the whole chromosome but the caller's input): two row buffers of cap = blk + W
-// staging rows used in turn (a full buffer finalises the rows whose W partners are all resident; its last W rows move to the
-// other buffer as the halo of the next block, as in ld.hip's sliding window), band tables [P][W][9] with P * W * 36 bytes within
-// PRUNE_TABLE_BUDGET, and the bit rows [P][ceil(W / 64)] copied to the host after each launch.
+// Device side, per call: the streamed band tables of ld_band.h (two row buffers of blk + W staging rows used in turn, tables
+// [P][W][9] within a fixed byte budget), and the bit rows [P][ceil(W / 64)] copied to the host after each launch.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <vector>
 
-#include "host_util.h"
+#include "ld_band.h"
 
 using namespace snpgpu;
 
 namespace {
 
-inline int64_t pr_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
-constexpr size_t PRUNE_TABLE_BUDGET = size_t(1) << 30;   // bytes of band tables per launch
-constexpr int64_t PRUNE_BLOCK_DEFAULT = 16384;          // rows per streamed block
-
-// the reference's window test: kept SNP j is still listed at candidate i (position differences exact in 64 bits)
-inline bool in_window(int64_t i, int64_t j, const int32_t *pos, int32_t max_bp, int32_t max_n)
-{
-    const int64_t d = i > j ? i - j : j - i;
-    const int64_t p = (int64_t)pos[i] - (int64_t)pos[j];
-    return d <= max_n && (p < 0 ? -p : p) <= max_bp;
-}
-
-// W: the largest |i - j| of a (kept j, candidate i) pair the scan can reach.  Every walk stops at its first miss; a walk that
-// cannot beat the W found so far is skipped, so a window spanning the chromosome costs O(M) checks.
+// W: the largest |i - j| of a (kept j, candidate i) pair the scan can reach (in_window, ld_band.h: kept SNP j is still listed at
+// candidate i).  Every walk stops at its first miss; a walk that cannot beat the W found so far is skipped, so a window spanning
+// the chromosome costs O(M) checks.
 int64_t prune_width(int64_t M, int64_t start, const int32_t *pos, int32_t max_bp, int32_t max_n)
 {
     if (M <= 1 || max_n <= 0 || max_bp < 0) return 0;
@@ -108,16 +95,6 @@ int prune_scan(int64_t M, int64_t start, const int32_t *pos, int32_t max_bp, int
     return 0;
 }
 
-// 64 x 64 tiles a band launch computes (ld_count_kernel<true>'s exit rule)
-int64_t band_tiles(int64_t n_i, int64_t n_b, int64_t W)
-{
-    int64_t t = 0;
-    for (int64_t x = 0; x < (n_i + 63) / 64; x++)
-        for (int64_t y = 0; y <= (63 + W) / 64; y++)
-            if (64 * y - 63 <= W && 64 * x + 64 * y < n_b) t++;
-    return t;
-}
-
 int check_args(const char *fn, const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, int64_t start_idx, int method)
 {
     if (check_geno(fn, geno, n_snp, n_samp, format, mem, LD_GENO)) return 1;
@@ -142,64 +119,29 @@ int prune_bits(const char *fn, const uint8_t *geno, int64_t M, int64_t N, int fo
     if (W == 0) return 0;
     if (W > 0x3fffffffLL) return fail(fn, "invalid band width");
 
-    const int64_t rbp = pr_up((N + 3) / 4, 32);
-    const int64_t irb = format == SNPGPU_GENO_U8 ? N : (N + 3) / 4;
-    const int64_t blk = o.max_block_snps > 0 ? o.max_block_snps : PRUNE_BLOCK_DEFAULT;
-    const int64_t cap = std::min(M, blk + W);
-    const int64_t P = std::max<int64_t>(64, std::min(pr_up(blk, 64), (int64_t)(PRUNE_TABLE_BUDGET / ((size_t)W * 36)) / 64 * 64));
-    // the table kernel reads whole 64-row tiles, up to 63 rows past the resident ones: one spare tile
-    const size_t rbytes = (size_t)(pr_up(cap, 64) + 64) * (size_t)rbp;
+    BandStream band;
     int rc = 0;
-    DevBuf *rows[2] = {c.bufs.get(rbytes, rc), cap < M ? c.bufs.get(rbytes, rc) : nullptr};
-    DevBuf *tab = c.bufs.get((size_t)(P * W * 36), rc), *dbits = c.bufs.get((size_t)(P * wpr * 8), rc), *raw = c.bufs.get(0, rc);
+    band.open(c.bufs, geno, M, N, format, mem, W, o.max_block_snps, rc);
+    DevBuf *dbits = c.bufs.get((size_t)(band.P * wpr * 8), rc);
     if (rc) return fail(fn, "device allocation failed");
-    // rows past the data only meet pairs the kernel never writes; a defined content all the same, for the spare tile only
-    for (DevBuf *r : rows)
-        if (r) SNPGPU_HIP_CHECK(hipMemsetAsync((uint8_t *)r->p + (size_t)cap * rbp, 0xFF, r->bytes - (size_t)cap * rbp, s));
 
     enum { ST = 0, TAB = 1, BITS = 2, CPY = 3 };
-    int64_t n_fed = 0, base = 0, n_res = 0, done = 0, launches = 0, tiles = 0;
-    int cur = 0;
-    while (n_fed < M) {
-        const int64_t m = std::min(M - n_fed, cap - n_res);
-        if (tm.begin(ST, s) || stage_ld_rows(s, *raw, geno + n_fed * irb, m, N, rbp, format, mem, (uint8_t *)rows[cur]->p + n_res * rbp) ||
-            tm.end(s))
-            return 1;
-        n_res += m; n_fed += m;
-        const bool last = n_fed == M;
-        const int64_t i_end = last ? M : base + n_res - W;
-        const uint8_t *res = (const uint8_t *)rows[cur]->p;
-        for (int64_t i0 = done; i0 < i_end; i0 += P) {
-            const int64_t n_i = std::min(P, i_end - i0);
-            if (tm.begin(TAB, s) || launch_ld_count_band(s, res, (int)(i0 - base), (int)n_i, (int)n_res, (int)W, rbp, (int32_t *)tab->p) ||
-                tm.end(s))
-                return 1;
-            if (tm.begin(BITS, s) ||
-                launch_ld_prune_bits(s, (const int32_t *)tab->p, n_i, (int)W, i0, M, start, method, threshold, (uint64_t *)dbits->p) ||
+    if (band.run(c, ST, TAB, [&](const int32_t *tab, int64_t i0, int64_t n_i) -> int {
+            if (tm.begin(BITS, s) || launch_ld_prune_bits(s, tab, n_i, (int)W, i0, M, start, method, threshold, (uint64_t *)dbits->p) ||
                 tm.end(s))
                 return 1;
             if (tm.begin(CPY, s)) return 1;
             SNPGPU_HIP_CHECK(hipMemcpyAsync(bits.data() + i0 * wpr, dbits->p, (size_t)(n_i * wpr) * 8, hipMemcpyDeviceToHost, s));
-            if (tm.end(s)) return 1;
-            launches++;
-            tiles += band_tiles(n_i, n_res - (i0 - base), W);
-        }
-        done = i_end;
-        if (!last) {
-            const int nxt = cur ^ 1;
-            if (tm.begin(ST, s)) return 1;
-            SNPGPU_HIP_CHECK(hipMemcpyAsync(rows[nxt]->p, res + (i_end - base) * rbp, (size_t)(W * rbp), hipMemcpyDeviceToDevice, s));
-            if (tm.end(s)) return 1;
-            cur = nxt; base = i_end; n_res = W;
-        }
-    }
+            return tm.end(s);
+        }))
+        return 1;
     if (hipStreamSynchronize(s) != hipSuccess) return fail(fn, "kernel failed");
     if (info) {
         if (tm.sum_ms(ST, &info->ms_stage) || tm.sum_ms(TAB, &info->ms_tables) || tm.sum_ms(BITS, &info->ms_bits) ||
             tm.sum_ms(CPY, &info->ms_copy))
             return 1;
-        info->table_launches = launches;
-        info->table_tiles = tiles;
+        info->table_launches = band.launches;
+        info->table_tiles = band.tiles;
     }
     return 0;
 }

@@ -170,6 +170,15 @@ int launch_ld_final_rect(hipStream_t st, const int32_t *tab, int64_t n_i, int64_
 // LD pruning: threshold bits of band tables [n_i][w][9] -> uint64 [n_i][ceil(w / 64)] (pairs with i0 + t < start transposed)
 int launch_ld_prune_bits(hipStream_t st, const int32_t *tab, int64_t n_i, int w, int64_t i0, int64_t n_snp, int64_t start, int method,
                          double threshold, uint64_t *bits);
+// LD scores (kernels_ld_score.hip): band tables [n_i][w][9] of rows i0 ... -> terms vals[(k - 1) n_i + (i - i0)] (NaN: not valid or
+// outside the window hi[]) and the number of valid ones added to the LD_SCORE_COUNT_SLOTS counters at n_valid (their sum counts);
+// then the ordered fold into acc / nv [n_snp]
+constexpr int LD_SCORE_COUNT_SLOTS = 256;
+int launch_ld_score_init(hipStream_t st, double *acc, int32_t *nv, int64_t n, double self);
+int launch_ld_score_terms(hipStream_t st, const int32_t *tab, int64_t n_i, int w, int64_t i0, const int32_t *hi, int method, int adjust,
+                          double *vals, uint64_t *n_valid);
+int launch_ld_score_fold(hipStream_t st, const double *vals, int64_t n_i, int w, int64_t i0, int64_t n_snp, const int32_t *lo,
+                         const int32_t *hi, double *acc, int32_t *nv);
 // staging a feed block (kernels_prep.hip)
 int launch_repack_stats(hipStream_t st, const void *src, int format, int64_t n_snp, int64_t n_samp, uint8_t *packed,
                         int64_t RB, int32_t *sum, int32_t *num, unsigned long long *d_missing);

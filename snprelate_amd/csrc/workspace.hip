@@ -1198,6 +1198,23 @@ int snpgpu_gnrLDpruning(int64_t start_idx, const int32_t *pos_bp, int32_t slide_
                            ld_threshold, method, keep, &o, nullptr);
 }
 
+// snpgpu_ld_score on the selected SNPs (one chromosome, as the caller's loop sets them) in one host block
+int snpgpu_gnrLDScore(const int32_t *pos_bp, int32_t slide_max_bp, int32_t slide_max_n, int method, int flags, int num_thread, int,
+                      double *score, int32_t *n_valid, int32_t *n_window)
+{
+    if (need_ws("snpgpu_gnrLDScore")) return 1;
+    if (num_thread <= 0) { set_error("Invalid 'num.thread'."); return 1; }
+    if (!score) { set_error("snpgpu_gnrLDScore: NULL argument: score is NULL"); return 1; }
+    const int64_t L = (int64_t)g_ws.sel.size();
+    if (L < 1) { set_error("snpgpu_gnrLDScore: no SNP in the working dataset"); return 1; }
+    std::vector<uint8_t> buf;
+    gather_block(0, L, buf);
+    snpgpu_opts o{};
+    o.device = g_ws.device;
+    return snpgpu_ld_score(buf.data(), L, g_ws.n_samp, SNPGPU_GENO_PACKED2, SNPGPU_HOST, pos_bp, slide_max_bp, slide_max_n, method, flags,
+                           score, n_valid, n_window, &o, nullptr);
+}
+
 // gnrIBD_MLE(AlleleFreq, KinshipConstraint, MaxIterCnt, RelTol, CoeffCorrect, method, IfOutNum, NumThread, Verbose),
 // src/genIBD.cpp:1465-1548, on the selected SNPs (method 0 = EM only)
 static int ws_rows(const char *fn, std::vector<uint8_t> &buf)
