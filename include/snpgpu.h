@@ -850,6 +850,38 @@ int snpgpu_gnrPairScore(const int32_t *idx1, const int32_t *idx2, int64_t n_pair
  * the transposition and the matrix kernel read */
 int snpgpu_pair_stats(double *stats);
 
+/* ---- (1j) selection and layout of genotypes: sample subsets, snp.order nodes, snpgdsGetGeno ---------------------------------------
+ * The selected rectangle of a genotype bit stream as SNPGPU_GENO_PACKED2 rows (gnrCopyGenoMem, src/SNPRelate.cpp:322-382, minus
+ * the byte per genotype): dst receives [n_snp_out][ceil(n_samp_out / 4)] bytes, sample samp_index[j] at code j of the row of SNP
+ * snp_index[k], the unused codes of a row's last byte 3.  One description covers byte-aligned PACKED2 rows (major 0, stride 8 rb),
+ * the raw sample.order node (major 0, stride 2 n_samp: a row starts at any even bit), the raw snp.order node (major 1, stride
+ * 2 n_snp), a window of either (pointer advanced, phase in bit0) and host-gathered segments with a phase per row (row_bit). */
+typedef struct snpgpu_geno_src {
+    const void    *bits;            /* 2 bits per genotype, LSB first, 3 = missing                          */
+    int32_t        mem;             /* SNPGPU_HOST / SNPGPU_DEVICE / SNPGPU_HOST_PINNED                      */
+    int32_t        major;           /* 0: a row is a SNP, columns are samples; 1: a row is a sample         */
+    int64_t        n_rows, n_cols;
+    int64_t        bit0;            /* element (r, c) lives at bit  bit0 + r * row_stride_bits + 2 c  ...    */
+    int64_t        row_stride_bits;
+    const int64_t *row_bit;         /* ... or, if not NULL (host, n_rows entries), at bit row_bit[r] + 2 c   */
+    int64_t        n_bytes;         /* extent of `bits`: no byte outside [bits, bits + n_bytes) is needed    */
+} snpgpu_geno_src;
+/* samp_index / snp_index: host, 0-based positions in the source, NULL = all in order; they may permute and repeat entries.
+ * dst in dst_mem (host, pinned host or device memory of `device`); stream: NULL or a stream of `device` (the call returns with the
+ * work complete either way).  The kernels load aligned dwords that hold a byte of [bits, bits + n_bytes) and nothing else, and
+ * store inside dst's n_snp_out * ceil(n_samp_out / 4) bytes only.  Host sources are staged in windows of whole source rows (a
+ * major 1 source larger than the staging size: in windows of SNPs); SNPGPU_SELECT_STAGE_BYTES forces the staging size.
+ * Refused before any device is touched: NULL src / bits / dst, an odd or negative bit position or stride, major other than 0 / 1,
+ * an index outside the source, an element outside n_bytes, dimensions beyond 2^30 - 1 samples or 2^31 - 1 SNPs, an unknown mem;
+ * refused before any launch: a device pointer or a stream that belongs to another device than `device`. */
+int snpgpu_geno_select(const snpgpu_geno_src *src, const int32_t *samp_index, int64_t n_samp_out, const int32_t *snp_index,
+                       int64_t n_snp_out, void *dst, int dst_mem, int device, void *stream);
+/* of the last snpgpu_geno_select on this thread (HIP events, summed over the windows): stats[0] ms of the host-to-device copies of
+ * the source, [1] ms of the copy kernel (major 0, consecutive samples), [2] ms of the gather kernel (major 0, a sample list), [3] ms
+ * of the transposition kernel (major 1), [4] kernel launches, [5] source bytes brought to the device, [6] ms of the copy of the
+ * result to the host, [7] staging windows */
+int snpgpu_geno_select_stats(double *stats);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------------------
  * What THIS device's matrix pipe sustains right now: a register-only stream of one MFMA instruction (never waiting on memory,
  * two waves per SIMD) run for `seconds`, rate taken over the second half.  The kernels of this library run against the socket

@@ -60,6 +60,7 @@ EXPORTS = [
     "snpgpu_pair_tables", "snpgpu_pair_score_final", "snpgpu_pair_score_matrix", "snpgpu_gnrPairScore", "snpgpu_pair_stats",
     "snpgpu_diag_plan", "snpgpu_diag_carry_fallbacks",
     "snpgpu_select_pairs", "snpgpu_multi_select_pairs", "snpgpu_gnrIBDPairs", "snpgpu_gnrIBDPairs_get", "snpgpu_select_stats",
+    "snpgpu_geno_select", "snpgpu_geno_select_stats",
 ]
 FST_WC84, FST_WH02 = 1, 2
 FST_METHODS = ("W&C84", "W&H02")
@@ -106,6 +107,12 @@ class MultiStatus(ctypes.Structure):   # snpgpu_multi_status
 class SelOpts(ctypes.Structure):       # snpgpu_sel_opts
     _fields_ = [("what", ctypes.c_int32), ("kinship_constraint", ctypes.c_int32), ("family", ctypes.c_void_p), ("e", ctypes.c_void_p),
                 ("kinship_cutoff", ctypes.c_double), ("samp_sel", ctypes.c_void_p)]
+
+
+class GenoSrc(ctypes.Structure):       # snpgpu_geno_src
+    _fields_ = [("bits", ctypes.c_void_p), ("mem", ctypes.c_int32), ("major", ctypes.c_int32), ("n_rows", ctypes.c_int64),
+                ("n_cols", ctypes.c_int64), ("bit0", ctypes.c_int64), ("row_stride_bits", ctypes.c_int64), ("row_bit", ctypes.c_void_p),
+                ("n_bytes", ctypes.c_int64)]
 
 
 class EigInfo(ctypes.Structure):       # snpgpu_eig_info
@@ -304,6 +311,8 @@ def lib():
     L.snpgpu_gnrIBDPairs.argtypes = [c_int, vp, vp, c_int, dbl, vp, c_int, c_int, ctypes.POINTER(i64)]
     L.snpgpu_gnrIBDPairs_get.argtypes = [vp, vp, vp, vp, vp]
     L.snpgpu_select_stats.argtypes = [vp]
+    L.snpgpu_geno_select.argtypes = [ctypes.POINTER(GenoSrc), vp, i64, vp, i64, vp, c_int, c_int, vp]
+    L.snpgpu_geno_select_stats.argtypes = [vp]
     _lib = L
     return L
 
@@ -1384,6 +1393,58 @@ def pair_score_matrix(geno, n_samp, idx1, idx2, method="IBS", dosage=True, bit2=
     check(lib().snpgpu_pair_score_matrix(ptr, n, int(n_samp), fmt, mem, _ptr(a), _ptr(b), len(a), _pair_method(method), int(bool(dosage)),
                                          PAIR_ELEM_BIT2 if bit2 else PAIR_ELEM_INT32, _ptr(out), int(device)))
     return out
+
+
+def geno_select(src, major, n_rows, n_cols, bit0=0, row_stride_bits=None, row_bit=None, samp_index=None, snp_index=None, out=None,
+                device=0, n_bytes=None, mem=None, out_mem=None, stream=None):
+    """snpgpu_geno_select: the selected rectangle of a 2-bit genotype stream as PACKED2 rows uint8 [n_snp_out][ceil(n_samp_out / 4)].
+    src: a numpy uint8 array (its bytes, host memory) or an address (int) with n_bytes -- device memory unless mem says HOST or
+    HOST_PINNED.  major 0: the n_rows rows are SNPs and the n_cols columns samples; major 1: the rows are samples.  Element (r, c)
+    lies at bit bit0 + r * row_stride_bits + 2 c (row_stride_bits None: 2 * n_cols, the continuous stream of a GDS node; byte-aligned
+    PACKED2 rows have 8 * ceil(n_cols / 4)), or at bit0 + row_bit[r] + 2 c with row_bit (int64 per row).  samp_index / snp_index:
+    0-based positions in the source, None = all in order.  out: None = a new host array (returned), a numpy uint8 array of the
+    result's size, or an address (device memory unless out_mem says otherwise); returned as given."""
+    keep = None
+    if isinstance(src, int):
+        if n_bytes is None:
+            raise ValueError("a source address needs n_bytes")
+        ptr, mem = ctypes.c_void_p(src), (DEVICE if mem is None else int(mem))
+    else:
+        keep = np.ascontiguousarray(src, dtype=np.uint8)
+        ptr, mem = _ptr(keep), (HOST if mem is None else int(mem))
+        n_bytes = keep.size if n_bytes is None else int(n_bytes)
+        if n_bytes > keep.size:
+            raise ValueError("n_bytes exceeds the source array")
+    major, n_rows, n_cols = int(major), int(n_rows), int(n_cols)
+    rbit = None if row_bit is None else np.ascontiguousarray(row_bit, dtype=np.int64)
+    if rbit is not None and rbit.shape != (n_rows,):
+        raise ValueError("row_bit should hold one bit position per source row")
+    samp = None if samp_index is None else np.ascontiguousarray(samp_index, dtype=np.int32).reshape(-1)
+    snp = None if snp_index is None else np.ascontiguousarray(snp_index, dtype=np.int32).reshape(-1)
+    n_samp_out = (n_rows if major else n_cols) if samp is None else samp.size
+    n_snp_out = (n_cols if major else n_rows) if snp is None else snp.size
+    rb = (n_samp_out + 3) // 4
+    if out is None:
+        out = np.empty((n_snp_out, rb), np.uint8)
+    if isinstance(out, int):
+        optr, out_mem = ctypes.c_void_p(out), (DEVICE if out_mem is None else int(out_mem))
+    else:
+        if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.size == n_snp_out * rb):
+            raise ValueError("out should be a contiguous uint8 array of n_snp_out * ceil(n_samp_out / 4) bytes")
+        optr, out_mem = _ptr(out), (HOST if out_mem is None else int(out_mem))
+    d = GenoSrc(ptr, mem, major, n_rows, n_cols, int(bit0), 2 * n_cols if row_stride_bits is None else int(row_stride_bits),
+                None if rbit is None else rbit.ctypes.data, int(n_bytes))
+    check(lib().snpgpu_geno_select(ctypes.byref(d), _ptr(samp), n_samp_out, _ptr(snp), n_snp_out, optr, out_mem, int(device),
+                                   ctypes.c_void_p(stream) if stream else None))
+    return out
+
+
+def geno_select_stats():
+    """dict of snpgpu_geno_select_stats for the last geno_select call on this thread"""
+    s = np.zeros(8, np.float64)
+    check(lib().snpgpu_geno_select_stats(_ptr(s)))
+    return dict(h2d_ms=float(s[0]), copy_ms=float(s[1]), gather_ms=float(s[2]), transpose_ms=float(s[3]), launches=int(s[4]),
+                source_bytes=float(s[5]), d2h_ms=float(s[6]), windows=int(s[7]))
 
 
 def select_stats():

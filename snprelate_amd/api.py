@@ -30,6 +30,7 @@ INTEGRATION.md):
     snpgdsIBDSelection            R/IBD.R:463-531  (table of pairs at or above a kinship cutoff, on the host)
     snpgdsIBDPairs                no reference counterpart: the same table straight from the GPU counters
     snpgdsLDScore                 no reference counterpart: per-SNP sums of squared LD over a window, folded on the GPU
+    snpgdsGetGeno                 R/AllUtilities.R:1006-1025 (the selected rectangle of the genotype node)
 
 All arithmetic on genotype matrices runs on the MI355X through libsnpgpu.so
 (`_lib`); there is no CPU fallback.  The one exception is snpgdsIndInbCoef, which
@@ -76,7 +77,7 @@ def _init_file2(cmd, gdsobj, sample_id, snp_id, autosome_only=True, remove_monos
     allele_freq follows the reference's bookkeeping: given per entry of `snp_id` (or per SNP of the file), it is
     brought into DATASET order with match(snp.ids[kept], snp.id) (R/Internal.R:355,370,405), drives the SNP filter
     (non-finite = excluded) and is returned subset to the surviving SNPs as ws["allele_freq"]."""
-    if not isinstance(gdsobj, GenoFile):
+    if not isinstance(gdsobj, (GenoFile, _gds.GenoStream)):
         raise TypeError("'gdsobj' should be a SNP GDS object (snpgdsOpen / GenoFile)")
     if num_thread is None or (isinstance(num_thread, float) and math.isnan(num_thread)):
         import os
@@ -134,14 +135,30 @@ def _init_file2(cmd, gdsobj, sample_id, snp_id, autosome_only=True, remove_monos
             allele_freq = allele_freq[snp_flag]
     snp_ids = snp_ids[snp_flag]
 
-    # gnrSetGenoSpace: the selected rectangle becomes the working space
-    packed = gdsobj.packed[snp_flag]
+    # gnrSetGenoSpace: the selected rectangle becomes the working space.  With a sample selection it comes from the device
+    # (snpgpu_geno_select: no byte per genotype on the way) -- out of the object's packed rows, or for a GenoStream out of the
+    # file's node through the reader; without a device the host unpacks, selects and packs (the same bytes).
     n_samp = gdsobj.n_samp
     if samp_flag is not None and not samp_flag.all():
-        from .gds import unpack_2bit_rows
-        g = unpack_2bit_rows(packed, n_samp)[:, samp_flag]
-        packed = pack_2bit_rows(g)
+        if _device_visible():
+            samp_index = np.flatnonzero(samp_flag).astype(np.int32)
+            if isinstance(gdsobj, _gds.GenoStream) and getattr(gdsobj, "_packed", None) is None:
+                # only the SNP range that holds a selected SNP is read; the flags pick the rows inside it
+                kept = np.flatnonzero(snp_flag)
+                k0, k1 = (int(kept[0]), int(kept[-1]) + 1) if kept.size else (0, 0)
+                rows = [r for _, _, r in gdsobj.select_blocks(65536, samp_index=samp_index, snp_begin=k0, snp_end=k1, device=device, to="host")]
+                packed = (np.concatenate(rows, 0) if rows else np.empty((0, (len(samp_index) + 3) // 4), np.uint8))[snp_flag[k0:k1]]
+            else:
+                packed = _lib.geno_select(gdsobj.packed, 0, gdsobj.n_snp, n_samp, row_stride_bits=8 * ((n_samp + 3) // 4),
+                                          samp_index=samp_index, device=device,
+                                          snp_index=None if snp_flag.all() else np.flatnonzero(snp_flag).astype(np.int32))
+        else:
+            from .gds import unpack_2bit_rows
+            g = unpack_2bit_rows(gdsobj.packed[snp_flag], n_samp)[:, samp_flag]
+            packed = pack_2bit_rows(g)
         n_samp = int(samp_flag.sum())
+    else:
+        packed = gdsobj.packed[snp_flag]
     packed = np.ascontiguousarray(packed)
     L = _lib.lib()
     _lib.check(L.snpgpu_ws_set_geno(_lib._ptr(packed), packed.shape[0], n_samp, _lib.GENO_PACKED2, int(device)))
@@ -175,6 +192,14 @@ def _init_file2(cmd, gdsobj, sample_id, snp_id, autosome_only=True, remove_monos
         print("    using %d thread%s (the GPU path ignores num.thread)" % (num_thread, "" if num_thread == 1 else "s"))
     return dict(sample_id=sample_ids, snp_id=snp_ids, n_snp=a.value, n_samp=b.value,
                 num_thread=num_thread, verbose=verbose, packed=packed, device=int(device), allele_freq=allele_freq)
+
+
+def _device_visible():
+    """whether snpgpu_device_count reports a device (the selection of _init_file2 runs there when it does)"""
+    try:
+        return _lib.device_count() > 0
+    except _lib.SnpGpuError:
+        return False
 
 
 def _tri_or_full(n, use_matrix):
@@ -1604,6 +1629,42 @@ def snpgdsSampMissRate(gdsobj, sample_id=None, snp_id=None, with_id=False, devic
     if with_id:
         return dict(sample_id=ws["sample_id"], MissingRate=rv)
     return rv
+
+
+def snpgdsGetGeno(gdsobj, sample_id=None, snp_id=None, snpfirstdim=None, with_id=False, verbose=True, device=0):
+    """A subset of the genotypes of a file (R/AllUtilities.R:1006-1025 -> gnrCopyGenoMem, src/SNPRelate.cpp:322-382).
+    gdsobj: a SNP GDS object, or a file name (opened and closed here).  The selection follows FILE order whatever the order of the
+    id lists, as .InitFile's flags do.  snpfirstdim None (R's NA) follows the file's layout: a snp.order file gives n_snp x n_samp,
+    a sample.order file n_samp x n_snp; True / False force one.  verbose prints the reference's line.  The result is uint8 with
+    3 for a missing call, as read_genotype returns it: numpy has no NA_integer_, which is what R's integer matrix holds there.
+    with_id: dict(genotype, sample_id, snp_id).  Selection and layout run on the device (snpgpu_geno_select, 2 bits per genotype);
+    only the final expansion to one byte per genotype is host numpy, since that part is bound by its own output."""
+    if snpfirstdim is not None and not isinstance(snpfirstdim, (bool, np.bool_)):
+        raise TypeError("is.logical(snpfirstdim) is not TRUE")
+    if not isinstance(with_id, (bool, np.bool_)):
+        raise TypeError("is.logical(with.id) is not TRUE")
+    if not isinstance(verbose, (bool, np.bool_)):
+        raise TypeError("is.logical(verbose) is not TRUE")
+    opened = isinstance(gdsobj, str)
+    if opened:
+        gdsobj = snpgdsOpen(gdsobj, stream=True)
+    try:
+        ws = _init_file(gdsobj, sample_id, snp_id, device)
+    finally:
+        if opened:
+            snpgdsClose(gdsobj)                     # on.exit({ snpgdsClose(gdsobj) })
+    if snpfirstdim is None:
+        snpfirstdim = not getattr(gdsobj, "sample_order", True)
+    g = _gds.unpack_2bit_rows(ws["packed"], ws["n_samp"])
+    if snpfirstdim:
+        _cat(verbose, "Genotype matrix: %d SNPs X %d samples" % (ws["n_snp"], ws["n_samp"]))
+        g = np.ascontiguousarray(g)
+    else:
+        _cat(verbose, "Genotype matrix: %d samples X %d SNPs" % (ws["n_samp"], ws["n_snp"]))
+        g = np.ascontiguousarray(g.T)
+    if with_id:
+        return dict(genotype=g, sample_id=ws["sample_id"], snp_id=ws["snp_id"])
+    return g
 
 
 def snpgdsHWE(gdsobj, sample_id=None, snp_id=None, with_id=False, device=0):

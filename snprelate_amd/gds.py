@@ -81,6 +81,9 @@ class GenoFile:
         self.sample_annot = {} if sample_annot is None else dict(sample_annot)
         # snpgdsOption() defaults (R/AllUtilities.R:1910-1991)
         self.autosome_start, self.autosome_end = 1, 22
+        # the layout of the file the object was read from (open_gds sets it; snpgdsGetGeno's snpfirstdim=None follows it): the
+        # rows held here are SNP-major either way
+        self.sample_order = True
         assert len(self.sample_id) == self.n_samp and len(self.snp_id) == self.n_snp
 
     def read_genotype(self, snp_sel=None, samp_sel=None):
@@ -246,8 +249,10 @@ def open_gds(path):
             dims, dsid, is_zip, _ = _node_info(streams[sid])
             return dims, (zlib.decompress(streams[dsid]) if is_zip else streams[dsid])
         annot = _sample_annot(_dir_entries(streams[entries["sample.annot"]]), raw_id)
-    return GenoFile(genotype=geno, sample_id=sample_id, snp_id=snp_id, snp_chromosome=chrom, snp_position=position,
-                    sample_annot=annot)
+    gf = GenoFile(genotype=geno, sample_id=sample_id, snp_id=snp_id, snp_chromosome=chrom, snp_position=position,
+                  sample_annot=annot)
+    gf.sample_order = b"sample.order" in attr
+    return gf
 
 
 # ---------------------------------------------------------------------------
@@ -330,6 +335,24 @@ def realign_bit2_rows(seg, seg_bit0, n_samp, row_begin, row_end, out=None):
     return out
 
 
+def gather_segments(src, start, w, out):
+    """out[j] = src[start[j] : start[j] + w] for a 1-D byte array (a memory map included): only those bytes of src are touched,
+    and the temporaries stay below 1 MiB whatever the sizes of src and out.  Segments of 256 bytes or more are copied one slice per
+    row (a memcpy each); shorter ones are gathered through index blocks of at most 2^17 entries, so that a block of few SNPs does
+    not pay a Python step per sample."""
+    n = len(start)
+    if w >= 256:
+        for j in range(n):
+            a = int(start[j])
+            out[j] = src[a:a + w]
+        return out
+    cols = np.arange(w, dtype=np.int64)
+    step = max(1, (1 << 17) // w)
+    for a in range(0, n, step):
+        np.take(src, start[a:a + step, None] + cols, out=out[a:a + step], mode="clip")
+    return out
+
+
 class GenoStream:
     """Streaming view of a SNP GDS file: metadata in memory, `genotype` on disk.
 
@@ -404,6 +427,92 @@ class GenoStream:
                 rows = out
                 turn += 1
             yield lo, hi - lo, rows
+
+    def _snp_order_bytes(self):
+        """the bytes of a snp.order node for select_blocks: a memory map of a raw single-extent node, else the node inflated once
+        into host memory under the rule (and the SNPGPU_GDS_INFLATE_MAX refusal) of _blocks_snp_order"""
+        if not (self._zipped or len(self._extents) != 1):
+            return np.memmap(self.path, dtype=np.uint8, mode="r", offset=self._extents[0][0], shape=(self._extents[0][1],))
+        mm = getattr(self, "_inflated", None)
+        if mm is None:
+            import os
+            need = (2 * self.n_samp * self.n_snp + 7) // 8
+            cap = int(os.environ.get("SNPGPU_GDS_INFLATE_MAX", 8 << 30))
+            if need > cap:
+                raise ValueError("a compressed snp.order genotype node of %d bytes does not fit the in-memory budget of %d bytes "
+                                 "(SNPGPU_GDS_INFLATE_MAX)" % (need, cap))
+            with open(self.path, "rb") as f:
+                mm = np.frombuffer(_ByteStream(f, self._extents, self._length, self._zipped).read(0, need), np.uint8)
+            self._inflated = mm
+        return mm
+
+    def select_blocks(self, block_snps, samp_index=None, snp_begin=0, snp_end=None, device=0, to="device"):
+        """Blocks (snp_begin, n_snp, rows) of the SELECTED samples for both file layouts, laid out on the device
+        (snpgpu_geno_select): rows are 2-bit rows [n_snp][ceil(n_sel / 4)] with sample samp_index[j] (0-based, any order, repeats
+        allowed; None = all) at code j.  to="device": rows is a torch uint8 tensor on cuda:`device`; the blocks alternate between
+        two buffers, so a block stays valid until the next-but-one next().  to="host": a new numpy array per block.
+        Only the bytes needed are read: the block's byte range of a sample.order node; of a snp.order node the selected samples'
+        segments of the block's SNP range, copied segment by segment (gather_segments) into a page-locked buffer with a bit phase
+        per row.  Not more: the memory map is never copied or viewed as a whole."""
+        from . import _lib
+        if to not in ("device", "host"):
+            raise ValueError("'to' should be \"device\" or \"host\"")
+        block_snps = int(block_snps)
+        if block_snps < 1:
+            raise ValueError("block_snps should be positive")
+        n, L = self.n_samp, self.n_snp
+        snp_begin = int(snp_begin)
+        snp_end = L if snp_end is None else min(int(snp_end), L)
+        samp = None
+        if samp_index is not None:
+            samp = np.ascontiguousarray(samp_index, dtype=np.int32).reshape(-1)
+            if samp.size == 0 or samp.min() < 0 or samp.max() >= n:
+                raise ValueError("samp_index should hold positions 0 ... n_samp - 1 of the file's samples")
+        n_out = n if samp is None else samp.size
+        rb = (n_out + 3) // 4
+        bmax = max(1, min(block_snps, snp_end - snp_begin))
+        dev_bufs = pinned = None
+        if to == "device":
+            import torch
+            dev_bufs = [torch.empty((bmax, rb), dtype=torch.uint8, device="cuda:%d" % int(device)) for _ in range(2)]
+
+        def out_of(turn, m):
+            if dev_bufs is None:
+                return np.empty((m, rb), np.uint8), None
+            t = dev_bufs[turn & 1][:m]
+            return int(t.data_ptr()), t
+
+        try:
+            if self.sample_order:
+                with open(self.path, "rb") as f:
+                    st = _ByteStream(f, self._extents, self._length, self._zipped)
+                    for turn, lo in enumerate(range(snp_begin, snp_end, block_snps)):
+                        hi = min(lo + block_snps, snp_end)
+                        b0, b1 = (2 * n * lo) >> 3, (2 * n * hi + 7) >> 3
+                        seg = np.frombuffer(st.read(b0, b1), np.uint8)
+                        out, t = out_of(turn, hi - lo)
+                        _lib.geno_select(seg, 0, hi - lo, n, bit0=2 * n * lo - 8 * b0, row_stride_bits=2 * n, samp_index=samp, out=out,
+                                         device=device)
+                        yield lo, hi - lo, (out if t is None else t)
+            else:
+                mm = self._snp_order_bytes()
+                rows = np.arange(n, dtype=np.int64) if samp is None else samp.astype(np.int64)
+                w = min(len(mm), (2 * bmax + 6 + 7) >> 3)                       # bytes of a segment at the worst phase
+                pinned = _lib.PinnedBuffer((n_out * w,))
+                for turn, lo in enumerate(range(snp_begin, snp_end, block_snps)):
+                    hi = min(lo + block_snps, snp_end)
+                    bit = 2 * (rows * L + lo)
+                    start = np.minimum(bit >> 3, len(mm) - w)                   # a window at the end of the node is moved back
+                    stage = pinned.array[:n_out * w].reshape(n_out, w)
+                    gather_segments(mm, start, w, stage)
+                    row_bit = 8 * w * np.arange(n_out, dtype=np.int64) + (bit - 8 * start)
+                    out, t = out_of(turn, hi - lo)
+                    _lib.geno_select(pinned.ptr, 1, n_out, hi - lo, row_bit=row_bit, n_bytes=n_out * w, mem=_lib.HOST_PINNED, out=out,
+                                     device=device)
+                    yield lo, hi - lo, (out if t is None else t)
+        finally:
+            if pinned is not None:
+                pinned.free()
 
     def read_packed(self, block_snps=65536):
         """the whole genotype node as 2-bit rows (small files; tests)"""
