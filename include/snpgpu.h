@@ -882,6 +882,34 @@ int snpgpu_geno_select(const snpgpu_geno_src *src, const int32_t *samp_index, in
  * result to the host, [7] staging windows */
 int snpgpu_geno_select_stats(double *stats);
 
+/* ---- (1k) PLINK BED: the other 2-bit code set and the other layout of dst ----------------------------------------------------------
+ * snpgpu_geno_select with a code set on either side and a choice of which axis dst packs.  Both code sets hold 2 bits per
+ * genotype, 4 per byte, LSB first:
+ *   SNPGPU_CODE_GDS  the number of A alleles 0 / 1 / 2, 3 = missing; the unused codes of a row's last byte are 3
+ *                    (SNPGPU_GENO_PACKED2, the GDS genotype node)
+ *   SNPGPU_CODE_BED  0 = homozygous A1, 1 = missing, 2 = heterozygous, 3 = homozygous A2; the unused codes of a row's last byte
+ *                    are 0 (a PLINK .bed file after its 3-byte header: mode 1 is major 0 with stride 8 ceil(n_samp / 4), mode 0
+ *                    is major 1 with stride 8 ceil(n_snp / 4))
+ * BED -> GDS is {2, 3, 1, 0} (src/ConvToGDS.cpp:585), GDS -> BED is {3, 2, 0, 1} (src/SNPRelate.cpp:801); equal codes copy.
+ * The padding of a source is never read as a genotype; dst's padding is that of dst_code.
+ *   dst_major 0  dst is [n_snp_out][ceil(n_samp_out / 4)]: SNP rows, as snpgpu_geno_select (BED mode 1)
+ *   dst_major 1  dst is [n_samp_out][ceil(n_snp_out / 4)]: sample rows, sample samp_index[j] in row j, SNP snp_index[k] at
+ *                code k (BED mode 0)
+ * dst_major 1 runs the same kernels with the two axes and the two index lists exchanged, so the limits follow dst's axes: the
+ * axis packed into dst's rows holds at most 2^30 - 1 entries, the row axis 2^31 - 1.  dst_major 0: 2^30 - 1 samples and
+ * 2^31 - 1 SNPs, as snpgpu_geno_select; dst_major 1: 2^30 - 1 SNPs, and samples stay at 2^30 - 1 (the description of a source
+ * allows no more).  Sources, staging windows, memory kinds, stream and every other refusal are those of snpgpu_geno_select; the
+ * staging windows of a host source larger than the staging size are whole source rows when the source's major equals dst_major,
+ * windows of dst's rows otherwise.  Also refused before any device is touched: a src_code, dst_code or dst_major that is none of
+ * the above.  snpgpu_geno_select is the call (SNPGPU_CODE_GDS, SNPGPU_CODE_GDS, dst_major 0). */
+enum { SNPGPU_CODE_GDS = 0, SNPGPU_CODE_BED = 1 };
+int snpgpu_geno_convert(const snpgpu_geno_src *src, int src_code, const int32_t *samp_index, int64_t n_samp_out,
+                        const int32_t *snp_index, int64_t n_snp_out, void *dst, int dst_major, int dst_code, int dst_mem, int device,
+                        void *stream);
+/* of the last snpgpu_geno_convert on this thread: the fields of snpgpu_geno_select_stats ([1], [2]: the source's major equals
+ * dst_major; [3]: it differs).  The two calls share the record: either one reports the last call of either. */
+int snpgpu_geno_convert_stats(double *stats);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------------------
  * What THIS device's matrix pipe sustains right now: a register-only stream of one MFMA instruction (never waiting on memory,
  * two waves per SIMD) run for `seconds`, rate taken over the second half.  The kernels of this library run against the socket

@@ -19,6 +19,7 @@ DISS = 8
 GENO_U8, GENO_PACKED2 = 0, 1
 LD_COMPOSITE, LD_R, LD_DPRIME, LD_CORR, LD_COV = 1, 2, 3, 4, 5
 HOST, DEVICE, HOST_PINNED = 0, 1, 2
+CODE_GDS, CODE_BED = 0, 1
 
 EXPORTS = [
     "snpgpu_abi_version", "snpgpu_last_error", "snpgpu_device_count",
@@ -61,6 +62,7 @@ EXPORTS = [
     "snpgpu_diag_plan", "snpgpu_diag_carry_fallbacks",
     "snpgpu_select_pairs", "snpgpu_multi_select_pairs", "snpgpu_gnrIBDPairs", "snpgpu_gnrIBDPairs_get", "snpgpu_select_stats",
     "snpgpu_geno_select", "snpgpu_geno_select_stats",
+    "snpgpu_geno_convert", "snpgpu_geno_convert_stats",
 ]
 FST_WC84, FST_WH02 = 1, 2
 FST_METHODS = ("W&C84", "W&H02")
@@ -313,6 +315,8 @@ def lib():
     L.snpgpu_select_stats.argtypes = [vp]
     L.snpgpu_geno_select.argtypes = [ctypes.POINTER(GenoSrc), vp, i64, vp, i64, vp, c_int, c_int, vp]
     L.snpgpu_geno_select_stats.argtypes = [vp]
+    L.snpgpu_geno_convert.argtypes = [ctypes.POINTER(GenoSrc), c_int, vp, i64, vp, i64, vp, c_int, c_int, c_int, c_int, vp]
+    L.snpgpu_geno_convert_stats.argtypes = [vp]
     _lib = L
     return L
 
@@ -1395,15 +1399,10 @@ def pair_score_matrix(geno, n_samp, idx1, idx2, method="IBS", dosage=True, bit2=
     return out
 
 
-def geno_select(src, major, n_rows, n_cols, bit0=0, row_stride_bits=None, row_bit=None, samp_index=None, snp_index=None, out=None,
-                device=0, n_bytes=None, mem=None, out_mem=None, stream=None):
-    """snpgpu_geno_select: the selected rectangle of a 2-bit genotype stream as PACKED2 rows uint8 [n_snp_out][ceil(n_samp_out / 4)].
-    src: a numpy uint8 array (its bytes, host memory) or an address (int) with n_bytes -- device memory unless mem says HOST or
-    HOST_PINNED.  major 0: the n_rows rows are SNPs and the n_cols columns samples; major 1: the rows are samples.  Element (r, c)
-    lies at bit bit0 + r * row_stride_bits + 2 c (row_stride_bits None: 2 * n_cols, the continuous stream of a GDS node; byte-aligned
-    PACKED2 rows have 8 * ceil(n_cols / 4)), or at bit0 + row_bit[r] + 2 c with row_bit (int64 per row).  samp_index / snp_index:
-    0-based positions in the source, None = all in order.  out: None = a new host array (returned), a numpy uint8 array of the
-    result's size, or an address (device memory unless out_mem says otherwise); returned as given."""
+def _geno_convert(call, src, major, n_rows, n_cols, bit0, row_stride_bits, row_bit, samp_index, snp_index, out, device, n_bytes, mem,
+                  out_mem, stream, dst_major=0):
+    """the argument handling geno_select and geno_convert share; call(desc, samp, n_samp_out, snp, n_snp_out, out pointer, out_mem,
+    device, stream) is the C entry point"""
     keep = None
     if isinstance(src, int):
         if n_bytes is None:
@@ -1423,26 +1422,64 @@ def geno_select(src, major, n_rows, n_cols, bit0=0, row_stride_bits=None, row_bi
     snp = None if snp_index is None else np.ascontiguousarray(snp_index, dtype=np.int32).reshape(-1)
     n_samp_out = (n_rows if major else n_cols) if samp is None else samp.size
     n_snp_out = (n_cols if major else n_rows) if snp is None else snp.size
-    rb = (n_samp_out + 3) // 4
+    shape = (n_samp_out, (n_snp_out + 3) // 4) if dst_major else (n_snp_out, (n_samp_out + 3) // 4)
     if out is None:
-        out = np.empty((n_snp_out, rb), np.uint8)
+        out = np.empty(shape, np.uint8)
     if isinstance(out, int):
         optr, out_mem = ctypes.c_void_p(out), (DEVICE if out_mem is None else int(out_mem))
     else:
-        if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.size == n_snp_out * rb):
-            raise ValueError("out should be a contiguous uint8 array of n_snp_out * ceil(n_samp_out / 4) bytes")
+        if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.size == shape[0] * shape[1]):
+            raise ValueError("out should be a contiguous uint8 array of n_samp_out * ceil(n_snp_out / 4) bytes" if dst_major else
+                             "out should be a contiguous uint8 array of n_snp_out * ceil(n_samp_out / 4) bytes")
         optr, out_mem = _ptr(out), (HOST if out_mem is None else int(out_mem))
     d = GenoSrc(ptr, mem, major, n_rows, n_cols, int(bit0), 2 * n_cols if row_stride_bits is None else int(row_stride_bits),
                 None if rbit is None else rbit.ctypes.data, int(n_bytes))
-    check(lib().snpgpu_geno_select(ctypes.byref(d), _ptr(samp), n_samp_out, _ptr(snp), n_snp_out, optr, out_mem, int(device),
-                                   ctypes.c_void_p(stream) if stream else None))
+    check(call(ctypes.byref(d), _ptr(samp), n_samp_out, _ptr(snp), n_snp_out, optr, out_mem, int(device),
+               ctypes.c_void_p(stream) if stream else None))
     return out
+
+
+def geno_select(src, major, n_rows, n_cols, bit0=0, row_stride_bits=None, row_bit=None, samp_index=None, snp_index=None, out=None,
+                device=0, n_bytes=None, mem=None, out_mem=None, stream=None):
+    """snpgpu_geno_select: the selected rectangle of a 2-bit genotype stream as PACKED2 rows uint8 [n_snp_out][ceil(n_samp_out / 4)].
+    src: a numpy uint8 array (its bytes, host memory) or an address (int) with n_bytes -- device memory unless mem says HOST or
+    HOST_PINNED.  major 0: the n_rows rows are SNPs and the n_cols columns samples; major 1: the rows are samples.  Element (r, c)
+    lies at bit bit0 + r * row_stride_bits + 2 c (row_stride_bits None: 2 * n_cols, the continuous stream of a GDS node; byte-aligned
+    PACKED2 rows have 8 * ceil(n_cols / 4)), or at bit0 + row_bit[r] + 2 c with row_bit (int64 per row).  samp_index / snp_index:
+    0-based positions in the source, None = all in order.  out: None = a new host array (returned), a numpy uint8 array of the
+    result's size, or an address (device memory unless out_mem says otherwise); returned as given."""
+    return _geno_convert(lib().snpgpu_geno_select, src, major, n_rows, n_cols, bit0, row_stride_bits, row_bit, samp_index, snp_index, out,
+                         device, n_bytes, mem, out_mem, stream)
+
+
+def geno_convert(src, major, n_rows, n_cols, src_code=CODE_GDS, dst_code=CODE_GDS, dst_major=0, bit0=0, row_stride_bits=None,
+                 row_bit=None, samp_index=None, snp_index=None, out=None, device=0, n_bytes=None, mem=None, out_mem=None, stream=None):
+    """snpgpu_geno_convert: geno_select with a code set on either side (CODE_GDS: 0 / 1 / 2 A alleles, 3 missing, padding 3;
+    CODE_BED: PLINK's 0 / 1 missing / 2 / 3, padding 0) and the layout of the result: dst_major 0 gives SNP rows uint8
+    [n_snp_out][ceil(n_samp_out / 4)] (.bed mode 1), dst_major 1 sample rows uint8 [n_samp_out][ceil(n_snp_out / 4)] (.bed mode 0).
+    Every other argument as geno_select."""
+    L = lib()
+
+    def call(d, samp, n_samp_out, snp, n_snp_out, optr, out_mem, device, stream):
+        return L.snpgpu_geno_convert(d, int(src_code), samp, n_samp_out, snp, n_snp_out, optr, int(dst_major), int(dst_code), out_mem,
+                                     device, stream)
+    return _geno_convert(call, src, major, n_rows, n_cols, bit0, row_stride_bits, row_bit, samp_index, snp_index, out, device, n_bytes,
+                         mem, out_mem, stream, dst_major=1 if dst_major == 1 else 0)
 
 
 def geno_select_stats():
     """dict of snpgpu_geno_select_stats for the last geno_select call on this thread"""
     s = np.zeros(8, np.float64)
     check(lib().snpgpu_geno_select_stats(_ptr(s)))
+    return dict(h2d_ms=float(s[0]), copy_ms=float(s[1]), gather_ms=float(s[2]), transpose_ms=float(s[3]), launches=int(s[4]),
+                source_bytes=float(s[5]), d2h_ms=float(s[6]), windows=int(s[7]))
+
+
+def geno_convert_stats():
+    """dict of snpgpu_geno_convert_stats for the last geno_convert (or geno_select) call on this thread: the fields of
+    geno_select_stats"""
+    s = np.zeros(8, np.float64)
+    check(lib().snpgpu_geno_convert_stats(_ptr(s)))
     return dict(h2d_ms=float(s[0]), copy_ms=float(s[1]), gather_ms=float(s[2]), transpose_ms=float(s[3]), launches=int(s[4]),
                 source_bytes=float(s[5]), d2h_ms=float(s[6]), windows=int(s[7]))
 

@@ -31,6 +31,9 @@ INTEGRATION.md):
     snpgdsIBDPairs                no reference counterpart: the same table straight from the GPU counters
     snpgdsLDScore                 no reference counterpart: per-SNP sums of squared LD over a window, folded on the GPU
     snpgdsGetGeno                 R/AllUtilities.R:1006-1025 (the selected rectangle of the genotype node)
+    snpgdsOpenBED                 R/Conversion.R:433-653 (snpgdsBED2GDS + snpgdsOpen: a PLINK .bed/.bim/.fam triple read in place)
+    snpgdsGDS2BED                 R/Conversion.R:310-425 (the selected rectangle as PLINK .bed/.bim/.fam)
+    snpgdsOption                  R/AllUtilities.R:1910-1990 (without a file: the chromosome codes snpgdsOpenBED takes)
 
 All arithmetic on genotype matrices runs on the MI355X through libsnpgpu.so
 (`_lib`); there is no CPU fallback.  The one exception is snpgdsIndInbCoef, which
@@ -46,6 +49,7 @@ import numpy as np
 
 from . import _lib
 from . import gds as _gds
+from . import bed as _bed
 from .gds import GenoFile, open_gds, pack_2bit_rows  # noqa: F401
 
 
@@ -116,6 +120,10 @@ def _init_file2(cmd, gdsobj, sample_id, snp_id, autosome_only=True, remove_monos
         raise ValueError("'length(allele.freq)' should be the number of SNPs.")
     if autosome_only is not False:
         chrom = gdsobj.snp_chromosome
+        if autosome_only is True and chrom.dtype.kind in "USO":
+            # a text node (snpgdsOpenBED(cvt_chr="char")): the labels that parse into the autosome range
+            val, ok = _bed.chrom_numeric(chrom)
+            chrom = np.where(ok, val, gdsobj.autosome_start - 1)
         if autosome_only is True:
             # gnrChromRangeNumeric, src/SNPRelate.cpp:1035-1062 with snpgdsOption() defaults
             auto = (chrom >= gdsobj.autosome_start) & (chrom <= gdsobj.autosome_end)
@@ -1665,6 +1673,175 @@ def snpgdsGetGeno(gdsobj, sample_id=None, snp_id=None, snpfirstdim=None, with_id
     if with_id:
         return dict(genotype=g, sample_id=ws["sample_id"], snp_id=ws["snp_id"])
     return g
+
+
+def snpgdsOption(autosome_start=1, autosome_end=22, **chromosome_code):
+    """snpgdsOption() without a file (R/AllUtilities.R:1910-1990): dict(autosome_start, autosome_end, chromosome_code), the codes
+    X, XY, Y, M = MT = autosome_end + 1 ... + 4 unless others are named.  The `option` of snpgdsOpenBED."""
+    return _bed.default_option(autosome_start, autosome_end, **chromosome_code)
+
+
+def snpgdsOpenBED(bed_fn, fam_fn=None, bim_fn=None, family=False, option=None, cvt_chr="int", cvt_snpid="auto", verbose=True):
+    """Open a PLINK binary PED file for every snpgds* function: snpgdsBED2GDS (R/Conversion.R:433-653) + snpgdsOpen in one step,
+    without the GDS file in between.  Returns a bed.BedStream -- a GenoStream whose sample_id, snp_id (snp_rs_id), snp_chromosome,
+    snp_position, snp_allele and sample_annot are what snpgdsBED2GDS would have stored, and whose genotypes stay in the .bed file
+    (memory-mapped; a .bed.gz is inflated once) and are recoded on the device, block by block, as they are read.
+    fam_fn and bim_fn both None: they are named after bed_fn (R/Conversion.R:440-446).  family: keep FamilyID, PatID, MatID in
+    sample_annot.  option: snpgdsOption(...) for cvt_chr="int" (chromosome labels through its codes, non-numeric ones become 0 with
+    a warning); cvt_chr="char" keeps the labels.  cvt_snpid="auto" keeps the .bim ids when they are unique, else 1 ... n_snp.
+    There is no snpgdsBED2GDS here: writing the GDS container is gdsfmt's work, which this package does not restate; the
+    arguments that only shape that file (out.gdsfn, snpfirstdim, compress.*) have no counterpart."""
+    if not isinstance(bed_fn, str):
+        raise TypeError("is.character(bed.fn) is not TRUE")
+    for v, name in ((family, "family"), (verbose, "verbose")):
+        if not isinstance(v, (bool, np.bool_)):
+            raise TypeError("is.logical(%s) is not TRUE" % name)
+    if fam_fn is None and bim_fn is None:
+        import re
+        fn = re.sub(r"\.bed$", "", bed_fn, flags=re.IGNORECASE)
+        bed_fn, fam_fn, bim_fn = fn + ".bed", fn + ".fam", fn + ".bim"
+    if not isinstance(fam_fn, str):
+        raise TypeError("is.character(fam.fn) is not TRUE")
+    if not isinstance(bim_fn, str):
+        raise TypeError("is.character(bim.fn) is not TRUE")
+    _cat(verbose, "Open a PLINK BED file as a SNP GDS object ...")
+    bs = _bed.BedStream(bed_fn, fam_fn, bim_fn, family=family, option=option, cvt_chr=cvt_chr, cvt_snpid=cvt_snpid)
+    if verbose:
+        import os
+        print("    BED file: '%s'" % bed_fn)
+        print("        %s, %d bytes" % ("SNP-major mode (Sample X SNP)" if bs.mode else "individual-major mode (SNP X Sample)",
+                                       os.path.getsize(bed_fn)))
+        print("    FAM file: '%s'" % fam_fn)
+        print("    BIM file: '%s'" % bim_fn)
+        print("    %d samples, %d SNPs" % (bs.n_samp, bs.n_snp))
+    return bs
+
+
+def _bim_chromosomes(gdsobj, chrom):
+    """the chromosome column of snpgdsGDS2BED (R/Conversion.R:354-379): labels through the object's chromosome codes, then PLINK's
+    numbers for X, Y, XY, M / MT when the autosomes are 1 ... 22.  The two substitutions run one after the other as the reference
+    runs them, so that with the default codes (XY = 24, Y = 25) 24 is written as 25 and 25 as 24."""
+    x = np.array([str(c) for c in chrom], dtype=object)
+    a0, a1 = getattr(gdsobj, "autosome_start", 1), getattr(gdsobj, "autosome_end", 22)
+    code = getattr(gdsobj, "chromosome_code", None)
+    if code is None:
+        code = _bed.default_option(a0, a1)["chromosome_code"]
+    for name, c in code.items():
+        x[x == str(c)] = name
+    if a0 == 1 and a1 == 22:
+        for name, c in (("X", "23"), ("Y", "24"), ("XY", "25"), ("M", "26"), ("MT", "26")):
+            x[x == name] = c
+    return x
+
+
+def snpgdsGDS2BED(gdsobj, bed_fn, sample_id=None, snp_id=None, snpfirstdim=None, verbose=True, device=0):
+    """Write the selected genotypes as PLINK binary PED (R/Conversion.R:310-425): bed_fn + ".bed", ".bim", ".fam".  gdsobj: a
+    SNP GDS object of any kind -- a BedStream gives BED -> BED subsetting -- or the name of a GDS file.  The selection follows FILE
+    order.  snpfirstdim=True writes mode byte 0 (individual-major), False mode byte 1 (SNP-major); None follows the object's
+    layout (a sample.order file gives False).  .bim: tab-separated, genetic distance 0, alleles from snp_allele or A / B with the
+    reference's warning; .fam: 0, id, 0, 0, 0, -9.  The genotype bytes come from the device (snpgpu_geno_convert) in the file's
+    layout, block by block; without a visible device numpy writes the same bytes."""
+    opened = isinstance(gdsobj, str)
+    if opened:
+        gdsobj = snpgdsOpen(gdsobj, stream=True)
+    if not isinstance(gdsobj, (GenoFile, _gds.GenoStream)):
+        raise TypeError("'gdsobj' should be a SNP GDS object (snpgdsOpen / GenoFile)")
+    if not isinstance(bed_fn, str):
+        raise TypeError("is.character(bed.fn) is not TRUE")
+    if not isinstance(verbose, (bool, np.bool_)):
+        raise TypeError("is.logical(verbose) is not TRUE")
+    if snpfirstdim is not None and not isinstance(snpfirstdim, (bool, np.bool_)):
+        raise TypeError("is.logical(snpfirstdim) is not TRUE")
+    flags = []
+    for want, have, name, what in ((sample_id, gdsobj.sample_id, "sample.id", "sample"), (snp_id, gdsobj.snp_id, "snp.id", "SNP")):
+        f = np.ones(len(have), bool)
+        if want is not None:
+            f = np.isin(have, np.asarray(want))
+            if int(f.sum()) != len(want):
+                raise ValueError("Some of %s do not exist!" % name)
+            if f.sum() <= 0:
+                raise ValueError("No %s in the working dataset." % what)
+        flags.append(f)
+    samp_flag, snp_flag = flags
+    if snpfirstdim is None:
+        snpfirstdim = not getattr(gdsobj, "sample_order", True)
+    n, ns, Ls = gdsobj.n_samp, int(samp_flag.sum()), int(snp_flag.sum())
+    _cat(verbose, "Converting from GDS to PLINK binary PED:")
+    _cat(verbose, "Working space: %d samples, %d SNPs" % (ns, Ls))
+
+    if gdsobj.snp_position is None:
+        raise ValueError("the object has no snp.position, which the .bim file needs")
+    allele = getattr(gdsobj, "snp_allele", None)
+    if allele is not None:
+        parts = [str(a).split("/") for a in np.asarray(allele)[snp_flag]]
+        ref, nonref = [p[0] for p in parts], [p[1] if len(p) > 1 else "" for p in parts]
+    else:
+        warnings.warn("There is no allele information in the GDS file. ``A/B'' is used for the last two columns.")
+        ref, nonref = ["A"] * Ls, ["B"] * Ls
+    xchr = _bim_chromosomes(gdsobj, np.asarray(gdsobj.snp_chromosome)[snp_flag])
+    with open(bed_fn + ".bim", "w") as f:
+        for c, rs, pos, a, b in zip(xchr, gdsobj.snp_id[snp_flag], gdsobj.snp_position[snp_flag], ref, nonref):
+            f.write("%s\t%s\t0\t%d\t%s\t%s\n" % (c, rs, pos, a, b))
+    _cat(verbose, "Output a BIM file.")
+    with open(bed_fn + ".fam", "w") as f:
+        for sid in gdsobj.sample_id[samp_flag]:
+            f.write("0\t%s\t0\t0\t0\t-9\n" % sid)
+    _cat(verbose, "Output a BED file ...")
+
+    # the body, in blocks of selected SNPs (a multiple of 4, so that a block is whole bytes of an individual-major row too)
+    rows, cols = (ns, Ls) if snpfirstdim else (Ls, ns)
+    with open(bed_fn + ".bed", "wb") as f:
+        f.write(_bed.MAGIC + bytes([0 if snpfirstdim else 1]))
+        f.truncate(3 + rows * ((cols + 3) // 4))
+    body = np.memmap(bed_fn + ".bed", dtype=np.uint8, mode="r+", offset=3, shape=(rows, (cols + 3) // 4))
+    try:
+        for a, b, blk in _bed_blocks(gdsobj, samp_flag, snp_flag, bool(snpfirstdim), 65536, device):
+            if snpfirstdim:
+                body[:, a >> 2:(b + 3) >> 2] = blk
+            else:
+                body[a:b] = blk
+        body.flush()
+    finally:
+        del body
+        if opened:
+            snpgdsClose(gdsobj)
+    _cat(verbose, "Done.")
+    return None
+
+
+def _bed_blocks(gdsobj, samp_flag, snp_flag, individual_major, block, device):
+    """(a, b, bytes) for the selected SNPs a ... b - 1 of snpgdsGDS2BED: their .bed bytes of the selected samples, uint8
+    [b - a][ceil(n_sel / 4)], or for individual_major [n_sel][ceil((b - a) / 4)].  With a device: one snpgpu_geno_convert per block
+    -- from the packed rows in host memory, or, for a stream that is read whole (no SNP selection) and not yet in memory, from
+    the device rows select_blocks lays out.  Without one: numpy (bed.encode_bed)."""
+    n, rb = gdsobj.n_samp, (gdsobj.n_samp + 3) // 4
+    samp_index = None if samp_flag.all() else np.flatnonzero(samp_flag).astype(np.int32)
+    ns = n if samp_index is None else len(samp_index)
+    dm = 1 if individual_major else 0
+    on_device = _device_visible()
+    if on_device and isinstance(gdsobj, _gds.GenoStream) and getattr(gdsobj, "_packed", None) is None and snp_flag.all():
+        for lo, m, rows in gdsobj.select_blocks(block, samp_index=samp_index, device=device, to="device"):
+            rbs = (ns + 3) // 4
+            yield lo, lo + m, _lib.geno_convert(int(rows.data_ptr()), 0, m, ns, dst_code=_lib.CODE_BED, dst_major=dm,
+                                                row_stride_bits=8 * rbs, n_bytes=m * rbs, device=device)
+        return
+    packed, pos = gdsobj.packed, np.flatnonzero(snp_flag)
+    for a in range(0, len(pos), block):
+        b = min(a + block, len(pos))
+        k0, k1 = int(pos[a]), int(pos[b - 1]) + 1
+        idx = None if k1 - k0 == b - a else (pos[a:b] - k0).astype(np.int32)
+        if on_device:
+            src, m, cols, sel = packed[k0:k1], k1 - k0, n, samp_index
+            if individual_major and sel is not None:
+                # samples are the rows of dst here, and a list of them cuts the transposition into one segment per run of
+                # consecutive samples: select first, then transpose all
+                src = _lib.geno_select(src, 0, m, n, row_stride_bits=8 * rb, samp_index=sel, snp_index=idx, device=device)
+                m, cols, sel, idx = b - a, ns, None, None
+            yield a, b, _lib.geno_convert(src, 0, m, cols, dst_code=_lib.CODE_BED, dst_major=dm, row_stride_bits=8 * ((cols + 3) // 4),
+                                          samp_index=sel, snp_index=idx, device=device)
+        else:
+            g = _gds.unpack_2bit_rows(packed[k0:k1] if idx is None else packed[k0:k1][idx], n)
+            yield a, b, _bed.encode_bed(g if samp_index is None else g[:, samp_index], individual_major)
 
 
 def snpgdsHWE(gdsobj, sample_id=None, snp_id=None, with_id=False, device=0):

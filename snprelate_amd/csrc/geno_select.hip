@@ -1,7 +1,11 @@
-// C ABI of libsnpgpu, selection and layout of genotypes (include/snpgpu.h section 1j): the selected rectangle of a 2-bit genotype
-// stream -- PACKED2 rows, the raw sample.order or snp.order node, a window of either, host-gathered segments -- as
-// SNPGPU_GENO_PACKED2 rows of the selected samples and SNPs (gnrCopyGenoMem, src/SNPRelate.cpp:322-382, without a byte per
-// genotype anywhere).  Kernels: kernels_geno_select.hip.
+// C ABI of libsnpgpu, selection and layout of genotypes (include/snpgpu.h sections 1j and 1k): the selected rectangle of a 2-bit
+// genotype stream -- PACKED2 rows, the raw sample.order or snp.order node, a PLINK .bed file of either mode, a window of any,
+// host-gathered segments -- as byte-aligned 2-bit rows of the selected samples and SNPs (gnrCopyGenoMem, src/SNPRelate.cpp:322-382,
+// without a byte per genotype anywhere), in the GDS or the BED code set, SNP rows or sample rows.  Kernels: kernels_geno_select.hip.
+//
+// The kernels know rows and columns of dst, not SNPs and samples: after the argument checks the call speaks of dst's rows (SNPs
+// for dst_major 0, samples for dst_major 1) and dst's columns, and a source is either `cross` (its rows are dst's columns: a
+// transposition) or not (a row selection and a column gather).  The comments below say SNP and sample as dst_major 0 reads.
 //
 // A source in device memory is read where it lies, and so is a host source that fits the staging size, after one copy of its
 // bytes.  A larger host source goes through one staging buffer in windows: whole source rows
@@ -24,6 +28,7 @@ thread_local double g_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
 constexpr size_t SEL_STAGE_BYTES = size_t(256) << 20;    // source bytes per staging window
 constexpr GenoLimits SEL_GENO = {1, int64_t(1) << 30, int64_t(1) << 31, false, "invalid number of samples (1 ... 2^30 - 1)"};
+constexpr GenoLimits SEL_GENO_MAJOR1 = {1, int64_t(1) << 30, int64_t(1) << 30, false, "invalid number of samples (1 ... 2^30 - 1)"};
 enum { T_H2D = 0, T_COPY = 1, T_GATHER = 2, T_TRANS = 3, T_D2H = 4 };
 
 size_t stage_bytes()
@@ -61,14 +66,14 @@ int timed_h2d(Call &c, void *dst, const void *src, size_t bytes)
 
 // SNP rows -> SNP rows of one view: the copy kernel for the run of samples from s0, the gather kernel for a list
 int run_major0(Call &c, const SelBits &v, const int32_t *d_srow, const int32_t *d_samp, int64_t s0, int64_t n_out, int64_t n_cols,
-               int64_t n_rows_out, uint8_t *dst)
+               int64_t n_rows_out, uint8_t *dst, SelRecode code)
 {
     hipStream_t s = c.st.s;
     g_stats[4] += 1;
     if (d_samp)
-        return c.log.begin(T_GATHER, s) || launch_geno_gather(s, v, d_srow, d_samp, n_out, n_cols, n_rows_out, lds_words(), dst) ||
+        return c.log.begin(T_GATHER, s) || launch_geno_gather(s, v, d_srow, d_samp, n_out, n_cols, n_rows_out, lds_words(), dst, code) ||
                c.log.end(s);
-    return c.log.begin(T_COPY, s) || launch_geno_copy(s, v, d_srow, s0, n_out, n_rows_out, dst) || c.log.end(s);
+    return c.log.begin(T_COPY, s) || launch_geno_copy(s, v, d_srow, s0, n_out, n_rows_out, dst, code) || c.log.end(s);
 }
 
 // output SNPs [k0, k1) as segments of consecutive source columns (relative to cmin), at most SEL_TW long
@@ -86,22 +91,18 @@ void build_segs(const int32_t *snp, int64_t k0, int64_t k1, int64_t cmin, std::v
 
 // dsegs: a device table of at least segs.size() entries, owned by the caller; segs stays alive until the stream is synchronised
 int run_transpose(Call &c, const SelBits &v, const int32_t *d_samp, const std::vector<SelSeg> &segs, SelSeg *dsegs, int64_t n_out,
-                  uint8_t *dst)
+                  uint8_t *dst, SelRecode code)
 {
     hipStream_t s = c.st.s;
     SNPGPU_HIP_CHECK(hipMemcpyAsync(dsegs, segs.data(), sizeof(SelSeg) * segs.size(), hipMemcpyHostToDevice, s));
     g_stats[4] += 1;
-    return c.log.begin(T_TRANS, s) || launch_geno_transpose(s, v, d_samp, dsegs, (int64_t)segs.size(), n_out, dst) || c.log.end(s);
+    return c.log.begin(T_TRANS, s) || launch_geno_transpose(s, v, d_samp, dsegs, (int64_t)segs.size(), n_out, dst, code) || c.log.end(s);
 }
 
-}  // namespace
-
-extern "C" {
-
-int snpgpu_geno_select(const snpgpu_geno_src *src, const int32_t *samp_index, int64_t n_samp_out, const int32_t *snp_index,
-                       int64_t n_snp_out, void *dst, int dst_mem, int device, void *stream)
+// fn: the entry point's name in the error messages
+int convert(const char *fn, const snpgpu_geno_src *src, int src_code, const int32_t *samp_index, int64_t n_samp_out,
+            const int32_t *snp_index, int64_t n_snp_out, void *dst, int dst_major, int dst_code, int dst_mem, int device, void *stream)
 {
-    const char *fn = "snpgpu_geno_select";
     if (!src) return fail(fn, "NULL argument: src is NULL");
     if (!src->bits) return fail(fn, "NULL argument: src->bits is NULL");
     if (!dst) return fail(fn, "NULL argument: dst is NULL");
@@ -109,13 +110,19 @@ int snpgpu_geno_select(const snpgpu_geno_src *src, const int32_t *samp_index, in
     if (!mem_ok(src->mem)) return fail(fn, "invalid memory kind");
     if (!mem_ok(dst_mem)) return fail(fn, "invalid dst_mem");
     if (src->major != 0 && src->major != 1) return fail(fn, "invalid major (0: a row is a SNP, 1: a row is a sample)");
+    const auto code_ok = [](int c) { return c == SNPGPU_CODE_GDS || c == SNPGPU_CODE_BED; };
+    if (!code_ok(src_code)) return fail(fn, "invalid src_code (SNPGPU_CODE_GDS or SNPGPU_CODE_BED)");
+    if (!code_ok(dst_code)) return fail(fn, "invalid dst_code (SNPGPU_CODE_GDS or SNPGPU_CODE_BED)");
+    if (dst_major != 0 && dst_major != 1) return fail(fn, "invalid dst_major (0: a row of dst is a SNP, 1: a row of dst is a sample)");
     const int major = src->major;
+    // the axis dst packs holds at most 2^30 - 1 entries: for sample rows that is the SNPs
+    const GenoLimits &lim = dst_major ? SEL_GENO_MAJOR1 : SEL_GENO;
     const int64_t n_rows = src->n_rows, n_cols = src->n_cols;
     const int64_t src_snp = major ? n_cols : n_rows, src_samp = major ? n_rows : n_cols;
-    if (check_dims(fn, src_snp, src_samp, SEL_GENO)) return 1;
+    if (check_dims(fn, src_snp, src_samp, lim)) return 1;
     if (!samp_index && n_samp_out != src_samp) return fail(fn, "samp_index is NULL: n_samp_out should be the source's number of samples");
     if (!snp_index && n_snp_out != src_snp) return fail(fn, "snp_index is NULL: n_snp_out should be the source's number of SNPs");
-    if (check_dims(fn, n_snp_out, n_samp_out, SEL_GENO)) return 1;
+    if (check_dims(fn, n_snp_out, n_samp_out, lim)) return 1;
     // the description: even, non-negative bit positions inside [bits, bits + n_bytes)
     if (src->n_bytes < 1) return fail(fn, "invalid n_bytes");
     if (src->bit0 < 0 || (src->bit0 & 1)) return fail(fn, "odd or negative bit position: bit0");
@@ -140,6 +147,12 @@ int snpgpu_geno_select(const snpgpu_geno_src *src, const int32_t *samp_index, in
         for (int64_t k = 0; k < n_snp_out; k++)
             if (snp_index[k] < 0 || snp_index[k] >= src_snp) return fail(fn, "an index outside the source: snp_index[" + std::to_string(k) + "]");
 
+    // from here on in dst's terms: rows and columns (see the head of this file)
+    const SelRecode code = sel_recode(src_code, dst_code);
+    const bool cross = major != dst_major;
+    const int32_t *row_index = dst_major ? samp_index : snp_index, *col_index = dst_major ? snp_index : samp_index;
+    const int64_t n_row_out = dst_major ? n_samp_out : n_snp_out, n_col_out = dst_major ? n_snp_out : n_samp_out;
+
     for (double &x : g_stats) x = 0;
     Call c;
     if (c.open(fn, device, true, stream)) return 1;
@@ -155,15 +168,15 @@ int snpgpu_geno_select(const snpgpu_geno_src *src, const int32_t *samp_index, in
         if (a.type == hipMemoryTypeDevice && a.device != device) return fail(fn, "a device pointer of another device");
     }
 
-    const int64_t rb = (n_samp_out + 3) / 4;
+    const int64_t rb = (n_col_out + 3) / 4;
     HostOut od;
-    if (od.open(c.bufs, dst, (size_t)n_snp_out * (size_t)rb, dst_mem == SNPGPU_DEVICE ? SNPGPU_DEVICE : SNPGPU_HOST, false, s)) return 1;
+    if (od.open(c.bufs, dst, (size_t)n_row_out * (size_t)rb, dst_mem == SNPGPU_DEVICE ? SNPGPU_DEVICE : SNPGPU_HOST, false, s)) return 1;
     uint8_t *ddst = (uint8_t *)od.dev;
 
     // the samples: a run of consecutive ones (from run_s0; NULL = all) or a list
-    int64_t run_s0 = samp_index ? samp_index[0] : 0;
-    for (int64_t j = 1; samp_index && j < n_samp_out && run_s0 >= 0; j++)
-        if (samp_index[j] != samp_index[0] + j) run_s0 = -1;
+    int64_t run_s0 = col_index ? col_index[0] : 0;
+    for (int64_t j = 1; col_index && j < n_col_out && run_s0 >= 0; j++)
+        if (col_index[j] != col_index[0] + j) run_s0 = -1;
     const bool host_src = src->mem != SNPGPU_DEVICE;
     const uint8_t *bits = (const uint8_t *)src->bits;
     std::vector<SelSeg> segs;
@@ -176,7 +189,7 @@ int snpgpu_geno_select(const snpgpu_geno_src *src, const int32_t *samp_index, in
         dbits = (const uint8_t *)raw->p;
     }
     int32_t *dsamp = nullptr;
-    if (run_s0 < 0 && (dbits || major == 0) && upload(c, samp_index, (size_t)n_samp_out, dsamp)) return 1;
+    if (run_s0 < 0 && (dbits || !cross) && upload(c, col_index, (size_t)n_col_out, dsamp)) return 1;
 
     if (dbits) {
         const int64_t shift = (int64_t)((uintptr_t)dbits & 3);
@@ -184,17 +197,17 @@ int snpgpu_geno_select(const snpgpu_geno_src *src, const int32_t *samp_index, in
         if (src->row_bit && upload(c, src->row_bit, (size_t)n_rows, drb)) return 1;
         SelBits v = {(const uint32_t *)(dbits - shift), (shift + src->n_bytes + 3) / 4, src->bit0 + 8 * shift, src->row_stride_bits, drb};
         g_stats[7] = 1;
-        if (major == 0) {
+        if (!cross) {
             int32_t *dsrow = nullptr;
-            if (snp_index && upload(c, snp_index, (size_t)n_snp_out, dsrow)) return 1;
-            if (run_major0(c, v, dsrow, dsamp, run_s0, n_samp_out, n_cols, n_snp_out, ddst)) return 1;
+            if (row_index && upload(c, row_index, (size_t)n_row_out, dsrow)) return 1;
+            if (run_major0(c, v, dsrow, dsamp, run_s0, n_col_out, n_cols, n_row_out, ddst, code)) return 1;
         } else {
             if (run_s0 > 0) { if (drb) v.row_bit += run_s0; else v.bit0 += run_s0 * v.stride; }
-            build_segs(snp_index, 0, n_snp_out, 0, segs);
+            build_segs(row_index, 0, n_row_out, 0, segs);
             DevBuf *dsegs = c.bufs.get(sizeof(SelSeg) * segs.size(), rc);
-            if (rc || run_transpose(c, v, dsamp, segs, (SelSeg *)dsegs->p, n_samp_out, ddst)) return 1;
+            if (rc || run_transpose(c, v, dsamp, segs, (SelSeg *)dsegs->p, n_col_out, ddst, code)) return 1;
         }
-    } else if (major == 0 && !snp_index && !src->row_bit) {
+    } else if (!cross && !row_index && !src->row_bit) {
         // whole source rows in order, straight from the caller's memory
         const int64_t stride = src->row_stride_bits, span = 2 * n_cols, stage = (int64_t)stage_bytes();
         const int64_t per = stride > 0 ? std::max<int64_t>(1, (8 * stage - span - 14) / stride + 1) : n_rows;
@@ -206,24 +219,24 @@ int snpgpu_geno_select(const snpgpu_geno_src *src, const int32_t *samp_index, in
             const int64_t lo = start >> 3, hi = (start + (m - 1) * stride + span + 7) >> 3;
             if (timed_h2d(c, raw->p, bits + lo, (size_t)(hi - lo))) return 1;
             const SelBits v = {(const uint32_t *)raw->p, (hi - lo + 3) / 4, start - 8 * lo, stride, nullptr};
-            if (run_major0(c, v, nullptr, dsamp, run_s0, n_samp_out, n_cols, m, ddst + k0 * rb)) return 1;
+            if (run_major0(c, v, nullptr, dsamp, run_s0, n_col_out, n_cols, m, ddst + k0 * rb, code)) return 1;
             SNPGPU_HIP_CHECK(hipStreamSynchronize(s));               // the staging buffer is reused by the next window
             g_stats[7] += 1;
         }
-    } else if (major == 0) {
+    } else if (!cross) {
         // the selected source rows, gathered on the host: a dword-aligned segment and a phase per row
         const int64_t span = 2 * n_cols, stage = (int64_t)stage_bytes();
-        std::vector<int64_t> rbit((size_t)n_snp_out), win(1, 0);
+        std::vector<int64_t> rbit((size_t)n_row_out), win(1, 0);
         int64_t off = 0, max_off = 0;
-        for (int64_t k = 0; k < n_snp_out; k++) {
-            const int64_t start = row_start(*src, snp_index ? snp_index[k] : k);
+        for (int64_t k = 0; k < n_row_out; k++) {
+            const int64_t start = row_start(*src, row_index ? row_index[k] : k);
             const int64_t seg = (((start + span + 7) >> 3) - (start >> 3) + 3) & ~int64_t(3);
             if (off > 0 && off + seg > stage) { win.push_back(k); off = 0; }
             rbit[(size_t)k] = 8 * off + (start & 7);
             off += seg;
             max_off = std::max(max_off, off);
         }
-        win.push_back(n_snp_out);
+        win.push_back(n_row_out);
         int64_t *drb = nullptr;
         if (upload(c, rbit.data(), rbit.size(), drb)) return 1;
         DevBuf *raw = c.bufs.get((size_t)max_off + 32, rc);
@@ -233,13 +246,13 @@ int snpgpu_geno_select(const snpgpu_geno_src *src, const int32_t *samp_index, in
             const int64_t k0 = win[w], k1 = win[w + 1];
             int64_t used = 0;
             for (int64_t k = k0; k < k1; k++) {
-                const int64_t start = row_start(*src, snp_index ? snp_index[k] : k), lo = start >> 3, hi = (start + span + 7) >> 3;
+                const int64_t start = row_start(*src, row_index ? row_index[k] : k), lo = start >> 3, hi = (start + span + 7) >> 3;
                 std::memcpy(hbuf.data() + (rbit[(size_t)k] >> 3), bits + lo, (size_t)(hi - lo));
                 used = (rbit[(size_t)k] >> 3) + ((hi - lo + 3) & ~int64_t(3));
             }
             if (timed_h2d(c, raw->p, hbuf.data(), (size_t)used)) return 1;
             const SelBits v = {(const uint32_t *)raw->p, used / 4, 0, 0, drb + k0};
-            if (run_major0(c, v, nullptr, dsamp, run_s0, n_samp_out, n_cols, k1 - k0, ddst + k0 * rb)) return 1;
+            if (run_major0(c, v, nullptr, dsamp, run_s0, n_col_out, n_cols, k1 - k0, ddst + k0 * rb, code)) return 1;
             SNPGPU_HIP_CHECK(hipStreamSynchronize(s));
             g_stats[7] += 1;
         }
@@ -247,33 +260,33 @@ int snpgpu_geno_select(const snpgpu_geno_src *src, const int32_t *samp_index, in
         // sample rows from the host in windows of output SNPs: every selected sample's segment of the window's range of source
         // SNPs, gathered on the host with a phase per row, so that every window's output is whole rows of its SNPs
         const int64_t stage = (int64_t)stage_bytes();
-        const auto col = [&](int64_t k) { return snp_index ? (int64_t)snp_index[k] : k; };
+        const auto col = [&](int64_t k) { return row_index ? (int64_t)row_index[k] : k; };
         const auto seg_max = [](int64_t ncol) { return (((2 * ncol + 14) >> 3) + 4) & ~int64_t(3); };
         struct Win { int64_t k0, k1, cmin, cmax; };
         std::vector<Win> wins;
         int64_t max_bytes = 0, max_snps = 0;
-        for (int64_t k = 0; k < n_snp_out;) {
+        for (int64_t k = 0; k < n_row_out;) {
             Win w = {k, k + 1, col(k), col(k)};
-            while (w.k1 < n_snp_out) {
+            while (w.k1 < n_row_out) {
                 const int64_t lo = std::min(w.cmin, col(w.k1)), hi = std::max(w.cmax, col(w.k1));
-                if (n_samp_out * seg_max(hi - lo + 1) > stage) break;
+                if (n_col_out * seg_max(hi - lo + 1) > stage) break;
                 w.cmin = lo; w.cmax = hi; w.k1++;
             }
-            max_bytes = std::max(max_bytes, n_samp_out * seg_max(w.cmax - w.cmin + 1));
+            max_bytes = std::max(max_bytes, n_col_out * seg_max(w.cmax - w.cmin + 1));
             max_snps = std::max(max_snps, w.k1 - w.k0);                 // a window has at most one segment per SNP
             wins.push_back(w);
             k = w.k1;
         }
-        DevBuf *raw = c.bufs.get((size_t)max_bytes + 32, rc), *drb = c.bufs.get(sizeof(int64_t) * (size_t)n_samp_out, rc);
+        DevBuf *raw = c.bufs.get((size_t)max_bytes + 32, rc), *drb = c.bufs.get(sizeof(int64_t) * (size_t)n_col_out, rc);
         DevBuf *dsegs = c.bufs.get(sizeof(SelSeg) * (size_t)max_snps, rc);
         if (rc) return 1;
         std::vector<uint8_t> hbuf((size_t)max_bytes, 0);
-        std::vector<int64_t> rbit((size_t)n_samp_out);
+        std::vector<int64_t> rbit((size_t)n_col_out);
         for (const Win &w : wins) {
             const int64_t span = 2 * (w.cmax - w.cmin + 1);
             int64_t off = 0;
-            for (int64_t j = 0; j < n_samp_out; j++) {
-                const int64_t start = row_start(*src, samp_index ? samp_index[j] : j) + 2 * w.cmin, lo = start >> 3, hi = (start + span + 7) >> 3;
+            for (int64_t j = 0; j < n_col_out; j++) {
+                const int64_t start = row_start(*src, col_index ? col_index[j] : j) + 2 * w.cmin, lo = start >> 3, hi = (start + span + 7) >> 3;
                 std::memcpy(hbuf.data() + off, bits + lo, (size_t)(hi - lo));
                 rbit[(size_t)j] = 8 * off + (start & 7);
                 off += (hi - lo + 3) & ~int64_t(3);
@@ -281,8 +294,8 @@ int snpgpu_geno_select(const snpgpu_geno_src *src, const int32_t *samp_index, in
             if (timed_h2d(c, raw->p, hbuf.data(), (size_t)off)) return 1;
             SNPGPU_HIP_CHECK(hipMemcpyAsync(drb->p, rbit.data(), sizeof(int64_t) * rbit.size(), hipMemcpyHostToDevice, s));
             const SelBits v = {(const uint32_t *)raw->p, off / 4, 0, 0, (const int64_t *)drb->p};
-            build_segs(snp_index, w.k0, w.k1, w.cmin, segs);
-            if (run_transpose(c, v, nullptr, segs, (SelSeg *)dsegs->p, n_samp_out, ddst)) return 1;
+            build_segs(row_index, w.k0, w.k1, w.cmin, segs);
+            if (run_transpose(c, v, nullptr, segs, (SelSeg *)dsegs->p, n_col_out, ddst, code)) return 1;
             SNPGPU_HIP_CHECK(hipStreamSynchronize(s));
             g_stats[7] += 1;
         }
@@ -296,11 +309,36 @@ int snpgpu_geno_select(const snpgpu_geno_src *src, const int32_t *samp_index, in
     return 0;
 }
 
+}  // namespace
+
+extern "C" {
+
+int snpgpu_geno_select(const snpgpu_geno_src *src, const int32_t *samp_index, int64_t n_samp_out, const int32_t *snp_index,
+                       int64_t n_snp_out, void *dst, int dst_mem, int device, void *stream)
+{
+    return convert("snpgpu_geno_select", src, SNPGPU_CODE_GDS, samp_index, n_samp_out, snp_index, n_snp_out, dst, 0, SNPGPU_CODE_GDS,
+                   dst_mem, device, stream);
+}
+
+int snpgpu_geno_convert(const snpgpu_geno_src *src, int src_code, const int32_t *samp_index, int64_t n_samp_out,
+                        const int32_t *snp_index, int64_t n_snp_out, void *dst, int dst_major, int dst_code, int dst_mem, int device,
+                        void *stream)
+{
+    return convert("snpgpu_geno_convert", src, src_code, samp_index, n_samp_out, snp_index, n_snp_out, dst, dst_major, dst_code, dst_mem,
+                   device, stream);
+}
+
 int snpgpu_geno_select_stats(double *stats)
 {
     if (!stats) { set_error("snpgpu_geno_select_stats: stats is NULL"); return 1; }
     for (int k = 0; k < 8; k++) stats[k] = g_stats[k];
     return 0;
+}
+
+int snpgpu_geno_convert_stats(double *stats)
+{
+    if (!stats) { set_error("snpgpu_geno_convert_stats: stats is NULL"); return 1; }
+    return snpgpu_geno_select_stats(stats);
 }
 
 }  // extern "C"

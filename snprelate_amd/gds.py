@@ -57,7 +57,7 @@ class GenoFile:
     """
 
     def __init__(self, genotype=None, sample_id=None, snp_id=None, snp_chromosome=None,
-                 packed=None, n_samp=None, snp_position=None, sample_annot=None):
+                 packed=None, n_samp=None, snp_position=None, sample_annot=None, snp_allele=None):
         if packed is None:
             genotype = np.asarray(genotype, dtype=np.uint8)
             n_snp, n_samp = genotype.shape
@@ -77,6 +77,9 @@ class GenoFile:
         # snp.position (int32 base pairs), read by snpgdsLDpruning; None when the file has no such node
         self.snp_position = None if snp_position is None else np.asarray(snp_position, np.int32)
         assert self.snp_position is None or len(self.snp_position) == self.n_snp
+        # snp.allele ("A/B" per SNP), written to the .bim file by snpgdsGDS2BED; None when the file has no such node
+        self.snp_allele = None if snp_allele is None else np.asarray(snp_allele)
+        assert self.snp_allele is None or len(self.snp_allele) == self.n_snp
         # columns of the sample.annot folder this reader can decode (e.g. "pop.group"), one entry per sample
         self.sample_annot = {} if sample_annot is None else dict(sample_annot)
         # snpgdsOption() defaults (R/AllUtilities.R:1910-1991)
@@ -195,6 +198,18 @@ def _sample_annot(columns, raw):
     return out
 
 
+def _snp_allele(read):
+    """the snp.allele node ("A/B" per SNP, NUL-separated like sample.id) when it is an uncompressed or ZIP text node, else None;
+    read() -> (dims, bytes) of the node"""
+    try:
+        dims, b = read()
+    except (ValueError, KeyError, IndexError, struct.error, zlib.error):
+        return None
+    if len(dims) != 1 or b.count(b"\x00") != dims[0]:
+        return None
+    return np.array([x.decode("latin1") for x in b.split(b"\x00")[:dims[0]]])
+
+
 def open_gds(path):
     """Read a SNPRelate-written SNP GDS file with an uncompressed bit2
     ``genotype`` node into a :class:`GenoFile`."""
@@ -249,8 +264,9 @@ def open_gds(path):
             dims, dsid, is_zip, _ = _node_info(streams[sid])
             return dims, (zlib.decompress(streams[dsid]) if is_zip else streams[dsid])
         annot = _sample_annot(_dir_entries(streams[entries["sample.annot"]]), raw_id)
+    allele = _snp_allele(lambda: raw("snp.allele")[:2]) if "snp.allele" in entries else None
     gf = GenoFile(genotype=geno, sample_id=sample_id, snp_id=snp_id, snp_chromosome=chrom, snp_position=position,
-                  sample_annot=annot)
+                  sample_annot=annot, snp_allele=allele)
     gf.sample_order = b"sample.order" in attr
     return gf
 
@@ -363,9 +379,10 @@ class GenoStream:
     `blocks(block_snps, buffers=[b0, b1])` fills caller-provided (page-locked) buffers in turn instead of allocating."""
 
     def __init__(self, path, sample_id, snp_id, snp_chromosome, dims, extents, length, zipped, sample_order, snp_position=None,
-                 sample_annot=None):
+                 sample_annot=None, snp_allele=None):
         self.path, self.sample_id, self.snp_id, self.snp_chromosome = path, sample_id, snp_id, snp_chromosome
         self.snp_position, self.sample_annot = snp_position, ({} if sample_annot is None else dict(sample_annot))
+        self.snp_allele = snp_allele
         self._dims, self._extents, self._length, self._zipped = dims, extents, length, zipped
         self.sample_order = sample_order
         self.n_snp, self.n_samp = (dims[0], dims[1]) if sample_order else (dims[1], dims[0])
@@ -618,6 +635,7 @@ def open_gds_stream(path):
                 b = load(dsid)
                 return dims, (zlib.decompress(b) if is_zip else b)
             annot = _sample_annot(_dir_entries(load(entries["sample.annot"])), raw_id)
+        allele = _snp_allele(lambda: small("snp.allele")) if "snp.allele" in entries else None
         gdesc = load(entries["genotype"])
         dims, sid, is_zip, attr = _node_info(gdesc)
         ext, slen = extents(sid)
@@ -628,7 +646,7 @@ def open_gds_stream(path):
         elif slen != (2 * dims[0] * dims[1] + 7) // 8:      # an uncompressed bit2 node is exactly its genotypes, no more, no less
             raise ValueError("the genotype node holds %d bytes where %d x %d 2-bit genotypes need %d: compressed or damaged data"
                              % (slen, dims[0], dims[1], (2 * dims[0] * dims[1] + 7) // 8))
-    return GenoStream(path, sample_id, snp_id, chrom, dims, ext, slen, is_zip, b"sample.order" in attr, position, annot)
+    return GenoStream(path, sample_id, snp_id, chrom, dims, ext, slen, is_zip, b"sample.order" in attr, position, annot, allele)
 
 
 # ---------------------------------------------------------------------------
