@@ -31,7 +31,10 @@
  *   memory    : `mem` says whether a caller pointer is host or device memory
  *               (device pointers must belong to the context's device)
  *   threading : one context is used from one host thread at a time; calls
- *               block until the result is in the caller's buffer.
+ *               block until the result is in the caller's buffer, in host or
+ *               in device memory.  The exceptions are named where they are
+ *               declared: snpgpu_feed of a device block, and the projector
+ *               calls (1b) whose every pointer is device memory.
  */
 #ifndef SNPGPU_H
 #define SNPGPU_H
@@ -179,7 +182,8 @@ int snpgpu_eigmix(snpgpu_ctx *ctx, int diagadj, double scale, double *out, int p
 int snpgpu_indiv_beta(snpgpu_ctx *ctx, int mode, double *out, double *avg_val, int packed, int mem);
 /* top-k eigenpairs of the (normalised, full-context) PCA covariance:
  * replaces CalcEigen / LAPACK dspevx (src/genPCA.cpp:1262-1346).
- * eigval: double [k] descending, eigvec: double [n_samp][k] column-major (n x k).
+ * eigval: HOST double [k] descending, whatever `mem` says (as snpgpu_panels_topk_eigen); eigvec: double [n_samp][k]
+ * column-major (n x k) in `mem`.
  * n <= SNPGPU_EIG_DENSE_MAX (default 2048): hipSOLVER's dense syevdx on the finalised matrix, index range 1..k as the
  * reference asks LAPACK; larger n: the block-Krylov solver below on the resident panel (no n x n copy). */
 int snpgpu_pca_eigen(snpgpu_ctx *ctx, int k, double *eigval, double *eigvec, int mem);
@@ -361,7 +365,14 @@ int snpgpu_multi_topk_eigen(snpgpu_multi *m, double scale, int k, const snpgpu_e
  * A projector holds the sample-side matrix and per-block scratch; the caller keeps its block reader
  * (CGenoReadBySNP) and hands over one block at a time, as for the accumulators.  All arithmetic is fp64.
  * Matrices use R's layouts: eigvec = n_samp x n_eig column-major ([n_eig][n_samp]); per-block outputs
- * = n_eig x n_snp column-major ([n_snp][n_eig]); sample loadings = n_samp x n_eig column-major. */
+ * = n_eig x n_snp column-major ([n_snp][n_eig]); sample loadings = n_samp x n_eig column-major.
+ * Synchronisation.  A call that is given any host pointer (block, inputs or results) blocks until its results are in the caller's
+ * buffers and its host inputs may be reused.  A call whose every pointer is device memory -- snpgpu_proj_set_eigvec of device
+ * eigenvectors; a block call with a device block, or geno == NULL, and device inputs and results -- is STREAM-ORDERED, as snpgpu_feed
+ * of a device block: it is enqueued on the projector's stream (opts->stream, or the projector's own non-blocking stream) and
+ * returns at once.  Its inputs must stay unchanged, and its results are complete, only after snpgpu_proj_sync or any work that
+ * orders after that stream; later calls on the same projector are ordered after it.  (The randomised PCA runs its per-block
+ * products this way, without a synchronisation per block.)  snpgpu_proj_samp_loading always blocks. */
 typedef struct snpgpu_proj snpgpu_proj;
 int snpgpu_proj_create(int64_t n_samp, int n_eig, const snpgpu_opts *opts, snpgpu_proj **out);
 int snpgpu_proj_destroy(snpgpu_proj *p);
@@ -386,10 +397,13 @@ int snpgpu_proj_snp_loading_ext(snpgpu_proj *p, const void *geno, int64_t n_snp,
  * (SNP loadings times sqrt(ss/eigenval), R/PCA.R:283-285), afreq / scale as returned above */
 int snpgpu_proj_samp_loading_feed(snpgpu_proj *p, const void *geno, int64_t n_snp, int format, int mem,
                                   const double *sload, const double *afreq, const double *scale, int in_mem);
+/* The sums accumulated so far, n_samp x n_eig.  The accumulator is only read: a second call returns the same bytes, and a
+ * block fed afterwards adds to the same sums.  A projector starts with zero sums. */
 int snpgpu_proj_samp_loading(snpgpu_proj *p, double *out, int out_mem);
+/* zero the accumulator for another pass (stream-ordered; the eigenvectors and the staged block stay) */
 int snpgpu_proj_samp_loading_reset(snpgpu_proj *p);
-/* In the three block calls geno == NULL reuses the block staged by the previous call on this projector
- * (same n_snp): the randomised PCA multiplies every block by Y and by Y^T in one pass. */
+/* In the four block calls geno == NULL reuses the block staged by the previous block call on this projector
+ * (same n_snp; format and mem are then ignored): the randomised PCA multiplies every block by Y and by Y^T in one pass. */
 
 /* ---- (2) workspace level: mirrors of the registered .Call routines ------ */
 /* gnrSetGenoSpace(Node, SelSamp, SelSNP), src/SNPRelate.cpp:76-114: install an
@@ -608,8 +622,9 @@ int snpgpu_gnrLDScore(const int32_t *pos_bp, int32_t slide_max_bp, int32_t slide
  * (:824-832), then EMAlg (:582-656) per pair with max_niter / reltol, and LOGLIK_ADJUST's six candidates when coeff_correct.
  * geno: SNPGPU_GENO_PACKED2 rows [n_snp][ceil(n_samp/4)] in `mem` (host or the device's memory).  Outputs in out_mem: full
  * n_samp x n_samp k0, k1 and (may be NULL) int32 niter, 0 on the diagonal; afreq_out: host [n_snp] (may be NULL), -1 where
- * InitAFreq gives -1.  row_begin / row_end: the pairs (i, j > i) with row_begin <= i < row_end and their mirrors only (0, 0 = the
- * whole matrix); other entries are left as they were.  n_samp < 2 or n_snp < 1 is an error. */
+ * InitAFreq gives -1.  row_begin / row_end: the pairs (i, j > i) with row_begin <= i < row_end, their mirrors and the diagonal
+ * entries (i, i) of those rows only (0, 0 = the whole matrix); other entries are left as they were.  n_samp < 2 or n_snp < 1
+ * is an error. */
 int snpgpu_ibd_mle(const void *geno, int64_t n_snp, int64_t n_samp, int format, int mem, const double *allele_freq,
                    int max_niter, double reltol, int coeff_correct, int64_t row_begin, int64_t row_end, double *k0, double *k1,
                    int32_t *niter, double *afreq_out, int out_mem, int device);

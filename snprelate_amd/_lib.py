@@ -377,6 +377,11 @@ def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _dptr(x):
+    """a DEVICE address (int; 0 / None = absent) as the pointer argument of a call"""
+    return ctypes.c_void_p(int(x)) if x else None
+
+
 class PinnedBuffer:
     """Page-locked host block buffer (snpgpu_host_alloc) exposed as a numpy uint8 array."""
 
@@ -540,12 +545,18 @@ class Accumulator:
         check(lib().snpgpu_ibs_num(self._h, _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), int(packed), HOST))
         return o
 
-    def ibs_ave(self, packed=False):
+    def ibs_ave(self, packed=False, out_ptr=None):
+        if out_ptr is not None:
+            check(lib().snpgpu_ibs_ave(self._h, _dptr(out_ptr), int(packed), DEVICE))
+            return None
         o = np.empty(self._shape(packed), np.float64)
         check(lib().snpgpu_ibs_ave(self._h, _ptr(o), int(packed), HOST))
         return o
 
-    def king_robust_counts(self):
+    def king_robust_counts(self, out_ptr=None):
+        if out_ptr is not None:
+            check(lib().snpgpu_king_robust_counts(self._h, _dptr(out_ptr), DEVICE))
+            return None
         o = np.empty((self.slab_size(), 5), np.uint32)
         check(lib().snpgpu_king_robust_counts(self._h, _ptr(o), HOST))
         return o
@@ -579,8 +590,12 @@ class Accumulator:
         check(lib().snpgpu_diss(self._h, _ptr(o), int(packed), HOST))
         return o
 
-    def diss_sums(self):
-        """(SumGeno uint32, SumAFreq fp64), packed slab: numerator and denominator of the dissimilarity."""
+    def diss_sums(self, out_ptrs=None):
+        """(SumGeno uint32, SumAFreq fp64), packed slab: numerator and denominator of the dissimilarity.  out_ptrs: two DEVICE
+        pointers receiving them (then nothing is returned)."""
+        if out_ptrs is not None:
+            check(lib().snpgpu_diss_sums(self._h, _dptr(out_ptrs[0]), _dptr(out_ptrs[1]), DEVICE))
+            return None
         g = np.empty(self.slab_size(), np.uint32)
         w = np.empty(self.slab_size(), np.float64)
         check(lib().snpgpu_diss_sums(self._h, _ptr(g), _ptr(w), HOST))
@@ -606,8 +621,13 @@ class Accumulator:
                                    ctypes.byref(tr), HOST))
         return o, tr.value
 
-    def ibd_mom(self, e, constraint=False, packed=False):
+    def ibd_mom(self, e, constraint=False, packed=False, out_ptrs=None):
+        """e: the five expectations, host memory whatever the destination; out_ptrs: two DEVICE pointers (k0, k1)."""
         e = np.ascontiguousarray(e, np.float64)
+        if out_ptrs is not None:
+            check(lib().snpgpu_ibd_mom(self._h, _ptr(e), int(bool(constraint)), _dptr(out_ptrs[0]), _dptr(out_ptrs[1]), int(packed),
+                                       DEVICE))
+            return None
         a = np.empty(self._shape(packed), np.float64)
         b = np.empty(self._shape(packed), np.float64)
         check(lib().snpgpu_ibd_mom(self._h, _ptr(e), int(bool(constraint)), _ptr(a), _ptr(b), int(packed), HOST))
@@ -621,14 +641,22 @@ class Accumulator:
         each; then only n_found is returned."""
         return _select_pairs(lib().snpgpu_select_pairs, self._h, self.n, what, cutoff, family, e, constraint, samp_sel, capacity, out_ptrs)
 
-    def eigmix(self, diagadj=True, scale=1.0, packed=False):
+    def eigmix(self, diagadj=True, scale=1.0, packed=False, out_ptr=None):
+        if out_ptr is not None:
+            check(lib().snpgpu_eigmix(self._h, int(bool(diagadj)), float(scale), _dptr(out_ptr), int(packed), DEVICE))
+            return None
         o = np.empty(self._shape(packed), np.float64)
         check(lib().snpgpu_eigmix(self._h, int(bool(diagadj)), float(scale), _ptr(o), int(packed), HOST))
         return o
 
-    def indiv_beta(self, mode=1, packed=False):
-        o = np.empty(self._shape(packed), np.float64)
+    def indiv_beta(self, mode=1, packed=False, out_ptr=None):
+        """(matrix, grm_avg_value); out_ptr: a DEVICE pointer receiving the matrix, then (None, grm_avg_value) -- the average is a
+        host scalar either way."""
         avg = ctypes.c_double(0)
+        if out_ptr is not None:
+            check(lib().snpgpu_indiv_beta(self._h, int(mode), _dptr(out_ptr), ctypes.byref(avg), int(packed), DEVICE))
+            return None, avg.value
+        o = np.empty(self._shape(packed), np.float64)
         check(lib().snpgpu_indiv_beta(self._h, int(mode), _ptr(o), ctypes.byref(avg), int(packed), HOST))
         return o, avg.value
 
@@ -651,8 +679,13 @@ class Accumulator:
         """fp64 result-plane entries (rows[k], cols[k]) of this panel (snpgpu_panel_entries)"""
         return panel_entries(self._h, rows, cols)
 
-    def pca_eigen(self, k):
+    def pca_eigen(self, k, out_ptr=None):
+        """(eigenvalues [k], eigenvectors [n, k]); out_ptr: a DEVICE pointer receiving the eigenvectors ([k][n]), then
+        (eigenvalues, None) -- the eigenvalues are host memory either way."""
         w = np.empty(k, np.float64)
+        if out_ptr is not None:
+            check(lib().snpgpu_pca_eigen(self._h, int(k), _ptr(w), _dptr(out_ptr), DEVICE))
+            return w, None
         v = np.empty((k, self.n), np.float64)   # column-major n x k
         check(lib().snpgpu_pca_eigen(self._h, int(k), _ptr(w), _ptr(v), HOST))
         return w, v.T
@@ -722,7 +755,11 @@ class LDMatrix:
     def feed_device(self, dev_ptr, n_snp, fmt=GENO_PACKED2):
         check(lib().snpgpu_ld_feed(self._h, ctypes.c_void_p(int(dev_ptr)), int(n_snp), fmt, DEVICE))
 
-    def result(self):
+    def result(self, out_ptr=None):
+        """out_ptr: a DEVICE pointer receiving the rows x cols matrix, column-major (then nothing is returned)."""
+        if out_ptr is not None:
+            check(lib().snpgpu_ld_result(self._h, _dptr(out_ptr), DEVICE))
+            return None
         r, c = self.dims()
         out = np.empty((c, r), np.float64)     # rows x cols column-major
         check(lib().snpgpu_ld_result(self._h, _ptr(out), HOST))
@@ -954,38 +991,61 @@ class MultiAccumulator:
         shape = (tri_size(self.n),) if cols is None else (tri_size(self.n), cols)
         return np.full(shape, -1 if np.issubdtype(dtype, np.integer) else np.nan, dtype)
 
-    def ibs_num(self, out=None):
+    def ibs_num(self, out=None, out_ptrs=None):
+        """out_ptrs (here and below: out_ptr / out_ptrs): DEVICE pointers on the first device receiving the packed triangle, then
+        nothing is returned."""
+        if out_ptrs is not None:
+            check(lib().snpgpu_multi_ibs_num(self._h, *[_dptr(x) for x in out_ptrs], DEVICE))
+            return None
         o = out or [self._tri(np.int32) for _ in range(3)]
         check(lib().snpgpu_multi_ibs_num(self._h, _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), HOST))
         return o
 
-    def king_robust(self, family=None, out=None):
+    def king_robust(self, family=None, out=None, out_ptrs=None):
         fam = None if family is None else np.ascontiguousarray(family, np.int32)
+        if out_ptrs is not None:
+            check(lib().snpgpu_multi_king_robust(self._h, _ptr(fam), _dptr(out_ptrs[0]), _dptr(out_ptrs[1]), DEVICE))
+            return None
         a, b = out or (self._tri(np.float64), self._tri(np.float64))
         check(lib().snpgpu_multi_king_robust(self._h, _ptr(fam), _ptr(a), _ptr(b), HOST))
         return a, b
 
-    def king_robust_counts(self, out=None):
+    def king_robust_counts(self, out=None, out_ptr=None):
+        if out_ptr is not None:
+            check(lib().snpgpu_multi_king_robust_counts(self._h, _dptr(out_ptr), DEVICE))
+            return None
         o = out if out is not None else np.zeros((tri_size(self.n), 5), np.uint32)
         check(lib().snpgpu_multi_king_robust_counts(self._h, _ptr(o), HOST))
         return o
 
-    def king_homo(self, out=None):
+    def king_homo(self, out=None, out_ptrs=None):
+        if out_ptrs is not None:
+            check(lib().snpgpu_multi_king_homo(self._h, _dptr(out_ptrs[0]), _dptr(out_ptrs[1]), DEVICE))
+            return None
         a, b = out or (self._tri(np.float64), self._tri(np.float64))
         check(lib().snpgpu_multi_king_homo(self._h, _ptr(a), _ptr(b), HOST))
         return a, b
 
-    def ibs_ave(self, out=None):
+    def ibs_ave(self, out=None, out_ptr=None):
+        if out_ptr is not None:
+            check(lib().snpgpu_multi_ibs_ave(self._h, _dptr(out_ptr), DEVICE))
+            return None
         o = out if out is not None else self._tri(np.float64)
         check(lib().snpgpu_multi_ibs_ave(self._h, _ptr(o), HOST))
         return o
 
-    def eigmix(self, diagadj=True, scale=1.0, out=None):
+    def eigmix(self, diagadj=True, scale=1.0, out=None, out_ptr=None):
+        if out_ptr is not None:
+            check(lib().snpgpu_multi_eigmix(self._h, int(bool(diagadj)), float(scale), _dptr(out_ptr), DEVICE))
+            return None
         o = out if out is not None else self._tri(np.float64)
         check(lib().snpgpu_multi_eigmix(self._h, int(bool(diagadj)), float(scale), _ptr(o), HOST))
         return o
 
-    def diss(self, out=None):
+    def diss(self, out=None, out_ptr=None):
+        if out_ptr is not None:
+            check(lib().snpgpu_multi_diss(self._h, _dptr(out_ptr), DEVICE))
+            return None
         o = out if out is not None else self._tri(np.float64)
         check(lib().snpgpu_multi_diss(self._h, _ptr(o), HOST))
         return o
@@ -1011,8 +1071,11 @@ class MultiAccumulator:
         check(lib().snpgpu_multi_pca_trace(self._h, ctypes.byref(tr)))
         return tr.value
 
-    def pca_cov(self, normalize=True, want_matrix=True):
+    def pca_cov(self, normalize=True, want_matrix=True, out_ptr=None):
         tr = ctypes.c_double(0)
+        if out_ptr is not None:
+            check(lib().snpgpu_multi_pca_cov(self._h, _dptr(out_ptr), int(normalize), ctypes.byref(tr), DEVICE))
+            return None, tr.value
         o = self._tri(np.float64) if want_matrix else None
         check(lib().snpgpu_multi_pca_cov(self._h, _ptr(o), int(normalize), ctypes.byref(tr), HOST))
         return o, tr.value
@@ -1020,27 +1083,36 @@ class MultiAccumulator:
     def finalize_inplace(self, diagadj=True, scale=1.0):
         check(lib().snpgpu_multi_finalize_inplace(self._h, int(bool(diagadj)), float(scale)))
 
-    def topk_eigen(self, k, scale=0.0, tol=1e-9, block=0, depth=0, seed=20240601, fp32_until=0.0):
-        """(eigenvalues [k], eigenvectors [n, k], info) on the host"""
+    def topk_eigen(self, k, scale=0.0, tol=1e-9, block=0, depth=0, seed=20240601, fp32_until=0.0, out_ptr=None):
+        """(eigenvalues [k], eigenvectors [n, k], info) on the host; out_ptr: a DEVICE pointer on the first device receiving the
+        eigenvectors ([k][n]), then (eigenvalues, None, info)"""
         opts = EigOpts(tol=float(tol), block=int(block), depth=int(depth), max_restarts=0, seed=int(seed), y_buf=None,
                        reduce=REDUCE_FN(), user=None, fp32_until=float(fp32_until))
         w = np.empty(k, np.float64)
         v = np.empty((k, self.n), np.float64)
         info = EigInfo()
-        check(lib().snpgpu_multi_topk_eigen(self._h, float(scale), int(k), ctypes.byref(opts), _ptr(w), _ptr(v), HOST,
+        check(lib().snpgpu_multi_topk_eigen(self._h, float(scale), int(k), ctypes.byref(opts), _ptr(w),
+                                            _ptr(v) if out_ptr is None else _dptr(out_ptr), HOST if out_ptr is None else DEVICE,
                                             ctypes.byref(info)))
-        return w, v.T, {"restarts": info.restarts, "matmuls": info.matmuls, "max_rel_residual": info.max_rel_residual,
+        return w, (v.T if out_ptr is None else None), {"restarts": info.restarts, "matmuls": info.matmuls, "max_rel_residual": info.max_rel_residual,
                         "block": info.block, "depth": info.depth, "matmuls_fp32": info.matmuls_fp32}
 
 
 class Projector:
     """RAII wrapper over snpgpu_proj (PCA projections, include/snpgpu.h section 1b).
-    Matrices follow R's layouts: eigvec [n_eig][n_samp]; per-block results [n_snp][n_eig]."""
+    Matrices follow R's layouts: eigvec [n_eig][n_samp]; per-block results [n_snp][n_eig].
 
-    def __init__(self, n_samp, n_eig, device=0, max_block_snps=16384):
+    Every block call takes the block as a numpy array (host), as a DEVICE address (int) with n_snp (and fmt, default 2-bit rows),
+    or as None = the block staged by the previous call (n_snp defaults to its size).  Results go to new host arrays, or with
+    out_ptr / out_ptrs to DEVICE memory (then nothing is returned).  A call whose every pointer is device memory is only enqueued
+    on the projector's stream: sync() is its completion point (include/snpgpu.h)."""
+
+    def __init__(self, n_samp, n_eig, device=0, max_block_snps=16384, stream=None):
         self._h = ctypes.c_void_p()
         self.n, self.k = int(n_samp), int(n_eig)
-        o = Opts(device=device, bayesian=0, row_begin=0, row_end=0, max_block_snps=max_block_snps, stream=None)
+        self._staged = 0
+        o = Opts(device=device, bayesian=0, row_begin=0, row_end=0, max_block_snps=max_block_snps,
+                 stream=ctypes.c_void_p(stream) if stream else None)
         check(lib().snpgpu_proj_create(self.n, self.k, ctypes.byref(o), ctypes.byref(self._h)))
 
     def close(self):
@@ -1060,45 +1132,116 @@ class Projector:
     def __exit__(self, *a):
         self.close()
 
-    def _block(self, geno):
+    def sync(self):
+        """wait for everything enqueued on the projector's stream (snpgpu_proj_sync)"""
+        check(lib().snpgpu_proj_sync(self._h))
+
+    def reset(self):
+        """zero the sample-loading accumulator (snpgpu_proj_samp_loading_reset; stream-ordered)"""
+        check(lib().snpgpu_proj_samp_loading_reset(self._h))
+
+    def _block(self, geno, n_snp=None, fmt=None):
+        """(pointer, n_snp, format, memory kind, keep-alive) of a block call"""
+        if geno is None:                               # the staged block
+            n = self._staged if n_snp is None else int(n_snp)
+            if n <= 0:
+                raise ValueError("no staged block to reuse")
+            return None, n, GENO_PACKED2, DEVICE, None
+        if isinstance(geno, int):
+            if n_snp is None:
+                raise ValueError("device rows need n_snp")
+            return ctypes.c_void_p(geno), int(n_snp), GENO_PACKED2 if fmt is None else int(fmt), DEVICE, None
         g = np.ascontiguousarray(geno, dtype=np.uint8)
-        fmt = GENO_U8 if g.shape[1] == self.n else GENO_PACKED2
+        if fmt is None:
+            fmt = GENO_U8 if g.shape[1] == self.n else GENO_PACKED2
         exp = self.n if fmt == GENO_U8 else (self.n + 3) // 4
         if g.ndim != 2 or g.shape[1] != exp:
             raise ValueError("genotype block has the wrong shape")
-        return g, fmt
+        return _ptr(g), g.shape[0], int(fmt), HOST, g
 
     def set_eigvec(self, eigvec):
+        """eigvec: numpy [n_eig][n_samp], or a DEVICE address (int) of that array (stream-ordered)"""
+        if isinstance(eigvec, int):
+            check(lib().snpgpu_proj_set_eigvec(self._h, ctypes.c_void_p(eigvec), DEVICE))
+            return
         e = np.ascontiguousarray(eigvec, dtype=np.float64)
         if e.shape != (self.k, self.n):
             raise ValueError("eigvec must be [n_eig][n_samp]")
         check(lib().snpgpu_proj_set_eigvec(self._h, _ptr(e), HOST))
 
-    def snp_corr(self, geno):
-        g, fmt = self._block(geno)
-        out = np.empty((g.shape[0], self.k), dtype=np.float64)
-        check(lib().snpgpu_proj_snp_corr(self._h, _ptr(g), g.shape[0], fmt, HOST, _ptr(out), HOST))
+    def snp_corr(self, geno, n_snp=None, fmt=None, out_ptr=None):
+        ptr, n, fmt, mem, _keep = self._block(geno, n_snp, fmt)
+        if out_ptr is not None:
+            check(lib().snpgpu_proj_snp_corr(self._h, ptr, n, fmt, mem, _dptr(out_ptr), DEVICE))
+            self._staged = n
+            return None
+        out = np.empty((n, self.k), dtype=np.float64)
+        check(lib().snpgpu_proj_snp_corr(self._h, ptr, n, fmt, mem, _ptr(out), HOST))
+        self._staged = n
         return out
 
-    def snp_loading(self, geno, bayesian=False):
-        g, fmt = self._block(geno)
-        out = np.empty((g.shape[0], self.k), dtype=np.float64)
-        af = np.empty(g.shape[0], dtype=np.float64)
-        sc = np.empty(g.shape[0], dtype=np.float64)
-        check(lib().snpgpu_proj_snp_loading(self._h, _ptr(g), g.shape[0], fmt, HOST, int(bool(bayesian)), _ptr(out),
-                                            _ptr(af), _ptr(sc), HOST))
+    def snp_loading(self, geno, bayesian=False, n_snp=None, fmt=None, out_ptrs=None):
+        """(loading [n_snp][n_eig], afreq [n_snp], scale [n_snp]); out_ptrs: three DEVICE pointers for them"""
+        ptr, n, fmt, mem, _keep = self._block(geno, n_snp, fmt)
+        if out_ptrs is not None:
+            check(lib().snpgpu_proj_snp_loading(self._h, ptr, n, fmt, mem, int(bool(bayesian)), _dptr(out_ptrs[0]), _dptr(out_ptrs[1]),
+                                                _dptr(out_ptrs[2]), DEVICE))
+            self._staged = n
+            return None
+        out = np.empty((n, self.k), dtype=np.float64)
+        af = np.empty(n, dtype=np.float64)
+        sc = np.empty(n, dtype=np.float64)
+        check(lib().snpgpu_proj_snp_loading(self._h, ptr, n, fmt, mem, int(bool(bayesian)), _ptr(out), _ptr(af), _ptr(sc), HOST))
+        self._staged = n
         return out, af, sc
 
-    def samp_loading_feed(self, geno, sload, afreq, scale):
-        g, fmt = self._block(geno)
+    def snp_loading_ext(self, geno, avg, scale, n_snp=None, fmt=None, out_ptr=None):
+        """loading [n_snp][n_eig] with the caller's centring avg [n_snp] and scaling scale [n_snp] (snpgpu_proj_snp_loading_ext):
+        both numpy arrays, or both DEVICE addresses (int)"""
+        ptr, n, fmt, mem, _keep = self._block(geno, n_snp, fmt)
+        if isinstance(avg, int) != isinstance(scale, int):
+            raise ValueError("avg and scale are both host arrays or both device addresses")
+        if isinstance(avg, int):
+            pa, ps, in_mem = ctypes.c_void_p(avg), ctypes.c_void_p(scale), DEVICE
+        else:
+            av = np.ascontiguousarray(avg, dtype=np.float64)
+            sv = np.ascontiguousarray(scale, dtype=np.float64)
+            if av.shape != (n,) or sv.shape != (n,):
+                raise ValueError("avg / scale do not match the block")
+            pa, ps, in_mem = _ptr(av), _ptr(sv), HOST
+        if out_ptr is not None:
+            check(lib().snpgpu_proj_snp_loading_ext(self._h, ptr, n, fmt, mem, pa, ps, in_mem, _dptr(out_ptr), DEVICE))
+            self._staged = n
+            return None
+        out = np.empty((n, self.k), dtype=np.float64)
+        check(lib().snpgpu_proj_snp_loading_ext(self._h, ptr, n, fmt, mem, pa, ps, in_mem, _ptr(out), HOST))
+        self._staged = n
+        return out
+
+    def samp_loading_feed(self, geno, sload, afreq, scale, n_snp=None, fmt=None):
+        """sload / afreq / scale: three numpy arrays, or three DEVICE addresses (int) of [n_snp][n_eig], [n_snp], [n_snp]"""
+        ptr, n, fmt, mem, _keep = self._block(geno, n_snp, fmt)
+        dev = [isinstance(x, int) for x in (sload, afreq, scale)]
+        if any(dev):
+            if not all(dev):
+                raise ValueError("sload / afreq / scale are all host arrays or all device addresses")
+            check(lib().snpgpu_proj_samp_loading_feed(self._h, ptr, n, fmt, mem, ctypes.c_void_p(sload), ctypes.c_void_p(afreq),
+                                                      ctypes.c_void_p(scale), DEVICE))
+            self._staged = n
+            return
         sl = np.ascontiguousarray(sload, dtype=np.float64)
         af = np.ascontiguousarray(afreq, dtype=np.float64)
         sc = np.ascontiguousarray(scale, dtype=np.float64)
-        if sl.shape != (g.shape[0], self.k) or af.shape != (g.shape[0],) or sc.shape != (g.shape[0],):
+        if sl.shape != (n, self.k) or af.shape != (n,) or sc.shape != (n,):
             raise ValueError("sload / afreq / scale do not match the block")
-        check(lib().snpgpu_proj_samp_loading_feed(self._h, _ptr(g), g.shape[0], fmt, HOST, _ptr(sl), _ptr(af), _ptr(sc), HOST))
+        check(lib().snpgpu_proj_samp_loading_feed(self._h, ptr, n, fmt, mem, _ptr(sl), _ptr(af), _ptr(sc), HOST))
+        self._staged = n
 
-    def samp_loading(self):
+    def samp_loading(self, out_ptr=None):
+        """the accumulated sample loadings [n_eig][n_samp]; the accumulator is left as it is (reset() clears it)"""
+        if out_ptr is not None:
+            check(lib().snpgpu_proj_samp_loading(self._h, _dptr(out_ptr), DEVICE))
+            return None
         out = np.empty((self.k, self.n), dtype=np.float64)
         check(lib().snpgpu_proj_samp_loading(self._h, _ptr(out), HOST))
         return out
@@ -1112,14 +1255,21 @@ def diag_fp64_rate(seconds=2.0, device=0):
 
 
 def ibd_mle(geno, n_samp, allele_freq=None, max_niter=1000, reltol=float(np.sqrt(np.finfo(float).eps)), coeff_correct=True,
-            rows=(0, 0), device=0, geno_dev_ptr=None, n_snp=None, out=None):
+            rows=(0, 0), device=0, geno_dev_ptr=None, n_snp=None, out=None, out_ptrs=None):
     """snpgpu_ibd_mle on 2-bit rows [n_snp][ceil(n_samp/4)] (numpy, or device memory via geno_dev_ptr + n_snp):
     returns (k0, k1, niter, afreq) with k0 / k1 / niter full n x n and afreq as InitAFreq leaves it (-1 = none).
     rows = (r0, r1): only the pairs of those upper-triangle rows (and their mirrors) are written, into `out` = (k0, k1, niter)
-    when given."""
+    when given.  out_ptrs: DEVICE pointers (k0, k1, niter; niter may be None) of n x n elements each; then
+    (None, None, None, afreq) is returned -- afreq is host memory either way."""
     ptr, n_snp, fmt, mem, _keep = _geno_input(geno if geno_dev_ptr is None else int(geno_dev_ptr), n_samp, GENO_PACKED2, n_snp,
                                               device_fmt_default=GENO_PACKED2)
     af_in = None if allele_freq is None else np.ascontiguousarray(allele_freq, np.float64)
+    if out_ptrs is not None:
+        af = np.empty(n_snp, np.float64)
+        check(lib().snpgpu_ibd_mle(ptr, n_snp, int(n_samp), fmt, mem, _ptr(af_in), int(max_niter), float(reltol),
+                                   int(bool(coeff_correct)), int(rows[0]), int(rows[1]), _dptr(out_ptrs[0]), _dptr(out_ptrs[1]),
+                                   _dptr(out_ptrs[2]), _ptr(af), DEVICE, int(device)))
+        return None, None, None, af
     if out is None:
         out = (np.empty((n_samp, n_samp), np.float64), np.empty((n_samp, n_samp), np.float64),
                np.empty((n_samp, n_samp), np.int32))
@@ -1132,11 +1282,13 @@ def ibd_mle(geno, n_samp, allele_freq=None, max_niter=1000, reltol=float(np.sqrt
 
 
 def ibd_mle_pairs(geno, n_samp, idx1, idx2, allele_freq=None, mode=0, kinship_constraint=False, max_niter=1000,
-                  reltol=float(np.sqrt(np.finfo(float).eps)), coeff_correct=True, device=0, geno_dev_ptr=None, n_snp=None):
+                  reltol=float(np.sqrt(np.finfo(float).eps)), coeff_correct=True, device=0, geno_dev_ptr=None, n_snp=None,
+                  out_ptrs=None):
     """snpgpu_ibd_mle_pairs on 2-bit rows [n_snp][ceil(n_samp/4)] (numpy, or device memory via geno_dev_ptr + n_snp) for the
     pairs (idx1[t], idx2[t]), 0-based: returns (k0, k1, loglik, niter, afreq), the first four of one entry per pair.
     mode 0: EM; mode 1: the start values (method of moments), loglik NaN and niter 0; mode 2: the downhill simplex, niter =
-    its count of function evaluations."""
+    its count of function evaluations.  out_ptrs: DEVICE pointers (k0, k1, loglik, niter; the last two may be None) of n_pairs
+    elements each; then (None, None, None, None, afreq) is returned.  idx1 / idx2 and afreq are host memory either way."""
     ptr, n_snp, fmt, mem, _keep = _geno_input(geno if geno_dev_ptr is None else int(geno_dev_ptr), n_samp, GENO_PACKED2, n_snp,
                                               device_fmt_default=GENO_PACKED2)
     af_in = None if allele_freq is None else np.ascontiguousarray(allele_freq, np.float64)
@@ -1144,6 +1296,13 @@ def ibd_mle_pairs(geno, n_samp, idx1, idx2, allele_freq=None, mode=0, kinship_co
     if i1.ndim != 1 or i1.shape != i2.shape:
         raise ValueError("idx1 and idx2 should be vectors of one length")
     P = i1.shape[0]
+    if out_ptrs is not None:
+        af = np.empty(n_snp, np.float64)
+        check(lib().snpgpu_ibd_mle_pairs(ptr, n_snp, int(n_samp), fmt, mem, _ptr(af_in), _ptr(i1), _ptr(i2), P, int(mode),
+                                         int(bool(kinship_constraint)), int(max_niter), float(reltol), int(bool(coeff_correct)),
+                                         _dptr(out_ptrs[0]), _dptr(out_ptrs[1]), _dptr(out_ptrs[2]), _dptr(out_ptrs[3]), _ptr(af),
+                                         DEVICE, int(device)))
+        return None, None, None, None, af
     k0, k1, ll, nit = np.empty(P, np.float64), np.empty(P, np.float64), np.empty(P, np.float64), np.empty(P, np.int32)
     af = np.empty(n_snp, np.float64)
     check(lib().snpgpu_ibd_mle_pairs(ptr, n_snp, int(n_samp), fmt, mem, _ptr(af_in), _ptr(i1), _ptr(i2), P, int(mode),
@@ -1153,9 +1312,10 @@ def ibd_mle_pairs(geno, n_samp, idx1, idx2, allele_freq=None, mode=0, kinship_co
 
 
 def ibd_jacquard_pairs(geno, n_samp, idx1, idx2, allele_freq=None, max_niter=1000, reltol=float(np.sqrt(np.finfo(float).eps)),
-                       device=0, geno_dev_ptr=None, n_snp=None):
+                       device=0, geno_dev_ptr=None, n_snp=None, out_ptrs=None):
     """snpgpu_ibd_jacquard_pairs on 2-bit rows (as ibd_mle_pairs) for the pairs (idx1[t], idx2[t]): returns (D, loglik, niter,
-    afreq) with D [8][n_pairs] = D1 ... D8.  SNPs at which both samples carry code 2 are skipped, as in the reference."""
+    afreq) with D [8][n_pairs] = D1 ... D8.  SNPs at which both samples carry code 2 are skipped, as in the reference.
+    out_ptrs: DEVICE pointers (D [8][n_pairs], loglik, niter; the last two may be None); then (None, None, None, afreq) is returned."""
     ptr, n_snp, fmt, mem, _keep = _geno_input(geno if geno_dev_ptr is None else int(geno_dev_ptr), n_samp, GENO_PACKED2, n_snp,
                                               device_fmt_default=GENO_PACKED2)
     af_in = None if allele_freq is None else np.ascontiguousarray(allele_freq, np.float64)
@@ -1163,6 +1323,12 @@ def ibd_jacquard_pairs(geno, n_samp, idx1, idx2, allele_freq=None, max_niter=100
     if i1.ndim != 1 or i1.shape != i2.shape:
         raise ValueError("idx1 and idx2 should be vectors of one length")
     P = i1.shape[0]
+    if out_ptrs is not None:
+        af = np.empty(n_snp, np.float64)
+        check(lib().snpgpu_ibd_jacquard_pairs(ptr, n_snp, int(n_samp), fmt, mem, _ptr(af_in), _ptr(i1), _ptr(i2), P, int(max_niter),
+                                              float(reltol), _dptr(out_ptrs[0]), _dptr(out_ptrs[1]), _dptr(out_ptrs[2]), _ptr(af),
+                                              DEVICE, int(device)))
+        return None, None, None, af
     d, ll, nit = np.empty((8, P), np.float64), np.empty(P, np.float64), np.empty(P, np.int32)
     af = np.empty(n_snp, np.float64)
     check(lib().snpgpu_ibd_jacquard_pairs(ptr, n_snp, int(n_samp), fmt, mem, _ptr(af_in), _ptr(i1), _ptr(i2), P, int(max_niter),
@@ -1177,12 +1343,16 @@ def ibd_mle_pairs_stats():
     return float(s[0]), float(s[1]), int(s[2]), int(s[3])
 
 
-def pop_counts(geno, n_samp, pop, n_pop, fmt=None, n_snp=None, device=0):
+def pop_counts(geno, n_samp, pop, n_pop, fmt=None, n_snp=None, device=0, out_ptrs=None):
     """(ACnt, Cnt) int32 [n_snp][n_pop] of snpgpu_pop_counts: per SNP and population the sum of the called genotypes and twice
     the number of called samples.  geno: host rows (numpy, U8 or PACKED2) or a device address (int) with n_snp (and fmt);
-    pop: 0-based population index per sample."""
+    pop: 0-based population index per sample (host memory); out_ptrs: two DEVICE pointers receiving the arrays."""
     p = _pop_array(pop, n_samp)
     ptr, n, fmt, mem, _keep = _geno_input(geno, n_samp, fmt, n_snp, device_fmt_default=GENO_PACKED2)
+    if out_ptrs is not None:
+        check(lib().snpgpu_pop_counts(ptr, n, int(n_samp), fmt, mem, _ptr(p), int(n_pop), _dptr(out_ptrs[0]), _dptr(out_ptrs[1]), DEVICE,
+                                      int(device)))
+        return None
     a = np.empty((n, int(n_pop)), np.int32)
     c = np.empty((n, int(n_pop)), np.int32)
     check(lib().snpgpu_pop_counts(ptr, n, int(n_samp), fmt, mem, _ptr(p), int(n_pop), _ptr(a), _ptr(c), HOST, int(device)))
@@ -1223,10 +1393,14 @@ def pop_stats():
     return float(s[0]), int(s[1]), float(s[2]), float(s[3])
 
 
-def geno_counts(geno, n_samp, fmt=None, n_snp=None, device=0, want_snp=True, want_samp=True):
+def geno_counts(geno, n_samp, fmt=None, n_snp=None, device=0, want_snp=True, want_samp=True, out_ptrs=None):
     """(snp_cnt int32 [n_snp][3] for g = 0, 1, 2; samp_missing int32 [n_samp]) of snpgpu_geno_counts; None for a part not asked
-    for.  geno: host rows (numpy, U8 or PACKED2) or a device address (int) with n_snp (and fmt)."""
+    for.  geno: host rows (numpy, U8 or PACKED2) or a device address (int) with n_snp (and fmt).  out_ptrs: two DEVICE pointers
+    (either may be None = not asked for) receiving the arrays."""
     ptr, n, fmt, mem, _keep = _geno_input(geno, n_samp, fmt, n_snp, device_fmt_default=GENO_PACKED2)
+    if out_ptrs is not None:
+        check(lib().snpgpu_geno_counts(ptr, n, int(n_samp), fmt, mem, _dptr(out_ptrs[0]), _dptr(out_ptrs[1]), DEVICE, int(device)))
+        return None
     c = np.empty((n, 3), np.int32) if want_snp else None
     m = np.empty(int(n_samp), np.int32) if want_samp else None
     check(lib().snpgpu_geno_counts(ptr, n, int(n_samp), fmt, mem, _ptr(c), _ptr(m), HOST, int(device)))
@@ -1241,8 +1415,14 @@ def hwe(geno, n_samp, fmt=None, n_snp=None, device=0):
     return p
 
 
-def hwe_counts(snp_cnt, device=0):
-    """snpgpu_hwe_counts on host counts int32 [n_snp][3] (g = 0, 1, 2)"""
+def hwe_counts(snp_cnt, device=0, n_snp=None, out_ptr=None):
+    """snpgpu_hwe_counts on host counts int32 [n_snp][3] (g = 0, 1, 2); or with snp_cnt a DEVICE address (int), n_snp and out_ptr
+    (DEVICE, n_snp doubles): the memory kind covers the counts and the p-values alike"""
+    if isinstance(snp_cnt, int) or out_ptr is not None:
+        if not (isinstance(snp_cnt, int) and out_ptr is not None and n_snp is not None):
+            raise ValueError("device counts go with a device result (and n_snp)")
+        check(lib().snpgpu_hwe_counts(ctypes.c_void_p(snp_cnt), int(n_snp), _dptr(out_ptr), DEVICE, int(device)))
+        return None
     c = np.ascontiguousarray(snp_cnt, np.int32)
     if c.ndim != 2 or c.shape[1] != 3:
         raise ValueError("snp_cnt should be [n_snp][3]")
@@ -1252,8 +1432,9 @@ def hwe_counts(snp_cnt, device=0):
 
 
 def ind_inb(geno, n_samp, method="mom.weir", allele_freq=None, reltol=float(np.finfo(float).eps ** 0.75), fmt=None, n_snp=None,
-            device=0):
-    """snpgpu_ind_inb: (coeff [n_samp], niter int32 [n_samp] or None unless "mle", afreq [n_snp] as used)"""
+            device=0, out_ptrs=None):
+    """snpgpu_ind_inb: (coeff [n_samp], niter int32 [n_samp] or None unless "mle", afreq [n_snp] as used).  out_ptrs: DEVICE
+    pointers (coeff, niter; niter may be None); then (None, None, afreq) is returned -- afreq is host memory either way."""
     if method not in INB_METHODS:
         raise ValueError("'method' should be one of %s" % ", ".join('"%s"' % m for m in INB_METHODS))
     ptr, n, fmt, mem, _keep = _geno_input(geno, n_samp, fmt, n_snp, device_fmt_default=GENO_PACKED2)
@@ -1261,6 +1442,11 @@ def ind_inb(geno, n_samp, method="mom.weir", allele_freq=None, reltol=float(np.f
     if af_in is not None and af_in.shape != (n,):
         raise ValueError("allele_freq should hold one frequency per SNP")
     code = INB_METHODS.index(method) + 1
+    if out_ptrs is not None:
+        af = np.empty(n, np.float64)
+        check(lib().snpgpu_ind_inb(ptr, n, int(n_samp), fmt, mem, _ptr(af_in), code, float(reltol), _dptr(out_ptrs[0]),
+                                   _dptr(out_ptrs[1]), _ptr(af), DEVICE, int(device)))
+        return None, None, af
     coeff = np.empty(int(n_samp), np.float64)
     nit = np.empty(int(n_samp), np.int32) if code == INB_MLE else None
     af = np.empty(n, np.float64)
@@ -1284,10 +1470,21 @@ def ibd_mle_stats():
     return float(s[0]), float(s[1]), int(s[2]), int(s[3])
 
 
-def ibd_loglik(geno, n_samp, allele_freq=None, k0=None, k1=None, k0_all=float("nan"), k1_all=float("nan"), device=0):
-    """snpgpu_ibd_loglik: EM_LogLik of every pair at the n x n (k0, k1), or at the global pair when k0 / k1 are None"""
-    ptr, n_snp, fmt, mem, _keep = _geno_input(geno, n_samp, GENO_PACKED2, None, device_fmt_default=GENO_PACKED2)
+def ibd_loglik(geno, n_samp, allele_freq=None, k0=None, k1=None, k0_all=float("nan"), k1_all=float("nan"), device=0, n_snp=None,
+               out_ptr=None):
+    """snpgpu_ibd_loglik: EM_LogLik of every pair at the n x n (k0, k1), or at the global pair when k0 / k1 are None.  out_ptr: a
+    DEVICE pointer receiving the n x n result; k0 / k1 are then DEVICE addresses (int) too, or None: the result's memory kind
+    covers them."""
+    ptr, n_snp, fmt, mem, _keep = _geno_input(geno, n_samp, GENO_PACKED2, n_snp, device_fmt_default=GENO_PACKED2)
     af_in = None if allele_freq is None else np.ascontiguousarray(allele_freq, np.float64)
+    if out_ptr is not None:
+        if not all(x is None or isinstance(x, int) for x in (k0, k1)):
+            raise ValueError("with a device result k0 / k1 are device addresses")
+        check(lib().snpgpu_ibd_loglik(ptr, n_snp, int(n_samp), fmt, mem, _ptr(af_in), _dptr(k0), _dptr(k1), float(k0_all),
+                                      float(k1_all), _dptr(out_ptr), None, DEVICE, int(device)))
+        return None
+    if isinstance(k0, int) or isinstance(k1, int):
+        raise ValueError("device k0 / k1 go with a device result (out_ptr)")
     m0 = None if k0 is None else np.ascontiguousarray(k0, np.float64)
     m1 = None if k1 is None else np.ascontiguousarray(k1, np.float64)
     out = np.empty((n_samp, n_samp), np.float64)
@@ -1355,12 +1552,17 @@ def _pair_method(method):
 
 
 def pair_tables(geno, n_samp, idx1, idx2, need_major=False, fmt=None, n_snp=None, device=0, want_pair=True, want_snp=True,
-                want_flip=True):
+                want_flip=True, out_ptrs=None):
     """(pair_tab int64 [n_pair][3][3], snp_tab int32 [n_snp][4][4], flip uint8 [n_snp]) of snpgpu_pair_tables; None for a part
     not asked for.  geno: host rows (numpy, U8 or PACKED2) or a device address (int) with n_snp (and fmt); idx1 / idx2: 0-based
-    sample indices of the pairs."""
+    sample indices of the pairs (host memory).  out_ptrs: three DEVICE pointers (any may be None = not asked for, not all)
+    receiving the tables."""
     a, b = _pair_lists(idx1, idx2)
     ptr, n, fmt, mem, _keep = _geno_input(geno, n_samp, fmt, n_snp, device_fmt_default=GENO_PACKED2)
+    if out_ptrs is not None:
+        check(lib().snpgpu_pair_tables(ptr, n, int(n_samp), fmt, mem, _ptr(a), _ptr(b), len(a), int(bool(need_major)),
+                                       _dptr(out_ptrs[0]), _dptr(out_ptrs[1]), _dptr(out_ptrs[2]), DEVICE, int(device)))
+        return None
     pt = np.empty((len(a), 3, 3), np.int64) if want_pair else None
     st = np.empty((n, 4, 4), np.int32) if want_snp else None
     fl = np.empty(n, np.uint8) if want_flip else None

@@ -181,9 +181,10 @@ static int snp_side(snpgpu_proj *p, int corr, const void *geno, int64_t n_snp, i
             if (copy_out(p, scale, d_sc, 8 * (size_t)n_snp, out_mem)) return 1;
         }
         SNPGPU_HIP_CHECK(hipStreamSynchronize(p->stream));
-    } else if (mem != SNPGPU_DEVICE) {
-        SNPGPU_HIP_CHECK(hipStreamSynchronize(p->stream));     // the caller may reuse its host block
+    } else if ((geno && mem != SNPGPU_DEVICE) || (ext_avg && ext_mem != SNPGPU_DEVICE)) {
+        SNPGPU_HIP_CHECK(hipStreamSynchronize(p->stream));     // the caller may reuse its host block / host avg and scale
     }
+    // every pointer device memory (or the staged block): stream-ordered, snpgpu_proj_sync is the completion point
     return 0;
 }
 
@@ -221,7 +222,7 @@ int snpgpu_proj_samp_loading_feed(snpgpu_proj *p, const void *geno, int64_t n_sn
     if (launch_proj_samp(p->stream, (const uint8_t *)p->packed.p, p->RB, p->N, n_snp, (const double *)p->sl.p, p->kp, p->k,
                          (const double *)p->af.p, (const double *)p->sc.p, (double *)p->acc.p))
         return 1;
-    if (mem != SNPGPU_DEVICE || in_mem != SNPGPU_DEVICE) SNPGPU_HIP_CHECK(hipStreamSynchronize(p->stream));
+    if ((geno && mem != SNPGPU_DEVICE) || in_mem != SNPGPU_DEVICE) SNPGPU_HIP_CHECK(hipStreamSynchronize(p->stream));
     return 0;
 }
 

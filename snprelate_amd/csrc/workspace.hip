@@ -403,8 +403,7 @@ static int dense_topk(int device, hipStream_t stream, double *A, int64_t n, int 
         std::vector<double> w((size_t)k);
         if (hipMemcpy(w.data(), W.p, sizeof(double) * (size_t)k, hipMemcpyDeviceToHost) != hipSuccess) { set_error("eigen copy failed"); rc = 1; break; }
         for (int i = 0; i < k; i++) w[(size_t)i] = -w[(size_t)i];
-        const hipMemcpyKind kind = (mem == SNPGPU_DEVICE) ? hipMemcpyHostToDevice : hipMemcpyHostToHost;
-        if (eigval && hipMemcpy(eigval, w.data(), sizeof(double) * (size_t)k, kind) != hipSuccess) { set_error("eigen copy failed"); rc = 1; break; }
+        if (eigval) memcpy(eigval, w.data(), sizeof(double) * (size_t)k);      // always host memory, as the Krylov route
         const hipMemcpyKind kv = (mem == SNPGPU_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
         if (eigvec && hipMemcpy(eigvec, A, sizeof(double) * (size_t)n * (size_t)k, kv) != hipSuccess) { set_error("eigen copy failed"); rc = 1; break; }
     } while (0);
