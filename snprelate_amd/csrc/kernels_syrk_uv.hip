@@ -491,6 +491,20 @@ __global__ __launch_bounds__(256, 1) void syrk_uv16_kernel(
 // With it this form takes 414 - 416 against 424 - 426 ms of kernel time per step (-2.4 %, at 2158 against 2136 MHz under the same 1370 W;
 // -2.0 ... -2.8 % on a second box) and moves 489 instead of 633 GB: the default since the end of round 6 (SNPGPU_SYRK_UV16=1: the lookup
 // kernel; SNPGPU_UVC_PACE=0: no pace-maker).
+// THE K LOOP'S BUDGET.  One wave per SIMD pays an issue turn for EVERY instruction of its stream (about 4 clocks, an MFMA 8; a gap runs
+// max(16, sum)): an MFMA hides its two companions, the conversion pair or the fma pair of an operand dword, and whatever else a 32-SNP
+// group of 64 MFMAs holds is time.  What has to be there: 16 word loads, 4 factor reads, 3 waits, 2 scalar adds = 25 (tools/isa_mix.py
+// counts 25.7 with the loop's own branch; tests/test_cpu_kloop_isa.py holds it below 30).  Until this budget was written down the group
+// held 44: the 64-bit product (group index) x 4 ncols_pad and the base add redone for every group (12 scalar), two v_lshl_add_u64 for
+// the sides' 64-bit address pairs, and a tighter vmcnt in front of nearly every first use of a word (9.7 waits).  Now a group's words are
+// addressed as (uniform 64-bit base in scalar registers) + (the lane's 32-bit byte offset, one per side) + 64 m as the instruction's
+// immediate; the base is made once per run in the prologue, from c_beg, and moves on by the constant 16 ncols_pad bytes behind MFMA 60,
+// which has no conversions behind it; and ONE vmcnt(32) behind a group's first MFMA covers the next group's sixteen words (requested
+// three groups earlier; vmcnt counts in order).  Same loads, same order, same conversions and MFMAs: results are bit-identical.
+// MEASURED (profiles/kloop_diet_ab.json, bench.py alternated with the parent commit on one device): 408.5 - 409.1 against 416.8 - 418.0 ms
+// per step, kernel 402.0 - 402.6 against 410.4 - 411.5 (-2.1 %); wave cycles per MFMA 21.2 against 22.2.  (SQ_WAIT_INST_ANY, a quarter
+// of the wave cycles before and after, counts issue stall -- cycles in which the wave had an instruction and could not issue it -- not
+// time parked at an s_waitcnt.)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Warray-bounds"
 __global__ __launch_bounds__(256, 1) void syrk_uv16c_kernel(
@@ -546,7 +560,11 @@ __global__ __launch_bounds__(256, 1) void syrk_uv16c_kernel(
 
     const auto [tid, lane, wave, wr, wc, li, kh, l16, kq] = wave_coord();
     const int64_t row_w = (int64_t)item.x * X1_TILE + wr * (16 * TS), col_w = (int64_t)item.y * X1_TILE + wc * (16 * TS);
-    const int la = (int)((int64_t)kq * ncols_pad + row_w + l16), lb = (int)((int64_t)kq * ncols_pad + col_w + l16);
+    // word addresses: a uniform 64-bit base per 32-SNP group (scalar registers, advanced by the constant stride of a group's four word
+    // rows) + this lane's 32-bit BYTE offset into those rows, once for the row side and once for the column side (at most 16 ncols_pad
+    // bytes: 8 MB at N = 500 000, whatever the size of the word array) + 64 m as the instruction's immediate
+    uint32_t la = (uint32_t)(4 * ((int64_t)kq * ncols_pad + row_w + l16)), lb = (uint32_t)(4 * ((int64_t)kq * ncols_pad + col_w + l16));
+    const int64_t wstride = 16 * ncols_pad;        // bytes from one group's words to the next group's
     double *__restrict__ pacc = acc + acc_off(ld, tiles_c, row_w + 4 * kq, col_w + l16);
     const int64_t rs = tiles_c ? ACC_TILE : ld;
 
@@ -595,6 +613,7 @@ __global__ __launch_bounds__(256, 1) void syrk_uv16c_kernel(
     u32x4 RF1[2], RF0[2];                          // row factors {2 u}, {-c_a u} of the lane's four pairs: group parity g & 1
     u32x4 CF1, CF0;                                // column factors of the NEXT group
     uint32_t fn;                                   // LDS position of the next group's factors (this lane's quarter)
+    __attribute__((address_space(1))) const char *wnext;   // the words of the group FOUR ahead of the loop's current one (uniform)
 
     // conversion L (0..63) of a group, issued around MFMA L (row r = L >> 3 of the 8 x 8 order, t = L & 7):
     //   t < 4:  dword t of row operand (r == 0 ? 7 of THIS group : r - 1 of the NEXT group)
@@ -629,12 +648,16 @@ __global__ __launch_bounds__(256, 1) void syrk_uv16c_kernel(
             _Pragma("unroll") for (int t_ = 0; t_ < 16; t_++) x1_lds_dma16(ps_ + 1024 * t_, x1_lds_off(&space[wave][0])); \
         }                                                                                                      \
     } while (0)
-#define C16_LOAD(CS_, g_abs, m)                                                               \
+#define C16_LOAD(CS_, wp_, m)                                                                 \
     do {                                                                                      \
-        const uint32_t *__restrict__ bs_ = w8 + (int64_t)(g_abs) * 4 * ncols_pad;              \
-        if ((m) < TS) Wa[CS_][(m) < TS ? (m) : 0] = bs_[la + 16 * (m)];                        \
-        else Wb[CS_][(m) >= TS ? (m) - TS : 0] = bs_[lb + 16 * ((m) - TS)];                    \
+        if ((m) < TS) Wa[CS_][(m) < TS ? (m) : 0] = *(__attribute__((address_space(1))) const uint32_t *)((wp_) + la + 64 * (m));          \
+        else Wb[CS_][(m) >= TS ? (m) - TS : 0] = *(__attribute__((address_space(1))) const uint32_t *)((wp_) + lb + 64 * ((m) - TS));      \
     } while (0)
+    // the words' ONE wait of a group: vmcnt counts in order, the next group's sixteen words were requested three groups ago and the 32
+    // requests of the two groups since are all that may still be under way (a chunk's factor copy and pace-maker pieces, where they lie
+    // in between, only make the true number larger: the loop body is shared by a chunk's four rounds, so it takes the count that holds
+    // in all of them)
+#define C16_WAIT_WORDS() __builtin_amdgcn_s_waitcnt(0x8F70)      /* vmcnt(32) */
 #define C16_MFMA(m, S_)                                                                                             \
         c16[(m) >> 3][(m) & 7] = __builtin_amdgcn_mfma_f32_16x16x32_f16(                                             \
             (f16x8)Av[(m) >> 3], (f16x8)Bv[S_][(m) & 7], c16[(m) >> 3][(m) & 7], 0, 0, 0)
@@ -644,6 +667,11 @@ __global__ __launch_bounds__(256, 1) void syrk_uv16c_kernel(
 #define C16_M(m, S_) do { C16_MFMA(m, S_); C16_SB(); } while (0)
 #define C16_C2(NS_, m, k)      /* conversions m + 4 + k, + 1 (the NEXT batch) into the other register half */                       \
     do {                                                                                                                            \
+        if ((m) == 0 && (k) == 0) { C16_WAIT_WORDS(); C16_SB(); }   /* behind MFMA 0: the first touch of the next group's words */ \
+        if ((m) == 60 && (k) == 0) {                     /* MFMA 60 has no conversions behind it: the word base moves on here */  \
+            wnext += wstride;                                                                                                       \
+            asm volatile("" : "+s"(wnext));              /* (a running base: no product of the group index) */                     \
+        }                                                                                                                           \
         if ((m) + 4 + (k) < 64) {                                                                                                   \
             x_[4 * ((((m) >> 2) + 1) & 1) + (k)] = C16_CVT(NS_, ((m) + 4 + (k)) & 63);                                              \
             x_[4 * ((((m) >> 2) + 1) & 1) + (k) + 1] = C16_CVT(NS_, ((m) + 5 + (k)) & 63);                                          \
@@ -656,41 +684,46 @@ __global__ __launch_bounds__(256, 1) void syrk_uv16c_kernel(
         C16_FMA(T_, P_, (m) + (k), x_[4 * (((m) >> 2) & 1) + (k)]); C16_FMA(T_, P_, (m) + (k) + 1, x_[4 * (((m) >> 2) & 1) + (k) + 1]); \
         C16_SB();                                                                                                                   \
     } while (0)
-#define C16_STEP4(m, S_, T_, CS_, NS_, P_, g_abs)                                                                   \
+#define C16_STEP4(m, S_, T_, CS_, NS_, P_)                                                                          \
     do {                                                                                                            \
         C16_M(m, S_);       C16_C2(NS_, m, 0);                                                                      \
         C16_M((m) + 1, S_); C16_F2(T_, P_, m, 0);                                                                   \
         C16_M((m) + 2, S_); C16_C2(NS_, m, 2);                                                                      \
         C16_M((m) + 3, S_); C16_F2(T_, P_, m, 2);                                                                   \
         if ((m) < 16) {     /* the words of group g + 4 into this group's set, four behind each of the first four batches */ \
-            C16_LOAD(CS_, (g_abs) + D, m); C16_LOAD(CS_, (g_abs) + D, (m) + 1); C16_LOAD(CS_, (g_abs) + D, (m) + 2); C16_LOAD(CS_, (g_abs) + D, (m) + 3); \
+            C16_LOAD(CS_, wnext, m); C16_LOAD(CS_, wnext, (m) + 1); C16_LOAD(CS_, wnext, (m) + 2); C16_LOAD(CS_, wnext, (m) + 3); \
             C16_SB();                                                                                               \
         }                                                                                                           \
     } while (0)
 #define C16_STEP8(m, ...) C16_STEP4(m, __VA_ARGS__); C16_STEP4((m) + 4, __VA_ARGS__)
-    // one 32-SNP group (absolute index g_abs, parity P_, word set CS_ = g_abs & 3, the next group's NS_): the next group's factors are
-    // requested first (row pairs first used behind MFMA 8, column pairs behind MFMA 4)
-#define C16_GROUP(S_, T_, CS_, NS_, P_, g_abs)                                                                      \
+    // one 32-SNP group g (parity P_, word set CS_ = g & 3, the next group's NS_; wnext = the words of group g + 4): the next group's
+    // factors are requested first (row pairs first used behind MFMA 8, column pairs behind MFMA 4)
+#define C16_GROUP(S_, T_, CS_, NS_, P_)                                                                             \
     do {                                                                                                            \
         wa7 = Wa[CS_][7];                                                                                           \
         asm volatile("" : "+v"(wa7));                                                                               \
+        asm volatile("" : "+v"(la), "+v"(lb));   /* (32-bit lane offsets where the loads are: hoisted as 64-bit pairs they cost an add each) */ \
         CF1 = x1_lds128(fn + 128); CF0 = x1_lds128(fn + 192);                                                       \
         RF1[(P_) ^ 1] = x1_lds128(fn); RF0[(P_) ^ 1] = x1_lds128(fn + 64);                                          \
         uint32_t x_[8];                                                                                             \
         x_[0] = C16_CVT(NS_, 0); x_[1] = C16_CVT(NS_, 1); x_[2] = C16_CVT(NS_, 2); x_[3] = C16_CVT(NS_, 3);         \
-        C16_STEP8(0, S_, T_, CS_, NS_, P_, g_abs);  C16_STEP8(8, S_, T_, CS_, NS_, P_, g_abs);                       \
-        C16_STEP8(16, S_, T_, CS_, NS_, P_, g_abs); C16_STEP8(24, S_, T_, CS_, NS_, P_, g_abs);                      \
-        C16_STEP8(32, S_, T_, CS_, NS_, P_, g_abs); C16_STEP8(40, S_, T_, CS_, NS_, P_, g_abs);                      \
-        C16_STEP8(48, S_, T_, CS_, NS_, P_, g_abs); C16_STEP8(56, S_, T_, CS_, NS_, P_, g_abs);                      \
+        C16_STEP8(0, S_, T_, CS_, NS_, P_);  C16_STEP8(8, S_, T_, CS_, NS_, P_);                                     \
+        C16_STEP8(16, S_, T_, CS_, NS_, P_); C16_STEP8(24, S_, T_, CS_, NS_, P_);                                    \
+        C16_STEP8(32, S_, T_, CS_, NS_, P_); C16_STEP8(40, S_, T_, CS_, NS_, P_);                                    \
+        C16_STEP8(48, S_, T_, CS_, NS_, P_); C16_STEP8(56, S_, T_, CS_, NS_, P_);                                    \
         fn += GST;                                                                                                  \
     } while (0)
 
     // prologue: factors of the first chunk, the words of the first four groups, the operands of group 0 (row operand 7 comes with row 0)
     C16_TABLE_ASYNC(c_beg, c_beg & 1);
-#define C16_L16(S) C16_LOAD(S, c_beg * GCH + S, 0); C16_LOAD(S, c_beg * GCH + S, 1); C16_LOAD(S, c_beg * GCH + S, 2); C16_LOAD(S, c_beg * GCH + S, 3);     \
-                   C16_LOAD(S, c_beg * GCH + S, 4); C16_LOAD(S, c_beg * GCH + S, 5); C16_LOAD(S, c_beg * GCH + S, 6); C16_LOAD(S, c_beg * GCH + S, 7);     \
-                   C16_LOAD(S, c_beg * GCH + S, 8); C16_LOAD(S, c_beg * GCH + S, 9); C16_LOAD(S, c_beg * GCH + S, 10); C16_LOAD(S, c_beg * GCH + S, 11);   \
-                   C16_LOAD(S, c_beg * GCH + S, 12); C16_LOAD(S, c_beg * GCH + S, 13); C16_LOAD(S, c_beg * GCH + S, 14); C16_LOAD(S, c_beg * GCH + S, 15)
+    // (the run's first group may lie anywhere in the block -- c_beg of a tile split along K, of a fused (tile, run) item, of a later
+    // run -- and anywhere in a word array of many GiB: the base is a 64-bit product, made here once per run)
+    wnext = (__attribute__((address_space(1))) const char *)w8 + (int64_t)c_beg * GCH * wstride;
+#define C16_L16(S) C16_LOAD(S, wnext, 0); C16_LOAD(S, wnext, 1); C16_LOAD(S, wnext, 2); C16_LOAD(S, wnext, 3);       \
+                   C16_LOAD(S, wnext, 4); C16_LOAD(S, wnext, 5); C16_LOAD(S, wnext, 6); C16_LOAD(S, wnext, 7);       \
+                   C16_LOAD(S, wnext, 8); C16_LOAD(S, wnext, 9); C16_LOAD(S, wnext, 10); C16_LOAD(S, wnext, 11);     \
+                   C16_LOAD(S, wnext, 12); C16_LOAD(S, wnext, 13); C16_LOAD(S, wnext, 14); C16_LOAD(S, wnext, 15);   \
+                   wnext += wstride
     C16_L16(0); C16_L16(1); C16_L16(2); C16_L16(3);
 #undef C16_L16
     __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0)
@@ -720,14 +753,13 @@ __global__ __launch_bounds__(256, 1) void syrk_uv16c_kernel(
         const bool more = (c + 1 < c_end);
         if (more) C16_TABLE_ASYNC(c + 1, cur ^ 1);  // every wave is past the barrier that freed this buffer
         for (int q = 0; q < q_cnt; q += 2 * D) {
-            const int g = c * GCH + q;
-            C16_GROUP(0, 1, 0, 1, 0, g);
-            C16_GROUP(1, 0, 1, 2, 1, g + 1);
-            C16_GROUP(0, 1, 2, 3, 0, g + 2);
-            C16_GROUP(1, 0, 3, 0, 1, g + 3);
-            C16_GROUP(0, 1, 0, 1, 0, g + 4);
-            C16_GROUP(1, 0, 1, 2, 1, g + 5);
-            C16_GROUP(0, 1, 2, 3, 0, g + 6);
+            C16_GROUP(0, 1, 0, 1, 0);
+            C16_GROUP(1, 0, 1, 2, 1);
+            C16_GROUP(0, 1, 2, 3, 0);
+            C16_GROUP(1, 0, 3, 0, 1);
+            C16_GROUP(0, 1, 0, 1, 0);
+            C16_GROUP(1, 0, 1, 2, 1);
+            C16_GROUP(0, 1, 2, 3, 0);
             // the chunk's last group prepares the NEXT chunk's first group (or, at the very end, harmlessly re-reads this chunk)
             if (q + 2 * D >= q_cnt) {
                 if (more) {
@@ -740,7 +772,7 @@ __global__ __launch_bounds__(256, 1) void syrk_uv16c_kernel(
                     fn = x1_lds_off(&sfac[cur][0]) + 16 * kq;
                 }
             }
-            C16_GROUP(1, 0, 3, 0, 1, g + 7);
+            C16_GROUP(1, 0, 3, 0, 1);
         }
     }
     {
@@ -822,6 +854,7 @@ __global__ __launch_bounds__(256, 1) void syrk_uv16c_kernel(
 #undef C16_M
 #undef C16_SB
 #undef C16_MFMA
+#undef C16_WAIT_WORDS
 #undef C16_LOAD
 #undef C16_TABLE_ASYNC
 #undef C16_FMA
