@@ -925,6 +925,47 @@ int snpgpu_geno_convert(const snpgpu_geno_src *src, int src_code, const int32_t 
  * dst_major; [3]: it differs).  The two calls share the record: either one reports the last call of either. */
 int snpgpu_geno_convert_stats(double *stats);
 
+/* ---- (1l) VCF text: the genotype columns of data lines as SNPGPU_GENO_PACKED2 rows ----------------------------------------------------
+ * What gnrParseVCF4 (src/ConvToGDS.cpp:667-997) does per sample cell, on the device: the file's own bytes go there and 2-bit rows
+ * come out, with nothing per cell in between.  The fixed columns (CHROM ... FORMAT) stay with the host: snpgpu_vcf_index finds
+ * them, the caller reads them and hands every kept line's allele count and reference allele to snpgpu_vcf_genotypes.
+ *
+ * snpgpu_vcf_index: the line index of a buffer of data lines (the '#' header is the caller's).  Makes no HIP call.
+ *   buf, n_bytes   whole lines; without `final` the buffer ends at its last '\n' and whatever follows is left to the next call:
+ *                  *consumed is the offset behind the last complete line.  With `final` a last line without '\n' is a line.
+ *   col_begin      [max_lines][10]: the offsets of the starts of columns 1 ... 10 (CHROM ... FORMAT, first sample cell)
+ *   line_end       [max_lines]: the end of the line, before its '\n' and before a '\r' in front of that
+ *   line_base      lines in front of this buffer: error messages name the 1-based line line_base + i + 1
+ * Refused: a line with fewer than 10 columns, an empty line, more than max_lines lines. */
+int snpgpu_vcf_index(const char *buf, int64_t n_bytes, int final, int64_t line_base, int64_t max_lines, int64_t *col_begin,
+                     int64_t *line_end, int64_t *n_lines, int64_t *consumed);
+/* snpgpu_vcf_genotypes: line i's sample cells are the tab-separated pieces of text[cell_begin[i], line_end[i]).
+ *   text, text_mem SNPGPU_HOST, SNPGPU_HOST_PINNED (both staged in windows of whole lines) or SNPGPU_DEVICE (any alignment, parsed
+ *                  where it lies); only aligned dwords that hold a byte of [text, text + n_bytes) are loaded
+ *   num_allele     per line: 1 + the number of ALT alleles; an allele index >= it is flagged
+ *   ref_index      per line: the allele that is counted (0 = REF); -1 counts none (every called genotype is 0)
+ *   rows           DEVICE memory of `device`: [n_lines][ceil(n_samp / 4)], the unused codes of a row's last byte 3.  A caller that
+ *                  wants the rows on the host composes with snpgpu_geno_select (device source, host dst).
+ *   line_flags, line_cells   host, n_lines: the flags below and the number of cells found
+ * A cell's GT is the cell up to its first ':'.  At every allele position a run of decimal digits is an allele index and '.' a
+ * missing allele; everything up to the next '|' or '/' is skipped.  The code is the number of alleles equal to ref_index, at
+ * most 2; 3 when any allele is missing; 0 for an empty GT.  Ploidy is whatever the cell holds.
+ * The kernel raises nothing: it flags the line, whose row may then hold anything (inside its own bytes), and the caller decides:
+ *   1  an allele position starts with a byte that is neither a digit nor '.' (whitespace, a sign, a quote, "/0", "0//0")
+ *   2  an allele index >= num_allele
+ *   4  an allele index of more than 9 digits
+ *   8  line_cells != n_samp, or the last cell is empty; cells beyond n_samp are counted and never stored
+ * No device memory grows with n_lines x n_samp but rows; no atomics touch global memory; the result is a pure function of the
+ * input.  Refused before any device is touched: NULL pointers, an unknown text_mem, offsets outside n_bytes or cell_begin >
+ * line_end, n_samp outside 1 ... 2^30 - 1, n_lines outside 1 ... 2^31 - 1, num_allele < 1, ref_index < -1; before any launch: a
+ * device pointer or a stream of another device. */
+int snpgpu_vcf_genotypes(const void *text, int text_mem, int64_t n_bytes, const int64_t *cell_begin, const int64_t *line_end,
+                         const int32_t *num_allele, const int32_t *ref_index, int64_t n_lines, int64_t n_samp, void *rows,
+                         int32_t *line_flags, int64_t *line_cells, int device, void *stream);
+/* of the last snpgpu_vcf_genotypes on this thread: [0] ms of the text's copies to the device, [1] ms of the kernel, [2] launches,
+ * [3] text bytes copied (or parsed in place), [4] bytes of a workgroup's chunk, [5] of a lane's segment, [6] of the halo */
+int snpgpu_vcf_stats(double *stats);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------------------
  * What THIS device's matrix pipe sustains right now: a register-only stream of one MFMA instruction (never waiting on memory,
  * two waves per SIMD) run for `seconds`, rate taken over the second half.  The kernels of this library run against the socket

@@ -63,6 +63,7 @@ EXPORTS = [
     "snpgpu_select_pairs", "snpgpu_multi_select_pairs", "snpgpu_gnrIBDPairs", "snpgpu_gnrIBDPairs_get", "snpgpu_select_stats",
     "snpgpu_geno_select", "snpgpu_geno_select_stats",
     "snpgpu_geno_convert", "snpgpu_geno_convert_stats",
+    "snpgpu_vcf_index", "snpgpu_vcf_genotypes", "snpgpu_vcf_stats",
 ]
 FST_WC84, FST_WH02 = 1, 2
 FST_METHODS = ("W&C84", "W&H02")
@@ -317,6 +318,9 @@ def lib():
     L.snpgpu_geno_select_stats.argtypes = [vp]
     L.snpgpu_geno_convert.argtypes = [ctypes.POINTER(GenoSrc), c_int, vp, i64, vp, i64, vp, c_int, c_int, c_int, c_int, vp]
     L.snpgpu_geno_convert_stats.argtypes = [vp]
+    L.snpgpu_vcf_index.argtypes = [vp, i64, c_int, i64, i64, vp, vp, vp, vp]
+    L.snpgpu_vcf_genotypes.argtypes = [vp, c_int, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, c_int, vp]
+    L.snpgpu_vcf_stats.argtypes = [vp]
     _lib = L
     return L
 
@@ -1684,6 +1688,62 @@ def geno_convert_stats():
     check(lib().snpgpu_geno_convert_stats(_ptr(s)))
     return dict(h2d_ms=float(s[0]), copy_ms=float(s[1]), gather_ms=float(s[2]), transpose_ms=float(s[3]), launches=int(s[4]),
                 source_bytes=float(s[5]), d2h_ms=float(s[6]), windows=int(s[7]))
+
+
+def vcf_index(buf, n_bytes=None, final=True, line_base=0, max_lines=None):
+    """snpgpu_vcf_index: (col_begin int64 [n_lines][10], line_end int64 [n_lines], consumed) of the data lines in buf (bytes, or a
+    numpy uint8 array of which the first n_bytes count).  Without `final` a cut last line is left: consumed is where it starts.
+    max_lines None: as many as the buffer has line ends."""
+    a = np.frombuffer(buf, np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else np.asarray(buf)
+    if a.dtype != np.uint8 or a.ndim != 1 or not a.flags.c_contiguous:
+        raise ValueError("buf should be bytes or a contiguous uint8 array")
+    n_bytes = a.size if n_bytes is None else int(n_bytes)
+    if n_bytes > a.size:
+        raise ValueError("n_bytes exceeds the buffer")
+    if max_lines is None:
+        max_lines = int(np.count_nonzero(a[:n_bytes] == 10)) + 1
+    max_lines = int(max_lines)
+    col = np.empty((max(max_lines, 1), 10), np.int64)
+    end = np.empty(max(max_lines, 1), np.int64)
+    n, used = ctypes.c_int64(0), ctypes.c_int64(0)
+    keep = a if a.size else np.zeros(1, np.uint8)
+    check(lib().snpgpu_vcf_index(_ptr(keep), n_bytes, int(bool(final)), int(line_base), max_lines, _ptr(col), _ptr(end), ctypes.byref(n),
+                                 ctypes.byref(used)))
+    return col[:n.value], end[:n.value], used.value
+
+
+def vcf_genotypes(text, cell_begin, line_end, num_allele, ref_index, n_samp, rows, n_bytes=None, text_mem=None, device=0, stream=None):
+    """snpgpu_vcf_genotypes: the sample cells of the lines text[cell_begin[i], line_end[i]) as PACKED2 rows in DEVICE memory at the
+    address `rows` ([n_lines][ceil(n_samp / 4)]).  text: bytes / a numpy uint8 array (host memory), or an address (int) with n_bytes
+    -- device memory unless text_mem says HOST or HOST_PINNED.  Returns (line_flags int32, line_cells int64)."""
+    keep = None
+    if isinstance(text, int):
+        if n_bytes is None:
+            raise ValueError("a text address needs n_bytes")
+        ptr, mem = ctypes.c_void_p(text), (DEVICE if text_mem is None else int(text_mem))
+    else:
+        keep = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8)
+        ptr, mem = _ptr(keep), (HOST if text_mem is None else int(text_mem))
+        n_bytes = keep.size if n_bytes is None else int(n_bytes)
+        if n_bytes > keep.size:
+            raise ValueError("n_bytes exceeds the text array")
+    cb, le = np.ascontiguousarray(cell_begin, np.int64).reshape(-1), np.ascontiguousarray(line_end, np.int64).reshape(-1)
+    na, ri = np.ascontiguousarray(num_allele, np.int32).reshape(-1), np.ascontiguousarray(ref_index, np.int32).reshape(-1)
+    n = cb.size
+    if not (le.size == n and na.size == n and ri.size == n):
+        raise ValueError("cell_begin, line_end, num_allele and ref_index should have one entry per line")
+    flags, cells = np.zeros(n, np.int32), np.zeros(n, np.int64)
+    check(lib().snpgpu_vcf_genotypes(ptr, mem, int(n_bytes), _ptr(cb), _ptr(le), _ptr(na), _ptr(ri), n, int(n_samp), _dptr(rows),
+                                     _ptr(flags), _ptr(cells), int(device), ctypes.c_void_p(stream) if stream else None))
+    return flags, cells
+
+
+def vcf_stats():
+    """dict of snpgpu_vcf_stats for the last vcf_genotypes call on this thread"""
+    s = np.zeros(7, np.float64)
+    check(lib().snpgpu_vcf_stats(_ptr(s)))
+    return dict(h2d_ms=float(s[0]), kernel_ms=float(s[1]), launches=int(s[2]), text_bytes=float(s[3]), chunk_bytes=int(s[4]),
+                segment_bytes=int(s[5]), halo_bytes=int(s[6]))
 
 
 def select_stats():

@@ -50,6 +50,7 @@ import numpy as np
 from . import _lib
 from . import gds as _gds
 from . import bed as _bed
+from . import vcf as _vcf
 from .gds import GenoFile, open_gds, pack_2bit_rows  # noqa: F401
 
 
@@ -1715,6 +1716,83 @@ def snpgdsOpenBED(bed_fn, fam_fn=None, bim_fn=None, family=False, option=None, c
         print("    BIM file: '%s'" % bim_fn)
         print("    %d samples, %d SNPs" % (bs.n_samp, bs.n_snp))
     return bs
+
+
+class VcfGenoFile(GenoFile):
+    """What snpgdsOpenVCF returns: a GenoFile (packed rows in host memory) with the nodes snpgdsVCF2GDS would have stored --
+    snp_rs_id, snp_allele, snp_annot["qual"] / ["filter"] and the chromosome labels as text."""
+
+    def __init__(self, packed, n_samp, sample_id, nodes):
+        GenoFile.__init__(self, packed=packed, n_samp=n_samp, sample_id=sample_id, snp_id=nodes["snp_id"],
+                          snp_chromosome=nodes["snp_chromosome"], snp_position=nodes["snp_position"], snp_allele=nodes["snp_allele"])
+        self.snp_rs_id = nodes["snp_rs_id"]
+        self.snp_annot = {"qual": nodes["qual"], "filter": nodes["filter"]}
+        # text labels, as BedStream(cvt_chr="char"): autosome_only=True keeps the labels that parse into 1 ... 22
+        self.chromosome_code = {}
+
+
+def snpgdsOpenVCF(vcf_fn, method="biallelic.only", ref_allele=None, ignore_chr_prefix="chr", verbose=True, device=0):
+    """Open VCF files for every snpgds* function: snpgdsVCF2GDS (R/Conversion.R:972-1155 -> gnrParseVCF4,
+    src/ConvToGDS.cpp:667-997) + snpgdsOpen in one step, without the GDS file in between.  vcf_fn: a file name or a list of
+    them (plain or .gz) with the same sample ids.  method "biallelic.only" keeps the lines whose REF and ALT are single
+    nucleotides, "copy.num.of.ref" all; the genotype is the number of copies of the reference allele (0 / 1 / 2, 3 = missing).
+    ref_allele: None, or one entry per data line of all files (None entries keep REF): the allele that is counted.
+    The sample cells are parsed on the device (vcf.VcfReader -> snpgpu_vcf_genotypes) and the rows are kept in host memory, at
+    most SNPGPU_VCF_MAX_BYTES (default 8 GiB) of them.  Returns a VcfGenoFile.  There is no CPU fallback: without a device the
+    call fails with SnpGpuError.  There is no snpgdsVCF2GDS here, for the reason there is no snpgdsBED2GDS: writing the GDS
+    container is gdsfmt's work, which this package does not restate."""
+    import os
+    files = [vcf_fn] if isinstance(vcf_fn, str) else list(vcf_fn)
+    if not files or not all(isinstance(f, str) for f in files):
+        raise TypeError("is.character(vcf.fn) & is.vector(vcf.fn) is not TRUE")
+    if method not in _vcf.VcfReader.METHODS:
+        raise ValueError("'arg' should be one of \"biallelic.only\", \"copy.num.of.ref\"")
+    if ref_allele is not None and not all(a is None or isinstance(a, str) for a in ref_allele):
+        raise TypeError("is.null(ref.allele) || is.character(ref.allele) is not TRUE")
+    if not isinstance(ignore_chr_prefix, str) and not all(isinstance(a, str) for a in ignore_chr_prefix):
+        raise TypeError("is.character(ignore.chr.prefix) is not TRUE")
+    if not isinstance(verbose, (bool, np.bool_)):
+        raise TypeError("is.logical(verbose) is not TRUE")
+    _cat(verbose, "Open VCF as a SNP GDS object ...")
+    _cat(verbose, "Method: extracting biallelic SNPs" if method == "biallelic.only"
+         else "Method: dosage (0,1,2) of reference allele for all variant sites")
+    samp_id = None
+    for fn in files:
+        ids = _vcf.sample_ids(fn)
+        if samp_id is None:
+            samp_id = ids
+            if len(samp_id) <= 0:
+                raise ValueError("No sample in the VCF file!")
+        elif ids != samp_id:
+            raise ValueError("'%s' has different sample id." % fn)
+    _cat(verbose, "Number of samples: %d" % len(samp_id))
+    if _lib.device_count() < 1:
+        raise _lib.SnpGpuError("snpgdsOpenVCF: no HIP device (the VCF genotype parser has no CPU fallback)")
+    budget = int(os.environ.get("SNPGPU_VCF_MAX_BYTES", 8 << 30))
+    rb = (len(samp_id) + 3) // 4
+    parts, readers, held = [], [], 0
+    next_id, lines = 1, 0
+    for fn in files:
+        _cat(verbose, "Parsing \"", fn, "\" ...")
+        r = _vcf.VcfReader(fn, method=method, ref_allele=ref_allele, ignore_chr_prefix=ignore_chr_prefix, snp_id_start=next_id,
+                           line_start=lines)
+        for _, m, rows in r.blocks(65536, device=device):
+            held += m * rb
+            if held > budget:
+                raise ValueError("the genotypes of %s need more than the %d bytes of SNPGPU_VCF_MAX_BYTES in host memory: read the "
+                                 "file block by block with snprelate_amd.vcf.VcfReader.blocks instead" % (", ".join(files), budget))
+            parts.append(rows.cpu().numpy())
+        _cat(verbose, "\timport %d variant%s." % (r.n_snp, "s" if r.n_snp > 1 else ""))
+        next_id, lines = r.next_snp_id, r.lines_seen
+        readers.append(r)
+    if not sum(r.n_snp for r in readers):
+        raise ValueError("No variant in the VCF file%s (method \"%s\")" % ("s" if len(files) > 1 else "", method))
+    cat = lambda name: np.concatenate([getattr(r, name) for r in readers])          # noqa: E731
+    nodes = dict(snp_id=cat("snp_id"), snp_chromosome=cat("snp_chromosome"), snp_position=cat("snp_position"),
+                 snp_allele=cat("snp_allele"), snp_rs_id=cat("snp_rs_id"),
+                 qual=np.concatenate([r.snp_annot["qual"] for r in readers]),
+                 filter=np.concatenate([r.snp_annot["filter"] for r in readers]))
+    return VcfGenoFile(np.concatenate(parts, 0), len(samp_id), np.array(samp_id), nodes)
 
 
 def _bim_chromosomes(gdsobj, chrom):
