@@ -1135,8 +1135,6 @@ int select_check_opts(const char *fn, const snpgpu_sel_opts *o, int64_t capacity
     return 0;
 }
 
-int select_kind(int what) { return what == SNPGPU_SEL_KING_ROBUST ? SNPGPU_KING_ROBUST : what == SNPGPU_SEL_KING_HOMO ? SNPGPU_KING_HOMO : SNPGPU_IBS; }
-
 struct EvPair {
     hipEvent_t a = nullptr, b = nullptr;
     ~EvPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }

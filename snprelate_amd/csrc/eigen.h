@@ -1,5 +1,9 @@
-// Internal interface of the top-k eigen solver (eigen.hip) shared with the multi-device driver (multi.hip).
+// Internal interface of the top-k eigen solver (eigen.hip) shared with the multi-device driver (multi.hip), and of the dense
+// route (eigen_dense.hip) shared with the working space (workspace.hip, pca_randomized.hip).
 #pragma once
+#include <hipsolver/hipsolver.h>
+
+#include <functional>
 #include <vector>
 
 #include "snpgpu_internal.h"
@@ -40,5 +44,23 @@ private:
 // largest-k eigenpairs: eigval_host [k] descending (host), eigvec [k][n] = column-major n x k (`mem`: host or op.device())
 int krylov_topk(EigOperator &op, int k, const snpgpu_eig_opts *opts, double *eigval_host, double *eigvec, int mem,
                 snpgpu_eig_info *info);
+
+struct SolverHandle {      // owns a hipSOLVER handle; declare it AFTER the buffers the handle is given, so that it goes first
+    hipsolverHandle_t h = nullptr;
+    ~SolverHandle() { if (h) hipsolverDestroy(h); }
+};
+
+// ---- the dense route (eigen_dense.hip) ----
+// top-k eigenpairs of a dense symmetric matrix A (device, n x n, overwritten) by hipSOLVER's syevdx.  eigval: k values (descending,
+// host), eigvec: n x k column-major in `mem`.  Returns 2 where the solver declines the size (the caller takes the Krylov solver).
+int dense_topk(int device, hipStream_t stream, double *A, int64_t n, int k, double *eigval, double *eigvec, int mem);
+bool dense_route(int64_t n, int k);         // whether n samples / k eigenpairs take the dense solver
+int krylov_scale(snpgpu_ctx *c, double *scale);
+
+// Top-k eigenpairs of a context's finalised matrix by whichever route dense_route picks.  fill_dense(A) writes the dense n x n
+// matrix to the device pointer A; prepare_panel(&scale) readies the resident panel for the Krylov solver and yields its scale
+// (also called when the dense solver declines the size).  eigval: k values on the host, eigvec: n x k column-major in `mem`.
+int ctx_topk_eigen(snpgpu_ctx *c, int k, const std::function<int(double *A)> &fill_dense,
+                   const std::function<int(double *scale)> &prepare_panel, double *eigval, double *eigvec, int mem);
 
 }  // namespace snpgpu

@@ -377,6 +377,8 @@ struct SelectArgs {
     uint32_t *counts; int64_t *offsets;
     int64_t capacity; int32_t *idx1, *idx2; double *v0, *v1, *kin;
 };
+// the context kind a selection's `what` accumulates on
+inline int select_kind(int what) { return what == SNPGPU_SEL_KING_ROBUST ? SNPGPU_KING_ROBUST : what == SNPGPU_SEL_KING_HOMO ? SNPGPU_KING_HOMO : SNPGPU_IBS; }
 int64_t select_segments(const PanelGeom &g);
 int launch_select_scan(hipStream_t st, const uint32_t *counts, int64_t n_seg, int64_t *offsets);
 int launch_select_king_robust(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const int32_t *family, const SelectArgs &s, bool write);
