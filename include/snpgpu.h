@@ -966,6 +966,74 @@ int snpgpu_vcf_genotypes(const void *text, int text_mem, int64_t n_bytes, const 
  * [3] text bytes copied (or parsed in place), [4] bytes of a workgroup's chunk, [5] of a lane's segment, [6] of the halo */
 int snpgpu_vcf_stats(double *stats);
 
+/* ---- (1m) text out: SNPGPU_GENO_PACKED2 rows as lines of text ---------------------------------------------------------------------------
+ * What gnrConvGDS2PED and gnrConvGDS2EIGEN (src/SNPRelate.cpp:685-767, :828-859) do with one `ofstream <<` per genotype, on the
+ * device: 2-bit rows go in, the file's own bytes come out.  Every row becomes one line: an optional prefix, one piece per column,
+ * '\n'.  Who is a row is the caller's business: a SNP for .eigenstratgeno, a sample for .ped (rows transposed with
+ * snpgpu_geno_convert, dst_major = 1, first).
+ *   rows           DEVICE memory of `device`: [n_rows][ceil(n_cols / 4)] codes, byte-aligned rows, any alignment of the first
+ *   format         the piece of a column with code 0 / 1 / 2 / 3:
+ *                    SNPGPU_TEXT_DIGIT        "0" "1" "2" "9"
+ *                    SNPGPU_TEXT_PED_AB       "\tB B" "\tA B" "\tA A" "\t0 0"
+ *                    SNPGPU_TEXT_PED_12       "\t2 2" "\t1 2" "\t1 1" "\t0 0"
+ *                    SNPGPU_TEXT_PED_ALLELE   "\t" s2 " " s2, "\t" s1 " " s2, "\t" s1 " " s1, "\t0 0" with the column's alleles
+ *   allele_pool, allele_off   SNPGPU_TEXT_PED_ALLELE only (host): s1, s2 of column c are the bytes [allele_off[2c], allele_off[2c + 1])
+ *                  and [allele_off[2c + 1], allele_off[2c + 2]) of the pool; 2 n_cols + 1 offsets, every allele at least one byte
+ *                  (the caller writes "0" for an empty one), of any length.  When all are one byte long every line has the same
+ *                  length and the fixed-width kernel runs with the pool as its table.
+ *   prefix_pool, prefix_off   both NULL, or (host) the bytes [prefix_off[r], prefix_off[r + 1]) copied to the head of line r
+ *   text           DEVICE memory of `device`, any alignment, line_off[n_rows] bytes -- or NULL: the call only sizes.  A caller that
+ *                  wants the text on the host copies it.
+ *   line_off       host, n_rows + 1: line r is text[line_off[r], line_off[r + 1]), line_off[0] = 0
+ * Sizing a fixed-width format (all but alleles of several lengths) is arithmetic and touches no device; else a first launch
+ * gives every line's length and the second one writes.  The kernels store only inside [text, text + line_off[n_rows]), load only
+ * aligned dwords that hold a byte of the rows, use no global atomics; the text is a pure function of the input.
+ * Refused before any device is touched: NULL pointers, an unknown format, n_cols outside 1 ... 2^30 - 1, n_rows outside
+ * 1 ... 2^31 - 1, offsets that are not ascending; before any launch: a device pointer or a stream of another device. */
+enum snpgpu_text_format { SNPGPU_TEXT_DIGIT = 0, SNPGPU_TEXT_PED_AB = 1, SNPGPU_TEXT_PED_12 = 2, SNPGPU_TEXT_PED_ALLELE = 3 };
+int snpgpu_text_render(const void *rows, int64_t n_rows, int64_t n_cols, int format, const char *allele_pool,
+                       const int64_t *allele_off, const char *prefix_pool, const int64_t *prefix_off, void *text, int64_t *line_off,
+                       int device, void *stream);
+/* of the last snpgpu_text_render on this thread: [0] ms of the length pass, [1] ms of the write pass, [2] launches, [3] bytes
+ * written, [4] bytes of a lane's segment, [5] columns of a workgroup's tile */
+int snpgpu_text_stats(double *stats);
+
+/* ---- (1n) PLINK .ped text in: allele tokens of data lines as SNPGPU_GENO_PACKED2 sample rows ----------------------------------------------
+ * What gnrParsePED (src/ConvToGDS.cpp:1175-1361) does per allele token -- one std::string and one std::map lookup, over two passes
+ * of the file --, on the device.  The six leading columns of a line stay with the host; it hands over where the seventh starts.
+ * The reference reads the file twice, and so do these calls: over every window of the text snpgpu_ped_tokens + snpgpu_ped_census,
+ * then the host picks every SNP's reference allele from the table, then over every window snpgpu_ped_tokens + snpgpu_ped_codes.
+ *
+ * snpgpu_ped_tokens: line i's tokens are the maximal runs of bytes of text[cell_begin[i], line_end[i]) that are neither tab nor
+ * space.
+ *   text           DEVICE memory of `device`, any alignment; only aligned dwords that hold a byte of [text, text + n_bytes) are loaded
+ *   tokens         DEVICE memory: the token matrix uint8 [n_lines][2 n_snp], token k of a line its k-th token's byte; tokens beyond
+ *                  2 n_snp are counted and never stored
+ *   line_flags, line_tokens   host, n_lines: the flags below and the number of tokens found
+ * A token is regular when it is one byte in 0x21 ... 0x7E and its separator is one tab or a run of spaces: then it is the cell
+ * CReadLine::GetCell (src/ConvToGDS.cpp:123-179) returns.  The kernel raises nothing: it flags the line, whose tokens may then
+ * hold anything (inside its own bytes), and the caller settles it:
+ *   1  a token of more than one byte, or a byte outside 0x21 ... 0x7E
+ *   2  an empty token: a tab behind a tab or a space, a space behind a tab, a separator at cell_begin, a tab at the line's end
+ *   8  line_tokens != 2 n_snp
+ * snpgpu_ped_census: adds to table (DEVICE, uint32 [n_snp][94], zeroed by the caller before the first window) the number of times
+ * byte 0x21 + c other than '0' is a token of SNP j in the lines whose line_flags (host) are 0: entry [j][c].  A workgroup owns a
+ * range of SNPs; successive windows add on the stream.
+ * snpgpu_ped_codes: rows (DEVICE, [n_lines][ceil(n_snp / 4)], tail padding 3) from the token matrix: [t1 == ref[j]] + [t2 == ref[j]],
+ * 3 when either token is '0'.  ref (host, n_snp): the reference allele's byte, 0 = it is not a single byte (no token equals it).
+ * The rows of flagged lines hold anything: the caller patches them.
+ * No atomics touch global memory; the results are pure functions of the input.  Refused before any device is touched: NULL
+ * pointers, offsets outside n_bytes or cell_begin > line_end, n_snp outside 1 ... 2^30 - 1, n_lines outside 1 ... 2^31 - 1; before
+ * any launch: a device pointer or a stream of another device. */
+int snpgpu_ped_tokens(const void *text, int64_t n_bytes, const int64_t *cell_begin, const int64_t *line_end, int64_t n_lines,
+                      int64_t n_snp, void *tokens, int32_t *line_flags, int64_t *line_tokens, int device, void *stream);
+int snpgpu_ped_census(const void *tokens, const int32_t *line_flags, int64_t n_lines, int64_t n_snp, void *table, int device,
+                      void *stream);
+int snpgpu_ped_codes(const void *tokens, int64_t n_lines, int64_t n_snp, const uint8_t *ref, void *rows, int device, void *stream);
+/* on this thread: [0] [1] [2] ms of the last tokens / census / codes kernel, [3] launches of the last call, [4] text bytes of the
+ * last snpgpu_ped_tokens, [5] bytes of a workgroup's chunk, [6] of a lane's segment, [7] of the halo */
+int snpgpu_ped_stats(double *stats);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------------------
  * What THIS device's matrix pipe sustains right now: a register-only stream of one MFMA instruction (never waiting on memory,
  * two waves per SIMD) run for `seconds`, rate taken over the second half.  The kernels of this library run against the socket

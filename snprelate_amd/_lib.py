@@ -20,6 +20,7 @@ GENO_U8, GENO_PACKED2 = 0, 1
 LD_COMPOSITE, LD_R, LD_DPRIME, LD_CORR, LD_COV = 1, 2, 3, 4, 5
 HOST, DEVICE, HOST_PINNED = 0, 1, 2
 CODE_GDS, CODE_BED = 0, 1
+TEXT_DIGIT, TEXT_PED_AB, TEXT_PED_12, TEXT_PED_ALLELE = 0, 1, 2, 3
 
 EXPORTS = [
     "snpgpu_abi_version", "snpgpu_last_error", "snpgpu_device_count",
@@ -64,6 +65,8 @@ EXPORTS = [
     "snpgpu_geno_select", "snpgpu_geno_select_stats",
     "snpgpu_geno_convert", "snpgpu_geno_convert_stats",
     "snpgpu_vcf_index", "snpgpu_vcf_genotypes", "snpgpu_vcf_stats",
+    "snpgpu_text_render", "snpgpu_text_stats",
+    "snpgpu_ped_tokens", "snpgpu_ped_census", "snpgpu_ped_codes", "snpgpu_ped_stats",
 ]
 FST_WC84, FST_WH02 = 1, 2
 FST_METHODS = ("W&C84", "W&H02")
@@ -321,6 +324,12 @@ def lib():
     L.snpgpu_vcf_index.argtypes = [vp, i64, c_int, i64, i64, vp, vp, vp, vp]
     L.snpgpu_vcf_genotypes.argtypes = [vp, c_int, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, c_int, vp]
     L.snpgpu_vcf_stats.argtypes = [vp]
+    L.snpgpu_text_render.argtypes = [vp, i64, i64, c_int, vp, vp, vp, vp, vp, vp, c_int, vp]
+    L.snpgpu_text_stats.argtypes = [vp]
+    L.snpgpu_ped_tokens.argtypes = [vp, i64, vp, vp, i64, i64, vp, vp, vp, c_int, vp]
+    L.snpgpu_ped_census.argtypes = [vp, vp, i64, i64, vp, c_int, vp]
+    L.snpgpu_ped_codes.argtypes = [vp, i64, i64, vp, vp, c_int, vp]
+    L.snpgpu_ped_stats.argtypes = [vp]
     _lib = L
     return L
 
@@ -1744,6 +1753,92 @@ def vcf_stats():
     check(lib().snpgpu_vcf_stats(_ptr(s)))
     return dict(h2d_ms=float(s[0]), kernel_ms=float(s[1]), launches=int(s[2]), text_bytes=float(s[3]), chunk_bytes=int(s[4]),
                 segment_bytes=int(s[5]), halo_bytes=int(s[6]))
+
+
+def _pool(pieces):
+    """(pool uint8, offsets int64) of a list of bytes / str pieces"""
+    pieces = [x if isinstance(x, (bytes, bytearray)) else str(x).encode("latin1") for x in pieces]
+    off = np.zeros(len(pieces) + 1, np.int64)
+    np.cumsum([len(x) for x in pieces], out=off[1:])
+    pool = np.frombuffer(b"".join(pieces) + b"\0", np.uint8)
+    return pool, off
+
+
+def text_render(rows, n_rows, n_cols, fmt, alleles=None, prefixes=None, text=None, device=0, stream=None):
+    """snpgpu_text_render: the n_rows x n_cols codes at the DEVICE address `rows` (PACKED2, [n_rows][ceil(n_cols / 4)]) as lines of
+    text at the DEVICE address `text`; text None only sizes.  fmt: TEXT_DIGIT / TEXT_PED_AB / TEXT_PED_12 / TEXT_PED_ALLELE.
+    alleles: for TEXT_PED_ALLELE the 2 n_cols pieces s1, s2 per column (bytes or str), or a ready (pool, offsets) pair;
+    prefixes: None, n_rows pieces, or a (pool, offsets) pair.  Returns line_off int64 [n_rows + 1]."""
+    def pair(x, n):
+        if x is None:
+            return None, None
+        if isinstance(x, tuple) and len(x) == 2 and isinstance(x[1], np.ndarray):
+            pool, off = np.ascontiguousarray(x[0], np.uint8), np.ascontiguousarray(x[1], np.int64)
+        else:
+            pool, off = _pool(x)
+        if off.shape != (n + 1,):
+            raise ValueError("%d pieces expected" % n)
+        if len(off) and off[-1] > pool.size:
+            raise ValueError("the offsets exceed the pool")
+        return pool, off
+    n_rows, n_cols = int(n_rows), int(n_cols)
+    apool, aoff = pair(alleles, 2 * n_cols)
+    ppool, poff = pair(prefixes, n_rows)
+    line_off = np.zeros(max(n_rows, 0) + 1, np.int64)
+    check(lib().snpgpu_text_render(_dptr(rows), n_rows, n_cols, int(fmt), _ptr(apool), _ptr(aoff), _ptr(ppool), _ptr(poff),
+                                   _dptr(text) if text else None, _ptr(line_off), int(device),
+                                   ctypes.c_void_p(stream) if stream else None))
+    return line_off
+
+
+def text_stats():
+    """dict of snpgpu_text_stats for the last text_render call on this thread"""
+    s = np.zeros(6, np.float64)
+    check(lib().snpgpu_text_stats(_ptr(s)))
+    return dict(lengths_ms=float(s[0]), write_ms=float(s[1]), launches=int(s[2]), text_bytes=float(s[3]), segment_bytes=int(s[4]),
+                tile_columns=int(s[5]))
+
+
+PED_FLAG_TOKEN, PED_FLAG_EMPTY, PED_FLAG_COUNT = 1, 2, 8
+PED_ALLELES = 94
+
+
+def ped_tokens(text, n_bytes, cell_begin, line_end, n_snp, tokens, device=0, stream=None):
+    """snpgpu_ped_tokens: the allele tokens of the lines text[cell_begin[i], line_end[i]) (text: a DEVICE address) into the token
+    matrix uint8 [n_lines][2 n_snp] at the DEVICE address `tokens`.  Returns (line_flags int32, line_tokens int64)."""
+    cb, le = np.ascontiguousarray(cell_begin, np.int64).reshape(-1), np.ascontiguousarray(line_end, np.int64).reshape(-1)
+    if cb.size != le.size:
+        raise ValueError("cell_begin and line_end should have one entry per line")
+    flags, count = np.zeros(cb.size, np.int32), np.zeros(cb.size, np.int64)
+    check(lib().snpgpu_ped_tokens(_dptr(text), int(n_bytes), _ptr(cb), _ptr(le), cb.size, int(n_snp), _dptr(tokens), _ptr(flags),
+                                  _ptr(count), int(device), ctypes.c_void_p(stream) if stream else None))
+    return flags, count
+
+
+def ped_census(tokens, line_flags, n_snp, table, device=0, stream=None):
+    """snpgpu_ped_census: the tokens of the unflagged lines of the token matrix (DEVICE address) added to the DEVICE table uint32
+    [n_snp][94]"""
+    fl = np.ascontiguousarray(line_flags, np.int32).reshape(-1)
+    check(lib().snpgpu_ped_census(_dptr(tokens), _ptr(fl), fl.size, int(n_snp), _dptr(table), int(device),
+                                  ctypes.c_void_p(stream) if stream else None))
+
+
+def ped_codes(tokens, n_lines, n_snp, ref, rows, device=0, stream=None):
+    """snpgpu_ped_codes: the token matrix (DEVICE address) against the reference allele bytes ref (uint8 [n_snp], 0 = none) as PACKED2
+    sample rows at the DEVICE address `rows`"""
+    r = np.ascontiguousarray(ref, np.uint8).reshape(-1)
+    if r.size != int(n_snp):
+        raise ValueError("ref should hold one byte per SNP")
+    check(lib().snpgpu_ped_codes(_dptr(tokens), int(n_lines), int(n_snp), _ptr(r), _dptr(rows), int(device),
+                                 ctypes.c_void_p(stream) if stream else None))
+
+
+def ped_stats():
+    """dict of snpgpu_ped_stats on this thread"""
+    s = np.zeros(8, np.float64)
+    check(lib().snpgpu_ped_stats(_ptr(s)))
+    return dict(tokens_ms=float(s[0]), census_ms=float(s[1]), codes_ms=float(s[2]), launches=int(s[3]), text_bytes=float(s[4]),
+                chunk_bytes=int(s[5]), segment_bytes=int(s[6]), halo_bytes=int(s[7]))
 
 
 def select_stats():

@@ -34,6 +34,9 @@ INTEGRATION.md):
     snpgdsOpenBED                 R/Conversion.R:433-653 (snpgdsBED2GDS + snpgdsOpen: a PLINK .bed/.bim/.fam triple read in place)
     snpgdsGDS2BED                 R/Conversion.R:310-425 (the selected rectangle as PLINK .bed/.bim/.fam)
     snpgdsOption                  R/AllUtilities.R:1910-1990 (without a file: the chromosome codes snpgdsOpenBED takes)
+    snpgdsGDS2PED                 R/Conversion.R:26-124  (the selected rectangle as PLINK text .ped/.map, the lines made on the GPU)
+    snpgdsGDS2Eigen               R/Conversion.R:695-785 (the selected rectangle as EIGENSTRAT .eigenstratgeno/.snp/.ind)
+    snpgdsOpenPED                 R/Conversion.R:132-302 (snpgdsPED2GDS + snpgdsOpen: PLINK text .ped/.map parsed on the GPU)
 
 All arithmetic on genotype matrices runs on the MI355X through libsnpgpu.so
 (`_lib`); there is no CPU fallback.  The one exception is snpgdsIndInbCoef, which
@@ -1920,6 +1923,165 @@ def _bed_blocks(gdsobj, samp_flag, snp_flag, individual_major, block, device):
         else:
             g = _gds.unpack_2bit_rows(packed[k0:k1] if idx is None else packed[k0:k1][idx], n)
             yield a, b, _bed.encode_bed(g if samp_index is None else g[:, samp_index], individual_major)
+
+
+def _file_order_flags(gdsobj, sample_id, snp_id, between=None):
+    """the selection flags of snpgdsGDS2PED / snpgdsGDS2Eigen (R/Conversion.R:34-64, :702-734): ids %in% the wanted ones, in FILE
+    order, with the reference's messages; `between` runs after the sample check, as the reference prints its first line there"""
+    flags = []
+    for want, have, name, what in ((sample_id, gdsobj.sample_id, "sample.id", "sample"), (snp_id, gdsobj.snp_id, "snp.id", "SNP")):
+        f = np.ones(len(have), bool)
+        if want is not None:
+            want = np.asarray(want).reshape(-1)
+            f = np.isin(have, want)
+            if int(f.sum()) != len(want):
+                raise ValueError("Some of %s do not exist!" % name)
+            if f.sum() <= 0:
+                raise ValueError("No %s in the working dataset." % what)
+        flags.append(f)
+        if between is not None and len(flags) == 1:
+            between()
+    return flags
+
+
+def _text_gdsobj(gdsobj):
+    opened = isinstance(gdsobj, str)
+    if opened:
+        gdsobj = snpgdsOpen(gdsobj, stream=True)
+    if not isinstance(gdsobj, (GenoFile, _gds.GenoStream)):
+        raise TypeError("'gdsobj' should be a SNP GDS object (snpgdsOpen / GenoFile)")
+    return gdsobj
+
+
+def snpgdsGDS2PED(gdsobj, ped_fn, sample_id=None, snp_id=None, use_snp_rsid=True, format="A/G/C/T", verbose=True, device=0):
+    """Write the selected genotypes as PLINK text PED (R/Conversion.R:26-124 -> gnrConvGDS2PED, src/SNPRelate.cpp:685-767):
+    ped_fn + ".map" and ped_fn + ".ped".  gdsobj: a SNP GDS object of any kind (GenoFile, GenoStream, BedStream, the VCF GenoFile)
+    or the name of a GDS file.  The selection follows FILE order.  format "A/G/C/T" writes the alleles of snp_allele ("s1/s2":
+    a third allele is ignored, an empty one is "0"; an allele may be any length) -- genotype 0 / 1 / 2 / missing is "s2 s2" /
+    "s1 s2" / "s1 s1" / "0 0" --, "A/B" the letters A and B, "1/2" the digits.  .map: tab-separated chromosome (23 -> X, 25 -> Y,
+    24 -> XY, 26 -> MT, the reference's four substitutions), snp_rs_id when the object has it and use_snp_rsid is set, else
+    snp_id, genetic distance 0, position.  .ped: "0 ID 0 0 0 -9" and the genotypes, tab-separated, one line per sample; its bytes
+    are made on the device (text.write_ped -> snpgpu_text_render) in windows of SNPGPU_TEXT_STAGE_BYTES and appended to the file.
+    There is no CPU fallback: without a device the call fails with SnpGpuError."""
+    from . import text as _text
+    gdsobj = _text_gdsobj(gdsobj)
+    if not isinstance(ped_fn, str):
+        raise TypeError("is.character(ped.fn) is not TRUE")
+    format = _match_arg(format, ("A/G/C/T", "A/B", "1/2"), "arg")
+    samp_flag, snp_flag = _file_order_flags(gdsobj, sample_id, snp_id, lambda: _cat(verbose, "Converting from GDS to PLINK PED:"))
+    alleles = None
+    if format == "A/G/C/T":
+        al = getattr(gdsobj, "snp_allele", None)
+        if al is None:
+            raise ValueError("There is no 'snp.allele' variable in the GDS file.")
+        if len(al) != len(gdsobj.snp_id):
+            raise ValueError("Invalid 'snp.allele' in the GDS file.")
+        alleles = _text.split_alleles(np.asarray(al)[snp_flag])
+    fmt = {"A/G/C/T": _lib.TEXT_PED_ALLELE, "A/B": _lib.TEXT_PED_AB, "1/2": _lib.TEXT_PED_12}[format]
+
+    rs = gdsobj.snp_id
+    if use_snp_rsid and getattr(gdsobj, "snp_rs_id", None) is not None:
+        rs = gdsobj.snp_rs_id
+    if gdsobj.snp_position is None:
+        raise ValueError("the object has no snp.position, which the .map file needs")
+    sub = {"23": "X", "25": "Y", "24": "XY", "26": "MT"}
+    with open(ped_fn + ".map", "w") as f:
+        for c, r, pos in zip(np.asarray(gdsobj.snp_chromosome)[snp_flag], np.asarray(rs)[snp_flag], gdsobj.snp_position[snp_flag]):
+            c = str(c)
+            f.write("%s\t%s\t0\t%d\n" % (sub.get(c, c), r, pos))
+    _cat(verbose, "\tOutput a MAP file DONE.")
+    _cat(verbose, "\tOutput a PED file ...")
+    with open(ped_fn + ".ped", "wb") as f:
+        _text.write_ped(f, gdsobj, samp_flag, snp_flag, [str(x) for x in np.asarray(gdsobj.sample_id)[samp_flag]], fmt, alleles, device)
+    return None
+
+
+def snpgdsGDS2Eigen(gdsobj, eigen_fn, sample_id=None, snp_id=None, verbose=True, device=0):
+    """Write the selected genotypes in EIGENSTRAT format (R/Conversion.R:695-785 -> gnrConvGDS2EIGEN, src/SNPRelate.cpp:828-859):
+    eigen_fn + ".snp" (id, chromosome, 0, position), ".ind" (id, sex, "control") and ".eigenstratgeno" (one line per SNP, one
+    digit per sample: the genotype, 9 = missing).  gdsobj and the selection as snpgdsGDS2PED.  The sex column is
+    sample_annot["sex"]: every value must be "M" or "F" (the reference's message otherwise), a missing value (None / NaN) is
+    "U", and so is every sample when the object has no such column.  The genotype lines are made on the device
+    (text.write_eigenstratgeno -> snpgpu_text_render); there is no CPU fallback."""
+    from . import text as _text
+    gdsobj = _text_gdsobj(gdsobj)
+    if not isinstance(eigen_fn, str):
+        raise TypeError("is.character(eigen.fn) is not TRUE")
+    samp_flag, snp_flag = _file_order_flags(gdsobj, sample_id, snp_id, lambda: _cat(verbose, "Converting from GDS to EIGENSOFT:"))
+    if gdsobj.snp_position is None:
+        raise ValueError("the object has no snp.position, which the .snp file needs")
+    Ls, ns = int(snp_flag.sum()), int(samp_flag.sum())
+    with open(eigen_fn + ".snp", "w") as f:
+        for i, c, pos in zip(np.asarray(gdsobj.snp_id)[snp_flag], np.asarray(gdsobj.snp_chromosome)[snp_flag],
+                             gdsobj.snp_position[snp_flag]):
+            f.write("%s\t%s\t0\t%d\n" % (i, c, pos))
+    _cat(verbose, "\tsave to *.snp: %d snps" % Ls)
+    sex = getattr(gdsobj, "sample_annot", {}).get("sex")
+    if sex is None:
+        sex = ["U"] * ns
+    else:
+        sex = [None if _is_na(x) else str(x) for x in np.asarray(sex, dtype=object)[samp_flag]]
+        if not all(x in ("F", "M") for x in sex if x is not None):
+            raise ValueError("The gender variable in GDS file should be either \"M\" or \"F\".")
+        sex = ["U" if x is None else x for x in sex]
+    with open(eigen_fn + ".ind", "w") as f:
+        for sid, x in zip(np.asarray(gdsobj.sample_id)[samp_flag], sex):
+            f.write("%s\t%s\tcontrol\n" % (sid, x))
+    _cat(verbose, "\tsave to *.ind: %d samples" % ns)
+    with open(eigen_fn + ".eigenstratgeno", "wb") as f:
+        _text.write_eigenstratgeno(f, gdsobj, samp_flag, snp_flag, device)
+    _cat(verbose, "Done.")
+    return None
+
+
+def snpgdsOpenPED(ped_fn, map_fn, family=True, verbose=True, device=0):
+    """Open a PLINK text PED/MAP pair for every snpgds* function: snpgdsPED2GDS (R/Conversion.R:132-302 -> gnrParsePED,
+    src/ConvToGDS.cpp:1175-1361) + snpgdsOpen in one step, without the GDS file in between.  ped_fn: plain or .gz.  Returns a
+    GenoFile: snp_id 1 ... n_snp, snp_rs_id / snp_position / snp_chromosome the MAP columns in the order of R/Conversion.R:164-170
+    (chromosome, then position; a numeric chromosome column as integers, else as text with the labels compared as bytes), snp_allele
+    "ref/alt1,alt2" with the most frequent allele as the reference (ties to the smaller string, "0" for an empty side), genotypes
+    the number of reference alleles (3 when either allele is "0"), sample_id column 2, and with `family` the sample_annot columns
+    family, father, mother, sex ("1" -> "M", "2" -> "F", anything else kept) and phenotype.
+    The allele tokens are read on the device (ped.PedReader: snpgpu_ped_tokens / _census / _codes, two sweeps over the text as the
+    reference reads the file twice) in chunks of SNPGPU_TEXT_STAGE_BYTES; lines the kernel flags (alleles of several bytes,
+    quoted or empty tokens) are settled on the host, and a wrong number of columns raises the reference's message with FILE:,
+    LINE:, COLUMN:.  There is no CPU fallback: without a device the call fails with SnpGpuError.
+    One deviation from the reference: gnrParsePED appends snp.allele in FILE order while it permutes the genotypes, rs ids and
+    positions by the MAP order (src/ConvToGDS.cpp:1272-1276 against :1353-1355), so that with an unsorted MAP its alleles belong
+    to other SNPs; here snp_allele is permuted with the rest.  For a sorted MAP nothing differs.
+    There is no snpgdsPED2GDS here, for the reason there is no snpgdsBED2GDS: writing the GDS container is gdsfmt's work."""
+    from . import ped as _ped
+    if not isinstance(ped_fn, str):
+        raise TypeError("is.character(ped.fn) is not TRUE")
+    if not isinstance(map_fn, str):
+        raise TypeError("is.character(map.fn) is not TRUE")
+    for v, name in ((family, "family"), (verbose, "verbose")):
+        if not isinstance(v, (bool, np.bool_)):
+            raise TypeError("is.logical(%s) is not TRUE" % name)
+    _cat(verbose, "Open PLINK PED/MAP as a SNP GDS object ...")
+    m = _ped.read_map(map_fn)
+    ii = m["ii"]
+    M = len(ii)
+    if np.any(ii[1:] < ii[:-1]):
+        print("Hint: the SNPs are sorted and merged into the GDS file.")
+    _cat(verbose, "Import %d variant%s from '%s'" % (M, "s" if M > 1 else "", map_fn))
+    if not _device_visible():
+        raise _lib.SnpGpuError("snpgdsOpenPED: no HIP device (the PED tokeniser has no CPU fallback)")
+    _cat(verbose, "Reading '", ped_fn, "'")
+    r = _ped.PedReader(ped_fn, M, device=device).run()
+    N, rb = r.n_samp, (M + 3) // 4
+    _cat(verbose, "Import %d sample%s" % (N, "s" if N > 1 else ""))
+    # sample rows in FILE order of the SNPs -> SNP rows in the MAP order
+    packed = _lib.geno_convert(int(r.rows.data_ptr()), 1, N, M, row_stride_bits=8 * rb, n_bytes=N * rb, snp_index=ii.astype(np.int32),
+                               device=device)
+    gf = GenoFile(packed=packed, n_samp=N, sample_id=r.sample_id, snp_id=np.arange(1, M + 1, dtype=np.int32),
+                  snp_chromosome=m["snp_chromosome"], snp_position=m["snp_position"], snp_allele=r.snp_allele[ii],
+                  sample_annot=r.sample_annot if family else None)
+    gf.snp_rs_id = m["snp_rs_id"]
+    gf.ped_flagged_lines, gf.ped_windows = r.flagged_lines, r.windows
+    if m["snp_chromosome"].dtype.kind == "U":
+        gf.chromosome_code = {}                            # text labels, as snpgdsOpenVCF keeps them
+    return gf
 
 
 def snpgdsHWE(gdsobj, sample_id=None, snp_id=None, with_id=False, device=0):

@@ -80,7 +80,7 @@ __global__ __launch_bounds__(VCF_THREADS) void vcf_parse_kernel(VcfText t, const
     __shared__ int s_wave[VCF_THREADS / 64];
     __shared__ uint32_t s_flags;
 
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t line = blockIdx.x;
     const VcfLine ln = lines[line];
     const int64_t b = ln.begin + t.delta, e = ln.end + t.delta;
@@ -94,46 +94,14 @@ __global__ __launch_bounds__(VCF_THREADS) void vcf_parse_kernel(VcfText t, const
     int64_t kb = 0;                // the cell whose code lies at bit 0 of s_codes: a multiple of 4
 
     for (int64_t cb = b & ~int64_t(VCF_SEG - 1);; cb += VCF_CHUNK) {
-        // ---- stage the chunk and its halo; the tab mask of this lane's segment --------------------------------------------------
+        // ---- stage the chunk and its halo; the tab mask of this lane's segment and its scan (text_chunk.h) ------------------------------
         uint32_t v[4];
-        {
-            const int64_t d0 = (cb >> 2) + 4 * tid;
-            if (d0 >= t.word_lo && d0 + 4 <= t.word_hi) {
-                const uint4 q = *reinterpret_cast<const uint4 *>(t.w + d0);
-                v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; i++) v[i] = (d0 + i >= t.word_lo && d0 + i < t.word_hi) ? t.w[d0 + i] : 0u;
-            }
-#pragma unroll
-            for (int i = 0; i < 4; i++) s_text[4 * tid + i] = v[i];
-            if (tid < VCF_HALO / 4) {
-                const int64_t d = ((cb + VCF_CHUNK) >> 2) + tid;
-                s_text[VCF_CHUNK / 4 + tid] = (d >= t.word_lo && d < t.word_hi) ? t.w[d] : 0u;
-            }
-        }
+        chunk_stage(t, cb, tid, s_text, v);
         const int64_t seg = cb + VCF_SEG * tid;
-        uint32_t mask = 0u;
-#pragma unroll
-        for (int j = 0; j < VCF_SEG; j++) {
-            const uint32_t c = (v[j >> 2] >> (8 * (j & 3))) & 0xFFu;
-            if (c == '\t' && seg + j >= b && seg + j < e) mask |= 1u << j;
-        }
+        uint32_t mask = chunk_mask(v, seg, b, e, [](uint32_t c) { return c == '\t'; });
         const int cnt = __popc(mask);
-        int incl = cnt;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += y;
-        }
-        if (lane == 63) s_wave[wv] = incl;
-        __syncthreads();
         int before = 0, total = 0;
-#pragma unroll
-        for (int i = 0; i < VCF_THREADS / 64; i++) {
-            if (i < wv) before += s_wave[i];
-            total += s_wave[i];
-        }
+        chunk_scan(cnt, tid, s_wave, before, total);
 
         // ---- the cells that start in this chunk ------------------------------------------------------------------------------
         ps.cb = cb;
@@ -143,7 +111,7 @@ __global__ __launch_bounds__(VCF_THREADS) void vcf_parse_kernel(VcfText t, const
             atomicOr(&s_codes[rel >> 4], code << (2 * ((uint32_t)rel & 15u)));
         };
         if (cb <= b && tid == 0) put(0, ps.parse(b));                            // the first chunk: the first cell has no tab of its own
-        int64_t k = n_cells + before + (incl - cnt);
+        int64_t k = n_cells + before;
         while (mask) {
             const int j = __ffs(mask) - 1;
             mask &= mask - 1u;

@@ -1,21 +1,16 @@
 // What vcf.hip (host layer) and kernels_vcf.hip share: the device view of VCF text, a line's description and the chunk geometry.
 #pragma once
-#include "snpgpu_internal.h"
+#include "text_chunk.h"
 
 namespace snpgpu {
 
-constexpr int VCF_THREADS = 256;                          // lanes of a line's workgroup
-constexpr int VCF_SEG = 16;                               // text bytes of a lane per chunk: four aligned dwords
-constexpr int VCF_CHUNK = VCF_THREADS * VCF_SEG;          // text bytes of a workgroup per step
-constexpr int VCF_HALO = 64;                              // bytes staged behind a chunk: a GT that crosses its end is read from LDS
+// the chunk geometry and the view of the text are the shared skeleton's (text_chunk.h)
+constexpr int VCF_THREADS = CHUNK_THREADS;
+constexpr int VCF_SEG = CHUNK_SEG;
+constexpr int VCF_CHUNK = CHUNK_BYTES;
+constexpr int VCF_HALO = CHUNK_HALO;                      // a GT that crosses a chunk's end is read from LDS
 constexpr int VCF_CODE_WORDS = (VCF_CHUNK + 1 + 3 + 15) / 16 + 1;     // dwords of 16 codes: a chunk's cells and the carried byte
-
-// Text (or a staged window of it) as the kernel sees it: 16-byte aligned dwords; the caller's offset p is byte p + delta of w.
-struct VcfText {
-    const uint32_t *w;
-    int64_t word_lo, word_hi;      // the dwords that hold a byte of the text: nothing outside them is loaded
-    int64_t delta;
-};
+using VcfText = TextView;
 
 // one line: [begin, end) from its first sample cell to the end of its last one, in the caller's offsets
 struct VcfLine { int64_t begin, end; int32_t num_allele, ref_index; };

@@ -80,6 +80,8 @@ class GenoFile:
         # snp.allele ("A/B" per SNP), written to the .bim file by snpgdsGDS2BED; None when the file has no such node
         self.snp_allele = None if snp_allele is None else np.asarray(snp_allele)
         assert self.snp_allele is None or len(self.snp_allele) == self.n_snp
+        # snp.rs.id (text per SNP) when the source has such a node: open_gds, the BED and VCF readers set it
+        self.snp_rs_id = None
         # columns of the sample.annot folder this reader can decode (e.g. "pop.group"), one entry per sample
         self.sample_annot = {} if sample_annot is None else dict(sample_annot)
         # snpgdsOption() defaults (R/AllUtilities.R:1910-1991)
@@ -267,6 +269,8 @@ def open_gds(path):
     allele = _snp_allele(lambda: raw("snp.allele")[:2]) if "snp.allele" in entries else None
     gf = GenoFile(genotype=geno, sample_id=sample_id, snp_id=snp_id, snp_chromosome=chrom, snp_position=position,
                   sample_annot=annot, snp_allele=allele)
+    # snp.rs.id: a text node read like snp.allele; the rs column of snpgdsGDS2PED's .map file
+    gf.snp_rs_id = _snp_allele(lambda: raw("snp.rs.id")[:2]) if "snp.rs.id" in entries else None
     gf.sample_order = b"sample.order" in attr
     return gf
 
@@ -383,6 +387,7 @@ class GenoStream:
         self.path, self.sample_id, self.snp_id, self.snp_chromosome = path, sample_id, snp_id, snp_chromosome
         self.snp_position, self.sample_annot = snp_position, ({} if sample_annot is None else dict(sample_annot))
         self.snp_allele = snp_allele
+        self.snp_rs_id = None
         self._dims, self._extents, self._length, self._zipped = dims, extents, length, zipped
         self.sample_order = sample_order
         self.n_snp, self.n_samp = (dims[0], dims[1]) if sample_order else (dims[1], dims[0])
@@ -636,6 +641,7 @@ def open_gds_stream(path):
                 return dims, (zlib.decompress(b) if is_zip else b)
             annot = _sample_annot(_dir_entries(load(entries["sample.annot"])), raw_id)
         allele = _snp_allele(lambda: small("snp.allele")) if "snp.allele" in entries else None
+        rs_id = _snp_allele(lambda: small("snp.rs.id")) if "snp.rs.id" in entries else None
         gdesc = load(entries["genotype"])
         dims, sid, is_zip, attr = _node_info(gdesc)
         ext, slen = extents(sid)
@@ -646,7 +652,9 @@ def open_gds_stream(path):
         elif slen != (2 * dims[0] * dims[1] + 7) // 8:      # an uncompressed bit2 node is exactly its genotypes, no more, no less
             raise ValueError("the genotype node holds %d bytes where %d x %d 2-bit genotypes need %d: compressed or damaged data"
                              % (slen, dims[0], dims[1], (2 * dims[0] * dims[1] + 7) // 8))
-    return GenoStream(path, sample_id, snp_id, chrom, dims, ext, slen, is_zip, b"sample.order" in attr, position, annot, allele)
+    gs = GenoStream(path, sample_id, snp_id, chrom, dims, ext, slen, is_zip, b"sample.order" in attr, position, annot, allele)
+    gs.snp_rs_id = rs_id
+    return gs
 
 
 # ---------------------------------------------------------------------------

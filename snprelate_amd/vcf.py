@@ -96,27 +96,42 @@ def get_float(txt):
 
 
 class _Cells:
-    """CReadLine::GetCell over one line split by tabs (src/ConvToGDS.cpp:123-179): the column count, the end-of-line checks and
-    the quotes it strips.  `cell` is what the reference's `cell` variable holds when an error is formatted."""
+    """CReadLine::GetCell over one line (src/ConvToGDS.cpp:123-179): the column count, the end-of-line checks and the quotes it
+    strips.  Split by tabs as gnrParseVCF4 sets it, or with `space` by tab and space as gnrParsePED does (SplitBySpaceTab): one
+    tab is one separator, a run of spaces is one separator, and spaces behind the last column are skipped.  `cell` is what the
+    reference's `cell` variable holds when an error is formatted."""
 
-    def __init__(self, line, pos=0, column=0, cell=b""):
-        self.s, self.p, self.column, self.cell = line, pos, column, cell
+    def __init__(self, line, pos=0, column=0, cell=b"", space=False):
+        self.s, self.p, self.column, self.cell, self.space = line, pos, column, cell, space
 
     def get(self, last):
         s, b = self.s, self.p
         e = s.find(b"\t", b)
+        if self.space:
+            e2 = s.find(b" ", b, e if e >= 0 else len(s))
+            e = e2 if e2 >= 0 else e
         at_end = e < 0
         if at_end:
             e = len(s)
         self.column += 1
         if b == e and at_end:
             raise VcfFormatError("fewer columns than what expected.", self.column, self.cell)
+        p = e
         if last:
-            if not at_end:
+            if self.space:
+                while p < len(s) and s[p] == 0x20:
+                    p += 1
+            if p < len(s):
                 raise VcfFormatError("more columns than what expected.", self.column, self.cell)
+            self.p = p
+        elif at_end:
             self.p = e
+        elif s[e] == 0x09 or not self.space:
+            self.p = e + 1
         else:
-            self.p = e if at_end else e + 1
+            while p < len(s) and s[p] == 0x20:
+                p += 1
+            self.p = p
         if e > b + 1 and ((s[b] == 0x22 and s[e - 1] == 0x22) or (s[b] == 0x27 and s[e - 1] == 0x27)):
             b, e = b + 1, e - 1
         self.cell = s[b:e]
