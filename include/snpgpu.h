@@ -1034,6 +1034,40 @@ int snpgpu_ped_codes(const void *tokens, int64_t n_lines, int64_t n_snp, const u
  * last snpgpu_ped_tokens, [5] bytes of a workgroup's chunk, [6] of a lane's segment, [7] of the halo */
 int snpgpu_ped_stats(double *stats);
 
+/* ---- (1o) data sets side by side: snpgdsCombineGeno, snpgdsAlleleSwitch ------------------------------------------------------------
+ * What snpgdsCombineGeno (R/AllUtilities.R:1525-1556) does with one int per genotype -- abs(t(x - t(g))), rbind, 1024 SNPs at a
+ * time -- and gnrStrandSwitch (src/SNPRelate.cpp:454-494) with a byte per genotype, on the device and at two bits per genotype
+ * all the way: the selected rectangles of several sources next to each other in one SNPGPU_GENO_PACKED2 row per output SNP, part
+ * i's columns from code n_samp_0 + ... + n_samp_(i-1) on (an offset that is in general no multiple of 4), with the rows named by
+ * `flip` re-coded to the other allele.  Which SNPs match and which are flipped is the caller's business (allele names, strands
+ * and frequencies: host work).
+ *   rows           DEVICE memory of `device`: [n_snp_out][ceil(N / 4)] bytes, N = the sum of n_samp; the unused codes of a row's
+ *                  last byte are 3.  The first row may start at any byte address; nothing outside those bytes is stored.
+ *                  rows must not overlap a source that lies in device memory: the sources are read while rows is written.
+ * A host source that fits the staging size of snpgpu_geno_select goes to the device once.  A major 0 source without row_bit
+ * whose samples are consecutive is then read where it lies on the device; every other part's rectangle of a window of output rows
+ * is first brought to byte-aligned device rows by the selection of snpgpu_geno_select (every layout, memory kind and staging
+ * window of a source is that call's).  One kernel splices a window.  A window holds the output rows whose staged bytes fit
+ * SNPGPU_MERGE_STAGE_BYTES (default: the staging size of snpgpu_geno_select), at least one, and all rows when no part is staged.
+ * There is no cap on n_parts: the descriptions of the parts live in device memory.
+ * Refused before any device is touched: NULL parts / rows / bits; n_parts < 1, n_samp < 1 or n_snp_out < 1; an index outside
+ * its source; N > 2^30 - 1; everything snpgpu_geno_select refuses about a source (the message names the part).  Refused before
+ * any launch: a device pointer or a stream that belongs to another device than `device`. */
+typedef struct snpgpu_merge_part {
+    snpgpu_geno_src src;            /* as for snpgpu_geno_select: any layout, host / pinned / device memory                    */
+    const int32_t  *snp_index;      /* host, n_snp_out entries: the source SNP of every output row; NULL = in order; may        */
+                                    /* permute and repeat                                                                      */
+    const int32_t  *samp_index;     /* host, n_samp entries: the source sample of every column this part contributes;          */
+                                    /* NULL = all, in order                                                                    */
+    int64_t         n_samp;         /* columns this part contributes (>= 1)                                                    */
+    const uint8_t  *flip;           /* host, n_snp_out entries: non-zero = codes 0 / 1 / 2 / 3 of that row become 2 / 1 / 0 / 3; */
+                                    /* NULL = none                                                                             */
+} snpgpu_merge_part;
+int snpgpu_geno_merge(const snpgpu_merge_part *parts, int n_parts, int64_t n_snp_out, void *rows, int device, void *stream);
+/* of the last snpgpu_geno_merge on this thread (HIP events, summed over the windows): stats[0] ms of bringing the parts to aligned
+ * rows (staging and selection), [1] ms of the splice kernel, [2] its launches, [3] windows, [4] bytes written to rows */
+int snpgpu_geno_merge_stats(double *stats);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------------------
  * What THIS device's matrix pipe sustains right now: a register-only stream of one MFMA instruction (never waiting on memory,
  * two waves per SIMD) run for `seconds`, rate taken over the second half.  The kernels of this library run against the socket

@@ -67,6 +67,7 @@ EXPORTS = [
     "snpgpu_vcf_index", "snpgpu_vcf_genotypes", "snpgpu_vcf_stats",
     "snpgpu_text_render", "snpgpu_text_stats",
     "snpgpu_ped_tokens", "snpgpu_ped_census", "snpgpu_ped_codes", "snpgpu_ped_stats",
+    "snpgpu_geno_merge", "snpgpu_geno_merge_stats",
 ]
 FST_WC84, FST_WH02 = 1, 2
 FST_METHODS = ("W&C84", "W&H02")
@@ -119,6 +120,11 @@ class GenoSrc(ctypes.Structure):       # snpgpu_geno_src
     _fields_ = [("bits", ctypes.c_void_p), ("mem", ctypes.c_int32), ("major", ctypes.c_int32), ("n_rows", ctypes.c_int64),
                 ("n_cols", ctypes.c_int64), ("bit0", ctypes.c_int64), ("row_stride_bits", ctypes.c_int64), ("row_bit", ctypes.c_void_p),
                 ("n_bytes", ctypes.c_int64)]
+
+
+class MergePart(ctypes.Structure):     # snpgpu_merge_part
+    _fields_ = [("src", GenoSrc), ("snp_index", ctypes.c_void_p), ("samp_index", ctypes.c_void_p), ("n_samp", ctypes.c_int64),
+                ("flip", ctypes.c_void_p)]
 
 
 class EigInfo(ctypes.Structure):       # snpgpu_eig_info
@@ -330,6 +336,8 @@ def lib():
     L.snpgpu_ped_census.argtypes = [vp, vp, i64, i64, vp, c_int, vp]
     L.snpgpu_ped_codes.argtypes = [vp, i64, i64, vp, vp, c_int, vp]
     L.snpgpu_ped_stats.argtypes = [vp]
+    L.snpgpu_geno_merge.argtypes = [ctypes.POINTER(MergePart), c_int, i64, vp, c_int, vp]
+    L.snpgpu_geno_merge_stats.argtypes = [vp]
     _lib = L
     return L
 
@@ -1839,6 +1847,72 @@ def ped_stats():
     check(lib().snpgpu_ped_stats(_ptr(s)))
     return dict(tokens_ms=float(s[0]), census_ms=float(s[1]), codes_ms=float(s[2]), launches=int(s[3]), text_bytes=float(s[4]),
                 chunk_bytes=int(s[5]), segment_bytes=int(s[6]), halo_bytes=int(s[7]))
+
+
+def merge_part(src, major, n_rows, n_cols, bit0=0, row_stride_bits=None, row_bit=None, samp_index=None, snp_index=None, flip=None,
+               n_bytes=None, mem=None):
+    """One part of geno_merge: a source described as for geno_select (src: a numpy uint8 array in host memory, or an address with
+    n_bytes -- device memory unless mem says HOST or HOST_PINNED), the samples it contributes (samp_index, None = all in order), the
+    source SNP of every output row (snp_index, None = in order) and flip (None, or one entry per output row: non-zero re-codes that
+    row 0 / 1 / 2 / 3 -> 2 / 1 / 0 / 3)."""
+    return dict(src=src, major=major, n_rows=n_rows, n_cols=n_cols, bit0=bit0, row_stride_bits=row_stride_bits, row_bit=row_bit,
+                samp_index=samp_index, snp_index=snp_index, flip=flip, n_bytes=n_bytes, mem=mem)
+
+
+def geno_merge(parts, rows, n_snp_out=None, device=0, stream=None):
+    """snpgpu_geno_merge: the parts (merge_part(...) each) side by side as PACKED2 rows [n_snp_out][ceil(N / 4)] in DEVICE memory at
+    the address `rows`, N = the samples of all parts, part i from code n_0 + ... + n_(i-1) on.  n_snp_out None: the length of the
+    first part's snp_index, else its number of SNPs.  Returns (n_snp_out, N)."""
+    keep, arr = [], (MergePart * max(len(parts), 1))()
+    N = 0
+    for i, p in enumerate(parts):
+        src, major, n_rows, n_cols = p["src"], int(p["major"]), int(p["n_rows"]), int(p["n_cols"])
+        if isinstance(src, int):
+            if p.get("n_bytes") is None:
+                raise ValueError("a source address needs n_bytes")
+            ptr, mem, n_bytes = src, (DEVICE if p.get("mem") is None else int(p["mem"])), int(p["n_bytes"])
+        else:
+            a = np.ascontiguousarray(src, dtype=np.uint8)
+            keep.append(a)
+            ptr, mem = a.ctypes.data, (HOST if p.get("mem") is None else int(p["mem"]))
+            n_bytes = a.size if p.get("n_bytes") is None else int(p["n_bytes"])
+            if n_bytes > a.size:
+                raise ValueError("n_bytes exceeds the source array")
+
+        def host(x, dtype):
+            if x is None:
+                return None, None
+            x = np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+            keep.append(x)
+            return x, x.ctypes.data
+        rbit, rbit_p = host(p.get("row_bit"), np.int64)
+        if rbit is not None and rbit.shape != (n_rows,):
+            raise ValueError("row_bit should hold one bit position per source row")
+        samp, samp_p = host(p.get("samp_index"), np.int32)
+        snp, snp_p = host(p.get("snp_index"), np.int32)
+        n_samp = (n_rows if major else n_cols) if samp is None else samp.size
+        n_snp = (n_cols if major else n_rows) if snp is None else snp.size
+        if n_snp_out is None:
+            n_snp_out = n_snp
+        flip = p.get("flip")
+        flip, flip_p = host(None if flip is None else (np.asarray(flip) != 0), np.uint8)
+        if (snp is not None and snp.size != int(n_snp_out)) or (flip is not None and flip.size != int(n_snp_out)):
+            raise ValueError("snp_index and flip should hold one entry per output row")
+        stride = p.get("row_stride_bits")
+        arr[i] = MergePart(GenoSrc(ptr, mem, major, n_rows, n_cols, int(p.get("bit0") or 0), 2 * n_cols if stride is None else int(stride),
+                                   rbit_p, n_bytes), snp_p, samp_p, n_samp, flip_p)
+        N += n_samp
+    n_snp_out = 0 if n_snp_out is None else int(n_snp_out)
+    check(lib().snpgpu_geno_merge(arr, len(parts), n_snp_out, _dptr(rows), int(device),
+                                  ctypes.c_void_p(stream) if stream else None))
+    return n_snp_out, N
+
+
+def geno_merge_stats():
+    """dict of snpgpu_geno_merge_stats for the last geno_merge call on this thread"""
+    s = np.zeros(5, np.float64)
+    check(lib().snpgpu_geno_merge_stats(_ptr(s)))
+    return dict(stage_ms=float(s[0]), splice_ms=float(s[1]), launches=int(s[2]), windows=int(s[3]), bytes_written=float(s[4]))
 
 
 def select_stats():

@@ -37,6 +37,10 @@ INTEGRATION.md):
     snpgdsGDS2PED                 R/Conversion.R:26-124  (the selected rectangle as PLINK text .ped/.map, the lines made on the GPU)
     snpgdsGDS2Eigen               R/Conversion.R:695-785 (the selected rectangle as EIGENSTRAT .eigenstratgeno/.snp/.ind)
     snpgdsOpenPED                 R/Conversion.R:132-302 (snpgdsPED2GDS + snpgdsOpen: PLINK text .ped/.map parsed on the GPU)
+    snpgdsSNPList                 R/AllUtilities.R:637-658   (SNP ids, positions, alleles and allele frequencies of one data set)
+    snpgdsSNPListIntersect        R/AllUtilities.R:667-736   (the SNPs several data sets share, and who counts the other allele)
+    snpgdsCombineGeno             R/AllUtilities.R:1285-1583 (data sets merged: the genotypes spliced on the GPU)
+    snpgdsAlleleSwitch            R/AllUtilities.R:1686-1751 (a data set re-coded against given A alleles, the rows flipped on the GPU)
 
 All arithmetic on genotype matrices runs on the MI355X through libsnpgpu.so
 (`_lib`); there is no CPU fallback.  The one exception is snpgdsIndInbCoef, which
@@ -54,6 +58,7 @@ from . import _lib
 from . import gds as _gds
 from . import bed as _bed
 from . import vcf as _vcf
+from . import merge as _merge
 from .gds import GenoFile, open_gds, pack_2bit_rows  # noqa: F401
 
 
@@ -2440,3 +2445,80 @@ def snpgdsCutTree(hc, z_threshold=15, outlier_n=5, n_perm=5000, samp_group=None,
     if verbose:
         _cat(True, "Create %d groups." % len(levels))
     return ans
+
+
+# ---- data sets put together ---------------------------------------------------------------------------------------------------------
+def snpgdsSNPList(gdsobj, sample_id=None, device=0):
+    """snpgdsSNPList (R/AllUtilities.R:637-658): snp_id, chromosome, position, allele and afreq (the allele frequency of
+    snpgdsSNPRateFreq over the selected samples) of every SNP, as the object snpgdsSNPListIntersect takes."""
+    if not isinstance(gdsobj, (GenoFile, _gds.GenoStream)):
+        raise TypeError("'gdsobj' should be a SNP GDS object (snpgdsOpen / GenoFile)")
+    return _merge.snp_list(gdsobj, snpgdsSNPRateFreq(gdsobj, sample_id=sample_id, device=device)["AlleleFreq"])
+
+
+def snpgdsSNPListIntersect(snplist1, snplist2, *more, method="position", na_rm=True, same_strand=False, verbose=True):
+    """snpgdsSNPListIntersect (R/AllUtilities.R:667-736): the SNPs all lists share -- by chromosome:position, or for "exact" by
+    snp.id:chromosome:position:allele -- in the order of list 1, duplicates dropped: dict idx1, idx2, ... (0-based positions, the
+    first occurrence in each list) and, for "position", flag2, ... per further list (int32; bit 1 = the list counts the other
+    allele, bit 2 = other strand, bit 4 = strand decided by the allele frequencies, NA = mismatched allele names, as
+    gnrAlleleStrand).  na_rm drops the SNPs with an NA flag.  Host work: strings and a hash join."""
+    if not isinstance(verbose, (bool, np.bool_)):
+        raise TypeError("is.logical(verbose) is not TRUE")
+    return _merge.snp_list_intersect([snplist1, snplist2] + list(more), method=method, na_rm=na_rm, same_strand=same_strand)
+
+
+def snpgdsCombineGeno(gds, method="position", same_strand=False, verbose=True, device=0):
+    """snpgdsCombineGeno (R/AllUtilities.R:1285-1583).  gds: at least two SNP GDS objects (GenoFile, GenoStream, BedStream, what
+    snpgdsOpenVCF / snpgdsOpenPED return) or file names for snpgdsOpen.  With samples common to all files their SNPs are
+    concatenated over those samples; without, the samples are concatenated over the SNPs snpgdsSNPListIntersect finds, mapped to
+    file 1, every other file's rows re-coded where it counts the other allele.  The genotypes are placed by snpgpu_geno_merge on the
+    device, two bits each.  Returns an in-memory GenoFile: this package does not write the GDS container (that is gdsfmt's work),
+    so out.fn, compress.* and snpfirstdim have no counterpart -- snpgdsGDS2BED / snpgdsGDS2PED give a file.  No CPU fallback."""
+    if isinstance(gds, (str, GenoFile, _gds.GenoStream)) or len(gds) < 2:
+        raise ValueError("length(gds.fn) >= 2L is not TRUE")
+    method = _match_arg(method, ("position", "exact"), "method")
+    for v, name in ((same_strand, "same.strand"), (verbose, "verbose")):
+        if not isinstance(v, (bool, np.bool_)):
+            raise TypeError("is.logical(%s) is not TRUE" % name)
+    _merge.need_device("snpgdsCombineGeno")
+    _cat(verbose, "Merge SNP GDS files:")
+    files, lists = [], []
+    for g in gds:
+        if isinstance(g, str):
+            _cat(verbose, "    open '", g, "' ...")
+            g = snpgdsOpen(g)
+        elif not isinstance(g, (GenoFile, _gds.GenoStream)):
+            raise TypeError("'gds' should hold SNP GDS objects or file names")
+        files.append(g)
+        lists.append(snpgdsSNPList(g, device=device))
+        _cat(verbose, "        %d samples, %d SNPs" % (g.n_samp, g.n_snp))
+    samp_id = list(dict.fromkeys(files[0].sample_id.tolist()))
+    for f in files[1:]:
+        have = set(f.sample_id.tolist())
+        samp_id = [s for s in samp_id if s in have]
+    if samp_id:
+        _cat(verbose, "Concatenating SNPs ...")
+        out = _merge.combine_common_samples(files, samp_id, device)
+    else:
+        _cat(verbose, "Concatenating samples (mapping to the first GDS file) ...")
+        snp = _merge.snp_list_intersect(lists, method=method, same_strand=same_strand)
+        if len(snp["idx1"]) <= 0:
+            raise ValueError("There is no common SNP.")
+        if verbose:
+            n = len(snp["idx1"])
+            print("    reference: %d SNPs (%.1f%%)" % (n, 100.0 * n / files[0].n_snp))
+            for i in range(2, len(files) + 1):
+                if "flag%d" % i in snp:
+                    _merge.print_flags(i, snp["flag%d" % i])
+        out = _merge.combine_common_snps(files, lists, snp, device)
+    _cat(verbose, "    %d samples, %d SNPs" % (out.n_samp, out.n_snp))
+    _cat(verbose, "Done.")
+    return out
+
+
+def snpgdsAlleleSwitch(gdsobj, A_allele, verbose=True, device=0):
+    """snpgdsAlleleSwitch (R/AllUtilities.R:1686-1751 -> gnrStrandSwitch, src/SNPRelate.cpp:386-499): where B of a SNP's "A/B" is
+    A_allele[i] the alleles become "B/A" and the SNP's genotypes 2 - g (on the device: snpgpu_geno_merge with one part).  The
+    object is modified in place, so it has to be an in-memory one (GenoFile); one that streams a file is refused as a read-only GDS
+    file is.  Returns the flags: int32 0 = unchanged, 1 = switched, NA (-2^31) = A_allele[i] is neither allele, or None."""
+    return _merge.allele_switch(gdsobj, A_allele, verbose=verbose, device=device)

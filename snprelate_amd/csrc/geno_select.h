@@ -1,4 +1,5 @@
 // What geno_select.hip (host layer) and kernels_geno_select.hip share: the device view of a source and the launch declarations.
+// geno_merge.hip builds on both: the argument checks and the staging size of a selection, and the splice kernel's declarations.
 #pragma once
 #include <algorithm>
 
@@ -45,5 +46,25 @@ int launch_geno_gather(hipStream_t st, const SelBits &s, const int32_t *srow, co
 // samp: source row of every output column (device) or NULL = in order
 int launch_geno_transpose(hipStream_t st, const SelBits &s, const int32_t *samp, const SelSeg *segs, int64_t n_segs, int64_t n_out,
                           uint8_t *dst, SelRecode rc);
+
+// ---- what snpgpu_geno_merge shares with the selection (geno_select.hip) ---------------------------------------------------------
+// every refusal of snpgpu_geno_select / snpgpu_geno_convert that needs no device, under the name fn; 0 = accepted
+int sel_check_args(const char *fn, const snpgpu_geno_src *src, int src_code, const int32_t *samp_index, int64_t n_samp_out,
+                   const int32_t *snp_index, int64_t n_snp_out, const void *dst, int dst_major, int dst_code, int dst_mem);
+// source bytes per staging window (SNPGPU_SELECT_STAGE_BYTES, else 256 MiB)
+size_t sel_stage_bytes();
+
+// ---- the splice (kernels_geno_merge.hip) ---------------------------------------------------------------------------------------
+// One part of a window of merged rows as the kernel sees it: row k of the window starts at bit bit0 + r * stride of the aligned
+// dwords w, r = srow[k] or k, and is flipped (0 / 1 / 2 / 3 -> 2 / 1 / 0 / 3) where flip[k] is not zero.
+struct SplicePart {
+    const uint32_t *w;
+    int64_t n_words;               // nothing beyond them is loaded
+    int64_t bit0, stride;
+    const int32_t *srow;           // device, the source row of every row of the window, or NULL = in order
+    const uint8_t *flip;           // device, one byte per row of the window, or NULL
+};
+// parts, off: device memory; off[i] is the first code of part i in a merged row, off[n_parts] = N.  dst: [n_rows][ceil(N / 4)]
+int launch_geno_splice(hipStream_t st, const SplicePart *parts, const int32_t *off, int n_parts, int64_t N, int64_t n_rows, uint8_t *dst);
 
 }  // namespace snpgpu

@@ -20,22 +20,79 @@
 
 using namespace snpgpu;
 
+namespace snpgpu {
+
+constexpr size_t SEL_STAGE_BYTES = size_t(256) << 20;    // source bytes per staging window
+constexpr GenoLimits SEL_GENO = {1, int64_t(1) << 30, int64_t(1) << 31, false, "invalid number of samples (1 ... 2^30 - 1)"};
+constexpr GenoLimits SEL_GENO_MAJOR1 = {1, int64_t(1) << 30, int64_t(1) << 30, false, "invalid number of samples (1 ... 2^30 - 1)"};
+
+size_t sel_stage_bytes()
+{
+    if (const char *e = getenv("SNPGPU_SELECT_STAGE_BYTES")) { if (atoll(e) > 0) return (size_t)atoll(e); }
+    return SEL_STAGE_BYTES;
+}
+
+// All argument errors of a selection: nothing here touches a device.
+int sel_check_args(const char *fn, const snpgpu_geno_src *src, int src_code, const int32_t *samp_index, int64_t n_samp_out,
+                   const int32_t *snp_index, int64_t n_snp_out, const void *dst, int dst_major, int dst_code, int dst_mem)
+{
+    if (!src) return fail(fn, "NULL argument: src is NULL");
+    if (!src->bits) return fail(fn, "NULL argument: src->bits is NULL");
+    if (!dst) return fail(fn, "NULL argument: dst is NULL");
+    const auto mem_ok = [](int m) { return m == SNPGPU_HOST || m == SNPGPU_DEVICE || m == SNPGPU_HOST_PINNED; };
+    if (!mem_ok(src->mem)) return fail(fn, "invalid memory kind");
+    if (!mem_ok(dst_mem)) return fail(fn, "invalid dst_mem");
+    if (src->major != 0 && src->major != 1) return fail(fn, "invalid major (0: a row is a SNP, 1: a row is a sample)");
+    const auto code_ok = [](int c) { return c == SNPGPU_CODE_GDS || c == SNPGPU_CODE_BED; };
+    if (!code_ok(src_code)) return fail(fn, "invalid src_code (SNPGPU_CODE_GDS or SNPGPU_CODE_BED)");
+    if (!code_ok(dst_code)) return fail(fn, "invalid dst_code (SNPGPU_CODE_GDS or SNPGPU_CODE_BED)");
+    if (dst_major != 0 && dst_major != 1) return fail(fn, "invalid dst_major (0: a row of dst is a SNP, 1: a row of dst is a sample)");
+    const int major = src->major;
+    // the axis dst packs holds at most 2^30 - 1 entries: for sample rows that is the SNPs
+    const GenoLimits &lim = dst_major ? SEL_GENO_MAJOR1 : SEL_GENO;
+    const int64_t n_rows = src->n_rows, n_cols = src->n_cols;
+    const int64_t src_snp = major ? n_cols : n_rows, src_samp = major ? n_rows : n_cols;
+    if (check_dims(fn, src_snp, src_samp, lim)) return 1;
+    if (!samp_index && n_samp_out != src_samp) return fail(fn, "samp_index is NULL: n_samp_out should be the source's number of samples");
+    if (!snp_index && n_snp_out != src_snp) return fail(fn, "snp_index is NULL: n_snp_out should be the source's number of SNPs");
+    if (check_dims(fn, n_snp_out, n_samp_out, lim)) return 1;
+    // the description: even, non-negative bit positions inside [bits, bits + n_bytes)
+    if (src->n_bytes < 1) return fail(fn, "invalid n_bytes");
+    if (src->bit0 < 0 || (src->bit0 & 1)) return fail(fn, "odd or negative bit position: bit0");
+    if (!src->row_bit && (src->row_stride_bits < 0 || (src->row_stride_bits & 1)))
+        return fail(fn, "odd or negative bit position: row_stride_bits");
+    {
+        const __int128 end = (__int128)src->n_bytes * 8, span = (__int128)2 * n_cols;
+        if (src->row_bit) {
+            for (int64_t r = 0; r < n_rows; r++) {
+                if (src->row_bit[r] < 0 || (src->row_bit[r] & 1)) return fail(fn, "odd or negative bit position: row_bit[" + std::to_string(r) + "]");
+                if ((__int128)src->bit0 + src->row_bit[r] + span > end)
+                    return fail(fn, "an element outside n_bytes: row " + std::to_string(r) + " ends beyond the source");
+            }
+        } else if ((__int128)src->bit0 + (__int128)(n_rows - 1) * src->row_stride_bits + span > end) {
+            return fail(fn, "an element outside n_bytes: row " + std::to_string(n_rows - 1) + " ends beyond the source");
+        }
+    }
+    if (samp_index)
+        for (int64_t j = 0; j < n_samp_out; j++)
+            if (samp_index[j] < 0 || samp_index[j] >= src_samp) return fail(fn, "an index outside the source: samp_index[" + std::to_string(j) + "]");
+    if (snp_index)
+        for (int64_t k = 0; k < n_snp_out; k++)
+            if (snp_index[k] < 0 || snp_index[k] >= src_snp) return fail(fn, "an index outside the source: snp_index[" + std::to_string(k) + "]");
+    return 0;
+}
+
+}  // namespace snpgpu
+
 namespace {
 
 // ms of: source copies to the device, copy kernel, gather kernel, transposition kernel; launches; source bytes copied; ms of the
 // result's copy to the host; staging windows
 thread_local double g_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
-constexpr size_t SEL_STAGE_BYTES = size_t(256) << 20;    // source bytes per staging window
-constexpr GenoLimits SEL_GENO = {1, int64_t(1) << 30, int64_t(1) << 31, false, "invalid number of samples (1 ... 2^30 - 1)"};
-constexpr GenoLimits SEL_GENO_MAJOR1 = {1, int64_t(1) << 30, int64_t(1) << 30, false, "invalid number of samples (1 ... 2^30 - 1)"};
 enum { T_H2D = 0, T_COPY = 1, T_GATHER = 2, T_TRANS = 3, T_D2H = 4 };
 
-size_t stage_bytes()
-{
-    if (const char *e = getenv("SNPGPU_SELECT_STAGE_BYTES")) { if (atoll(e) > 0) return (size_t)atoll(e); }
-    return SEL_STAGE_BYTES;
-}
+size_t stage_bytes() { return sel_stage_bytes(); }
 // SNPGPU_SELECT_LDS_WORDS: a smaller LDS budget of the gather kernel (0: source rows stay in global memory), to test that path
 int64_t lds_words()
 {
@@ -103,49 +160,9 @@ int run_transpose(Call &c, const SelBits &v, const int32_t *d_samp, const std::v
 int convert(const char *fn, const snpgpu_geno_src *src, int src_code, const int32_t *samp_index, int64_t n_samp_out,
             const int32_t *snp_index, int64_t n_snp_out, void *dst, int dst_major, int dst_code, int dst_mem, int device, void *stream)
 {
-    if (!src) return fail(fn, "NULL argument: src is NULL");
-    if (!src->bits) return fail(fn, "NULL argument: src->bits is NULL");
-    if (!dst) return fail(fn, "NULL argument: dst is NULL");
-    const auto mem_ok = [](int m) { return m == SNPGPU_HOST || m == SNPGPU_DEVICE || m == SNPGPU_HOST_PINNED; };
-    if (!mem_ok(src->mem)) return fail(fn, "invalid memory kind");
-    if (!mem_ok(dst_mem)) return fail(fn, "invalid dst_mem");
-    if (src->major != 0 && src->major != 1) return fail(fn, "invalid major (0: a row is a SNP, 1: a row is a sample)");
-    const auto code_ok = [](int c) { return c == SNPGPU_CODE_GDS || c == SNPGPU_CODE_BED; };
-    if (!code_ok(src_code)) return fail(fn, "invalid src_code (SNPGPU_CODE_GDS or SNPGPU_CODE_BED)");
-    if (!code_ok(dst_code)) return fail(fn, "invalid dst_code (SNPGPU_CODE_GDS or SNPGPU_CODE_BED)");
-    if (dst_major != 0 && dst_major != 1) return fail(fn, "invalid dst_major (0: a row of dst is a SNP, 1: a row of dst is a sample)");
+    if (sel_check_args(fn, src, src_code, samp_index, n_samp_out, snp_index, n_snp_out, dst, dst_major, dst_code, dst_mem)) return 1;
     const int major = src->major;
-    // the axis dst packs holds at most 2^30 - 1 entries: for sample rows that is the SNPs
-    const GenoLimits &lim = dst_major ? SEL_GENO_MAJOR1 : SEL_GENO;
     const int64_t n_rows = src->n_rows, n_cols = src->n_cols;
-    const int64_t src_snp = major ? n_cols : n_rows, src_samp = major ? n_rows : n_cols;
-    if (check_dims(fn, src_snp, src_samp, lim)) return 1;
-    if (!samp_index && n_samp_out != src_samp) return fail(fn, "samp_index is NULL: n_samp_out should be the source's number of samples");
-    if (!snp_index && n_snp_out != src_snp) return fail(fn, "snp_index is NULL: n_snp_out should be the source's number of SNPs");
-    if (check_dims(fn, n_snp_out, n_samp_out, lim)) return 1;
-    // the description: even, non-negative bit positions inside [bits, bits + n_bytes)
-    if (src->n_bytes < 1) return fail(fn, "invalid n_bytes");
-    if (src->bit0 < 0 || (src->bit0 & 1)) return fail(fn, "odd or negative bit position: bit0");
-    if (!src->row_bit && (src->row_stride_bits < 0 || (src->row_stride_bits & 1)))
-        return fail(fn, "odd or negative bit position: row_stride_bits");
-    {
-        const __int128 end = (__int128)src->n_bytes * 8, span = (__int128)2 * n_cols;
-        if (src->row_bit) {
-            for (int64_t r = 0; r < n_rows; r++) {
-                if (src->row_bit[r] < 0 || (src->row_bit[r] & 1)) return fail(fn, "odd or negative bit position: row_bit[" + std::to_string(r) + "]");
-                if ((__int128)src->bit0 + src->row_bit[r] + span > end)
-                    return fail(fn, "an element outside n_bytes: row " + std::to_string(r) + " ends beyond the source");
-            }
-        } else if ((__int128)src->bit0 + (__int128)(n_rows - 1) * src->row_stride_bits + span > end) {
-            return fail(fn, "an element outside n_bytes: row " + std::to_string(n_rows - 1) + " ends beyond the source");
-        }
-    }
-    if (samp_index)
-        for (int64_t j = 0; j < n_samp_out; j++)
-            if (samp_index[j] < 0 || samp_index[j] >= src_samp) return fail(fn, "an index outside the source: samp_index[" + std::to_string(j) + "]");
-    if (snp_index)
-        for (int64_t k = 0; k < n_snp_out; k++)
-            if (snp_index[k] < 0 || snp_index[k] >= src_snp) return fail(fn, "an index outside the source: snp_index[" + std::to_string(k) + "]");
 
     // from here on in dst's terms: rows and columns (see the head of this file)
     const SelRecode code = sel_recode(src_code, dst_code);

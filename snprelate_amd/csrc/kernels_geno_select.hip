@@ -11,21 +11,12 @@
 // the funnel shifts, the gather and transpose_2bit_64x64), PAD is the code of dst's unused codes.  Codes that no source element
 // fills are written in the SOURCE's code set as the code MAP sends to PAD (sel_pad_src), so that one map per output dword serves.
 #include "geno_select.h"
+#include "geno_select_device.h"
 #include "prep_device.h"
 
 namespace snpgpu {
 
 __device__ __forceinline__ int64_t sel_row_bit(const SelBits &s, int64_t r) { return s.bit0 + (s.row_bit ? s.row_bit[r] : r * s.stride); }
-
-// 32 bits from bit p (>= 0, inside the source) of the stream; dwords beyond the source read as 0
-__device__ __forceinline__ uint32_t sel_fetch32(const uint32_t *__restrict__ w, int64_t n_words, int64_t p)
-{
-    const int64_t d = p >> 5;
-    const uint32_t sh = (uint32_t)p & 31u;
-    const uint32_t lo = d < n_words ? w[d] : 0u;
-    const uint32_t hi = (sh && d + 1 < n_words) ? w[d + 1] : 0u;
-    return __builtin_amdgcn_alignbit(hi, lo, sh);
-}
 
 enum { SEL_MAP_ID = 0, SEL_MAP_BED_GDS = 1, SEL_MAP_GDS_BED = 2 };
 
@@ -44,23 +35,6 @@ template <int MAP, int PAD> __device__ __forceinline__ constexpr uint32_t sel_pa
     return MAP == SEL_MAP_BED_GDS ? (PAD == 3 ? 0x55555555u : 0xFFFFFFFFu)
          : MAP == SEL_MAP_GDS_BED ? (PAD == 0 ? 0xAAAAAAAAu : 0u)
                                   : (PAD == 3 ? 0xFFFFFFFFu : 0u);
-}
-
-// codes rem ... 15 of a dword of 16 codes (rem ... 3 of a byte of 4) become PAD: 3 is the padding of pack_2bit_rows, 0 that of a
-// .bed row
-template <int PAD> __device__ __forceinline__ uint32_t sel_pad16(uint32_t v, int64_t rem)
-{
-    if (PAD == 3) return rem >= 16 ? v : rem <= 0 ? ~0u : v | (~0u << (2 * rem));
-    return rem >= 16 ? v : rem <= 0 ? 0u : v & ~(~0u << (2 * rem));
-}
-
-// the dword of dst at row byte i0 (any of its bytes may lie outside the row [0, rb)): one store when whole, bytes otherwise
-__device__ __forceinline__ void sel_store_unit(uint8_t *__restrict__ row, int64_t i0, int64_t rb, uint32_t v)
-{
-    if (i0 >= 0 && i0 + 4 <= rb) { *reinterpret_cast<uint32_t *>(row + i0) = v; return; }
-#pragma unroll
-    for (int b = 0; b < 4; b++)
-        if (i0 + b >= 0 && i0 + b < rb) row[i0 + b] = (uint8_t)(v >> (8 * b));
 }
 
 // ---- SNP rows -> SNP rows, samples s0 ... s0 + n_out - 1 ---------------------------------------------------------------------
