@@ -448,6 +448,9 @@ int snpgpu_gnrGRM(int num_thread, const char *method, int use_matrix, int verbos
  * average, as the reference's gnrGRM_avg_val does. */
 int snpgpu_gnrGRMMerge(int n_grm, int64_t N, const double *const *grm, const char *cmd, const double *avg_val,
                        const double *weight, double *out, int device);
+/* of the last snpgpu_gnrGRMMerge on this thread that passed its argument checks: stats[0] row slabs copied to the device (every
+ * input travels in slabs of the staging budget, once for the weighted sum and twice for the beta merge), [1] kernels launched */
+int snpgpu_grm_merge_stats(double *stats);
 /* gnrIBD_PLINK(NumThread, AlleleFreq, UseSpecificAFreq, KinshipConstrict, useMatrix, Verbose),
  * src/genIBS.cpp:558-639.  allele_freq may be NULL (then the allele-count correction is used);
  * afreq_out: double [n_snp] */
@@ -718,7 +721,8 @@ int snpgpu_fst_windows(const void *geno, int64_t n_snp, int64_t n_samp, int form
                        double *fst_snp, int device);
 /* of the last call above on this thread: stats[0] ms of the counter kernel (HIP events, summed over the blocks), [1] its launches,
  * [2] ms from the first to the last Fst kernel (per-SNP terms, window sums; the device-to-host copies of the window results that
- * lie between the launches of a W&H02 scan included), [3] genotype bytes the counter kernel read */
+ * lie between the launches of a W&H02 scan included), [3] genotype bytes the counter kernel read, [4] launches of the W&H02 window
+ * sums (each takes as many windows as its buffer of K x K sums holds; 0 for W&C84 and for snpgpu_pop_counts).  stats: 5 doubles */
 int snpgpu_pop_stats(double *stats);
 /* gnrFst(Pop, nPop, Method) on the working space's selected SNPs: pop 1-based as R passes a factor, method "W&C84" / "W&H02" */
 int snpgpu_gnrFst(const int32_t *pop, int n_pop, const char *method, double *fst, double *fst_snp, double *beta);

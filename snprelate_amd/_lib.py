@@ -68,6 +68,7 @@ EXPORTS = [
     "snpgpu_text_render", "snpgpu_text_stats",
     "snpgpu_ped_tokens", "snpgpu_ped_census", "snpgpu_ped_codes", "snpgpu_ped_stats",
     "snpgpu_geno_merge", "snpgpu_geno_merge_stats",
+    "snpgpu_grm_merge_stats",
 ]
 FST_WC84, FST_WH02 = 1, 2
 FST_METHODS = ("W&C84", "W&H02")
@@ -245,6 +246,7 @@ def lib():
     L.snpgpu_gnrIBD_KING_Homo.argtypes = [c_int, c_int, c_int, vp, vp]
     L.snpgpu_gnrGRM.argtypes = [c_int, ctypes.c_char_p, c_int, c_int, vp]
     L.snpgpu_gnrGRMMerge.argtypes = [c_int, i64, ctypes.POINTER(vp), ctypes.c_char_p, vp, vp, vp, c_int]
+    L.snpgpu_grm_merge_stats.argtypes = [vp]
     L.snpgpu_gnrPCA.argtypes = [c_int, c_int, c_int, c_int, ctypes.POINTER(dbl), vp, vp, vp,
                                 ctypes.POINTER(dbl)]
     L.snpgpu_proj_create.argtypes = [i64, c_int, ctypes.POINTER(Opts), ctypes.POINTER(vp)]
@@ -1408,10 +1410,11 @@ def fst_windows(geno, n_samp, pop, n_pop, offsets, snp_index, method=FST_WC84, f
 
 
 def pop_stats():
-    """(counter kernel ms, its launches, Fst kernels ms, genotype bytes read) of the last pop_counts / fst call on this thread"""
-    s = np.zeros(4, np.float64)
+    """(counter kernel ms, its launches, Fst kernels ms, genotype bytes read, launches of the W&H02 window sums) of the last
+    pop_counts / fst call on this thread"""
+    s = np.zeros(5, np.float64)
     check(lib().snpgpu_pop_stats(_ptr(s)))
-    return float(s[0]), int(s[1]), float(s[2]), float(s[3])
+    return float(s[0]), int(s[1]), float(s[2]), float(s[3]), int(s[4])
 
 
 def geno_counts(geno, n_samp, fmt=None, n_snp=None, device=0, want_snp=True, want_samp=True, out_ptrs=None):
@@ -1913,6 +1916,37 @@ def geno_merge_stats():
     s = np.zeros(5, np.float64)
     check(lib().snpgpu_geno_merge_stats(_ptr(s)))
     return dict(stage_ms=float(s[0]), splice_ms=float(s[1]), launches=int(s[2]), windows=int(s[3]), bytes_written=float(s[4]))
+
+
+def grm_merge(grms, weight, cmd=":method = GCTA", avg_val=None, device=0):
+    """snpgpu_gnrGRMMerge: (merged N x N matrix, avg_val or None) of the N x N float64 matrices `grms`; cmd: the second element of
+    the files' "command" node, ":method = IndivBeta" selects the beta merge, which needs the avg_val of every input"""
+    mats = [np.ascontiguousarray(g, np.float64) for g in grms]
+    n = mats[0].shape[0]
+    if any(m.shape != (n, n) for m in mats):
+        raise ValueError("every GRM should be N x N")
+    w = np.ascontiguousarray(weight, np.float64)
+    if w.shape != (len(mats),):
+        raise ValueError("one weight per GRM")
+    beta = cmd == ":method = IndivBeta"
+    avg_in = np.ascontiguousarray(avg_val, np.float64) if beta else None
+    if beta and avg_in.shape != (len(mats),):
+        raise ValueError("one avg_val per GRM")
+    ptrs = (ctypes.c_void_p * len(mats))(*[m.ctypes.data for m in mats])
+    out = np.empty((n, n), np.float64)
+    check(lib().snpgpu_gnrGRMMerge(len(mats), n, ptrs, cmd.encode(), _ptr(avg_in), _ptr(w), _ptr(out), int(device)))
+    if not beta:
+        return out, None
+    avg = ctypes.c_double(0)
+    check(lib().snpgpu_gnrGRM_avg_val(ctypes.byref(avg)))
+    return out, avg.value
+
+
+def grm_merge_stats():
+    """dict of snpgpu_grm_merge_stats for the last grm_merge (api.snpgdsMergeGRM) on this thread"""
+    s = np.zeros(2, np.float64)
+    check(lib().snpgpu_grm_merge_stats(_ptr(s)))
+    return dict(slabs=int(s[0]), launches=int(s[1]))
 
 
 def select_stats():

@@ -394,27 +394,19 @@ def snpgdsMergeGRM(filelist, out_fn=None, weight=None, verbose=True, device=0):
     sid = np.array([], dtype=files[0]["snp.id"].dtype)
     for w, f in zip(weight, files):                             # R/IBD.R:704-712
         sid = np.concatenate([sid, f["snp.id"]]) if w >= 0 else sid[~np.isin(sid, f["snp.id"])]
-    n = int(dm[0])
     beta = cmd[1] == ":method = IndivBeta"
-    mats = [np.ascontiguousarray(f["grm"], np.float64) for f in files]
-    ptrs = (ctypes.c_void_p * len(mats))(*[m.ctypes.data for m in mats])
-    avg_in = np.ascontiguousarray([float(f["avg_val"]) for f in files], np.float64) if beta else None
-    out = np.empty((n, n), np.float64)
-    _lib.check(_lib.lib().snpgpu_gnrGRMMerge(len(mats), n, ptrs, cmd[1].encode(), _lib._ptr(avg_in) if beta else None,
-                                             _lib._ptr(weight), _lib._ptr(out), int(device)))
-    avg = ctypes.c_double(0)
-    if beta:
-        _lib.check(_lib.lib().snpgpu_gnrGRM_avg_val(ctypes.byref(avg)))
+    out, avg = _lib.grm_merge([f["grm"] for f in files], weight, cmd[1], [float(f["avg_val"]) for f in files] if beta else None,
+                              device=device)
     if out_fn is not None:
         _cat(verbose, "Output: " + out_fn)
         nodes = {"command": np.array(cmd), "sample.id": sampid, "snp.id": sid, "grm": out}
         if beta:
-            nodes["avg_val"] = avg.value
+            nodes["avg_val"] = avg
         _gds.write_output(out_fn, nodes)
         return None
     rv = dict(sample_id=sampid, snp_id=sid, grm=out)
     if beta:
-        rv["avg_val"] = avg.value
+        rv["avg_val"] = avg
     return rv
 
 

@@ -14,6 +14,8 @@ namespace {
 
 constexpr size_t MERGE_SLAB_BYTES = (size_t)256 << 20;
 
+thread_local double g_stats[2] = {0, 0};   // row slabs copied to the device, kernels launched
+
 __device__ inline void atomic_min_f64(double *addr, double v)
 {
     unsigned long long *a = (unsigned long long *)addr, old = *a;
@@ -119,6 +121,7 @@ extern "C" int snpgpu_gnrGRMMerge(int n_grm, int64_t N, const double *const *grm
         if (!grm[k]) { set_error("snpgpu_gnrGRMMerge: invalid arguments"); return 1; }
     const bool beta = cmd && strcmp(cmd, ":method = IndivBeta") == 0;       // src/genPCA.cpp:1744
     if (beta && !avg_val) { set_error("snpgpu_gnrGRMMerge: 'avg_val' of every input is needed for IndivBeta"); return 1; }
+    for (double &s : g_stats) s = 0;
     SNPGPU_HIP_CHECK(hipSetDevice(device));
     const size_t nn = (size_t)N * (size_t)N;
     const int64_t slab_rows = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t)(MERGE_SLAB_BYTES / (sizeof(double) * (size_t)N))));
@@ -136,6 +139,7 @@ extern "C" int snpgpu_gnrGRMMerge(int n_grm, int64_t N, const double *const *grm
                 const size_t cnt = (size_t)rows * (size_t)N;
                 ok = hipMemcpyAsync(slab.p, grm[k] + (size_t)r0 * (size_t)N, sizeof(double) * cnt, hipMemcpyHostToDevice, st) == hipSuccess;
                 if (!ok) break;
+                g_stats[0] += 1; g_stats[1] += 1;
                 double *dst = (double *)M.p + (size_t)r0 * (size_t)N;
                 if (pass == 0)
                     hipLaunchKernelGGL(merge_offdiag_sum_kernel, dim3(merge_grid(cnt)), dim3(256), 0, st,
@@ -168,7 +172,15 @@ extern "C" int snpgpu_gnrGRMMerge(int n_grm, int64_t N, const double *const *grm
         g_grm_avg_value = r[0] / ((double)N * (double)(N - 1));                    // :1809
         hipLaunchKernelGGL(merge_beta_final_kernel, dim3(merge_grid(nn)), dim3(256), 0, st, (double *)M.p, N, r[1],
                            2 / (1 - r[1]));
+        g_stats[1] += 2;
     }
     if (hipMemcpy(out, M.p, sizeof(double) * nn, hipMemcpyDeviceToHost) != hipSuccess) { set_error("snpgpu_gnrGRMMerge: copy failed"); return 1; }
+    return 0;
+}
+
+extern "C" int snpgpu_grm_merge_stats(double *stats)
+{
+    if (!stats) { set_error("snpgpu_grm_merge_stats: stats is NULL"); return 1; }
+    for (int k = 0; k < 2; k++) stats[k] = g_stats[k];
     return 0;
 }

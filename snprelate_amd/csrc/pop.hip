@@ -28,7 +28,8 @@ using namespace snpgpu;
 
 namespace {
 
-thread_local double g_stats[4] = {0, 0, 0, 0};   // counter kernel ms, its launches, Fst kernels ms, genotype bytes the counter kernel read
+// counter kernel ms, its launches, Fst kernels ms, genotype bytes the counter kernel read, launches of the W&H02 window sums
+thread_local double g_stats[5] = {0, 0, 0, 0, 0};
 
 constexpr size_t POP_STAGE_BYTES = size_t(256) << 20;    // genotype bytes per streamed block
 constexpr size_t POP_SUMH_BYTES = size_t(64) << 20;      // W&H02 window sums per launch
@@ -143,6 +144,7 @@ int fst_core(Call &c, const int32_t *dacnt, const int32_t *dcnt, int64_t n_snp, 
             if (launch_fst_sum_wh02(st.s, dacnt, dcnt, (const uint8_t *)dvalid->p, K, (const int64_t *)doff->p, idx, w0, nw,
                                     (double *)dsum->p, (double *)dout->p))
                 return 1;
+            g_stats[4] += 1;
             SNPGPU_HIP_CHECK(hipMemcpyAsync(fst_win + w0, dout->p, sizeof(double) * (size_t)nw, hipMemcpyDeviceToHost, st.s));
             if (beta_win)
                 SNPGPU_HIP_CHECK(hipMemcpyAsync(beta_win + (size_t)w0 * kk, dsum->p, sizeof(double) * kk * (size_t)nw,
@@ -218,7 +220,7 @@ int snpgpu_fst(const void *geno, int64_t n_snp, int64_t n_samp, int format, int 
 int snpgpu_pop_stats(double *stats)
 {
     if (!stats) { set_error("snpgpu_pop_stats: stats is NULL"); return 1; }
-    for (int k = 0; k < 4; k++) stats[k] = g_stats[k];
+    for (int k = 0; k < 5; k++) stats[k] = g_stats[k];
     return 0;
 }
 

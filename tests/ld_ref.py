@@ -41,26 +41,35 @@ def _haplo(nAA, nAB, nBA, nBB, nDH2):
     def plog(v):
         return np.log(v + DBL_EPS)
 
-    def loglik(qAA, qAB, qBA, qBB):
+    def loglik(a, b, c, d, dh, qAA, qAB, qBA, qBB):
         return a * plog(qAA) + b * plog(qAB) + c * plog(qBA) + d * plog(qBB) + dh * plog(qAA * qBB + qAB * qBA)
 
-    old = loglik(qAA, qAB, qBA, qBB)
+    old = loglik(a, b, c, d, dh, qAA, qAB, qBA, qBB)
     tol = np.abs(tol_rel * old)
     tol = np.where(tol < DBL_EPS, DBL_EPS, tol)
-    act = np.ones(a.shape, bool)
+    # only the pairs still iterating are carried along (`idx`: where they go in `res`); a pair keeps the proportions of the
+    # iteration at which it stopped
+    res = [qAA.copy(), qAB.copy(), qBA.copy(), qBB.copy()]
+    q = [qAA, qAB, qBA, qBB]
+    idx = np.arange(a.size)
     for _ in range(1000):
-        x, y = qAA * qBB, qAB * qBA
+        x, y = q[0] * q[3], q[1] * q[2]
         dAA = x / (x + y) * dh
         dAB = dh - dAA
-        nq = ((a + dAA) / T, (b + dAB) / T, (c + dAB) / T, (d + dAA) / T)
-        qAA, qAB, qBA, qBB = (np.where(act, n, q) for n, q in zip(nq, (qAA, qAB, qBA, qBB)))
-        ll = loglik(qAA, qAB, qBA, qBB)
-        stop = act & (np.abs(ll - old) <= tol)
-        act = act & ~stop
-        old = np.where(act, ll, old)
-        if not act.any():
+        q = [(a + dAA) / T, (b + dAB) / T, (c + dAB) / T, (d + dAA) / T]
+        ll = loglik(a, b, c, d, dh, *q)
+        go = ~(np.abs(ll - old) <= tol)
+        old = ll
+        if not go.all():
+            for r, v in zip(res, q):
+                r[idx[~go]] = v[~go]
+            a, b, c, d, dh, T, tol, old, idx = (v[go] for v in (a, b, c, d, dh, T, tol, old, idx))
+            q = [v[go] for v in q]
+        if idx.size == 0:
             break
-    for full, part in ((pAA, qAA), (pAB, qAB), (pBA, qBA), (pBB, qBB)):
+    for r, v in zip(res, q):
+        r[idx] = v
+    for full, part in zip((pAA, pAB, pBA, pBB), res):
         full[e] = part
     return pAA, pAB, pBA, pBB
 

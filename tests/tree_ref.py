@@ -151,6 +151,21 @@ def dist_perm_counter(dist, merge, n_perm, z_threshold, seed):
     return out
 
 
+def caterpillar_obs(dist, merge):
+    """(n1, n2, obs) of dist_perm_counter for a caterpillar -- the first merge joins two samples, every later one a new sample
+    (first column) to the cluster before it (second column) -- without the loop over merges: with the matrix reordered by the
+    order in which the samples join, the observed value of merge k >= 1 is the mean of row k + 1 over its first k + 1 columns."""
+    dist = np.asarray(dist, np.float64)
+    merge = np.asarray(merge)
+    nm = len(merge)
+    assert (merge[0] < 0).all() and (merge[1:, 0] < 0).all() and np.array_equal(merge[1:, 1], np.arange(1, nm))
+    join = np.concatenate([-merge[0] - 1, -merge[1:, 0] - 1])
+    dp = dist[np.ix_(join, join)]
+    obs = np.tril(dp, -1).sum(1)[1:] / np.arange(1, nm + 1)
+    obs[0] = dp[0, 1]                                     # the first merge reads (first column, second column)
+    return np.ones(nm, np.int32), np.arange(1, nm + 1, dtype=np.int32), obs
+
+
 def dist_perm_sequential(dist, merge, n_perm, z_threshold, rng):
     """the reference's procedure as it stands (:526-626): within a merge the arrangement is carried over from permutation to
     permutation, the uniforms come from rng.random() in call order"""
