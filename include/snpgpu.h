@@ -1072,6 +1072,57 @@ int snpgpu_geno_merge(const snpgpu_merge_part *parts, int n_parts, int64_t n_snp
  * rows (staging and selection), [1] ms of the splice kernel, [2] its launches, [3] windows, [4] bytes written to rows */
 int snpgpu_geno_merge_stats(double *stats);
 
+/* ---- (1p) Oxford GEN text: genotype probabilities of data lines called to SNPGPU_GENO_PACKED2 rows ---------------------------------------
+ * What gnrParseGEN (src/ConvToGDS.cpp:1015-1157) does per sample -- three std::string cells, three strtof, one decision tree --, on
+ * the device: the file's own bytes go there and 2-bit rows come out.  The five leading columns of a line (SNP id, rs id, position,
+ * allele A, allele B) stay with the host; it hands over where the sixth starts.
+ *
+ * snpgpu_gen_genotypes: line i's tokens are the maximal runs of bytes of text[cell_begin[i], line_end[i]) that are neither tab nor
+ * space; token t is probability t % 3 (AA, AB, BB) of sample t / 3.
+ *   text, text_mem SNPGPU_HOST, SNPGPU_HOST_PINNED (both staged in windows of whole lines of at most SNPGPU_TEXT_STAGE_BYTES,
+ *                  default 256 MiB) or SNPGPU_DEVICE (any alignment, parsed where it lies); only aligned dwords that hold a byte
+ *                  of [text, text + n_bytes) are loaded
+ *   call_threshold the double the reference compares with: a sample is called when its largest probability is >= it
+ *   rows           DEVICE memory of `device`: [n_lines][ceil(n_samp / 4)], the unused codes of a row's last byte 0
+ *   line_flags, line_cells   host, n_lines: the flags below and the number of tokens found
+ * A regular token is `digits [ '.' digits ]` or `'.' digits` with at most 15 significant digits (leading zeros not counted) and at
+ * most 22 digits behind the point.  Its digits are an integer m < 10^15 and a count k, both exact in fp64, so m / 10^k is the
+ * correctly rounded double; it is rounded to single precision once more WITHOUT double rounding -- when it is exactly a midpoint
+ * of two floats the sign of fma(d, 10^k, -m) says on which side the decimal number lies -- and is then the float strtof gives
+ * (getFloat, src/ConvToGDS.cpp:506-532).  The three floats are widened to double and go through the tree of
+ * src/ConvToGDS.cpp:1134-1145 with >= throughout: 2 = AA, 1 = AB, 0 = BB, 3 = no probability reaches call_threshold.
+ * The kernel raises nothing: it flags the line, whose row may then hold anything (inside its own bytes), and the caller settles it
+ * with snpgpu_gen_line_host:
+ *    1  a token byte that is neither a digit nor the token's one point (signs, exponents, inf, nan, hex forms, quotes, '\r' and
+ *       other isspace bytes, NUL)
+ *    2  a token without a digit: "."
+ *    4  more than 15 significant digits, or more than 22 digits behind the point
+ *    8  a token longer than the halo (64 bytes)
+ *   16  an empty cell: a tab beside a separator or at the line's end, a separator at cell_begin
+ *   32  line_cells != 3 n_samp; tokens beyond 3 n_samp are counted and never stored
+ * No device memory grows with n_lines x n_samp but rows; no atomics touch global memory; the result is a pure function of the
+ * input.  Refused before any device is touched: NULL pointers, an unknown text_mem, offsets outside n_bytes or cell_begin >
+ * line_end, n_samp outside 1 ... 2^30 - 1, n_lines outside 1 ... 2^31 - 1, host text with a line longer than a window; before any
+ * launch: a device pointer or a stream of another device. */
+int snpgpu_gen_genotypes(const void *text, int text_mem, int64_t n_bytes, const int64_t *cell_begin, const int64_t *line_end,
+                         int64_t n_lines, int64_t n_samp, double call_threshold, void *rows, int32_t *line_flags,
+                         int64_t *line_cells, int device, void *stream);
+/* snpgpu_gen_line_host: the 3 n_samp cells of one line from its sixth column on (line, n_bytes: without the line end; the line ends
+ * at a NUL if it holds one), read as the reference reads them: cells split by space and tab (CReadLine::GetCell,
+ * src/ConvToGDS.cpp:123-179: a run of spaces is one separator, a tab is one, matching quotes are dropped, spaces may follow the
+ * last cell), every cell through getFloat with the C library's strtof ("." is NaN, isspace bytes around the number are skipped),
+ * the tree as above.  Makes no HIP call.
+ *   codes          host, n_samp: one code 0 / 1 / 2 / 3 per sample
+ *   column         0 when the line is read; else the 1-based number of the failing cell counted from `line` (the reference's
+ *                  COLUMN is 5 more), and message (message_bytes) holds the reference's text: "fewer columns than what
+ *                  expected.", "more columns than what expected.", "Invalid float conversion \"...\"."
+ * The return value is non-zero for an argument error only (NULL pointers, n_samp outside 1 ... 2^30 - 1, n_bytes < 0). */
+int snpgpu_gen_line_host(const char *line, int64_t n_bytes, int64_t n_samp, double call_threshold, uint8_t *codes,
+                         int64_t *column, char *message, int64_t message_bytes);
+/* of the last snpgpu_gen_genotypes on this thread: [0] ms of the text's copies to the device, [1] ms of the kernel, [2] launches,
+ * [3] text bytes copied (or parsed in place), [4] bytes of a workgroup's chunk, [5] of a lane's segment, [6] of the halo */
+int snpgpu_gen_stats(double *stats);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------------------
  * What THIS device's matrix pipe sustains right now: a register-only stream of one MFMA instruction (never waiting on memory,
  * two waves per SIMD) run for `seconds`, rate taken over the second half.  The kernels of this library run against the socket

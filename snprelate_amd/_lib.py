@@ -68,6 +68,7 @@ EXPORTS = [
     "snpgpu_text_render", "snpgpu_text_stats",
     "snpgpu_ped_tokens", "snpgpu_ped_census", "snpgpu_ped_codes", "snpgpu_ped_stats",
     "snpgpu_geno_merge", "snpgpu_geno_merge_stats",
+    "snpgpu_gen_genotypes", "snpgpu_gen_line_host", "snpgpu_gen_stats",
     "snpgpu_grm_merge_stats",
 ]
 FST_WC84, FST_WH02 = 1, 2
@@ -340,6 +341,9 @@ def lib():
     L.snpgpu_ped_stats.argtypes = [vp]
     L.snpgpu_geno_merge.argtypes = [ctypes.POINTER(MergePart), c_int, i64, vp, c_int, vp]
     L.snpgpu_geno_merge_stats.argtypes = [vp]
+    L.snpgpu_gen_genotypes.argtypes = [vp, c_int, i64, vp, vp, i64, i64, dbl, vp, vp, vp, c_int, vp]
+    L.snpgpu_gen_line_host.argtypes = [ctypes.c_char_p, i64, i64, dbl, vp, vp, ctypes.c_char_p, i64]
+    L.snpgpu_gen_stats.argtypes = [vp]
     _lib = L
     return L
 
@@ -1850,6 +1854,57 @@ def ped_stats():
     check(lib().snpgpu_ped_stats(_ptr(s)))
     return dict(tokens_ms=float(s[0]), census_ms=float(s[1]), codes_ms=float(s[2]), launches=int(s[3]), text_bytes=float(s[4]),
                 chunk_bytes=int(s[5]), segment_bytes=int(s[6]), halo_bytes=int(s[7]))
+
+
+GEN_FLAG_BYTE, GEN_FLAG_DOT, GEN_FLAG_DIGITS, GEN_FLAG_LONG, GEN_FLAG_EMPTY, GEN_FLAG_COUNT = 1, 2, 4, 8, 16, 32
+
+
+def gen_genotypes(text, cell_begin, line_end, n_samp, call_threshold, rows, n_bytes=None, text_mem=None, device=0, stream=None):
+    """snpgpu_gen_genotypes: the probability triples of the lines text[cell_begin[i], line_end[i]) called to PACKED2 rows in DEVICE
+    memory at the address `rows` ([n_lines][ceil(n_samp / 4)], padding codes 0).  text: bytes / a numpy uint8 array (host memory),
+    or an address (int) with n_bytes -- device memory unless text_mem says HOST or HOST_PINNED.  Returns (line_flags int32,
+    line_cells int64)."""
+    keep = None
+    if isinstance(text, int):
+        if n_bytes is None:
+            raise ValueError("a text address needs n_bytes")
+        ptr, mem = ctypes.c_void_p(text), (DEVICE if text_mem is None else int(text_mem))
+    else:
+        keep = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8)
+        ptr, mem = _ptr(keep), (HOST if text_mem is None else int(text_mem))
+        n_bytes = keep.size if n_bytes is None else int(n_bytes)
+        if n_bytes > keep.size:
+            raise ValueError("n_bytes exceeds the text array")
+    cb, le = np.ascontiguousarray(cell_begin, np.int64).reshape(-1), np.ascontiguousarray(line_end, np.int64).reshape(-1)
+    n = cb.size
+    if le.size != n:
+        raise ValueError("cell_begin and line_end should have one entry per line")
+    flags, cells = np.zeros(n, np.int32), np.zeros(n, np.int64)
+    check(lib().snpgpu_gen_genotypes(ptr, mem, int(n_bytes), _ptr(cb), _ptr(le), n, int(n_samp), float(call_threshold), _dptr(rows),
+                                     _ptr(flags), _ptr(cells), int(device), ctypes.c_void_p(stream) if stream else None))
+    return flags, cells
+
+
+def gen_line_host(line, n_samp, call_threshold):
+    """snpgpu_gen_line_host: the 3 n_samp cells of one line (bytes from its sixth column on, without the line end) as the reference
+    reads them.  Returns (codes uint8 [n_samp], 0, "") or (None, column, message): the 1-based cell counted from `line` at which
+    the reference raises `message`.  No device is needed."""
+    line = bytes(line)
+    codes = np.zeros(max(int(n_samp), 1), np.uint8)
+    col = ctypes.c_int64(0)
+    msg = ctypes.create_string_buffer(256)
+    check(lib().snpgpu_gen_line_host(line, len(line), int(n_samp), float(call_threshold), _ptr(codes), ctypes.byref(col), msg, len(msg)))
+    if col.value:
+        return None, col.value, msg.value.decode("latin1")
+    return codes, 0, ""
+
+
+def gen_stats():
+    """dict of snpgpu_gen_stats for the last gen_genotypes call on this thread"""
+    s = np.zeros(7, np.float64)
+    check(lib().snpgpu_gen_stats(_ptr(s)))
+    return dict(h2d_ms=float(s[0]), kernel_ms=float(s[1]), launches=int(s[2]), text_bytes=float(s[3]), chunk_bytes=int(s[4]),
+                segment_bytes=int(s[5]), halo_bytes=int(s[6]))
 
 
 def merge_part(src, major, n_rows, n_cols, bit0=0, row_stride_bits=None, row_bit=None, samp_index=None, snp_index=None, flip=None,

@@ -37,6 +37,7 @@ INTEGRATION.md):
     snpgdsGDS2PED                 R/Conversion.R:26-124  (the selected rectangle as PLINK text .ped/.map, the lines made on the GPU)
     snpgdsGDS2Eigen               R/Conversion.R:695-785 (the selected rectangle as EIGENSTRAT .eigenstratgeno/.snp/.ind)
     snpgdsOpenPED                 R/Conversion.R:132-302 (snpgdsPED2GDS + snpgdsOpen: PLINK text .ped/.map parsed on the GPU)
+    snpgdsOpenGEN                 R/Conversion.R:795-964 (snpgdsGEN2GDS + snpgdsOpen: Oxford .gen/.sample read and called on the GPU)
     snpgdsSNPList                 R/AllUtilities.R:637-658   (SNP ids, positions, alleles and allele frequencies of one data set)
     snpgdsSNPListIntersect        R/AllUtilities.R:667-736   (the SNPs several data sets share, and who counts the other allele)
     snpgdsCombineGeno             R/AllUtilities.R:1285-1583 (data sets merged: the genotypes spliced on the GPU)
@@ -2077,6 +2078,72 @@ def snpgdsOpenPED(ped_fn, map_fn, family=True, verbose=True, device=0):
     gf.snp_rs_id = m["snp_rs_id"]
     gf.ped_flagged_lines, gf.ped_windows = r.flagged_lines, r.windows
     if m["snp_chromosome"].dtype.kind == "U":
+        gf.chromosome_code = {}                            # text labels, as snpgdsOpenVCF keeps them
+    return gf
+
+
+def snpgdsOpenGEN(gen_fn, sample_fn, chr_code=None, call_threshold=0.9, version=">=2.0", verbose=True, device=0):
+    """Open Oxford GEN files (IMPUTE2, SNPTEST, SHAPEIT) and their sample file for every snpgds* function: snpgdsGEN2GDS
+    (R/Conversion.R:795-964 -> gnrParseGEN, src/ConvToGDS.cpp:1015-1157) + snpgdsOpen in one step, without the GDS file in between.
+    gen_fn: a file name or a list of them (plain or .gz), appended in order; chr_code: one entry per file, all numbers (integers,
+    NA -> 0) or all strings.  A sample is called AA (2), AB (1) or BB (0) when the largest of its three probabilities, read as
+    strtof reads them, is >= call_threshold, else it is missing (3).  version ">=2.0": the sample file has a line of column types
+    under its header; "<=1.1.5": it has none.  Returns a GenoFile: sample_id the sample file's first column, all its columns in
+    sample_annot under the header's names (text), snp_id column 1 of the .gen lines (text), snp_rs_id column 2, snp_position
+    column 3, snp_allele "A/B" of columns 4 and 5, snp_chromosome the file's chr_code.
+    The probabilities are read and called on the device (gen.GenReader -> snpgpu_gen_genotypes) in chunks of
+    SNPGPU_TEXT_STAGE_BYTES; lines the kernel flags (exponents, signs, quotes, '\\r', "." ...) are settled on the host by
+    snpgpu_gen_line_host, and a malformed line raises the reference's message with FILE:, LINE:, COLUMN:.  There is no CPU
+    fallback: without a device the call fails with SnpGpuError.  There is no snpgdsGEN2GDS here, for the reason there is no
+    snpgdsBED2GDS: writing the GDS container is gdsfmt's work."""
+    from . import gen as _gen
+    files = [gen_fn] if isinstance(gen_fn, str) else list(gen_fn)
+    if not files or not all(isinstance(f, str) for f in files):
+        raise TypeError("is.character(gen.fn) & is.vector(gen.fn) is not TRUE")
+    if not isinstance(sample_fn, str):
+        raise TypeError("is.character(sample.fn) & is.vector(sample.fn) is not TRUE")
+    if chr_code is None:
+        raise ValueError("Please specify the argument 'chr.code', e.g., 'chr.code=1'.")
+    codes = [chr_code] if isinstance(chr_code, (str, int, float, np.integer, np.floating)) else list(chr_code)
+    is_text = all(c is None or isinstance(c, str) for c in codes) and any(isinstance(c, str) for c in codes)
+    if not is_text and not all(c is None or _is_number(c) for c in codes):
+        raise TypeError("is.numeric(chr.code) | is.character(chr.code) is not TRUE")
+    if len(codes) != len(files):
+        raise ValueError("length(gen.fn) == length(chr.code) is not TRUE")
+    if not _is_number(call_threshold) or not math.isfinite(float(call_threshold)):
+        raise TypeError("is.finite(call.threshold) is not TRUE")
+    if version not in _gen.VERSIONS:
+        raise ValueError("'arg' should be one of \">=2.0\", \"<=1.1.5\"")
+    if not isinstance(verbose, (bool, np.bool_)):
+        raise TypeError("is.logical(verbose) is not TRUE")
+    _cat(verbose, "Oxford GEN/BGEN format ---> GDS SNP format:")
+    if is_text:
+        codes = ["" if c is None else c for c in codes]
+    else:
+        codes = [0 if c is None or _is_na(c) else int(c) for c in codes]
+    samp_id, annot = _gen.read_sample(sample_fn, version)
+    N, rb = len(samp_id), (len(samp_id) + 3) // 4
+    _cat(verbose, "The number of samples: %d, with SNPTEST version (%s)." % (N, version))
+    if not _device_visible():
+        raise _lib.SnpGpuError("snpgdsOpenGEN: no HIP device (the GEN genotype caller has no CPU fallback)")
+    parts, readers, chrom = [], [], []
+    for fn, code in zip(files, codes):
+        _cat(verbose, "Parsing \"", fn, "\" ...")
+        r = _gen.GenReader(fn, N, call_threshold)
+        for _, m, rows in r.blocks(4096, device=device):
+            parts.append(rows.cpu().numpy())
+        _cat(verbose, "\tImport %d variant%s on chromosome %s." % (r.n_snp, "s" if r.n_snp > 1 else "", code))
+        chrom += [code] * r.n_snp
+        readers.append(r)
+    if not chrom:
+        raise ValueError("No variant in the GEN file%s" % ("s" if len(files) > 1 else ""))
+    cat = lambda name: np.concatenate([getattr(r, name) for r in readers])          # noqa: E731
+    gf = GenoFile(packed=np.concatenate(parts, 0), n_samp=N, sample_id=samp_id, snp_id=cat("snp_id"),
+                  snp_chromosome=np.array(chrom, dtype=str) if is_text else np.array(chrom, np.int32),
+                  snp_position=cat("snp_position"), snp_allele=cat("snp_allele"), sample_annot=annot)
+    gf.snp_rs_id = cat("snp_rs_id")
+    gf.gen_flagged_lines, gf.gen_windows = sum(r.flagged_lines for r in readers), sum(r.windows for r in readers)
+    if is_text:
         gf.chromosome_code = {}                            # text labels, as snpgdsOpenVCF keeps them
     return gf
 
