@@ -409,6 +409,27 @@ def _dptr(x):
     return ctypes.c_void_p(int(x)) if x else None
 
 
+def _stats(name, k):
+    """the k doubles of snpgpu_<name>_stats"""
+    s = np.zeros(k, np.float64)
+    check(getattr(lib(), "snpgpu_%s_stats" % name)(_ptr(s)))
+    return s
+
+
+def _text_input(text, n_bytes, text_mem):
+    """text as the parsers take it -- bytes / a numpy uint8 array (host memory), or an address (int) with n_bytes, device memory
+    unless text_mem says HOST or HOST_PINNED: (pointer, memory kind, n_bytes, what keeps the memory alive)"""
+    if isinstance(text, int):
+        if n_bytes is None:
+            raise ValueError("a text address needs n_bytes")
+        return ctypes.c_void_p(text), (DEVICE if text_mem is None else int(text_mem)), int(n_bytes), None
+    keep = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8)
+    n_bytes = keep.size if n_bytes is None else int(n_bytes)
+    if n_bytes > keep.size:
+        raise ValueError("n_bytes exceeds the text array")
+    return _ptr(keep), (HOST if text_mem is None else int(text_mem)), n_bytes, keep
+
+
 class PinnedBuffer:
     """Page-locked host block buffer (snpgpu_host_alloc) exposed as a numpy uint8 array."""
 
@@ -1365,8 +1386,7 @@ def ibd_jacquard_pairs(geno, n_samp, idx1, idx2, allele_freq=None, max_niter=100
 
 def ibd_mle_pairs_stats():
     """(kernel ms, all kernels ms, wave-sweeps, pairs) of the last ibd_mle_pairs / ibd_jacquard_pairs on this thread"""
-    s = np.zeros(4, np.float64)
-    check(lib().snpgpu_ibd_mle_pairs_stats(_ptr(s)))
+    s = _stats("ibd_mle_pairs", 4)
     return float(s[0]), float(s[1]), int(s[2]), int(s[3])
 
 
@@ -1416,8 +1436,7 @@ def fst_windows(geno, n_samp, pop, n_pop, offsets, snp_index, method=FST_WC84, f
 def pop_stats():
     """(counter kernel ms, its launches, Fst kernels ms, genotype bytes read, launches of the W&H02 window sums) of the last
     pop_counts / fst call on this thread"""
-    s = np.zeros(5, np.float64)
-    check(lib().snpgpu_pop_stats(_ptr(s)))
+    s = _stats("pop", 5)
     return float(s[0]), int(s[1]), float(s[2]), float(s[3]), int(s[4])
 
 
@@ -1485,16 +1504,14 @@ def ind_inb(geno, n_samp, method="mom.weir", allele_freq=None, reltol=float(np.f
 
 def qc_stats():
     """dict of snpgpu_qc_stats for the last geno_counts / hwe / hwe_counts / ind_inb call on this thread"""
-    s = np.zeros(8, np.float64)
-    check(lib().snpgpu_qc_stats(_ptr(s)))
+    s = _stats("qc", 8)
     return dict(count_ms=float(s[0]), count_launches=int(s[1]), count_bytes=float(s[2]), mom_ms=float(s[3]), mle_ms=float(s[4]),
                 mle_lane_steps_useful=int(s[5]), mle_lane_steps_issued=int(s[6]), hwe_ms=float(s[7]))
 
 
 def ibd_mle_stats():
     """(EM kernel ms, all kernels ms, useful lane-sweeps, issued lane-sweeps) of the last ibd_mle on this thread"""
-    s = np.zeros(4, np.float64)
-    check(lib().snpgpu_ibd_mle_stats(_ptr(s)))
+    s = _stats("ibd_mle", 4)
     return float(s[0]), float(s[1]), int(s[2]), int(s[3])
 
 
@@ -1560,8 +1577,7 @@ def dist_perm(dist, merge, n_perm=5000, z_threshold=15.0, seed=0, device=0, n=No
 
 def tree_stats():
     """dict of snpgpu_tree_stats for the last dist_perm on this thread"""
-    s = np.zeros(6, np.float64)
-    check(lib().snpgpu_tree_stats(_ptr(s)))
+    s = _stats("tree", 6)
     return dict(prep_ms=float(s[0]), perm_ms=float(s[1]), prep_launches=int(s[2]), perm_launches=int(s[3]), gathered=float(s[4]),
                 permutations=float(s[5]))
 
@@ -1699,8 +1715,7 @@ def geno_convert(src, major, n_rows, n_cols, src_code=CODE_GDS, dst_code=CODE_GD
 
 def geno_select_stats():
     """dict of snpgpu_geno_select_stats for the last geno_select call on this thread"""
-    s = np.zeros(8, np.float64)
-    check(lib().snpgpu_geno_select_stats(_ptr(s)))
+    s = _stats("geno_select", 8)
     return dict(h2d_ms=float(s[0]), copy_ms=float(s[1]), gather_ms=float(s[2]), transpose_ms=float(s[3]), launches=int(s[4]),
                 source_bytes=float(s[5]), d2h_ms=float(s[6]), windows=int(s[7]))
 
@@ -1708,8 +1723,7 @@ def geno_select_stats():
 def geno_convert_stats():
     """dict of snpgpu_geno_convert_stats for the last geno_convert (or geno_select) call on this thread: the fields of
     geno_select_stats"""
-    s = np.zeros(8, np.float64)
-    check(lib().snpgpu_geno_convert_stats(_ptr(s)))
+    s = _stats("geno_convert", 8)
     return dict(h2d_ms=float(s[0]), copy_ms=float(s[1]), gather_ms=float(s[2]), transpose_ms=float(s[3]), launches=int(s[4]),
                 source_bytes=float(s[5]), d2h_ms=float(s[6]), windows=int(s[7]))
 
@@ -1740,32 +1754,21 @@ def vcf_genotypes(text, cell_begin, line_end, num_allele, ref_index, n_samp, row
     """snpgpu_vcf_genotypes: the sample cells of the lines text[cell_begin[i], line_end[i]) as PACKED2 rows in DEVICE memory at the
     address `rows` ([n_lines][ceil(n_samp / 4)]).  text: bytes / a numpy uint8 array (host memory), or an address (int) with n_bytes
     -- device memory unless text_mem says HOST or HOST_PINNED.  Returns (line_flags int32, line_cells int64)."""
-    keep = None
-    if isinstance(text, int):
-        if n_bytes is None:
-            raise ValueError("a text address needs n_bytes")
-        ptr, mem = ctypes.c_void_p(text), (DEVICE if text_mem is None else int(text_mem))
-    else:
-        keep = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8)
-        ptr, mem = _ptr(keep), (HOST if text_mem is None else int(text_mem))
-        n_bytes = keep.size if n_bytes is None else int(n_bytes)
-        if n_bytes > keep.size:
-            raise ValueError("n_bytes exceeds the text array")
+    ptr, mem, n_bytes, _keep = _text_input(text, n_bytes, text_mem)
     cb, le = np.ascontiguousarray(cell_begin, np.int64).reshape(-1), np.ascontiguousarray(line_end, np.int64).reshape(-1)
     na, ri = np.ascontiguousarray(num_allele, np.int32).reshape(-1), np.ascontiguousarray(ref_index, np.int32).reshape(-1)
     n = cb.size
     if not (le.size == n and na.size == n and ri.size == n):
         raise ValueError("cell_begin, line_end, num_allele and ref_index should have one entry per line")
     flags, cells = np.zeros(n, np.int32), np.zeros(n, np.int64)
-    check(lib().snpgpu_vcf_genotypes(ptr, mem, int(n_bytes), _ptr(cb), _ptr(le), _ptr(na), _ptr(ri), n, int(n_samp), _dptr(rows),
+    check(lib().snpgpu_vcf_genotypes(ptr, mem, n_bytes, _ptr(cb), _ptr(le), _ptr(na), _ptr(ri), n, int(n_samp), _dptr(rows),
                                      _ptr(flags), _ptr(cells), int(device), ctypes.c_void_p(stream) if stream else None))
     return flags, cells
 
 
 def vcf_stats():
     """dict of snpgpu_vcf_stats for the last vcf_genotypes call on this thread"""
-    s = np.zeros(7, np.float64)
-    check(lib().snpgpu_vcf_stats(_ptr(s)))
+    s = _stats("vcf", 7)
     return dict(h2d_ms=float(s[0]), kernel_ms=float(s[1]), launches=int(s[2]), text_bytes=float(s[3]), chunk_bytes=int(s[4]),
                 segment_bytes=int(s[5]), halo_bytes=int(s[6]))
 
@@ -1808,8 +1811,7 @@ def text_render(rows, n_rows, n_cols, fmt, alleles=None, prefixes=None, text=Non
 
 def text_stats():
     """dict of snpgpu_text_stats for the last text_render call on this thread"""
-    s = np.zeros(6, np.float64)
-    check(lib().snpgpu_text_stats(_ptr(s)))
+    s = _stats("text", 6)
     return dict(lengths_ms=float(s[0]), write_ms=float(s[1]), launches=int(s[2]), text_bytes=float(s[3]), segment_bytes=int(s[4]),
                 tile_columns=int(s[5]))
 
@@ -1850,8 +1852,7 @@ def ped_codes(tokens, n_lines, n_snp, ref, rows, device=0, stream=None):
 
 def ped_stats():
     """dict of snpgpu_ped_stats on this thread"""
-    s = np.zeros(8, np.float64)
-    check(lib().snpgpu_ped_stats(_ptr(s)))
+    s = _stats("ped", 8)
     return dict(tokens_ms=float(s[0]), census_ms=float(s[1]), codes_ms=float(s[2]), launches=int(s[3]), text_bytes=float(s[4]),
                 chunk_bytes=int(s[5]), segment_bytes=int(s[6]), halo_bytes=int(s[7]))
 
@@ -1864,23 +1865,13 @@ def gen_genotypes(text, cell_begin, line_end, n_samp, call_threshold, rows, n_by
     memory at the address `rows` ([n_lines][ceil(n_samp / 4)], padding codes 0).  text: bytes / a numpy uint8 array (host memory),
     or an address (int) with n_bytes -- device memory unless text_mem says HOST or HOST_PINNED.  Returns (line_flags int32,
     line_cells int64)."""
-    keep = None
-    if isinstance(text, int):
-        if n_bytes is None:
-            raise ValueError("a text address needs n_bytes")
-        ptr, mem = ctypes.c_void_p(text), (DEVICE if text_mem is None else int(text_mem))
-    else:
-        keep = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8)
-        ptr, mem = _ptr(keep), (HOST if text_mem is None else int(text_mem))
-        n_bytes = keep.size if n_bytes is None else int(n_bytes)
-        if n_bytes > keep.size:
-            raise ValueError("n_bytes exceeds the text array")
+    ptr, mem, n_bytes, _keep = _text_input(text, n_bytes, text_mem)
     cb, le = np.ascontiguousarray(cell_begin, np.int64).reshape(-1), np.ascontiguousarray(line_end, np.int64).reshape(-1)
     n = cb.size
     if le.size != n:
         raise ValueError("cell_begin and line_end should have one entry per line")
     flags, cells = np.zeros(n, np.int32), np.zeros(n, np.int64)
-    check(lib().snpgpu_gen_genotypes(ptr, mem, int(n_bytes), _ptr(cb), _ptr(le), n, int(n_samp), float(call_threshold), _dptr(rows),
+    check(lib().snpgpu_gen_genotypes(ptr, mem, n_bytes, _ptr(cb), _ptr(le), n, int(n_samp), float(call_threshold), _dptr(rows),
                                      _ptr(flags), _ptr(cells), int(device), ctypes.c_void_p(stream) if stream else None))
     return flags, cells
 
@@ -1901,8 +1892,7 @@ def gen_line_host(line, n_samp, call_threshold):
 
 def gen_stats():
     """dict of snpgpu_gen_stats for the last gen_genotypes call on this thread"""
-    s = np.zeros(7, np.float64)
-    check(lib().snpgpu_gen_stats(_ptr(s)))
+    s = _stats("gen", 7)
     return dict(h2d_ms=float(s[0]), kernel_ms=float(s[1]), launches=int(s[2]), text_bytes=float(s[3]), chunk_bytes=int(s[4]),
                 segment_bytes=int(s[5]), halo_bytes=int(s[6]))
 
@@ -1968,8 +1958,7 @@ def geno_merge(parts, rows, n_snp_out=None, device=0, stream=None):
 
 def geno_merge_stats():
     """dict of snpgpu_geno_merge_stats for the last geno_merge call on this thread"""
-    s = np.zeros(5, np.float64)
-    check(lib().snpgpu_geno_merge_stats(_ptr(s)))
+    s = _stats("geno_merge", 5)
     return dict(stage_ms=float(s[0]), splice_ms=float(s[1]), launches=int(s[2]), windows=int(s[3]), bytes_written=float(s[4]))
 
 
@@ -1999,21 +1988,18 @@ def grm_merge(grms, weight, cmd=":method = GCTA", avg_val=None, device=0):
 
 def grm_merge_stats():
     """dict of snpgpu_grm_merge_stats for the last grm_merge (api.snpgdsMergeGRM) on this thread"""
-    s = np.zeros(2, np.float64)
-    check(lib().snpgpu_grm_merge_stats(_ptr(s)))
+    s = _stats("grm_merge", 2)
     return dict(slabs=int(s[0]), launches=int(s[1]))
 
 
 def select_stats():
     """ms of the last select_pairs call on this thread: count pass, scan, write pass (device) and the whole call (host clock)"""
-    s = np.zeros(4, np.float64)
-    check(lib().snpgpu_select_stats(_ptr(s)))
+    s = _stats("select", 4)
     return dict(count_ms=s[0], scan_ms=s[1], write_ms=s[2], call_ms=s[3])
 
 
 def pair_stats():
     """dict of snpgpu_pair_stats for the last pair_tables / pair_score_matrix call on this thread"""
-    s = np.zeros(8, np.float64)
-    check(lib().snpgpu_pair_stats(_ptr(s)))
+    s = _stats("pair", 8)
     return dict(snp_table_ms=float(s[0]), snp_table_launches=int(s[1]), snp_table_bytes=float(s[2]), words_ms=float(s[3]),
                 pair_count_ms=float(s[4]), matrix_ms=float(s[5]), other_launches=int(s[6]), other_bytes=float(s[7]))

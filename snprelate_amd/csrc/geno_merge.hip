@@ -26,11 +26,7 @@ thread_local double g_stats[5] = {0, 0, 0, 0, 0};
 enum { T_STAGE = 0, T_SPLICE = 1 };
 constexpr int64_t MERGE_SAMP_END = int64_t(1) << 30;
 
-size_t merge_stage_bytes()
-{
-    if (const char *e = getenv("SNPGPU_MERGE_STAGE_BYTES")) { if (atoll(e) > 0) return (size_t)atoll(e); }
-    return sel_stage_bytes();
-}
+size_t merge_stage_bytes() { return env_bytes("SNPGPU_MERGE_STAGE_BYTES", sel_stage_bytes()); }
 
 // what one part is for the length of the call
 struct PartPlan {
@@ -92,20 +88,11 @@ int snpgpu_geno_merge(const snpgpu_merge_part *parts, int n_parts, int64_t n_snp
 
     for (double &x : g_stats) x = 0;
     Call c;
-    if (c.open(fn, device, true, stream)) return 1;
-    hipStream_t s = c.st.s;
-    if (stream) {
-        hipDevice_t d = -1;
-        if (hipStreamGetDevice(s, &d) == hipSuccess && (int)d != device) return fail(fn, "the stream belongs to another device");
-    }
-    const auto other_device = [&](const void *p) {
-        hipPointerAttribute_t a;
-        if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-        return a.type == hipMemoryTypeDevice && a.device != device;
-    };
-    if (other_device(rows)) return fail(fn, "a device pointer of another device");
+    std::vector<const void *> dev_ptrs(1, rows);
     for (int i = 0; i < n_parts; i++)
-        if (parts[i].src.mem == SNPGPU_DEVICE && other_device(parts[i].src.bits)) return fail(fn, "a device pointer of another device");
+        if (parts[i].src.mem == SNPGPU_DEVICE) dev_ptrs.push_back(parts[i].src.bits);
+    if (c.open_on(fn, device, stream, dev_ptrs)) return 1;
+    hipStream_t s = c.st.s;
 
     const int64_t rb = (N + 3) / 4;
 

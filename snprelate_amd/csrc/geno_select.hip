@@ -26,11 +26,7 @@ constexpr size_t SEL_STAGE_BYTES = size_t(256) << 20;    // source bytes per sta
 constexpr GenoLimits SEL_GENO = {1, int64_t(1) << 30, int64_t(1) << 31, false, "invalid number of samples (1 ... 2^30 - 1)"};
 constexpr GenoLimits SEL_GENO_MAJOR1 = {1, int64_t(1) << 30, int64_t(1) << 30, false, "invalid number of samples (1 ... 2^30 - 1)"};
 
-size_t sel_stage_bytes()
-{
-    if (const char *e = getenv("SNPGPU_SELECT_STAGE_BYTES")) { if (atoll(e) > 0) return (size_t)atoll(e); }
-    return SEL_STAGE_BYTES;
-}
+size_t sel_stage_bytes() { return env_bytes("SNPGPU_SELECT_STAGE_BYTES", SEL_STAGE_BYTES); }
 
 // All argument errors of a selection: nothing here touches a device.
 int sel_check_args(const char *fn, const snpgpu_geno_src *src, int src_code, const int32_t *samp_index, int64_t n_samp_out,
@@ -172,18 +168,9 @@ int convert(const char *fn, const snpgpu_geno_src *src, int src_code, const int3
 
     for (double &x : g_stats) x = 0;
     Call c;
-    if (c.open(fn, device, true, stream)) return 1;
+    if (c.open_on(fn, device, stream, {src->mem == SNPGPU_DEVICE ? src->bits : nullptr, dst_mem == SNPGPU_DEVICE ? (const void *)dst : nullptr}))
+        return 1;
     hipStream_t s = c.st.s;
-    if (stream) {
-        hipDevice_t d = -1;
-        if (hipStreamGetDevice(s, &d) == hipSuccess && (int)d != device) return fail(fn, "the stream belongs to another device");
-    }
-    for (const void *p : {src->mem == SNPGPU_DEVICE ? src->bits : nullptr, dst_mem == SNPGPU_DEVICE ? (const void *)dst : nullptr}) {
-        hipPointerAttribute_t a;
-        if (!p) continue;
-        if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); continue; }
-        if (a.type == hipMemoryTypeDevice && a.device != device) return fail(fn, "a device pointer of another device");
-    }
 
     const int64_t rb = (n_col_out + 3) / 4;
     HostOut od;

@@ -15,6 +15,13 @@ namespace snpgpu {
 
 inline int fail(const char *fn, const std::string &msg) { set_error(std::string(fn) + ": " + msg); return 1; }
 
+// a size from the environment (staging bytes, a forced block size): the variable's value when it is positive, else `fallback`
+inline size_t env_bytes(const char *name, size_t fallback)
+{
+    const char *e = getenv(name);
+    return e && atoll(e) > 0 ? (size_t)atoll(e) : fallback;
+}
+
 // ---- argument checks (no HIP call) -------------------------------------------------------------------------------------------
 // The ranges a call accepts: n_samp in [samp_min, samp_end), n_snp in [1, snp_end); samp_msg states the sample range.
 struct GenoLimits {
@@ -196,6 +203,23 @@ struct Call {
         log.on = timed;
         return st.open(fn, device, user_stream);
     }
+    // open() with timing, then the checks that need the runtime: the caller's stream and every pointer of dev_ptrs that is
+    // device memory (NULL and what the runtime does not know are skipped) belong to `device`
+    int open_on(const char *fn, int device, void *user_stream, const std::vector<const void *> &dev_ptrs)
+    {
+        if (open(fn, device, true, user_stream)) return 1;
+        if (user_stream) {
+            hipDevice_t d = -1;
+            if (hipStreamGetDevice(st.s, &d) == hipSuccess && (int)d != device) return fail(fn, "the stream belongs to another device");
+        }
+        for (const void *p : dev_ptrs) {
+            hipPointerAttribute_t a;
+            if (!p) continue;
+            if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); continue; }
+            if (a.type == hipMemoryTypeDevice && a.device != device) return fail(fn, "a device pointer of another device");
+        }
+        return 0;
+    }
 };
 
 // ---- genotype rows in SNP blocks ---------------------------------------------------------------------------------------------
@@ -217,7 +241,7 @@ struct RowBlocks {
         rb_in = repack ? N : (N + 3) / 4;
         rb = repack ? (N + 255) / 256 * 64 : rb_in;
         B = (mem == SNPGPU_DEVICE && !repack) ? (n_snp + 15) / 16 * 16 : (int64_t)(stage_bytes / (size_t)rb_in);
-        if (const char *e = getenv(env_name)) { if (atoll(e) > 0) B = atoll(e); }
+        B = (int64_t)env_bytes(env_name, (size_t)B);
         B = std::min(B, max_block_snps);
         B = std::max<int64_t>(16, B / 16 * 16);
         B = std::min(B, (n_snp + 15) / 16 * 16);

@@ -5,8 +5,8 @@
 // codes over every window again.  All argument errors are found before any device is touched.
 #include <vector>
 
-#include "host_util.h"
 #include "ped.h"
+#include "text_host.h"
 
 using namespace snpgpu;
 
@@ -20,23 +20,6 @@ int check_dims_ped(const char *fn, int64_t n_lines, int64_t n_snp)
 {
     if (n_lines < 1 || n_lines >= (int64_t(1) << 31)) return fail(fn, "invalid number of lines (1 ... 2^31 - 1)");
     if (n_snp < 1 || n_snp >= (int64_t(1) << 30)) return fail(fn, "invalid number of SNPs (1 ... 2^30 - 1)");
-    return 0;
-}
-
-// the stream of the call on `device`, after the checks that need the runtime
-int open_call(Call &c, const char *fn, int device, void *stream, std::initializer_list<const void *> dev_ptrs)
-{
-    if (c.open(fn, device, true, stream)) return 1;
-    if (stream) {
-        hipDevice_t d = -1;
-        if (hipStreamGetDevice(c.st.s, &d) == hipSuccess && (int)d != device) return fail(fn, "the stream belongs to another device");
-    }
-    for (const void *p : dev_ptrs) {
-        hipPointerAttribute_t a;
-        if (!p) continue;
-        if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); continue; }
-        if (a.type == hipMemoryTypeDevice && a.device != device) return fail(fn, "a device pointer of another device");
-    }
     return 0;
 }
 
@@ -64,17 +47,15 @@ int snpgpu_ped_tokens(const void *text, int64_t n_bytes, const int64_t *cell_beg
     }
 
     Call c;
-    if (open_call(c, fn, device, stream, {text, (const void *)tokens})) return 1;
+    if (c.open_on(fn, device, stream, {text, (const void *)tokens})) return 1;
     hipStream_t s = c.st.s;
     int rc = 0;
     DevBuf *dlines = c.bufs.get(sizeof(PedLine) * (size_t)n_lines, rc);
     DevBuf *dflags = c.bufs.get(sizeof(int32_t) * (size_t)n_lines, rc), *dcounts = c.bufs.get(sizeof(int64_t) * (size_t)n_lines, rc);
     if (rc) return 1;
     SNPGPU_HIP_CHECK(hipMemcpyAsync(dlines->p, lines.data(), sizeof(PedLine) * (size_t)n_lines, hipMemcpyHostToDevice, s));
-    const int64_t shift = (int64_t)((uintptr_t)text & 15);
-    const TextView t = {(const uint32_t *)((const uint8_t *)text - shift), shift >> 2, (shift + n_bytes + 3) >> 2, shift};
     if (c.log.begin(0, s) ||
-        launch_ped_tokens(s, t, (const PedLine *)dlines->p, n_lines, 2 * n_snp, (uint8_t *)tokens, (int32_t *)dflags->p, (int64_t *)dcounts->p) ||
+        launch_ped_tokens(s, text_view_in_place(text, n_bytes), (const PedLine *)dlines->p, n_lines, 2 * n_snp, (uint8_t *)tokens, (int32_t *)dflags->p, (int64_t *)dcounts->p) ||
         c.log.end(s))
         return 1;
     SNPGPU_HIP_CHECK(hipMemcpyAsync(line_flags, dflags->p, sizeof(int32_t) * (size_t)n_lines, hipMemcpyDeviceToHost, s));
@@ -93,7 +74,7 @@ int snpgpu_ped_census(const void *tokens, const int32_t *line_flags, int64_t n_l
     if (!table) return fail(fn, "NULL argument: table is NULL");
     if (check_dims_ped(fn, n_lines, n_snp)) return 1;
     Call c;
-    if (open_call(c, fn, device, stream, {tokens, (const void *)table})) return 1;
+    if (c.open_on(fn, device, stream, {tokens, (const void *)table})) return 1;
     hipStream_t s = c.st.s;
     int rc = 0;
     DevBuf *dflags = c.bufs.get(sizeof(int32_t) * (size_t)n_lines, rc);
@@ -115,7 +96,7 @@ int snpgpu_ped_codes(const void *tokens, int64_t n_lines, int64_t n_snp, const u
     if (!rows) return fail(fn, "NULL argument: rows is NULL");
     if (check_dims_ped(fn, n_lines, n_snp)) return 1;
     Call c;
-    if (open_call(c, fn, device, stream, {tokens, (const void *)rows})) return 1;
+    if (c.open_on(fn, device, stream, {tokens, (const void *)rows})) return 1;
     hipStream_t s = c.st.s;
     int rc = 0;
     DevBuf *dref = c.bufs.get((size_t)n_snp, rc);

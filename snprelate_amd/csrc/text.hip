@@ -61,18 +61,8 @@ int snpgpu_text_render(const void *rows, int64_t n_rows, int64_t n_cols, int for
     }
 
     Call c;
-    if (c.open(fn, device, true, stream)) return 1;
+    if (c.open_on(fn, device, stream, {rows, (const void *)text})) return 1;
     hipStream_t s = c.st.s;
-    if (stream) {
-        hipDevice_t d = -1;
-        if (hipStreamGetDevice(s, &d) == hipSuccess && (int)d != device) return fail(fn, "the stream belongs to another device");
-    }
-    for (const void *p : {rows, (const void *)text}) {
-        hipPointerAttribute_t a;
-        if (!p) continue;
-        if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); continue; }
-        if (a.type == hipMemoryTypeDevice && a.device != device) return fail(fn, "a device pointer of another device");
-    }
 
     // the caller's pools on the device, offsets relative to the copies
     int rc = 0;

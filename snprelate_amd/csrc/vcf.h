@@ -1,16 +1,11 @@
-// What vcf.hip (host layer) and kernels_vcf.hip share: the device view of VCF text, a line's description and the chunk geometry.
+// What vcf.hip (host layer) and kernels_vcf.hip share: a line's description, the flags and the code words of a chunk.  The chunk
+// geometry and the view of the text are text_chunk.h's.
 #pragma once
 #include "text_chunk.h"
 
 namespace snpgpu {
 
-// the chunk geometry and the view of the text are the shared skeleton's (text_chunk.h)
-constexpr int VCF_THREADS = CHUNK_THREADS;
-constexpr int VCF_SEG = CHUNK_SEG;
-constexpr int VCF_CHUNK = CHUNK_BYTES;
-constexpr int VCF_HALO = CHUNK_HALO;                      // a GT that crosses a chunk's end is read from LDS
-constexpr int VCF_CODE_WORDS = (VCF_CHUNK + 1 + 3 + 15) / 16 + 1;     // dwords of 16 codes: a chunk's cells and the carried byte
-using VcfText = TextView;
+constexpr int VCF_CODE_WORDS = (CHUNK_BYTES + 1 + 3 + 15) / 16 + 1;   // dwords of 16 codes: a chunk's cells and the carried byte
 
 // one line: [begin, end) from its first sample cell to the end of its last one, in the caller's offsets
 struct VcfLine { int64_t begin, end; int32_t num_allele, ref_index; };
@@ -18,7 +13,7 @@ struct VcfLine { int64_t begin, end; int32_t num_allele, ref_index; };
 enum { VCF_FLAG_GRAMMAR = 1, VCF_FLAG_RANGE = 2, VCF_FLAG_DIGITS = 4, VCF_FLAG_CELLS = 8 };
 
 // rows: [n_lines][ceil(n_samp / 4)]; flags, cells: [n_lines] (all device memory)
-int launch_vcf_parse(hipStream_t st, const VcfText &t, const VcfLine *lines, int64_t n_lines, int64_t n_samp, uint8_t *rows,
+int launch_vcf_parse(hipStream_t st, const TextView &t, const VcfLine *lines, int64_t n_lines, int64_t n_samp, uint8_t *rows,
                      int32_t *flags, int64_t *cells);
 
 }  // namespace snpgpu

@@ -5,7 +5,7 @@ The division of work follows the text.  A .gen line is five short columns and th
 of a line at 100 000 samples.  So
 
 * the host reads the sample file (:func:`read_sample`), reads a .gen file (plain or ``.gz``) in chunks of whole lines into
-  page-locked buffers, finds the lines and reads the five leading columns of each with ``vcf._Cells`` -- the restatement of
+  page-locked buffers, finds the lines and reads the five leading columns of each with ``textio.Cells`` -- the restatement of
   ``CReadLine::GetCell`` (src/ConvToGDS.cpp:123-179) splitting by space and tab -- and ``vcf.get_int32`` for the position;
 * the device reads the numbers of the rest of every line, rounds each once to single precision as ``strtof`` does and calls
   every sample through the tree of gnrParseGEN (src/ConvToGDS.cpp:1134-1145): ``snpgpu_gen_genotypes``, the chunk's own bytes
@@ -17,13 +17,15 @@ of a line at 100 000 samples.  So
 
 There is no CPU fallback for the calls: without a device :meth:`GenReader.blocks` fails with ``SnpGpuError``.
 """
+import functools
+
 import numpy as np
 
+from . import textio
 from .gds import pack_2bit_rows
-from .ped import _c_string, last_cell, stage_bytes
-from .vcf import VcfFormatError, _Cells, get_int32, open_binary
+from .textio import Cells, VcfFormatError, c_string, last_cell, open_binary, stage_bytes
+from .vcf import get_int32
 
-_HEAD = 1024           # bytes of a line looked at for its five leading columns before the whole line is taken
 VERSIONS = (">=2.0", "<=1.1.5")
 
 
@@ -59,7 +61,7 @@ def host_head(line):
     the offset of the sixth, as gnrParseGEN reads them (src/ConvToGDS.cpp:1094-1110); VcfFormatError carries the column and what
     the reference's `cell` variable holds there: the alleles are read into variables of their own, so from column 4 to the first
     probability it is still the position."""
-    rl = _Cells(line, space=True)
+    rl = Cells(line, space=True)
     snp, rs, pos = rl.get(False), rl.get(False), rl.get(False)
     try:
         position = get_int32(pos)
@@ -76,7 +78,7 @@ def error_cell(line, column, message, tail=b""):
     """what the reference's `cell` variable holds when reading cell `column` (1-based, of the whole line) fails with `message`:
     the cell itself for a conversion, else the last cell read into it -- the position up to column 6, the last cell of the line
     in front (`tail`) at column 1"""
-    rl = _Cells(_c_string(line), space=True)
+    rl = Cells(c_string(line), space=True)
     cells = []
     try:
         for _ in range(column):
@@ -118,37 +120,6 @@ class GenReader:
     def _raise(self, message, column, cell, file_line):
         raise ValueError("%s\nFILE: %s\nLINE: %d, COLUMN: %d, %s\n" % (message, self.path, file_line, column, cell.decode("latin1")))
 
-    @staticmethod
-    def _lines(buf, n, final):
-        """the whole lines of buf[:n]: (begin, end) arrays without the '\\n' (a '\\r' in front of it stays: the reference's isspace
-        skips it), and the bytes consumed"""
-        nl = np.flatnonzero(buf[:n] == 10)
-        begin = np.concatenate(([0], nl + 1)).astype(np.int64)
-        end = nl.astype(np.int64)
-        used = int(nl[-1]) + 1 if len(nl) else 0
-        if final and used < n:
-            end = np.concatenate((end, [n]))
-            used = n
-        else:
-            begin = begin[:len(end)]
-        return begin, end, used
-
-    @staticmethod
-    def _head(buf, b, e):
-        """the leading cells of the line buf[b:e] and the offset of the sixth: from the line's first _HEAD bytes when they hold
-        them, else from the whole line"""
-        head = bytes(buf[b:min(e, b + _HEAD)])
-        if e - b > _HEAD or b"\0" in head:
-            if b"\0" not in head:
-                try:
-                    cells, p = host_head(head)
-                    if p < len(head):
-                        return cells, p
-                except VcfFormatError:
-                    pass
-            head = _c_string(bytes(buf[b:e]))
-        return host_head(head)
-
     def _finish(self):
         d = self._nodes
         text = lambda v: np.array(v, dtype=str) if v else np.empty(0, dtype="<U1")          # noqa: E731
@@ -172,55 +143,34 @@ class GenReader:
         size, N, rb = self.chunk_bytes, self.n_samp, (self.n_samp + 3) // 4
         pinned = [_lib.PinnedBuffer((size,)) for _ in range(2)]
         dev = [None, None]
-        turn, blk, left, file_line, done, nodes = 0, 0, 0, 0, 0, self._nodes
+        blk, file_line, done, nodes = 0, 0, 0, self._nodes
+        lines = functools.partial(textio.split_lines, strip_cr=False)           # a '\r' stays: the reference's isspace skips it
         try:
             with open_binary(self.path) as f:
-                while True:
-                    buf = pinned[turn].array
-                    n = left
-                    while n < size:
-                        got = f.readinto(memoryview(buf)[n:size])
-                        if not got:
-                            break
-                        n += got
-                    final = n < size
-                    if n == 0:
-                        break
-                    begin, end, used = self._lines(buf, n, final)
-                    if used == 0:
-                        raise ValueError("'%s': a line longer than the %d bytes of a chunk (SNPGPU_TEXT_STAGE_BYTES)" % (self.path, size))
+                for buf, n, _final, begin, end in textio.chunks(f, [p.array for p in pinned], lines, self.path, "SNPGPU_TEXT_STAGE_BYTES"):
+                    ptr = pinned[0].ptr if buf is pinned[0].array else pinned[1].ptr
                     # ---- the leading columns; a line that fails there ends the chunk, the lines in front of it are still called --------
-                    cell_begin, pending = np.empty(len(begin), np.int64), None
-                    for i in range(len(begin)):
-                        b, e = int(begin[i]), int(end[i])
-                        try:
-                            cells, p = self._head(buf, b, e)
-                        except VcfFormatError as err:
-                            cell = err.cell
-                            if err.column == 1:            # no cell of this line was read: `cell` is the line before's last one
-                                cell = last_cell(bytes(buf[int(begin[i - 1]):int(end[i - 1])])) if i else self._tail
-                            pending = (err.message, err.column, cell, file_line + i + 1)
-                            begin, end, cell_begin = begin[:i], end[:i], cell_begin[:i]
-                            break
-                        cell_begin[i] = b + p
+                    cell_begin, heads, err = textio.leading_columns(buf, begin, end, host_head, self._tail)
+                    n_lines = len(cell_begin)
+                    for cells in heads:
                         nodes["snp"].append(cells[0].decode("latin1"))
                         nodes["rs"].append(cells[1].decode("latin1"))
                         nodes["pos"].append(cells[2])
                         nodes["allele"].append((cells[3] + b"/" + cells[4]).decode("latin1"))
                     # ---- the probabilities: blocks of lines on the device ------------------------------------------------------------------
-                    for lo in range(0, len(begin), block_snps):
-                        hi = min(lo + block_snps, len(begin))
+                    for lo in range(0, n_lines, block_snps):
+                        hi = min(lo + block_snps, n_lines)
                         m = hi - lo
                         if dev[blk & 1] is None or dev[blk & 1].shape[0] < m:
                             dev[blk & 1] = torch.empty((m, rb), dtype=torch.uint8, device="cuda:%d" % int(device))
                         rows = dev[blk & 1][:m]
                         blk += 1
-                        flags, _cells = _lib.gen_genotypes(pinned[turn].ptr, cell_begin[lo:hi], end[lo:hi], N, self.call_threshold,
+                        flags, _cells = _lib.gen_genotypes(ptr, cell_begin[lo:hi], end[lo:hi], N, self.call_threshold,
                                                            int(rows.data_ptr()), n_bytes=n, text_mem=_lib.HOST_PINNED, device=device)
                         for i in np.flatnonzero(flags):
                             k = lo + int(i)
                             b, e = int(begin[k]), int(end[k])
-                            codes, column, message = _lib.gen_line_host(_c_string(bytes(buf[int(cell_begin[k]):e])), N, self.call_threshold)
+                            codes, column, message = _lib.gen_line_host(c_string(bytes(buf[int(cell_begin[k]):e])), N, self.call_threshold)
                             if codes is None:
                                 line = bytes(buf[b:e])
                                 tail = last_cell(bytes(buf[int(begin[k - 1]):int(end[k - 1])])) if k else self._tail
@@ -232,17 +182,11 @@ class GenReader:
                         self.n_snp = done + m
                         yield done, m, rows
                         done += m
-                    if pending is not None:
-                        self._raise(*pending)
+                    if err is not None:
+                        self._raise(err.message, err.column, err.cell, file_line + n_lines + 1)
                     self.windows += 1
-                    file_line += len(begin)
+                    file_line += n_lines
                     self._tail = last_cell(bytes(buf[int(begin[-1]):int(end[-1])]))
-                    left = n - used
-                    if left:
-                        pinned[1 - turn].array[:left] = buf[used:n]
-                    turn = 1 - turn
-                    if final:
-                        break
         finally:
             self._done = True
             for p in pinned:

@@ -5,7 +5,7 @@ The division of work follows the text.  A .ped line is six short columns and the
 
 * the host reads the MAP file and orders its SNPs as R/Conversion.R:164-170 does (:func:`read_map`), reads the .ped file (plain or
   ``.gz``) in chunks of whole lines into page-locked buffers, finds the lines and reads the six leading columns of each with
-  ``vcf._Cells`` -- the restatement of ``CReadLine::GetCell`` (src/ConvToGDS.cpp:123-179) splitting by space and tab;
+  ``textio.Cells`` -- the restatement of ``CReadLine::GetCell`` (src/ConvToGDS.cpp:123-179) splitting by space and tab;
 * the device turns the rest of every line into allele tokens (``snpgpu_ped_tokens``), counts them per SNP
   (``snpgpu_ped_census``) and, once the host has picked every SNP's reference allele as src/ConvToGDS.cpp:1238-1270 does, codes
   them into 2-bit sample rows (``snpgpu_ped_codes``) -- two sweeps over the text, as the reference reads the file twice; a file
@@ -22,18 +22,13 @@ R's ``order`` collates by locale.  And ``snp_allele`` is permuted by the MAP ord
 gnrParsePED appends it in file order (src/ConvToGDS.cpp:1272-1276 against :1353-1355), so that with an unsorted MAP the
 reference's alleles belong to other SNPs; for a sorted MAP nothing differs.
 """
-import os
+import functools
 
 import numpy as np
 
+from . import textio
 from .gds import pack_2bit_rows
-from .vcf import VcfFormatError, _Cells, open_binary
-
-_HEAD = 1024           # bytes of a line looked at for its six leading columns before the whole line is taken
-
-
-def stage_bytes():
-    return max(1, int(os.environ.get("SNPGPU_TEXT_STAGE_BYTES", 256 << 20)))
+from .textio import Cells, VcfFormatError, c_string, last_cell, open_binary, stage_bytes
 
 
 # ---- the MAP file ------------------------------------------------------------------------------------------------------------------
@@ -87,32 +82,19 @@ def read_map(map_fn):
 
 
 # ---- a line on the host --------------------------------------------------------------------------------------------------------------
-def _c_string(line):
-    z = line.find(b"\0")
-    return line if z < 0 else line[:z]
-
-
 def host_head(line):
     """the six leading cells of a .ped line and the offset of the seventh, as GetCell reads them"""
-    rl = _Cells(line, space=True)
+    rl = Cells(line, space=True)
     return [rl.get(False) for _ in range(6)], rl.p
 
 
 def host_tokens(line, n_snp):
     """the 2 n_snp allele cells of a whole .ped line (bytes without the line end) as the reference reads them, or VcfFormatError
     with the column and cell it would report"""
-    rl = _Cells(_c_string(line), space=True)
+    rl = Cells(c_string(line), space=True)
     for _ in range(6):
         rl.get(False)
     return [rl.get(k >= 2 * n_snp - 1) for k in range(2 * n_snp)]
-
-
-def last_cell(line):
-    """the last cell of a line that was read without an error: what the reference's `cell` variable still holds when the first
-    cell of the next line fails"""
-    s = _c_string(line).rstrip(b" ")
-    c = s[max(s.rfind(b"\t"), s.rfind(b" ")) + 1:]
-    return c[1:-1] if len(c) > 1 and c[0] == c[-1] and c[0] in b"\"'" else c
 
 
 def pick_alleles(counts):
@@ -143,36 +125,6 @@ class PedReader:
     def _raise(self, e, file_line):
         raise ValueError("%s\nFILE: %s\nLINE: %d, COLUMN: %d, %s\n" % (e.message, self.path, file_line, e.column, e.cell.decode("latin1")))
 
-    def _lines(self, buf, n, final):
-        """the whole lines of buf[:n]: (begin, end) arrays without the line ends, and the bytes consumed"""
-        nl = np.flatnonzero(buf[:n] == 10)
-        begin = np.concatenate(([0], nl + 1)).astype(np.int64)
-        end = nl.astype(np.int64)
-        used = int(nl[-1]) + 1 if len(nl) else 0
-        if final and used < n:
-            end = np.concatenate((end, [n]))
-            used = n
-        else:
-            begin = begin[:len(end)]
-        cr = (end > begin) & (buf[np.maximum(end - 1, 0)] == 13)
-        return begin, end - cr, used
-
-    @staticmethod
-    def _head(buf, b, e):
-        """the six leading cells of the line buf[b:e] and the offset of the seventh: from the line's first _HEAD bytes when they
-        hold them, else from the whole line"""
-        head = bytes(buf[b:min(e, b + _HEAD)])
-        if e - b > _HEAD or b"\0" in head:
-            if b"\0" not in head:
-                try:
-                    cells, p = host_head(head)
-                    if p < len(head):
-                        return cells, p
-                except VcfFormatError:
-                    pass
-            head = _c_string(bytes(buf[b:e]))
-        return host_head(head)
-
     def _chunks(self, heads):
         """(device text, n_bytes, cell_begin, line_end, first file line, pending error) per chunk of whole lines; with `heads` the
         six leading cells of every line are appended to it.  A line whose leading columns fail ends its chunk: the lines in
@@ -182,51 +134,23 @@ class PedReader:
         size = self.chunk_bytes
         pinned = [_lib.PinnedBuffer((size,)) for _ in range(2)]
         dev = torch.empty(size, dtype=torch.uint8, device="cuda:%d" % self.device)
-        turn, left, file_line = 0, 0, 0
+        lines = functools.partial(textio.split_lines, strip_cr=True)
+        file_line = 0
         try:
             with open_binary(self.path) as f:
-                while True:
-                    buf = pinned[turn].array
-                    n = left
-                    while n < size:
-                        got = f.readinto(memoryview(buf)[n:size])
-                        if not got:
-                            break
-                        n += got
-                    final = n < size
-                    if n == 0:
-                        break
-                    begin, end, used = self._lines(buf, n, final)
-                    if used == 0:
-                        raise ValueError("'%s': a line longer than the %d bytes of a chunk (SNPGPU_TEXT_STAGE_BYTES)" % (self.path, size))
-                    cell_begin, pending = np.empty(len(begin), np.int64), None
-                    for i in range(len(begin)):
-                        b, e = int(begin[i]), int(end[i])
-                        try:
-                            cells, p = self._head(buf, b, e)
-                        except VcfFormatError as err:
-                            if err.column == 1:            # no cell of this line was read: `cell` is the line before's last one
-                                err.cell = last_cell(bytes(buf[int(begin[i - 1]):int(end[i - 1])])) if i else self._tail
-                            pending = (err, file_line + i + 1)
-                            begin, end, cell_begin = begin[:i], end[:i], cell_begin[:i]
-                            break
-                        cell_begin[i] = b + p
-                        if heads is not None:
-                            heads.append(cells)
-                    if len(begin):
+                for buf, n, _final, begin, end in textio.chunks(f, [p.array for p in pinned], lines, self.path, "SNPGPU_TEXT_STAGE_BYTES"):
+                    cell_begin, cells, err = textio.leading_columns(buf, begin, end, host_head, self._tail)
+                    m = len(cell_begin)
+                    if heads is not None:
+                        heads.extend(cells)
+                    if m:
                         dev[:n].copy_(torch.from_numpy(buf[:n]))
                         torch.cuda.synchronize(self.device)
-                        yield dev, n, cell_begin, end, file_line, buf
-                    if pending is not None:
-                        self._raise(*pending)
-                    file_line += len(begin)
+                        yield dev, n, cell_begin, end[:m], file_line, buf
+                    if err is not None:
+                        self._raise(err, file_line + m + 1)
+                    file_line += m
                     self._tail = last_cell(bytes(buf[int(begin[-1]):int(end[-1])]))
-                    left = n - used
-                    if left:
-                        pinned[1 - turn].array[:left] = buf[used:n]
-                    turn = 1 - turn
-                    if final:
-                        break
         finally:
             for p in pinned:
                 p.free()

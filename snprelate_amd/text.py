@@ -6,15 +6,10 @@ windows of whole lines: as many as fit SNPGPU_TEXT_STAGE_BYTES (default 256 MiB)
 least one.  A window is: select (and for .ped transpose) its rows with snpgpu_geno_select / snpgpu_geno_convert, render, copy to
 page-locked memory, append.  There is no CPU fallback: without a device the calls fail with ``SnpGpuError``.
 """
-import os
-
 import numpy as np
 
 from . import _lib
-
-
-def stage_bytes():
-    return max(1, int(os.environ.get("SNPGPU_TEXT_STAGE_BYTES", 256 << 20)))
+from .textio import stage_bytes
 
 
 def split_alleles(allele):

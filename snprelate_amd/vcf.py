@@ -14,26 +14,19 @@ the cells are 0.4 to 1.5 MB of a line and the fixed columns a few dozen bytes.  
 
 There is no CPU fallback for the cells: without a device :meth:`VcfReader.blocks` fails with ``SnpGpuError``.
 """
-import gzip
 import os
 import re
 
 import numpy as np
 
 from .gds import pack_2bit_rows
+from . import textio
+from .textio import Cells, VcfFormatError, open_binary
 
 NA_INTEGER = -2147483648
 _SPACE = b" \t\n\v\f\r"
 _FLOAT = re.compile(rb"[+-]?(?:(?:\d+\.?\d*|\.\d+)(?:[eE][+-]?\d+)?|inf(?:inity)?|nan)", re.I)
 _BIALLELIC = frozenset(b"ACGTacgt"[i:i + 1] for i in range(8))
-
-
-class VcfFormatError(ValueError):
-    """an error of the reference's parser: .message is its text, .column / .cell what COREARRAY_TRY_END appends"""
-
-    def __init__(self, message, column=0, cell=b""):
-        ValueError.__init__(self, message)
-        self.message, self.column, self.cell = message, int(column), cell
 
 
 def _short(p):
@@ -95,49 +88,6 @@ def get_float(txt):
         return np.float32(float(m.group().decode("latin1")))
 
 
-class _Cells:
-    """CReadLine::GetCell over one line (src/ConvToGDS.cpp:123-179): the column count, the end-of-line checks and the quotes it
-    strips.  Split by tabs as gnrParseVCF4 sets it, or with `space` by tab and space as gnrParsePED does (SplitBySpaceTab): one
-    tab is one separator, a run of spaces is one separator, and spaces behind the last column are skipped.  `cell` is what the
-    reference's `cell` variable holds when an error is formatted."""
-
-    def __init__(self, line, pos=0, column=0, cell=b"", space=False):
-        self.s, self.p, self.column, self.cell, self.space = line, pos, column, cell, space
-
-    def get(self, last):
-        s, b = self.s, self.p
-        e = s.find(b"\t", b)
-        if self.space:
-            e2 = s.find(b" ", b, e if e >= 0 else len(s))
-            e = e2 if e2 >= 0 else e
-        at_end = e < 0
-        if at_end:
-            e = len(s)
-        self.column += 1
-        if b == e and at_end:
-            raise VcfFormatError("fewer columns than what expected.", self.column, self.cell)
-        p = e
-        if last:
-            if self.space:
-                while p < len(s) and s[p] == 0x20:
-                    p += 1
-            if p < len(s):
-                raise VcfFormatError("more columns than what expected.", self.column, self.cell)
-            self.p = p
-        elif at_end:
-            self.p = e
-        elif s[e] == 0x09 or not self.space:
-            self.p = e + 1
-        else:
-            while p < len(s) and s[p] == 0x20:
-                p += 1
-            self.p = p
-        if e > b + 1 and ((s[b] == 0x22 and s[e - 1] == 0x22) or (s[b] == 0x27 and s[e - 1] == 0x27)):
-            b, e = b + 1, e - 1
-        self.cell = s[b:e]
-        return self.cell
-
-
 def gt_code(cell, num_allele, ref_index):
     """the dosage code of one sample cell (src/ConvToGDS.cpp:917-986): 0 / 1 / 2 copies of allele ref_index, 3 = missing"""
     c = cell.find(b":")
@@ -172,7 +122,7 @@ def gt_code(cell, num_allele, ref_index):
 def host_cells(line, n_samp, num_allele, ref_index, pos=0, column=9, cell=b""):
     """the n_samp sample cells of `line` (bytes without the line end) from offset `pos`, as the reference reads them: uint8 codes,
     or VcfFormatError with the column and cell the reference would report"""
-    rl = _Cells(line, pos, column, cell)
+    rl = Cells(line, pos, column, cell)
     out = np.empty(n_samp, np.uint8)
     for j in range(n_samp):
         c = rl.get(j >= n_samp - 1)
@@ -196,10 +146,6 @@ def allele_text(ref, alt, want):
         rest = alleles[:i] + alleles[i + 1:]
         return want + "/" + ",".join(rest), i
     return want + "/" + ref + "," + alt, -1
-
-
-def open_binary(fn):
-    return gzip.open(fn, "rb") if str(fn).lower().endswith(".gz") else open(fn, "rb")
 
 
 def read_header(f):
@@ -290,7 +236,7 @@ class VcfReader:
                     # the reference still walks the line's cells: a wrong number of them is an error on a skipped line too
                     n_tab = int(np.count_nonzero(buf[int(c[9]):e] == 9))
                     if n_tab + 1 != n_samp or int(c[9]) == e or buf[e - 1] == 9:
-                        rl = _Cells(bytes(buf[int(c[0]):e]), int(c[5]) - int(c[0]), 5, f[4])
+                        rl = Cells(bytes(buf[int(c[0]):e]), int(c[5]) - int(c[0]), 5, f[4])
                         for k in range(n_samp + 4, 0, -1):
                             rl.get(k <= 1)
                     continue
@@ -341,30 +287,9 @@ class VcfReader:
             raise ValueError("a VcfReader goes through its file once")
         if buffers is None:
             buffers = [np.empty(self.chunk_bytes, np.uint8) for _ in range(2)]
-        size = min(len(b) for b in buffers)
-        turn, left = 0, 0                                 # `left` bytes of a cut line stand at the head of buffers[turn]
         try:
-            while True:
-                buf = buffers[turn]
-                n = left
-                while n < size:
-                    got = self._f.readinto(memoryview(buf)[n:size])
-                    if not got:
-                        break
-                    n += got
-                final = n < size
-                if n == 0:
-                    break
-                kept, used = self._scan(buf, n, final)
-                if used == 0 and not final:
-                    raise ValueError("'%s': a line longer than the %d bytes of a chunk (SNPGPU_VCF_CHUNK_BYTES)" % (self.path, size))
+            for buf, n, _final, kept in textio.chunks(self._f, buffers, self._scan, self.path, "SNPGPU_VCF_CHUNK_BYTES"):
                 yield buf, n, kept
-                left = n - used
-                if left:
-                    buffers[1 - turn][:left] = buf[used:n]
-                turn = 1 - turn
-                if final:
-                    break
         finally:
             self._done = True
             self.close()
