@@ -184,8 +184,9 @@ int snpgpu_indiv_beta(snpgpu_ctx *ctx, int mode, double *out, double *avg_val, i
  * replaces CalcEigen / LAPACK dspevx (src/genPCA.cpp:1262-1346).
  * eigval: HOST double [k] descending, whatever `mem` says (as snpgpu_panels_topk_eigen); eigvec: double [n_samp][k]
  * column-major (n x k) in `mem`.
- * n <= SNPGPU_EIG_DENSE_MAX (default 2048): hipSOLVER's dense syevdx on the finalised matrix, index range 1..k as the
- * reference asks LAPACK; larger n: the block-Krylov solver below on the resident panel (no n x n copy). */
+ * n <= SNPGPU_EIG_DENSE_MAX (default 2048): hipSOLVER's dense syevd on the finalised matrix, the k largest pairs of it
+ * (the reference asks LAPACK for the index range 1..k; syevdx with that range fails on multiple eigenvalues);
+ * larger n: the block-Krylov solver below on the resident panel (no n x n copy). */
 int snpgpu_pca_eigen(snpgpu_ctx *ctx, int k, double *eigval, double *eigvec, int mem);
 
 /* Building block of the distributed top-k eigen solver (snprelate_amd/eigen.py) that replaces

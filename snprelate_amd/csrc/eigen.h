@@ -51,7 +51,7 @@ struct SolverHandle {      // owns a hipSOLVER handle; declare it AFTER the buff
 };
 
 // ---- the dense route (eigen_dense.hip) ----
-// top-k eigenpairs of a dense symmetric matrix A (device, n x n, overwritten) by hipSOLVER's syevdx.  eigval: k values (descending,
+// top-k eigenpairs of a dense symmetric matrix A (device, n x n, overwritten) by hipSOLVER's syevd.  eigval: k values (descending,
 // host), eigvec: n x k column-major in `mem`.  Returns 2 where the solver declines the size (the caller takes the Krylov solver).
 int dense_topk(int device, hipStream_t stream, double *A, int64_t n, int k, double *eigval, double *eigvec, int mem);
 bool dense_route(int64_t n, int k);         // whether n samples / k eigenpairs take the dense solver

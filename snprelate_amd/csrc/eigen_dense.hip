@@ -1,4 +1,4 @@
-// The dense route to the top-k eigenpairs of a context's matrix (hipSOLVER syevdx on an n x n copy), the choice between it and the
+// The dense route to the top-k eigenpairs of a context's matrix (hipSOLVER syevd on an n x n copy), the choice between it and the
 // block-Krylov solver of eigen.hip, and snpgpu_pca_eigen, the level-1 call behind gnrPCA.
 #include <cmath>
 #include <cstring>
@@ -18,9 +18,9 @@ __global__ void negate_kernel(double *a, size_t n)
 }
 
 // samples up to which the dense solver is used (the reference's own route: exact to LAPACK's tolerance, O(n^3)); beyond it
-// the block-Krylov solver works on the resident panel, without an n x n copy.  hipSOLVER's syevdx takes 4 s at n = 4096, 21 s at
-// 8192, 124 s at 16 384 and 210 s at 20 000 on an MI355X (tools/scratch measurement, round 3) against seconds for the Krylov
-// solver: the dense route is kept for small n only.
+// the block-Krylov solver works on the resident panel, without an n x n copy.  The threshold dates from syevdx (4 s at n = 4096,
+// 21 s at 8192, 124 s at 16 384 and 210 s at 20 000 on an MI355X, round 3); the syevd that replaced it takes 0.014 s at n = 540
+// and 0.056 s at 2048 (syevdx: 0.070 and 0.89 s) and has not been measured beyond 2304: the threshold stays where it was.
 int64_t dense_eigen_max()
 {
     if (const char *e = getenv("SNPGPU_EIG_DENSE_MAX")) { const long long v = atoll(e); if (v >= 0 && v <= 46340) return v; }
@@ -33,8 +33,13 @@ namespace snpgpu {
 
 // top-k eigenpairs of a dense symmetric matrix A (device, n x n, overwritten): the reference negates
 // the packed matrix and asks LAPACK dspevx for eigenvalues IL=1..IU=k (src/genPCA.cpp:1308-1341,
-// :1419; src/genEIGMIX.cpp:700-702); here A is negated on the device and hipSOLVER's syevdx is asked
-// for the same index range.  eigval: k values (descending), eigvec: n x k column-major.
+// :1419; src/genEIGMIX.cpp:700-702); here A is negated on the device, hipSOLVER's syevd decomposes it
+// whole and the first k pairs (ascending in -A) are the answer.  NOT syevdx with that index range: on
+// multiple eigenvalues (copies of one block of samples: clusters that the fp32 parts of the accumulation
+// split by 1e-7) it returned, now and then, a value from elsewhere in the spectrum with a vector that is
+// no eigenvector at all -- relative residual of order 1, at k = 1 as at k = 16, INFO = 0
+// (tests/test_gpu_eigen_spectra.py); syevd, which also serves the Krylov solver's projected matrices, is
+// exact there.  eigval: k values (descending), eigvec: n x k column-major.
 int dense_topk(int device, hipStream_t stream, double *A, int64_t n, int k, double *eigval, double *eigvec, int mem)
 {
     if (k <= 0 || k > n) { set_error("Invalid 'eigen.cnt'."); return 1; }
@@ -48,18 +53,16 @@ int dense_topk(int device, hipStream_t stream, double *A, int64_t n, int k, doub
     if (hipStreamSynchronize(stream) != hipSuccess) { set_error("dense_topk: negate failed"); return 1; }
     if (hipsolverCreate(&sv.h) != HIPSOLVER_STATUS_SUCCESS) { set_error("hipsolverCreate failed"); return 1; }
     hipsolverSetStream(sv.h, stream);
-    int lwork = 0, nev = 0;
-    if (hipsolverDnDsyevdx_bufferSize(sv.h, HIPSOLVER_EIG_MODE_VECTOR, HIPSOLVER_EIG_RANGE_I, HIPBLAS_FILL_MODE_LOWER,
-                                      (int)n, A, (int)n, 0.0, 0.0, 1, k, &nev, (double *)W.p,
-                                      &lwork) != HIPSOLVER_STATUS_SUCCESS) {
-        // (seen at n = 24 000: the workspace size does not fit the interface) -- the callers fall back to the block-Krylov solver
-        set_error("hipsolverDnDsyevdx_bufferSize failed");
+    int lwork = 0;
+    if (hipsolverDnDsyevd_bufferSize(sv.h, HIPSOLVER_EIG_MODE_VECTOR, HIPSOLVER_FILL_MODE_LOWER, (int)n, A, (int)n, (double *)W.p,
+                                     &lwork) != HIPSOLVER_STATUS_SUCCESS) {
+        // (a workspace size that does not fit the interface) -- the callers fall back to the block-Krylov solver
+        set_error("hipsolverDnDsyevd_bufferSize failed");
         return 2;
     }
     if (work.alloc(sizeof(double) * (size_t)std::max(lwork, 1))) return 1;
-    hipsolverStatus_t s = hipsolverDnDsyevdx(sv.h, HIPSOLVER_EIG_MODE_VECTOR, HIPSOLVER_EIG_RANGE_I,
-                                             HIPBLAS_FILL_MODE_LOWER, (int)n, A, (int)n, 0.0, 0.0, 1, k,
-                                             &nev, (double *)W.p, (double *)work.p, lwork, (int *)info.p);
+    hipsolverStatus_t s = hipsolverDnDsyevd(sv.h, HIPSOLVER_EIG_MODE_VECTOR, HIPSOLVER_FILL_MODE_LOWER, (int)n, A, (int)n,
+                                            (double *)W.p, (double *)work.p, lwork, (int *)info.p);
     int hinfo = 0;
     hipError_t e = hipMemcpyAsync(&hinfo, info.p, sizeof(int), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
@@ -81,7 +84,7 @@ int dense_topk(int device, hipStream_t stream, double *A, int64_t n, int k, doub
 // A request for a large share of the spectrum (eigen.cnt <= 0 = all, eigen.method = "DSPEV", or k of the order of n) is not a
 // top-k problem: the Krylov solver's block would be k + 8 vectors wide with room for one or two blocks per cycle (n = 3000,
 // k = 1000: one new block per restart), and with k = n it degenerates to a full QR + syevd inside six n x n work arrays.  Up to
-// 16 384 samples (124 s of syevdx) such requests take the dense route whatever SNPGPU_EIG_DENSE_MAX says.
+// 16 384 samples such requests take the dense route whatever SNPGPU_EIG_DENSE_MAX says.
 bool dense_route(int64_t n, int k)
 {
     if (n <= dense_eigen_max()) return true;
