@@ -1124,6 +1124,42 @@ int snpgpu_gen_line_host(const char *line, int64_t n_bytes, int64_t n_samp, doub
  * [3] text bytes copied (or parsed in place), [4] bytes of a workgroup's chunk, [5] of a lane's segment, [6] of the halo */
 int snpgpu_gen_stats(double *stats);
 
+/* ---- (1q) classical multidimensional scaling of a distance matrix: snpgdsMDS ---------------------------------------------------------
+ * For a symmetric n x n matrix dist (double, row-major, leading dimension ld >= n, in `mem`: SNPGPU_HOST, SNPGPU_HOST_PINNED, or
+ * SNPGPU_DEVICE = memory of `device`) the k algebraically largest eigenpairs of
+ *     B = -1/2 J (D o D) J,   J = I - 1 1^T / n,   D o D = dist with every entry squared
+ * -- what R's cmdscale(dist, k) decomposes.  Largest by value, never by magnitude: B is indefinite for distances that are not
+ * Euclidean (IBS, dissimilarity) and always has the eigenpair (0, 1).
+ *   eigval      host [k], descending
+ *   vectors     host [k][n], unit eigenvectors; in each the entry of largest magnitude (the lowest index on ties) is positive.  The
+ *               points of cmdscale are vectors[i] * sqrt(eigval[i]) for the positive eigenvalues
+ *   all_eigval  host [n] or NULL: every eigenvalue, descending, on the dense route; NaN on the Krylov route
+ *   trace_b     the trace of B, (sum_ij d_ij^2 / n - sum_i d_ii^2) / 2, or NULL
+ *   route       0 dense, 1 Krylov, or NULL
+ * The matrix is read where it lies and never written; host memory is copied to the device in row windows of
+ * SNPGPU_MDS_STAGE_BYTES (default 256 MiB).  One scan checks the entries and makes the row sums of D o D in a fixed order.  Up to
+ * the dense threshold of snpgpu_pca_eigen (SNPGPU_EIG_DENSE_MAX) B is written to a buffer of its own and decomposed whole; beyond
+ * it the block-Krylov solver works on q -> B q = -1/2 centre((D o D) centre(q)), D read once per product and squared on the way, B
+ * never formed.  No atomics: the same input gives the same bits on the dense route and in every product.
+ * That solver accepts a pair on |B v - theta v| / |theta|, which says nothing at theta ~ 0: a call in which it does not converge, or
+ * returns an eigenvalue at or below n 2^-52 max_i sum_j d_ij^2 / 2 (what rounding makes of an exact zero), fails with "fewer than
+ * k = ... eigenvalues appear to be positive"; the dense route returns such eigenvalues as they are.
+ * Refused before any device is touched: NULL dist / eigval / vectors, n < 2, ld < n, an unknown memory kind, k outside
+ * 1 ... n - 1 ("'k' must be in {1, 2, ..  n - 1}"); by the scan: a non-finite entry ("NA values not allowed in 'd'"), a pair
+ * d[i][j] != d[j][i] (bitwise: "'d' must be exactly symmetric"); a matrix that does not fit the device beside the solver's work is
+ * refused with both figures.  There is no CPU fallback. */
+int snpgpu_mds(const double *dist, int64_t n, int64_t ld, int mem, int k, double *eigval, double *vectors, double *all_eigval,
+               double *trace_b, int *route, int device);
+/* Y = B Q for b >= 1 vectors, Q and Y host [b][n]: the operator of the Krylov route alone, with the same staging, scan and refusals */
+int snpgpu_mds_apply(const double *dist, int64_t n, int64_t ld, int mem, const double *Q, int b, double *Y, int device);
+/* snpgpu_mds on the working space: the IBS (what = 0: 1 - ibs, made on the device) or dissimilarity (what = 1) matrix of the selected
+ * SNPs is finalised into device memory and decomposed there; the n x n matrix never reaches the host */
+int snpgpu_gnrMDS(int what, int k, double *eigval, double *vectors, double *all_eigval, double *trace_b, int *route);
+/* of the last snpgpu_mds / snpgpu_mds_apply / snpgpu_gnrMDS on this thread: stats[0] ms of the staging copies, [1] ms of the scan,
+ * [2] ms of the eigen solve (host clock), [3] ms of the whole call (host clock), [4] the route, [5] operator products, [6] their
+ * summed ms (HIP events), [7] staging windows, [8] the value at or below which an eigenvalue does not count as positive */
+int snpgpu_mds_stats(double *stats);
+
 /* ---- diagnostics (no reference counterpart) ---------------------------------------------------------------------------
  * What THIS device's matrix pipe sustains right now: a register-only stream of one MFMA instruction (never waiting on memory,
  * two waves per SIMD) run for `seconds`, rate taken over the second half.  The kernels of this library run against the socket

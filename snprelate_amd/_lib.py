@@ -70,6 +70,7 @@ EXPORTS = [
     "snpgpu_geno_merge", "snpgpu_geno_merge_stats",
     "snpgpu_gen_genotypes", "snpgpu_gen_line_host", "snpgpu_gen_stats",
     "snpgpu_grm_merge_stats",
+    "snpgpu_mds", "snpgpu_mds_apply", "snpgpu_gnrMDS", "snpgpu_mds_stats",
 ]
 FST_WC84, FST_WH02 = 1, 2
 FST_METHODS = ("W&C84", "W&H02")
@@ -344,6 +345,10 @@ def lib():
     L.snpgpu_gen_genotypes.argtypes = [vp, c_int, i64, vp, vp, i64, i64, dbl, vp, vp, vp, c_int, vp]
     L.snpgpu_gen_line_host.argtypes = [ctypes.c_char_p, i64, i64, dbl, vp, vp, ctypes.c_char_p, i64]
     L.snpgpu_gen_stats.argtypes = [vp]
+    L.snpgpu_mds.argtypes = [vp, i64, i64, c_int, c_int, vp, vp, vp, ctypes.POINTER(dbl), ctypes.POINTER(c_int), c_int]
+    L.snpgpu_mds_apply.argtypes = [vp, i64, i64, c_int, vp, c_int, vp, c_int]
+    L.snpgpu_gnrMDS.argtypes = [c_int, c_int, vp, vp, vp, ctypes.POINTER(dbl), ctypes.POINTER(c_int)]
+    L.snpgpu_mds_stats.argtypes = [vp]
     _lib = L
     return L
 
@@ -2003,3 +2008,74 @@ def pair_stats():
     s = _stats("pair", 8)
     return dict(snp_table_ms=float(s[0]), snp_table_launches=int(s[1]), snp_table_bytes=float(s[2]), words_ms=float(s[3]),
                 pair_count_ms=float(s[4]), matrix_ms=float(s[5]), other_launches=int(s[6]), other_bytes=float(s[7]))
+
+
+def _mds_matrix(dist, n, ld, device):
+    """(pointer, n, ld, mem, device, keep-alive) of a distance matrix: a square float64 numpy array (host memory; a view of a wider
+    array keeps its leading dimension), a device address (int) with n, or a torch tensor on a GPU, used where it lies"""
+    if isinstance(dist, int):
+        if n is None:
+            raise ValueError("a device matrix needs n")
+        return ctypes.c_void_p(dist), int(n), int(n if ld is None else ld), DEVICE, int(device), None
+    if not isinstance(dist, np.ndarray) and hasattr(dist, "data_ptr") and hasattr(dist, "is_cuda"):
+        import torch
+        if not dist.is_cuda or dist.dtype != torch.float64 or dist.dim() != 2 or dist.shape[0] != dist.shape[1]:
+            raise ValueError("dist should be a square float64 matrix (a torch tensor: on a GPU)")
+        if dist.stride(1) != 1 and dist.shape[1] > 1:
+            dist = dist.contiguous()
+        torch.cuda.current_stream(dist.device).synchronize()      # the library's stream waits for no other: the matrix is complete
+        return (ctypes.c_void_p(dist.data_ptr()), int(dist.shape[0]), int(max(dist.stride(0), dist.shape[1])), DEVICE,
+                int(dist.device.index or 0), dist)
+    d = np.asarray(dist)
+    if d.ndim != 2 or d.shape[0] != d.shape[1]:
+        raise ValueError("dist should be a square matrix")
+    if d.dtype != np.float64 or d.strides[1] != 8 or d.strides[0] % 8 or d.strides[0] < 8 * d.shape[1]:
+        d = np.ascontiguousarray(d, np.float64)
+    return _ptr(d), int(d.shape[0]), int(d.strides[0] // 8), HOST, int(device), d
+
+
+def _mds_result(n, k, call):
+    eigval, vectors, all_eigval = np.zeros(k, np.float64), np.zeros((k, n), np.float64), np.zeros(n, np.float64)
+    trace, route = ctypes.c_double(0), ctypes.c_int(-1)
+    check(call(_ptr(eigval), _ptr(vectors), _ptr(all_eigval), ctypes.byref(trace), ctypes.byref(route)))
+    return dict(eigval=eigval, vectors=vectors, all_eigval=all_eigval if route.value == 0 else None, trace=trace.value,
+                route=route.value, pos_tol=mds_stats()["pos_tol"])
+
+
+def mds(dist, k, device=0, n=None, ld=None):
+    """snpgpu_mds: dict(eigval [k], vectors [k][n], all_eigval [n] or None (Krylov route), trace, route, pos_tol) of the classical
+    scaling of a distance matrix.  dist: a square float64 numpy array, a device address (int) with n (and ld), or a torch tensor on
+    a GPU, used where it lies (then its device is the call's)."""
+    ptr, n, ld, mem, device, _keep = _mds_matrix(dist, n, ld, device)
+    k = int(k)
+    if n < 2:
+        raise ValueError("'d' must have at least two rows")
+    if k < 1 or k > n - 1:
+        raise ValueError("'k' must be in {1, 2, ..  n - 1}")
+    return _mds_result(n, k, lambda w, v, a, t, r: lib().snpgpu_mds(ptr, n, ld, mem, k, w, v, a, t, r, device))
+
+
+def gnr_mds(what, k, n_samp):
+    """snpgpu_gnrMDS on the working space of n_samp samples: what = 0 (1 - IBS) or 1 (dissimilarity); the dict of mds()"""
+    n_samp, k = int(n_samp), int(k)
+    if k < 1 or k > n_samp - 1:
+        raise ValueError("'k' must be in {1, 2, ..  n - 1}")
+    return _mds_result(n_samp, k, lambda w, v, a, t, r: lib().snpgpu_gnrMDS(int(what), k, w, v, a, t, r))
+
+
+def mds_apply(dist, Q, device=0, n=None, ld=None):
+    """snpgpu_mds_apply: Y = B Q for Q [b][n] (host), B = -1/2 J (D o D) J of the distance matrix (as mds() takes it)"""
+    ptr, n, ld, mem, device, _keep = _mds_matrix(dist, n, ld, device)
+    q = np.ascontiguousarray(Q, np.float64)
+    if q.ndim != 2 or q.shape[1] != n or q.shape[0] < 1:
+        raise ValueError("Q should be [b][n]")
+    y = np.zeros_like(q)
+    check(lib().snpgpu_mds_apply(ptr, n, ld, mem, _ptr(q), int(q.shape[0]), _ptr(y), device))
+    return y
+
+
+def mds_stats():
+    """dict of snpgpu_mds_stats for the last mds / mds_apply / gnr_mds on this thread"""
+    s = _stats("mds", 9)
+    return dict(stage_ms=float(s[0]), scan_ms=float(s[1]), eigen_ms=float(s[2]), total_ms=float(s[3]), route=int(s[4]),
+                products=int(s[5]), product_ms=float(s[6]), windows=int(s[7]), pos_tol=float(s[8]))

@@ -42,6 +42,7 @@ INTEGRATION.md):
     snpgdsSNPListIntersect        R/AllUtilities.R:667-736   (the SNPs several data sets share, and who counts the other allele)
     snpgdsCombineGeno             R/AllUtilities.R:1285-1583 (data sets merged: the genotypes spliced on the GPU)
     snpgdsAlleleSwitch            R/AllUtilities.R:1686-1751 (a data set re-coded against given A alleles, the rows flipped on the GPU)
+    snpgdsMDS                     no reference counterpart: the tutorial's cmdscale(1 - ibs$ibs, k), the eigenpairs found on the GPU
 
 All arithmetic on genotype matrices runs on the MI355X through libsnpgpu.so
 (`_lib`); there is no CPU fallback.  The one exception is snpgdsIndInbCoef, which
@@ -2581,3 +2582,78 @@ def snpgdsAlleleSwitch(gdsobj, A_allele, verbose=True, device=0):
     object is modified in place, so it has to be an in-memory one (GenoFile); one that streams a file is refused as a read-only GDS
     file is.  Returns the flags: int32 0 = unchanged, 1 = switched, NA (-2^31) = A_allele[i] is neither allele, or None."""
     return _merge.allele_switch(gdsobj, A_allele, verbose=verbose, device=device)
+
+
+def _mds_host_matrix(d, k, sample_id):
+    """the refusals of snpgdsMDS that a host matrix allows without the device; returns the matrix as float64"""
+    d = np.asarray(d)
+    if d.ndim != 2 or d.shape[0] != d.shape[1]:
+        raise ValueError("distances must be result of 'dist' or a square matrix")
+    d = np.asarray(d, np.float64)
+    _mds_check_dims(d.shape[0], k, sample_id)
+    if not np.isfinite(d).all():
+        raise ValueError("NA values not allowed in 'd'")
+    return d
+
+
+def _mds_check_dims(n, k, sample_id):
+    if n < 2:
+        raise ValueError("'d' must have at least two rows")
+    if k > n - 1:
+        raise ValueError("'k' must be in {1, 2, ..  n - 1}")
+    if sample_id is not None and len(sample_id) != n:
+        raise ValueError("nrow(dist) == length(sample.id) is not TRUE")
+
+
+def snpgdsMDS(obj, k=2, method="ibs", sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True,
+              maf=float("nan"), missing_rate=0.01, num_thread=1, verbose=True, device=0):
+    """Classical multidimensional scaling of IBS or dissimilarity distances -- the tutorial's cmdscale(1 - ibs$ibs, k) -- on the
+    GPU (snpgpu_mds / snpgpu_gnrMDS; no reference counterpart: the reference leaves the step to R's cmdscale).
+
+    obj: a dict with "diss" (a snpgdsDiss result) or "ibs" (a snpgdsIBS result: 1 - ibs is scaled, as snpgdsHCluster takes it); a
+    square array or a torch tensor on a GPU (a bare distance matrix, `sample_id` its labels); or a SNP GDS object, filtered like
+    snpgdsIBS, whose `method` distances ("ibs": 1 - IBS, "diss": snpgdsDiss) are made and scaled on the device without reaching the
+    host.  Returns dict(sample_id, points [n][k1], eigenval [k], GOF, trace, n_pos = k1, route): points[:, i] = v_i sqrt(lambda_i)
+    for the k1 of the k algebraically largest eigenvalues of B = -1/2 J (D o D) J that are positive (above the rounding of an exact
+    zero, include/snpgpu.h 1q); in every eigenvector the entry of largest magnitude is positive.  GOF: cmdscale's two figures,
+    sum(eigenval) / sum(|lambda|) and sum(eigenval) / sum(max(lambda, 0)), where all eigenvalues are known (route 0, the dense
+    solver), else None.  Not taken: cmdscale's add = TRUE, a packed triangle."""
+    if method not in ("ibs", "diss"):
+        raise ValueError("'method' should be one of \"ibs\", \"diss\"")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError("'k' must be in {1, 2, ..  n - 1}")
+    k = int(k)
+    is_tensor = not isinstance(obj, (dict, np.ndarray, list, tuple)) and hasattr(obj, "data_ptr") and hasattr(obj, "is_cuda")
+    if isinstance(obj, (GenoFile, _gds.GenoStream)):
+        ws = _init_file2("Multidimensional scaling of %s distances:" % ("IBS" if method == "ibs" else "dissimilarity"), obj, sample_id,
+                         snp_id, autosome_only, remove_monosnp, maf, missing_rate, num_thread, verbose, device)
+        _mds_check_dims(ws["n_samp"], k, None)
+        sample_id = ws["sample_id"]
+        r = _lib.gnr_mds(0 if method == "ibs" else 1, k, ws["n_samp"])
+    elif is_tensor:
+        if obj.dim() != 2 or obj.shape[0] != obj.shape[1]:
+            raise ValueError("distances must be result of 'dist' or a square matrix")
+        _mds_check_dims(int(obj.shape[0]), k, sample_id)
+        r = _lib.mds(obj, k, device=device)
+    else:
+        if isinstance(obj, dict):
+            if "diss" in obj:
+                sample_id, d = obj["sample_id"], obj["diss"]
+            elif "ibs" in obj:
+                sample_id, d = obj["sample_id"], 1 - np.asarray(obj["ibs"], np.float64)
+            else:
+                raise TypeError("'obj' should be a snpgdsDiss or snpgdsIBS result, a square matrix or a SNP GDS object")
+        else:
+            d = obj
+        r = _lib.mds(_mds_host_matrix(d, k, sample_id), k, device=device)
+    w, v = r["eigval"], r["vectors"]
+    k1 = int(np.count_nonzero(w > r["pos_tol"]))
+    if k1 < k:
+        warnings.warn("only %d of the first %d eigenvalues are > 0" % (k1, k))
+    points = np.ascontiguousarray((v[:k1] * np.sqrt(w[:k1])[:, None]).T)
+    gof = None
+    if r["all_eigval"] is not None:
+        a = r["all_eigval"]
+        gof = np.array([w.sum() / np.abs(a).sum(), w.sum() / np.maximum(a, 0).sum()])
+    return dict(sample_id=None if sample_id is None else np.asarray(sample_id), points=points, eigenval=w, GOF=gof, trace=r["trace"],
+                n_pos=k1, route=r["route"])

@@ -21,6 +21,9 @@ int ws_stats(std::vector<int32_t> &sum, std::vector<int32_t> &num, std::vector<i
 // their gathered 2-bit host rows.  Stops at the first non-zero return, which it returns.
 int ws_for_each_block(const std::function<int(const uint8_t *rows, int64_t i0, int64_t nb)> &f);
 
+// A context of `kind` for the working space's samples and device, fed the selected SNPs by that loop; the caller destroys it.
+int ws_run_stream(int kind, int bayesian, snpgpu_ctx **out);
+
 // All selected rows in one host block: refuses without a working space, with fewer than min_samp samples (callers ask for two or
 // none) or without a selected SNP.
 int ws_all_rows(const char *fn, int64_t min_samp, std::vector<uint8_t> &buf);

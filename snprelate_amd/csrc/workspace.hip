@@ -88,6 +88,8 @@ int need_ws(const char *fn)
     return 0;
 }
 
+int ws_run_stream(int kind, int bayesian, snpgpu_ctx **out) { return run_stream(kind, bayesian, out); }
+
 int64_t ws_n_samp() { return g_ws.n_samp; }
 int64_t ws_n_snp() { return (int64_t)g_ws.sel.size(); }
 int ws_device() { return g_ws.device; }
