@@ -1,4 +1,4 @@
-// Accumulator contexts (api.hip): the environment switches, and the kernel path they select for a context -- decided ONCE, by a
+// Accumulator contexts (ctx_*.hip): the environment switches, and the kernel path they select for a context -- decided ONCE, by a
 // function that makes no HIP call and allocates nothing.  snpgpu_create allocates from the plan, the feed reads it
 // (DESIGN.md 17a).  Below them: the context itself, the plan next to its runtime state.
 #pragma once
@@ -398,7 +398,7 @@ struct snpgpu_ctx {
     bool het_pending = false;
     snpgpu::DevBuf ccoef, tcorr;   // exact-row-side SYRK: per-SNP {u, v} and per-chunk column terms [Bmax / H3_LUTCH + 1][ncols_pad]
     snpgpu::DevBuf colterm;        // ... their running total per column (fp64 [ncols_pad]), subtracted from every row of the
-    bool colterm_pending = false;  //     panel once, before a result is read (ctx_settle, api.hip)
+    bool colterm_pending = false;  //     panel once, before a result is read (ctx_settle, ctx_results.hip)
     snpgpu::DevBuf wt12;           // EIGMIX: 12 * code words of a block with missing calls (exact-row kernel of the numerator)
     snpgpu::DevBuf uvpace;         // syrk_uv16c_kernel: 64 KiB per table chunk that every workgroup fetches (zeros; see the kernel)
     snpgpu::DevBuf uvcarry, uvcarry_flags;   // ... its carry scratch (plan.uvc_carry_all: slots of 116 KiB) and the slots' flag words
@@ -414,7 +414,7 @@ struct snpgpu_ctx {
     snpgpu::DevBuf acc_u32, acc_f64;
     snpgpu::TileGrid tg_pc{}, tg_mm{};
     snpgpu::DevBuf tg_pc_tab, tg_mm_tab;
-    int i8_blocks = 0;         // work items (= workgroups) of the MFMA pair kernel, see build_worklist
+    int i8_blocks = 0;         // work items (= workgroups) of the MFMA pair kernel, see build_worklist (worklist.h)
     snpgpu::DevBuf i8_work;    // int4 {tile row, tile col, K part, K parts} per workgroup, XCD-interleaved
     snpgpu::DevBuf mm256, sp_work;   // GCTA denominators, sparse form: per (256-sample group, SNP) set of missing calls; its 256 x 256 work list
     int sp_blocks = 0;
@@ -424,7 +424,7 @@ struct snpgpu_ctx {
     snpgpu::DevBuf x1_work;
 
     snpgpu_ctx() = default;
-    ~snpgpu_ctx();              // api.hip: events, streams and the rocBLAS handle on the context's device; the buffers follow
+    ~snpgpu_ctx();              // ctx_life.hip: events, streams and the rocBLAS handle on the context's device; the buffers follow
 
     // scalars layout: SCALAR_SLOTS slots of 8 bytes (unsigned long long / double) -- the allocation in snpgpu_create is exactly
     // this many, a ninth scalar needs SCALAR_SLOTS raised with it:

@@ -607,7 +607,7 @@ template <int MODE, bool SPREAD> struct I8PipeSel { typedef I8Pipe<MODE> type; }
 template <int MODE> struct I8PipeSel<MODE, true> { typedef I8PipeSpread<MODE> type; };
 
 // Workgroup = 4 waves as 2 x 2, tile (64 TM) x (64 TN).  Workgroup b executes work item b of a host-built
-// list (api.hip: build_i8_worklist): {tile row, tile col, K part, K parts}; the list is interleaved so
+// list (worklist.h: build_worklist): {tile row, tile col, K part, K parts}; the list is interleaved so
 // that the items of one XCD (b % 8) walk neighbouring tiles, and its tail holds K-split items so that the
 // last, partially filled round of workgroups is short.  The flush is atomic, parts may share a tile.
 template <int MODE>

@@ -3,7 +3,7 @@
 //   repack        caller block (uint8 or 2-bit rows)  -> aligned 2-bit rows, pad samples = missing
 //   snp_stats     per-SNP genotype sum / non-missing count   (vec_u8_geno_count, src/dVect.cpp:30-117)
 //   repack_stats  both in one pass over the caller's block
-// Launched by every context's feed (api.hip), the projections (proj.hip), the row blocks of host_util.h and ws_stats (workspace.hip).
+// Launched by every context's feed (ctx_feed.hip), the projections (proj.hip), the row blocks of host_util.h and ws_stats (workspace.hip).
 #include "snpgpu_internal.h"
 #include "prep_device.h"
 

@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256, 1) void syrk_uv_kernel(
     int4 item = work[wi];
     if (item.w == 0) return;
     {
-        // work lists with several copies of every tile (build_worklist `copies`): the copy index picks its own tables and plane
+        // work lists with several copies of every tile (worklist.h: build_worklist, `copies`): the copy index picks its own tables and plane
         // (written out here and in syrk_uv16_kernel: as a shared function it changes the code of both)
         const int copy = item.w >> 16;
         item.w &= 0xFFFF;

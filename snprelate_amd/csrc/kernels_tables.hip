@@ -1,4 +1,4 @@
-// Per-SNP tables of a feed block, from the block's sum / num (O(B) work, launched by feed_syrk, api.hip):
+// Per-SNP tables of a feed block, from the block's sum / num (O(B) work, launched by feed_syrk, ctx_feed.hip):
 //   build_lut       decode table of one SYRK table            (DivideGeno/rsqrt_prod, src/genPCA.cpp:98-181)
 //   uv_factor / uv_assign / uv_tables   tables, coefficients and slot map of the single-product SYRK (launch_build_uv)
 //   homo_uv_tables / homo_totals        KING-homo tables, effective weights and block totals (launch_homo_tables)

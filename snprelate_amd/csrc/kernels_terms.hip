@@ -1,5 +1,5 @@
 // Per-sample terms that travel beside the SYRK products of a feed block (fp64, from the pair-coded words or the packed rows;
-// launched by feed_syrk, api.hip, after the tables of kernels_tables.hip and the words of kernels_transpose.hip):
+// launched by feed_syrk, ctx_feed.hip, after the tables of kernels_tables.hip and the words of kernels_transpose.hip):
 //   colcorr / colterm_add           column term of the exact-row SYRK
 //   uvcorr / uvterm_add             row / column terms of the single-product SYRK
 //   homo_miss_sums / homo_miss_add  KING-homo per-sample missing sums (launch_homo_miss_sums)

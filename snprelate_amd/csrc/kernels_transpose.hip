@@ -1,4 +1,4 @@
-// SNP-major 2-bit rows -> sample-major words (HBM-bound; launched by feed_counters and feed_syrk, api.hip, and proj.hip):
+// SNP-major 2-bit rows -> sample-major words (HBM-bound; launched by feed_counters and feed_syrk, ctx_feed.hip, and proj.hip):
 //   transpose8        pair-coded words for the SYRK kernels
 //   transpose2<0/1>   2-bit words for the MFMA pair kernels (<1>: the missing mask of the GCTA denominators, + miss_diag2)
 //   transpose2_direct the same words straight from a caller block of 2-bit rows (+ het_commit)

@@ -33,7 +33,6 @@ using namespace snpgpu;
 namespace {
 
 inline int64_t tri_offset(int64_t n, int64_t i) { return i * n - i * (i - 1) / 2; }
-inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 
 // row boundaries of `parts` panels of equal TIME, interior boundaries multiples of 256: the twin of dist.panel_rows (same
 // arithmetic, same order of operations).  cost(panel [r0, r1)) = pairs + alpha * (n - r0): the pre-pass transposes the panel's
@@ -82,7 +81,7 @@ std::vector<int64_t> plan_rows(int64_t n, int parts)
     return b;
 }
 
-int64_t plan_storage(int64_t n, int64_t r0, int64_t r1) { return r1 > r0 ? round_up(r1 - r0, PANEL_ALIGN) * round_up(n - r0, PANEL_ALIGN) : 0; }
+int64_t plan_storage(int64_t n, int64_t r0, int64_t r1) { return r1 > r0 ? plan_round_up(r1 - r0, PANEL_ALIGN) * plan_round_up(n - r0, PANEL_ALIGN) : 0; }
 
 // owned[pass][device] = sorted panel indices: largest storage first into the least loaded slot (dist.pass_plan)
 std::vector<std::vector<std::vector<int>>> plan_owners(int64_t n, const std::vector<int64_t> &bounds, int n_dev, int ppd, int passes)
@@ -123,7 +122,7 @@ std::vector<std::vector<std::vector<int>>> plan_owners(int64_t n, const std::vec
 // kinds: + 4 bytes per pair), then without.
 int64_t panel_scratch_bytes(int kind, int64_t n, int64_t bmax, int64_t r0)
 {
-    const int64_t np = round_up(n - r0, PANEL_ALIGN), rb = round_up(n, 256) / 4, bp = round_up(bmax, 1024);
+    const int64_t np = plan_round_up(n - r0, PANEL_ALIGN), rb = plan_round_up(n, 256) / 4, bp = plan_round_up(bmax, 1024);
     int64_t b = bmax * rb;                                                           // packed
     const bool pc = kind != SNPGPU_PCA_COV && kind != SNPGPU_EIGMIX, mm = kind == SNPGPU_KING_HOMO || kind == SNPGPU_GRM_GCTA ||
                     kind == SNPGPU_PCA_COV || kind == SNPGPU_EIGMIX || kind == SNPGPU_DISS;
@@ -453,7 +452,7 @@ int snpgpu_multi_create(int kind, int64_t n_samp, const snpgpu_opts *opts, const
     // automatic: the fewest panels per device whose accumulators AND per-panel scratch fit by the estimate (auto_panels_per_device);
     // the estimate is not the allocator -- when a context of that plan still fails with "out of memory" the next larger count is
     // tried instead of failing the job
-    const int64_t bmax = round_up(opts && opts->max_block_snps > 0 ? opts->max_block_snps : 32768, 64);
+    const int64_t bmax = plan_round_up(opts && opts->max_block_snps > 0 ? opts->max_block_snps : 32768, 64);
     for (int at_least = 1;;) {
         std::string why;
         const int ppd = auto_panels_per_device(kind, n_samp, bmax, mo->devices, mo->n_devices, passes, &why, at_least);
@@ -474,7 +473,7 @@ static int multi_create_with(int kind, int64_t n_samp, const snpgpu_opts *opts, 
     if (o.stream) { set_error("snpgpu_multi_create: a caller stream cannot serve several devices"); return 1; }
     std::unique_ptr<snpgpu_multi, void (*)(snpgpu_multi *)> m(new snpgpu_multi(), multi_free);
     m->kind = kind; m->N = n_samp; m->ppd = ppd;
-    m->Bmax = round_up(o.max_block_snps > 0 ? o.max_block_snps : 32768, 64);
+    m->Bmax = plan_round_up(o.max_block_snps > 0 ? o.max_block_snps : 32768, 64);
     const int nd = mo->n_devices;
     m->bounds = plan_rows(n_samp, nd * ppd * passes);
     const auto owned = plan_owners(n_samp, m->bounds, nd, ppd, passes);
@@ -929,14 +928,10 @@ int snpgpu_multi_select_pairs(snpgpu_multi *m, const snpgpu_sel_opts *o, int64_t
 {
     const char *fn = "snpgpu_multi_select_pairs";
     // what needs no device first, with this call's name (snpgpu_select_pairs repeats the checks per panel)
-    if (!o) { set_error(std::string(fn) + ": NULL opts"); return 1; }
-    if (o->what != SNPGPU_SEL_KING_ROBUST && o->what != SNPGPU_SEL_KING_HOMO && o->what != SNPGPU_SEL_MOM) { set_error(std::string(fn) + ": invalid 'what'"); return 1; }
-    if (o->what == SNPGPU_SEL_MOM && !o->e) { set_error(std::string(fn) + ": e is NULL (SNPGPU_SEL_MOM needs the five expectations)"); return 1; }
-    if (capacity < 0) { set_error(std::string(fn) + ": negative capacity"); return 1; }
-    if (capacity == 0 && (idx1 || idx2 || v0 || v1 || kinship)) { set_error(std::string(fn) + ": capacity 0 with a non-NULL output (count only: every output NULL)"); return 1; }
+    const void *outs[5] = {idx1, idx2, v0, v1, kinship};
+    if (select_check_opts(fn, o, capacity, outs, 5)) return 1;
     if (!m) { set_error(std::string(fn) + ": NULL object"); return 1; }
-    const int kind = o->what == SNPGPU_SEL_KING_ROBUST ? SNPGPU_KING_ROBUST : o->what == SNPGPU_SEL_KING_HOMO ? SNPGPU_KING_HOMO : SNPGPU_IBS;
-    if (m->kind != kind) { set_error(std::string(fn) + ": 'what' does not match the object's kind"); return 1; }
+    if (m->kind != select_kind(o->what)) { set_error(std::string(fn) + ": 'what' does not match the object's kind"); return 1; }
     if (mem != SNPGPU_HOST) { set_error(std::string(fn) + ": results go to host memory"); return 1; }
     std::vector<size_t> order(m->ctx.size());
     for (size_t i = 0; i < order.size(); i++) order[i] = i;

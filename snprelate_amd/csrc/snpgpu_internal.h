@@ -387,9 +387,20 @@ int launch_select_king_homo(hipStream_t st, const PanelGeom &g, const uint32_t *
 int launch_select_mom(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const double *e, int constraint, const SelectArgs &s, bool write);
 int launch_mirror_diag_tiles(hipStream_t st, const PanelGeom &g, double *num, int T);
 
-// context-level pieces shared between api.hip and eigen.hip / multi.hip
-int ctx_settle(snpgpu_ctx *c);                                   // pending column / row terms of the fp16 SYRK -> panel
+// context-level pieces shared between the ctx_*.hip files, eigen.hip and multi.hip
+int ctx_settle(snpgpu_ctx *c);                                   // pending column / row terms of the fp16 SYRK -> panel (ctx_results.hip)
 int ctx_panel_matmul_enqueue(snpgpu_ctx *c, double scale, const double *Q, int m, double *Y, bool fp32_products = false);   // no host synchronisation
+// what every result call starts with (ctx_results.hip): the context is of kind_a or kind_b, a full matrix comes from a full context,
+// the pending terms are in the panel (`settle`: the column / row terms too), the context's device is current; `fn`: the public name
+int check_out(snpgpu_ctx *c, int kind_a, int kind_b, int packed, const char *fn, bool settle = true);
+int finish(snpgpu_ctx *c);                                       // waits for the context's stream
+// KING-robust family codes [N] of the caller in the context's `family` buffer: *dfam, nullptr without codes
+int upload_family(snpgpu_ctx *c, const int32_t *family, const int32_t **dfam);
+// what the KING-homo values take beside the counters and the fp64 sums (launch_fin_king_homo, launch_select_king_homo)
+struct HomoTerms { double fscale; const double *w_const, *msum; const uint32_t *called, *nosh; };
+HomoTerms homo_terms(snpgpu_ctx *c);
+// the refusals of a selection that need neither a context nor a device (ctx_select.hip); `fn`: the public name
+int select_check_opts(const char *fn, const snpgpu_sel_opts *o, int64_t capacity, const void *const *outs, int n_outs);
 
 struct DevBuf {            // owns its device memory: released with the object, movable, not copyable
     void *p = nullptr;
@@ -418,6 +429,46 @@ struct DevBuf {            // owns its device memory: released with the object, 
         bytes = 0;
     }
 };
+
+// output staging: finalisers write device buffers; host destinations go through a temporary
+struct OutBuf {
+    hipStream_t st;
+    void *user;
+    void *dev = nullptr;
+    size_t bytes;
+    int mem;
+    bool temp = false;
+    OutBuf(hipStream_t st_, void *user_, size_t bytes_, int mem_) : st(st_), user(user_), bytes(bytes_), mem(mem_) {}
+    int prepare()
+    {
+        if (mem == SNPGPU_DEVICE) { dev = user; return 0; }
+        SNPGPU_HIP_CHECK(hipMalloc(&dev, bytes ? bytes : 16));
+        temp = true;
+        return 0;
+    }
+    int commit()
+    {
+        if (temp) SNPGPU_HIP_CHECK(hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, st));
+        return 0;
+    }
+    ~OutBuf()
+    {
+        if (temp && dev) {
+            (void)hipStreamSynchronize(st);
+            (void)hipFree(dev);
+        }
+    }
+};
+
+// The one sequence of every result, after its check_out: the temporaries in the order of `outs`, ONE launch (launch() returns
+// nonzero with the error set), the copies to the host in that order, one wait for the stream.  The temporaries go with the OutBufs.
+template <class Launch> int stage_out(snpgpu_ctx *c, const std::vector<OutBuf *> &outs, Launch &&launch)
+{
+    for (OutBuf *b : outs) if (b->prepare()) return 1;
+    if (launch()) return 1;
+    for (OutBuf *b : outs) if (b->commit()) return 1;
+    return finish(c);
+}
 
 }  // namespace snpgpu
 

@@ -3,10 +3,13 @@
 Every expected value below is written down from the rules of snpgpu_create as they stood before the plan existed and from
 DESIGN.md 4 / 17a -- which kernel a block takes under which switch -- not printed from the library."""
 import os
+import subprocess
 
 import pytest
 
 from snprelate_amd import _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SWITCHES = ["SNPGPU_ACC_LAYOUT", "SNPGPU_EIG_BLAS", "SNPGPU_PAIR_BACKEND", "SNPGPU_PAIR_FP4", "SNPGPU_PAIR_FP4_GENERAL",
             "SNPGPU_GCTA_MISS_FP4", "SNPGPU_I8_NO_NOMISS", "SNPGPU_GCTA_SPARSE", "SNPGPU_GCTA_SPARSE_MAX_RATE", "SNPGPU_SYRK",
@@ -345,3 +348,16 @@ def test_bench_roofline_names_the_kernel_of_the_plan(clean_env, workload, missin
     assert roof["kernel"].split("<PM_")[0] == want
     if workload == "king_homo":      # its second kernel: the weight product of the blocks with missing calls
         assert d["syrk_kernel_missing"] in roof["kernels_ms_per_step"]
+
+
+def test_work_lists_against_brute_force(tmp_path):
+    """tests/worklist_check.cpp includes only worklist.h (the work lists of the MFMA pair and SYRK kernels, the super-tile tables of
+    the others); built with the host compiler under the address and undefined-behaviour sanitizers and run as a process of its own,
+    it prints nothing and exits 0"""
+    exe = str(tmp_path / "worklist_check")
+    r = subprocess.run(["g++", "-std=gnu++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                        "-I" + os.path.join(ROOT, "snprelate_amd", "csrc"), os.path.join(ROOT, "tests", "worklist_check.cpp"), "-o", exe],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and not r.stderr, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stdout == "" and r.stderr == "", (r.stdout + r.stderr)[-3000:]

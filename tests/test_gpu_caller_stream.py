@@ -193,7 +193,7 @@ def test_two_contexts_on_one_caller_stream():
 @pytest.mark.parametrize("fmt", ["u8", "packed"])
 def test_pinned_feeds_on_a_caller_stream(kind, fmt):
     """the two-buffer loop of input_forms.feed on a context created on a caller's stream: the copies run on the context's copy
-    stream, ordered against the caller's stream by events (hipStreamWaitEvent in api.hip), while that stream is busy.  The first
+    stream, ordered against the caller's stream by events (hipStreamWaitEvent in ctx_feed.hip), while that stream is busy.  The first
     feed out of either buffer allocates its staging copy on the device and waits for the stream, so the delay starts after two
     blocks; the four that follow reuse both buffers while the kernels that read their staging copies are still held up behind it."""
     import torch

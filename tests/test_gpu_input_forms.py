@@ -3,7 +3,7 @@ Projector and MultiAccumulator must give the oracle's result whether one canonic
 whose missing cells hold any byte of 3 .. 255, or as 2-bit rows with random bits in the unused codes of the last byte -- from
 host memory, from device memory at odd byte offsets, through two page-locked buffers, or with the caller's own per-SNP
 statistics (snpgpu_block_stats + snpgpu_feed_stats).  What is under test is the pre-pass of kernels_prep.hip
-(repack_stats_kernel, repack_kernel) and kernels_transpose.hip (transpose2_direct_kernel) and its routing in api.hip's stage_block.
+(repack_stats_kernel, repack_kernel) and kernels_transpose.hip (transpose2_direct_kernel) and its routing in ctx_feed.hip's stage_block.
 
 Data: 700 SNPs fed as ragged blocks of 256, 300 and 144 with max_block_snps = 512; 4 % missing calls except in the middle block,
 which has none, so a context alternates between its two kernel routes while the padding stays dirty.  Sample counts: 61 .. 64
@@ -90,7 +90,7 @@ def _set_backend(monkeypatch, backend):
 
 def _routes(form):
     """a 2-bit form runs with the default route and with SNPGPU_PREP_TWO_PASS=1.  The variable changes the path only where
-    _takes_one_pass holds for an IBS / KING-robust context on the mfma_i8 counters (api.hip, stage_block); everywhere else the
+    _takes_one_pass holds for an IBS / KING-robust context on the mfma_i8 counters (ctx_feed.hip, stage_block); everywhere else the
     second run repeats the first one's path"""
     return (False, True) if form.fmt == F.GENO_PACKED2 else (False,)
 

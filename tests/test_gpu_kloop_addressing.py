@@ -91,7 +91,7 @@ def test_partial_last_chunk_and_odd_block(data, monkeypatch):
 @pytest.mark.parametrize("promote", [1024, None])
 def test_tiles_split_along_k(data, promote, monkeypatch):
     """The same data without SNPGPU_I8_TAIL_PARTS=1: six tiles fill a fraction of one round of the device, so the work list splits each
-    along K (tail_parts = 0 in the plan: chosen per list, api.hip) and the parts start at their own c_beg.  With 1024-slot runs a run is
+    along K (tail_parts = 0 in the plan: chosen per list, worklist.h) and the parts start at their own c_beg.  With 1024-slot runs a run is
     one chunk and only part 0 has work; at the default run length a run holds three chunks (two runs per block) and parts 1 and 2
     start in the middle of it.  That the split path ran shows in the sums: K parts meet in the fp64 panel instead of in one fp32
     accumulator, so some of the 245 350 entries round differently from the whole-tile walk."""
