@@ -249,6 +249,38 @@ int snpgpu_select_pairs(snpgpu_ctx *ctx, const snpgpu_sel_opts *o, int64_t capac
  * scan, write pass} on the device and the whole call on the host clock; no reference counterpart */
 int snpgpu_select_stats(double *ms4);
 
+/* The sparse GRM straight from the resident sums: every sample's own entry (diag) and the pairs idx1 < idx2 of the panel with
+ * samp_sel[idx1] && samp_sel[idx2] and value >= cutoff (a NaN value is never selected; a non-finite cutoff selects every pair), in
+ * the order of snpgpu_select_pairs (idx1 ascending, then idx2 ascending), by the same count pass, scan and write pass: no atomic,
+ * the same call gives the same arrays.  The values are those of the kind's finaliser, bit for bit:
+ *   SNPGPU_SEL_GRM_GCTA        GRM_GCTA context:   snpgpu_grm_gcta (pending terms folded on the fly: further feeds may follow)
+ *   SNPGPU_SEL_GRM_EIGENSTRAT  PCA_COV context:    snpgpu_pca_cov(normalize = 1, trace_in); a panel needs trace_in > 0
+ *   SNPGPU_SEL_GRM_EIGMIX      EIGMIX context:     snpgpu_eigmix(diagadj = mode, scale)
+ *   SNPGPU_SEL_GRM_INDIV_BETA  INDIV_BETA context: snpgpu_indiv_beta(mode), full contexts only
+ * Contexts frozen by snpgpu_finalize_inplace (GCTA, EIGMIX) are read as their finalisers read them.  The correlation form of
+ * snpgpu_gnrGRM ("Corr") is not built: G_ij / sqrt(G_ii G_jj) needs the diagonal of every column, which a row panel does not hold.
+ * No reference counterpart (the reference builds the whole matrix). */
+enum snpgpu_grm_sel_kind { SNPGPU_SEL_GRM_GCTA = 1, SNPGPU_SEL_GRM_EIGENSTRAT = 2, SNPGPU_SEL_GRM_EIGMIX = 3, SNPGPU_SEL_GRM_INDIV_BETA = 4 };
+typedef struct snpgpu_grm_sel_opts {
+    int32_t what;            /* snpgpu_grm_sel_kind; must match the context's kind                     */
+    int32_t mode;            /* EIGMIX: diagadj; INDIV_BETA: 0 / 1 / 2 as snpgpu_indiv_beta            */
+    double  scale;           /* EIGMIX only (2 for snpgdsGRM(method = "EIGMIX"))                       */
+    double  trace_in;        /* EIGENSTRAT on a panel: the trace of ALL panels; 0 = the context's own  */
+    double  cutoff;          /* value >= cutoff; non-finite: every pair                                */
+    const uint8_t *samp_sel; /* host [n_samp] or NULL                                                  */
+} snpgpu_grm_sel_opts;
+/* Host outputs only (a device destination is not built).  idx1, idx2, value: `capacity` elements each, the first `capacity` pairs
+ * are stored and nothing is written behind them, *n_found is always the number of ALL selected pairs; capacity 0 with the three
+ * NULL counts only.  diag: double [min(row_end, n_samp) - row_begin], the finaliser's entry (i, i) of every row of the panel
+ * whatever samp_sel says; avg_val: the grm_avg_value of INDIV_BETA; both independent of capacity, each may be NULL.  Refused
+ * before any device call: NULL opts, an unknown `what`, EIGMIX with a non-finite or non-positive scale, a mode out of range, a
+ * negative capacity, a pair output with capacity 0, a NULL context; then a `what` that does not match the context kind. */
+int snpgpu_select_grm(snpgpu_ctx *ctx, const snpgpu_grm_sel_opts *o, int64_t capacity, int32_t *idx1, int32_t *idx2,
+                      double *value, double *diag, double *avg_val, int64_t *n_found);
+/* diagnostics (tools/grm_pairs_bench.py): milliseconds of the last snpgpu_select_grm on this thread, double [5] = {count pass, scan,
+ * write pass, diagonal kernel} on the device and the whole call on the host clock; no reference counterpart */
+int snpgpu_select_grm_stats(double *ms5);
+
 /* Top-k eigenpairs of the symmetric matrix held as row panels: replaces CalcEigen / LAPACK dspevx for ANY n
  * (src/genPCA.cpp:1262-1346; the same call behind gnrEigMix, src/genEIGMIX.cpp:700-702).  Thick-restarted block Krylov +
  * Rayleigh-Ritz in C++ / HIP (csrc/eigen.hip): the O(n^2) product runs on the panels, the tall-skinny algebra on their
@@ -349,6 +381,12 @@ int snpgpu_multi_eigmix(snpgpu_multi *m, int diagadj, double scale, double *out,
  * to the concatenation.  Host outputs only.  No reference counterpart, as snpgpu_select_pairs. */
 int snpgpu_multi_select_pairs(snpgpu_multi *m, const snpgpu_sel_opts *o, int64_t capacity, int32_t *idx1, int32_t *idx2,
                               double *v0, double *v1, double *kinship, int mem /* host */, int64_t *n_found);
+/* snpgpu_select_grm over the resident panels in order of row_begin, the pairs concatenated as in snpgpu_multi_select_pairs.
+ * diag: double [n_samp]; every resident panel writes its own rows, a pass of an n_passes > 1 object leaves the other rows
+ * untouched.  EIGENSTRAT with trace_in == 0 takes snpgpu_multi_pca_trace (the whole trace only when all panels are resident).
+ * INDIV_BETA is refused: it needs a full context. */
+int snpgpu_multi_select_grm(snpgpu_multi *m, const snpgpu_grm_sel_opts *o, int64_t capacity, int32_t *idx1, int32_t *idx2,
+                            double *value, double *diag, int64_t *n_found);
 int snpgpu_multi_pca_trace(snpgpu_multi *m, double *trace);
 /* out may be NULL (trace only); normalize != 0: C *= (n-1)/trace with the trace of ALL panels */
 int snpgpu_multi_pca_cov(snpgpu_multi *m, double *out, int normalize, double *trace_xtx, int mem);
@@ -466,6 +504,12 @@ int snpgpu_gnrIBDPairs(int what, const int32_t *family, const double *allele_fre
                        const uint8_t *samp_sel, int num_thread, int verbose, int64_t *n_found);
 /* the kept selection: host arrays of n_found elements each, any may be NULL (v1 is 0 for KING_ROBUST) */
 int snpgpu_gnrIBDPairs_get(int32_t *idx1, int32_t *idx2, double *v0, double *v1, double *kinship);
+/* The sparse GRM of the working space without the n x n matrix: accumulate once as snpgpu_gnrGRM does (method "GCTA", "Eigenstrat",
+ * "EIGMIX", "IndivBeta"; "Corr" is refused, see snpgpu_select_grm), select with snpgpu_select_grm, keep the result in the working
+ * space until the next call or snpgpu_ws_clear.  samp_sel: host uint8 [n_samp] or NULL.  No reference counterpart. */
+int snpgpu_gnrGRMPairs(const char *method, double cutoff, const uint8_t *samp_sel, int num_thread, int verbose, int64_t *n_found);
+/* the kept result: idx1, idx2, value of n_found elements, diag of n_samp, avg_val (IndivBeta; 0 otherwise); any may be NULL */
+int snpgpu_gnrGRMPairs_get(int32_t *idx1, int32_t *idx2, double *value, double *diag, double *avg_val);
 /* gnrIBD_Beta(Inbreeding, NumThread, useMatrix, Verbose), src/genBeta.cpp:361-460 */
 int snpgpu_gnrIBD_Beta(int inbreeding, int num_thread, int use_matrix, int verbose, double *out, double *avg_val);
 /* gnrGRM_avg_val(), src/genPCA.cpp:1605-1611 */

@@ -62,6 +62,7 @@ EXPORTS = [
     "snpgpu_pair_tables", "snpgpu_pair_score_final", "snpgpu_pair_score_matrix", "snpgpu_gnrPairScore", "snpgpu_pair_stats",
     "snpgpu_diag_plan", "snpgpu_diag_carry_fallbacks",
     "snpgpu_select_pairs", "snpgpu_multi_select_pairs", "snpgpu_gnrIBDPairs", "snpgpu_gnrIBDPairs_get", "snpgpu_select_stats",
+    "snpgpu_select_grm", "snpgpu_multi_select_grm", "snpgpu_gnrGRMPairs", "snpgpu_gnrGRMPairs_get", "snpgpu_select_grm_stats",
     "snpgpu_geno_select", "snpgpu_geno_select_stats",
     "snpgpu_geno_convert", "snpgpu_geno_convert_stats",
     "snpgpu_vcf_index", "snpgpu_vcf_genotypes", "snpgpu_vcf_stats",
@@ -81,6 +82,7 @@ PAIR_TYPES = ("per.pair", "per.snp", "matrix", "gds.file")
 PAIR_TABLE, SNP_TABLE = 0, 1
 PAIR_ELEM_INT32, PAIR_ELEM_BIT2 = 0, 1
 SEL_KING_ROBUST, SEL_KING_HOMO, SEL_MOM = 1, 2, 3
+SEL_GRM_GCTA, SEL_GRM_EIGENSTRAT, SEL_GRM_EIGMIX, SEL_GRM_INDIV_BETA = 1, 2, 3, 4
 LDSCORE_ADJUST, LDSCORE_SELF = 1, 2
 
 
@@ -117,6 +119,11 @@ class MultiStatus(ctypes.Structure):   # snpgpu_multi_status
 class SelOpts(ctypes.Structure):       # snpgpu_sel_opts
     _fields_ = [("what", ctypes.c_int32), ("kinship_constraint", ctypes.c_int32), ("family", ctypes.c_void_p), ("e", ctypes.c_void_p),
                 ("kinship_cutoff", ctypes.c_double), ("samp_sel", ctypes.c_void_p)]
+
+
+class GrmSelOpts(ctypes.Structure):    # snpgpu_grm_sel_opts
+    _fields_ = [("what", ctypes.c_int32), ("mode", ctypes.c_int32), ("scale", ctypes.c_double), ("trace_in", ctypes.c_double),
+                ("cutoff", ctypes.c_double), ("samp_sel", ctypes.c_void_p)]
 
 
 class GenoSrc(ctypes.Structure):       # snpgpu_geno_src
@@ -327,6 +334,11 @@ def lib():
     L.snpgpu_gnrIBDPairs.argtypes = [c_int, vp, vp, c_int, dbl, vp, c_int, c_int, ctypes.POINTER(i64)]
     L.snpgpu_gnrIBDPairs_get.argtypes = [vp, vp, vp, vp, vp]
     L.snpgpu_select_stats.argtypes = [vp]
+    L.snpgpu_select_grm.argtypes = [vp, ctypes.POINTER(GrmSelOpts), i64, vp, vp, vp, vp, ctypes.POINTER(dbl), ctypes.POINTER(i64)]
+    L.snpgpu_multi_select_grm.argtypes = [vp, ctypes.POINTER(GrmSelOpts), i64, vp, vp, vp, vp, ctypes.POINTER(i64)]
+    L.snpgpu_gnrGRMPairs.argtypes = [ctypes.c_char_p, dbl, vp, c_int, c_int, ctypes.POINTER(i64)]
+    L.snpgpu_gnrGRMPairs_get.argtypes = [vp, vp, vp, vp, ctypes.POINTER(dbl)]
+    L.snpgpu_select_grm_stats.argtypes = [vp]
     L.snpgpu_geno_select.argtypes = [ctypes.POINTER(GenoSrc), vp, i64, vp, i64, vp, c_int, c_int, vp]
     L.snpgpu_geno_select_stats.argtypes = [vp]
     L.snpgpu_geno_convert.argtypes = [ctypes.POINTER(GenoSrc), c_int, vp, i64, vp, i64, vp, c_int, c_int, c_int, c_int, vp]
@@ -495,6 +507,26 @@ def _select_pairs(fn, handle, n, what, cutoff, family, e, constraint, samp_sel, 
     if int(what) == SEL_KING_ROBUST:
         out[3] = None                      # (not written for this kind)
     return out[0], out[1], out[2], out[3], out[4], found.value
+
+
+def _select_grm(call, n, n_diag, what, cutoff, mode, scale, trace_in, samp_sel, capacity, diag_fill=float("nan")):
+    """snpgpu_select_grm / snpgpu_multi_select_grm behind Accumulator.select_grm and MultiAccumulator.select_grm; call(opts, capacity,
+    idx1, idx2, value, diag, found) runs one of them.  diag is fetched with the pairs (with the count when capacity is 0); the
+    entries the call does not write keep diag_fill."""
+    sel = None if samp_sel is None else np.ascontiguousarray(np.asarray(samp_sel) != 0, np.uint8)
+    if sel is not None and sel.shape != (n,):
+        raise ValueError("'samp_sel' should have %d entries" % n)
+    o = GrmSelOpts(int(what), int(mode), float(scale), float(trace_in), float(cutoff), _ptr(sel))      # (sel stays alive to the end)
+    found = ctypes.c_int64(0)
+    diag = np.full(n_diag, diag_fill, np.float64)
+    if capacity is None:                   # count, then fetch everything
+        call(o, 0, None, None, None, None, found)
+        capacity = found.value
+    capacity = int(capacity)
+    out = [np.empty(capacity, np.int32), np.empty(capacity, np.int32), np.empty(capacity, np.float64)]
+    call(o, capacity, *([_ptr(a) for a in out] if capacity > 0 else [None] * 3), _ptr(diag), found)
+    m = min(capacity, found.value)
+    return out[0][:m], out[1][:m], out[2][:m], diag, found.value
 
 
 class Accumulator:
@@ -701,6 +733,18 @@ class Accumulator:
         o = np.empty(self._shape(packed), np.float64)
         check(lib().snpgpu_eigmix(self._h, int(bool(diagadj)), float(scale), _ptr(o), int(packed), HOST))
         return o
+
+    def select_grm(self, what, cutoff=0.05, mode=0, scale=1.0, trace_in=0.0, samp_sel=None, capacity=None):
+        """The sparse GRM of this panel (snpgpu_select_grm): (idx1, idx2, value, diag, avg_val, n_found) -- the pairs idx1 < idx2 with
+        samp_sel[idx1] && samp_sel[idx2] and value >= cutoff (non-finite: every pair) in the order idx1, then idx2, with the value the
+        kind's finaliser writes; diag: the finaliser's own entry of every row of the panel; avg_val: IndivBeta's average (0 otherwise).
+        mode: EIGMIX's diagadj or IndivBeta's mode.  capacity=None fetches every pair; a number stores the first `capacity` (0: count)."""
+        avg = ctypes.c_double(0)
+
+        def call(o, cap, i1, i2, v, d, found):
+            check(lib().snpgpu_select_grm(self._h, ctypes.byref(o), cap, i1, i2, v, d, ctypes.byref(avg), ctypes.byref(found)))
+        r = _select_grm(call, self.n, min(self.row_end, self.n) - self.row_begin, what, cutoff, mode, scale, trace_in, samp_sel, capacity)
+        return r[0], r[1], r[2], r[3], avg.value, r[4]
 
     def indiv_beta(self, mode=1, packed=False, out_ptr=None):
         """(matrix, grm_avg_value); out_ptr: a DEVICE pointer receiving the matrix, then (None, grm_avg_value) -- the average is a
@@ -1117,6 +1161,13 @@ class MultiAccumulator:
         if out_ptrs is not None:
             raise ValueError("MultiAccumulator.select_pairs returns host arrays (out_ptrs is for Accumulator.select_pairs)")
         return _select_pairs(lib().snpgpu_multi_select_pairs, self._h, self.n, what, cutoff, family, e, constraint, samp_sel, capacity, None)
+
+    def select_grm(self, what, cutoff=0.05, mode=0, scale=1.0, trace_in=0.0, samp_sel=None, capacity=None, diag_fill=float("nan")):
+        """Accumulator.select_grm over the resident panels in order of row_begin, the pairs concatenated (snpgpu_multi_select_grm):
+        (idx1, idx2, value, diag [n], n_found).  The rows of diag that no resident panel holds (n_passes > 1) keep diag_fill."""
+        def call(o, cap, i1, i2, v, d, found):
+            check(lib().snpgpu_multi_select_grm(self._h, ctypes.byref(o), cap, i1, i2, v, d, ctypes.byref(found)))
+        return _select_grm(call, self.n, self.n, what, cutoff, mode, scale, trace_in, samp_sel, capacity, diag_fill)
 
     def pca_trace(self):
         """TraceXTX: the sum of the resident panels' diagonal parts (snpgpu_multi_pca_trace)"""
@@ -1995,6 +2046,13 @@ def grm_merge_stats():
     """dict of snpgpu_grm_merge_stats for the last grm_merge (api.snpgdsMergeGRM) on this thread"""
     s = _stats("grm_merge", 2)
     return dict(slabs=int(s[0]), launches=int(s[1]))
+
+
+def select_grm_stats():
+    """ms of the last select_grm call on this thread: count pass, scan, write pass, diagonal kernel (device) and the whole call (host clock)"""
+    v = np.zeros(5, np.float64)
+    check(lib().snpgpu_select_grm_stats(_ptr(v)))
+    return dict(count_ms=v[0], scan_ms=v[1], write_ms=v[2], diag_ms=v[3], call_ms=v[4])
 
 
 def select_stats():

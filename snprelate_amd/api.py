@@ -361,6 +361,96 @@ def snpgdsGRM(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remove_mo
     return out
 
 
+def write_sparse_grm(prefix, sample_id, idx1, idx2, value, diag, samp_sel=None):
+    """The text files of snpgdsGRMPairs(out_fn=prefix), from host arrays:
+        prefix.grm.id   one line per sample: the id twice, tab-separated (family id, individual id)
+        prefix.grm.sp   one line per stored entry, `row<TAB>col<TAB>value`: 0-based indices into prefix.grm.id with row >= col, sorted by
+                        row, then by col, so the diagonal line `i i diag[i]` closes the lines of row i; values as %.17g, which reads
+                        back to the same double
+    idx1 < idx2 index sample_id; a pair becomes the line idx2, idx1.  samp_sel (a mask over sample_id): prefix.grm.id lists the selected
+    samples only, the indices refer to that list, and the pairs must lie among them."""
+    ids = np.asarray(sample_id)
+    n = ids.size
+    idx1, idx2 = np.asarray(idx1, np.int64), np.asarray(idx2, np.int64)
+    value, diag = np.asarray(value, np.float64), np.asarray(diag, np.float64)
+    if not (idx1.shape == idx2.shape == value.shape and idx1.ndim == 1) or diag.shape != (n,):
+        raise ValueError("idx1, idx2 and value should have one entry per pair, diag one per sample")
+    if idx1.size and not ((0 <= idx1).all() and (idx1 < idx2).all() and (idx2 < n).all()):
+        raise ValueError("pairs should be 0 <= idx1 < idx2 < %d" % n)
+    keep = np.ones(n, bool) if samp_sel is None else np.asarray(samp_sel) != 0
+    if keep.shape != (n,):
+        raise ValueError("'samp_sel' should have %d entries" % n)
+    if not (keep[idx1].all() and keep[idx2].all()):
+        raise ValueError("a pair holds a sample that 'samp_sel' leaves out")
+    new = np.cumsum(keep) - 1                                   # index within the list of selected samples
+    own = np.flatnonzero(keep)
+    row = np.concatenate([new[idx2], new[own]])
+    col = np.concatenate([new[idx1], new[own]])
+    val = np.concatenate([value, diag[own]])
+    order = np.lexsort((col, row))
+    with open(prefix + ".grm.id", "w") as f:
+        f.writelines("%s\t%s\n" % (s, s) for s in ids[own].tolist())
+    with open(prefix + ".grm.sp", "w") as f:
+        f.writelines("%d\t%d\t%.17g\n" % t for t in zip(row[order].tolist(), col[order].tolist(), val[order].tolist()))
+
+
+def snpgdsGRMPairs(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True,
+                   maf=float("nan"), missing_rate=0.01, method="GCTA", cutoff=0.05, samp_sel=None, num_thread=1,
+                   with_id=True, out_fn=None, verbose=True, device=0):
+    """The sparse GRM of snpgdsGRM(gdsobj, ..., method) without its n x n matrix: every sample's own entry and the pairs at or above
+    `cutoff` (a non-finite cutoff: every pair; a NaN entry is never a pair).  No reference counterpart.  The sums are accumulated once
+    on the GPU as for snpgdsGRM and only the diagonal and the selected pairs come back (snpgpu_gnrGRMPairs), each with the value
+    snpgdsGRM would hold at that place.  method: "GCTA", "Eigenstrat", "EIGMIX" (= "Weighted"), "IndivBeta"; "Corr" is refused -- its
+    entries need the diagonal of every column, which a row panel of the sums does not hold.  samp_sel: a logical vector over the
+    working samples or strictly increasing 0-based indices; it restricts the pairs, not `diag`.
+    Returns sample_id, snp_id, method, ID1, ID2 (sample ids), idx1 < idx2 (0-based into sample_id, ordered by idx1, then idx2), value,
+    diag [n], n_pairs and, for IndivBeta, avg_val; with_id=False leaves the ids out.  out_fn="prefix" also writes prefix.grm.id and
+    prefix.grm.sp (write_sparse_grm): sample ids, and `row col value` lines of the lower triangle with the diagonal.  That is the
+    layout sparse-GRM readers of the GCTA family are understood to take; it has not been checked against such a program."""
+    all_methods = ("GCTA", "Eigenstrat", "EIGMIX", "Weighted", "Corr", "IndivBeta")
+    if method not in all_methods:
+        raise ValueError("'arg' should be one of " + ", ".join("'%s'" % m for m in all_methods))
+    if method == "Corr":
+        raise ValueError("snpgdsGRMPairs: method 'Corr' is not built for the sparse GRM (its entries need the diagonal of every column); "
+                         "use snpgdsGRM")
+    if method == "Weighted":          # R/IBD.R:552-556
+        method = "EIGMIX"
+    if isinstance(cutoff, (bool, np.bool_)) or not isinstance(cutoff, (int, float, np.integer, np.floating)):
+        raise TypeError("is.numeric(cutoff) is not TRUE")
+    mtxt = {"EIGMIX": "EIGMIX / Weighted GCTA"}.get(method, method)
+    ws = _init_file2("Genetic Relationship Matrix (GRM, %s):" % mtxt, gdsobj, sample_id, snp_id,
+                     autosome_only, remove_monosnp, maf, missing_rate, num_thread, verbose, device)
+    n = ws["n_samp"]
+    mask = None
+    if samp_sel is not None:
+        sel = np.asarray(samp_sel)
+        if sel.dtype.kind == "b" and sel.shape == (n,):
+            mask = sel
+        elif sel.dtype.kind in "iu" and sel.ndim == 1 and (sel.size == 0 or (sel.min() >= 0 and sel.max() < n and np.all(np.diff(sel) > 0))):
+            mask = np.zeros(n, bool)
+            mask[sel] = True
+        else:
+            raise ValueError("snpgdsGRMPairs: 'samp.sel' should be a logical vector over the %d samples or strictly increasing indices" % n)
+        mask = np.ascontiguousarray(mask, np.uint8)
+    L = _lib.lib()
+    found = ctypes.c_int64(0)
+    _lib.check(L.snpgpu_gnrGRMPairs(method.encode(), float(cutoff), _lib._ptr(mask), ws["num_thread"], int(bool(verbose)), ctypes.byref(found)))
+    m = found.value
+    i1, i2, val, diag = np.empty(m, np.int32), np.empty(m, np.int32), np.empty(m, np.float64), np.empty(n, np.float64)
+    avg = ctypes.c_double(0)
+    _lib.check(L.snpgpu_gnrGRMPairs_get(_lib._ptr(i1), _lib._ptr(i2), _lib._ptr(val), _lib._ptr(diag), ctypes.byref(avg)))
+    ids = np.asarray(ws["sample_id"])
+    if out_fn is not None:
+        write_sparse_grm(out_fn, ids, i1, i2, val, diag, mask)
+    rv = dict(method=method, idx1=i1, idx2=i2, value=val, diag=diag, n_pairs=m)
+    if with_id:
+        rv.update(sample_id=ws["sample_id"], snp_id=ws["snp_id"], ID1=ids[i1], ID2=ids[i2])
+    if method == "IndivBeta":
+        rv["avg_val"] = avg.value
+    _cat(verbose, "%d pair%s selected" % (m, "" if m == 1 else "s"))
+    return rv
+
+
 def snpgdsMergeGRM(filelist, out_fn=None, weight=None, verbose=True, device=0):
     """R/IBD.R:624-741 -> gnrGRMMerge (src/genPCA.cpp:1721-1853): combine the GRMs that snpgdsGRM(out_fn=) stored
     for disjoint SNP sets.  weight: None (by SNP count), a bool per file (False = subtract that SNP set) or numbers."""

@@ -72,6 +72,25 @@ HomoTerms snpgpu::homo_terms(snpgpu_ctx *c)
                      c->plan.homo_uv ? (const uint32_t *)c->nosh.p : nullptr};
 }
 
+int snpgpu::beta_terms(snpgpu_ctx *c, int mode, double *avg, double *mn_out, const char *fn)
+{
+    const int nb = 1024;
+    DevBuf part;
+    if (part.alloc(sizeof(double) * 2 * nb)) return 1;
+    std::vector<double> h(2 * nb);
+    int rc = launch_beta_reduce(c->stream, c->geom(), (const uint32_t *)c->acc_u32.p, mode != 0, (double *)part.p,
+                                (double *)part.p + nb, nb);
+    if (!rc && hipMemcpyAsync(h.data(), part.p, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = 1;
+    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = 1;
+    part.release();
+    if (rc) { set_error(std::string(fn) + ": reduction failed"); return 1; }
+    double mn = h[0], sum = 0;
+    for (int i = 0; i < nb; i++) { if (h[i] < mn) mn = h[i]; sum += h[nb + i]; }
+    *avg = sum / (double)(c->plan.N * (c->plan.N - 1) / 2);
+    *mn_out = mn;
+    return 0;
+}
+
 namespace {
 
 size_t out_elems(snpgpu_ctx *c, int packed) { return packed ? (size_t)snpgpu_slab_size(c) : (size_t)c->plan.N * (size_t)c->plan.N; }
@@ -221,19 +240,8 @@ int snpgpu_indiv_beta(snpgpu_ctx *c, int mode, double *out, double *avg_val, int
     if (check_out(c, SNPGPU_INDIV_BETA, SNPGPU_INDIV_BETA, packed, "snpgpu_indiv_beta")) return 1;
     if (!c->plan.full) { set_error("snpgpu_indiv_beta: needs a full (non-panel) context"); return 1; }
     if (mode < 0 || mode > 2) { set_error("snpgpu_indiv_beta: invalid mode"); return 1; }
-    const int nb = 1024;
-    DevBuf part;
-    if (part.alloc(sizeof(double) * 2 * nb)) return 1;
-    std::vector<double> h(2 * nb);
-    int rc = launch_beta_reduce(c->stream, c->geom(), (const uint32_t *)c->acc_u32.p, mode != 0, (double *)part.p,
-                                (double *)part.p + nb, nb);
-    if (!rc && hipMemcpyAsync(h.data(), part.p, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = 1;
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = 1;
-    part.release();
-    if (rc) { set_error("snpgpu_indiv_beta: reduction failed"); return 1; }
-    double mn = h[0], sum = 0;
-    for (int i = 0; i < nb; i++) { if (h[i] < mn) mn = h[i]; sum += h[nb + i]; }
-    const double avg = sum / (double)(c->plan.N * (c->plan.N - 1) / 2);
+    double avg = 0, mn = 0;
+    if (beta_terms(c, mode, &avg, &mn, "snpgpu_indiv_beta")) return 1;
     if (avg_val) *avg_val = avg;
     if (!out) return 0;
     OutBuf b(c->stream, out, out_elems(c, packed) * sizeof(double), mem);

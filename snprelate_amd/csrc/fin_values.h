@@ -1,6 +1,6 @@
-// The VALUE part of the relatedness finalisers, shared by the finaliser functors (kernels_final.hip), which write every pair of a panel,
-// and the selection kernels (kernels_select.hip), which write the pairs at or above a kinship cutoff: one source of each expression,
-// so that a selected pair carries the bits the finaliser would have written for it.
+// The VALUE part of the relatedness and GRM finalisers, shared by the finaliser functors (kernels_final.hip), which write every pair of
+// a panel, and the selection kernels (kernels_select.hip), which write the pairs at or above a cutoff (and, for the GRM kinds, the
+// diagonal): one source of each expression, so that a selected pair carries the bits the finaliser would have written for it.
 // Index conventions, as in the functors: `rel` / `relf` are element offsets in the uint32 / fp64 accumulator planes (panel-relative),
 // msum, called and nosh are indexed relative to the panel's first column (i - col0), fam by ABSOLUTE sample.
 #pragma once
@@ -109,5 +109,69 @@ __device__ __forceinline__ void mom_value(const MomArgs &m, int64_t rel, double 
 // kinship of a pair from its k0 / k1 (snpgdsIBDSelection, R/IBD.R:487).  0.5 and 0.25 are powers of two: both products are exact, the
 // sum rounds once with or without a fused multiply-add
 __device__ __forceinline__ double kinship_k0k1(double k0, double k1) { return (1 - k0 - k1) * 0.5 + k1 * 0.25; }
+
+// ---- the GRM kinds: ANY entry i <= j of the panel, the diagonal included (FinGcta / FinCov / FinEigmix / FinBeta, the GRM selection and its
+// diagonal kernel).  diag, het, dmiss, dsq are indexed by ABSOLUTE sample, colterm / uvterm relative to the panel ------------------------------
+
+// GCTA: Denom(i,j) = #polymorphic SNPs where i or j is missing = M(i,i) + M(j,j) - M(i,j) with M = both-missing counts;
+// result = num / (2 (nLocus - Denom)), no guard (genPCA.cpp:1232-1236)
+struct GctaArgs {
+    const double *num; const uint32_t *miss; const unsigned long long *nlocus;
+    const uint32_t *diag;  // M(s,s) for every sample s (absolute index)
+    // the pending column / row / constant terms of the fp16 SYRK kernels (colterm_settle_kernel's job, folded in here: the
+    // sums stay as they are, so further blocks may follow): num - (T[c] + Q[c] + R[r] - K), panel-relative r, c
+    const double *colterm, *uvterm; int64_t row0, col0, ncols_pad;
+};
+__device__ __forceinline__ double gcta_value(const GctaArgs &a, int64_t rel, int64_t relf, int64_t i, int64_t j)
+{
+    const long long nl = (long long)*a.nlocus;
+    const long long den = (long long)a.diag[i] + (long long)a.diag[j] - (long long)a.miss[rel];
+    double s = a.num[relf];
+    if (a.colterm) {
+        const int64_t r = i - a.row0, c = j - a.col0;
+        s -= a.colterm[c] + (a.uvterm ? a.uvterm[a.ncols_pad + c] + a.uvterm[r] - a.uvterm[2 * a.ncols_pad] : 0.0);
+    }
+    return s / (double)(2 * (nl - den));
+}
+
+// a plane times a factor: the trace-normalised covariance, and a panel finalised in place (snpgpu_finalize_inplace)
+struct CovArgs {
+    const double *num; double scale;
+};
+__device__ __forceinline__ double cov_value(const CovArgs &a, int64_t relf) { return a.num[relf] * a.scale; }
+
+// EIGMIX: ibd = (num - diagadj*het_i [i==j]) / (SumDenominator - Denom),  Denom(i,j) = sum of 4p(1-p) over the SNPs where i or j is
+// missing = dmiss[i] + dmiss[j] - dd(i,j)   (src/genEIGMIX.cpp:113-155)
+struct EigmixArgs {
+    const double *num, *dd; const uint32_t *het; const double *dmiss, *dsq; const double *sumden; int diagadj; double scale;
+};
+__device__ __forceinline__ double eigmix_value(const EigmixArgs &a, int64_t relf, int64_t i, int64_t j)
+{
+    double v = (i == j) ? a.dsq[i] : a.num[relf];     // diagonal numerator from the fp64 per-sample sums
+    if (i == j && a.diagadj) v -= (double)a.het[i];
+    return v / (*a.sumden - (a.dmiss[i] + a.dmiss[j] - a.dd[relf])) * a.scale;
+}
+
+// individual beta: kernel counters {num, x1, x2}: ibscnt = x1 + 2*x2 (src/genBeta.cpp:170-176)
+__device__ __forceinline__ double beta_raw(const uint32_t *acc, int64_t plane, int64_t rel, bool diag_m1)
+{
+    const uint32_t num = acc[rel], ibscnt = acc[plane + rel] + 2u * acc[2 * plane + rel];
+    return diag_m1 ? ((double)ibscnt / num - 1) : ((0.5 * ibscnt) / num);
+}
+// mn, avg: the minimum of all raw values and the mean of the off-diagonal ones (beta_reduce_kernel)
+struct BetaArgs {
+    const uint32_t *acc; int64_t plane; int mode; double avg, mn;
+};
+__device__ __forceinline__ double beta_value(const BetaArgs &a, int64_t rel, int64_t i, int64_t j)
+{
+    if (a.mode == 2) {                   // CalcIndivBetaGRM, src/genBeta.cpp:263-357
+        const double r = beta_raw(a.acc, a.plane, rel, i == j);
+        const double scale = 2.0 / (1 - a.mn);
+        return (i == j) ? ((r - a.mn) * scale * 0.5 + 1) : ((r - a.mn) * scale);
+    }
+    // gnrIBD_Beta, src/genBeta.cpp:384-452
+    const double r = beta_raw(a.acc, a.plane, rel, (i == j) && a.mode == 1);
+    return (r - a.avg) * (1.0 / (1 - a.avg));
+}
 
 }  // namespace snpgpu

@@ -271,42 +271,29 @@ int launch_fin_diss(hipStream_t st, const PanelGeom &g, const uint32_t *acc, con
 }
 
 // ---- GCTA / covariance ---------------------------------------------------------
-// Denom(i,j) = #polymorphic SNPs where i or j is missing = M(i,i) + M(j,j) - M(i,j) with
-// M = both-missing counts; result = num / (2 (nLocus - Denom)), no guard (genPCA.cpp:1232-1236).
+// gcta_value, cov_value: fin_values.h
 struct FinGcta {
-    const double *num; const uint32_t *miss; const unsigned long long *nlocus;
-    const uint32_t *diag;  // M(s,s) for every sample s (absolute index)
-    double *out;
-    // the pending column / row / constant terms of the fp16 SYRK kernels (colterm_settle_kernel's job, folded in here: the
-    // sums stay as they are, so further blocks may follow): num - (T[c] + Q[c] + R[r] - K), panel-relative r, c
-    const double *colterm, *uvterm; int64_t row0, col0, ncols_pad;
+    GctaArgs v; double *out;
     __device__ void apply(int64_t rel, int64_t relf, int64_t i, int64_t j, OutPos p) const
     {
-        const long long nl = (long long)*nlocus;
-        const long long den = (long long)diag[i] + (long long)diag[j] - (long long)miss[rel];
-        double s = num[relf];
-        if (colterm) {
-            const int64_t r = i - row0, c = j - col0;
-            s -= colterm[c] + (uvterm ? uvterm[ncols_pad + c] + uvterm[r] - uvterm[2 * ncols_pad] : 0.0);
-        }
-        const double v = s / (double)(2 * (nl - den));
-        out[p.a] = v;
-        if (p.b >= 0) out[p.b] = v;
+        const double x = gcta_value(v, rel, relf, i, j);
+        out[p.a] = x;
+        if (p.b >= 0) out[p.b] = x;
     }
 };
 
 struct FinCov {
-    const double *num; double scale; double *out;
+    CovArgs v; double *out;
     __device__ void apply(int64_t rel, int64_t relf, int64_t, int64_t, OutPos p) const
     {
-        const double v = num[relf] * scale;
-        out[p.a] = v;
-        if (p.b >= 0) out[p.b] = v;
+        const double x = cov_value(v, relf);
+        out[p.a] = x;
+        if (p.b >= 0) out[p.b] = x;
     }
 };
 int launch_fin_cov(hipStream_t st, const PanelGeom &g, const double *num, double scale, double *out, int packed)
 {
-    FinCov f{num, scale, out};
+    FinCov f{CovArgs{num, scale}, out};
     return run_fin(st, g, packed, f);
 }
 
@@ -330,35 +317,26 @@ int launch_fin_mom(hipStream_t st, const PanelGeom &g, const uint32_t *acc, cons
 }
 
 // ---- EIGMIX -------------------------------------------------------------------------
-// ibd = (num - diagadj*het_i [i==j]) / (SumDenominator - Denom),  Denom(i,j) = sum of 4p(1-p) over
-// the SNPs where i or j is missing = dmiss[i] + dmiss[j] - dd(i,j)   (src/genEIGMIX.cpp:113-155)
+// eigmix_value, fin_values.h
 struct FinEigmix {
-    const double *num, *dd; const uint32_t *het; const double *dmiss, *dsq; const double *sumden; int diagadj; double scale;
-    double *out;
+    EigmixArgs v; double *out;
     __device__ void apply(int64_t rel, int64_t relf, int64_t i, int64_t j, OutPos p) const
     {
-        double v = (i == j) ? dsq[i] : num[relf];     // diagonal numerator from the fp64 per-sample sums
-        if (i == j && diagadj) v -= (double)het[i];
-        v = v / (*sumden - (dmiss[i] + dmiss[j] - dd[relf])) * scale;
-        out[p.a] = v;
-        if (p.b >= 0) out[p.b] = v;
+        const double x = eigmix_value(v, relf, i, j);
+        out[p.a] = x;
+        if (p.b >= 0) out[p.b] = x;
     }
 };
 int launch_fin_eigmix(hipStream_t st, const PanelGeom &g, const double *num, const double *dd, const uint32_t *het,
                       const double *dmiss, const double *dsq, const double *d_sumden, int diagadj, double scale,
                       double *out, int packed)
 {
-    FinEigmix f{num, dd, het, dmiss, dsq, d_sumden, diagadj, scale, out};
+    FinEigmix f{EigmixArgs{num, dd, het, dmiss, dsq, d_sumden, diagadj, scale}, out};
     return run_fin(st, g, packed, f);
 }
 
 // ---- individual beta ------------------------------------------------------------------
-// kernel counters {num, x1, x2}: ibscnt = x1 + 2*x2 (src/genBeta.cpp:170-176)
-__device__ __forceinline__ double beta_raw(const uint32_t *acc, int64_t plane, int64_t rel, bool diag_m1)
-{
-    const uint32_t num = acc[rel], ibscnt = acc[plane + rel] + 2u * acc[2 * plane + rel];
-    return diag_m1 ? ((double)ibscnt / num - 1) : ((0.5 * ibscnt) / num);
-}
+// beta_raw, beta_value: fin_values.h
 
 // min over all entries and sum over the off-diagonal entries of the raw values
 __global__ __launch_bounds__(256) void beta_reduce_kernel(PanelGeom g, const uint32_t *__restrict__ acc,
@@ -396,26 +374,18 @@ int launch_beta_reduce(hipStream_t st, const PanelGeom &g, const uint32_t *acc, 
 }
 
 struct FinBeta {
-    const uint32_t *acc; int64_t plane; int mode; double avg, mn; double *out;
+    BetaArgs v; double *out;
     __device__ void apply(int64_t rel, int64_t relf, int64_t i, int64_t j, OutPos p) const
     {
-        double v;
-        if (mode == 2) {                 // CalcIndivBetaGRM, src/genBeta.cpp:263-357
-            const double r = beta_raw(acc, plane, rel, i == j);
-            const double scale = 2.0 / (1 - mn);
-            v = (i == j) ? ((r - mn) * scale * 0.5 + 1) : ((r - mn) * scale);
-        } else {                         // gnrIBD_Beta, src/genBeta.cpp:384-452
-            const double r = beta_raw(acc, plane, rel, (i == j) && mode == 1);
-            v = (r - avg) * (1.0 / (1 - avg));
-        }
-        out[p.a] = v;
-        if (p.b >= 0) out[p.b] = v;
+        const double x = beta_value(v, rel, i, j);
+        out[p.a] = x;
+        if (p.b >= 0) out[p.b] = x;
     }
 };
 int launch_fin_beta(hipStream_t st, const PanelGeom &g, const uint32_t *acc, int mode, double avg, double mn, double *out,
                     int packed)
 {
-    FinBeta f{acc, g.rows_pad * g.ncols_pad, mode, avg, mn, out};
+    FinBeta f{BetaArgs{acc, g.rows_pad * g.ncols_pad, mode, avg, mn}, out};
     return run_fin(st, g, packed, f);
 }
 
@@ -486,7 +456,7 @@ int launch_fin_gcta(hipStream_t st, const PanelGeom &g, const double *num, const
                     const uint32_t *diag, const unsigned long long *d_nlocus, double *out, int packed,
                     const double *colterm, const double *uvterm)
 {
-    FinGcta f{num, miss, d_nlocus, diag, out, colterm, uvterm, g.row0, g.col0, g.ncols_pad};
+    FinGcta f{GctaArgs{num, miss, d_nlocus, diag, colterm, uvterm, g.row0, g.col0, g.ncols_pad}, out};
     return run_fin(st, g, packed, f);
 }
 

@@ -13,6 +13,8 @@
 // same hits) instead of reading a bit mask left by the count pass: DESIGN.md 20.
 // Chunks are aligned to 64 columns (a wave reads 256 contiguous bytes of each uint32 plane); rows are spread over grid.x with a stride
 // loop (a panel may have more rows than grid.y allows).
+// The sparse GRM (snpgpu_select_grm) is the same walk over the GCTA / covariance / EIGMIX / IndivBeta value functions,
+// one value per pair, plus a small kernel for the diagonal.
 #include "fin_values.h"
 
 #include <cmath>
@@ -48,13 +50,44 @@ struct SelMom {
     }
 };
 
+// The GRM kinds: ONE value per pair, what the kind's finaliser writes at (i, j), compared with the cutoff and stored in `kin`; value()
+// serves the diagonal kernel too (i == j).  The fp64 planes are tile-major (acc_off): 256 x 256 tiles whose rows are 256 contiguous
+// doubles, so the 64 aligned columns of a chunk never leave a tile and are 512 contiguous bytes -- four full 128-byte lines per
+// wave and plane, as coalesced as the 256 bytes of a uint32 plane.  These kinds keep the walk and its 64-column alignment.
+struct SelGcta {
+    GctaArgs v;
+    __device__ __forceinline__ double value(int64_t rel, int64_t relf, int64_t i, int64_t j) const { return gcta_value(v, rel, relf, i, j); }
+};
+struct SelCov {
+    CovArgs v;
+    __device__ __forceinline__ double value(int64_t, int64_t relf, int64_t, int64_t) const { return cov_value(v, relf); }
+};
+struct SelEigmix {
+    EigmixArgs v;
+    __device__ __forceinline__ double value(int64_t, int64_t relf, int64_t i, int64_t j) const { return eigmix_value(v, relf, i, j); }
+};
+struct SelBeta {
+    BetaArgs v;
+    __device__ __forceinline__ double value(int64_t rel, int64_t, int64_t i, int64_t j) const { return beta_value(v, rel, i, j); }
+};
+// a GRM functor behind the three-value interface of the walk (NV = 1: only `kin` is stored)
+template <class G>
+struct SelOne {
+    G g;
+    __device__ __forceinline__ void values(int64_t rel, int64_t relf, int64_t i, int64_t j, double &, double &, double &kin) const
+    {
+        kin = g.value(rel, relf, i, j);
+    }
+};
+
 struct SelOut {
     int32_t *idx1, *idx2; double *v0, *v1, *kin;       // any may be nullptr
     int64_t capacity;
 };
 
-// WRITE = false: counts[seg] = hits of the segment;  WRITE = true: the hits stored from offsets[seg] on
-template <class F, bool WRITE>
+// WRITE = false: counts[seg] = hits of the segment;  WRITE = true: the hits stored from offsets[seg] on.  NV: values stored per pair
+// (3: v0, v1, kin;  1: kin alone)
+template <class F, bool WRITE, int NV = 3>
 __global__ __launch_bounds__(64 * SEL_WAVES) void select_kernel(PanelGeom g, F f, const uint8_t *__restrict__ sel, int all, double cutoff,
                                                                uint32_t *__restrict__ counts, const int64_t *__restrict__ offsets, SelOut o)
 {
@@ -88,8 +121,10 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void select_kernel(PanelGeom g, F f
                     if (hit && pos < o.capacity) {
                         if (o.idx1) o.idx1[pos] = (int32_t)i;
                         if (o.idx2) o.idx2[pos] = (int32_t)j;
-                        if (o.v0) o.v0[pos] = v0;
-                        if (o.v1) o.v1[pos] = v1;
+                        if (NV == 3) {
+                            if (o.v0) o.v0[pos] = v0;
+                            if (o.v1) o.v1[pos] = v1;
+                        }
                         if (o.kin) o.kin[pos] = kin;
                     }
                     off += __popcll(m);
@@ -124,7 +159,18 @@ __global__ __launch_bounds__(256) void select_scan_kernel(const uint32_t *__rest
     for (int64_t k = a; k < b; k++) { offsets[k] = run; run += counts[k]; }
 }
 
-template <class F>
+// diag[k] = the entry (row0 + k, row0 + k) of the panel's real rows, by the value function of the pairs
+template <class G>
+__global__ __launch_bounds__(256) void select_diag_kernel(PanelGeom g, G f, double *__restrict__ diag)
+{
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x, i = g.row0 + k;
+    if (i >= g.row1 || i >= g.N) return;
+    const int64_t rel = k * g.ncols_pad + (i - g.col0);
+    const int64_t relf = acc_off(g.ncols_pad, g.f64_tiles_c, k, i - g.col0);
+    diag[k] = f.value(rel, relf, i, i);
+}
+
+template <class F, int NV = 3>
 int run_select(hipStream_t st, const PanelGeom &g, const F &f, const SelectArgs &s, bool write)
 {
     const int64_t nrows = g.row1 - g.row0;
@@ -133,9 +179,21 @@ int run_select(hipStream_t st, const PanelGeom &g, const F &f, const SelectArgs 
     const int all = std::isfinite(s.cutoff) ? 0 : 1;
     SelOut o{s.idx1, s.idx2, s.v0, s.v1, s.kin, s.capacity};
     if (write)
-        hipLaunchKernelGGL((select_kernel<F, true>), dim3(grid), dim3(64 * SEL_WAVES), 0, st, g, f, s.sel, all, s.cutoff, s.counts, s.offsets, o);
+        hipLaunchKernelGGL((select_kernel<F, true, NV>), dim3(grid), dim3(64 * SEL_WAVES), 0, st, g, f, s.sel, all, s.cutoff, s.counts, s.offsets, o);
     else
-        hipLaunchKernelGGL((select_kernel<F, false>), dim3(grid), dim3(64 * SEL_WAVES), 0, st, g, f, s.sel, all, s.cutoff, s.counts, s.offsets, o);
+        hipLaunchKernelGGL((select_kernel<F, false, NV>), dim3(grid), dim3(64 * SEL_WAVES), 0, st, g, f, s.sel, all, s.cutoff, s.counts, s.offsets, o);
+    SNPGPU_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// a GRM kind's count pass, write pass or diagonal
+template <class G>
+int run_select_grm(hipStream_t st, const PanelGeom &g, const G &f, const SelectArgs &s, SelPass pass, double *diag)
+{
+    if (pass != SEL_DIAG) return run_select<SelOne<G>, 1>(st, g, SelOne<G>{f}, s, pass == SEL_WRITE);
+    const int64_t nrows = (g.row1 < g.N ? g.row1 : g.N) - g.row0;
+    if (nrows <= 0) return 0;
+    hipLaunchKernelGGL(select_diag_kernel<G>, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, st, g, f, diag);
     SNPGPU_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -168,6 +226,34 @@ int launch_select_mom(hipStream_t st, const PanelGeom &g, const uint32_t *acc, c
 {
     SelMom f{MomArgs{acc, g.rows_pad * g.ncols_pad, e[0], e[1], e[2], e[3], e[4], constraint}};
     return run_select(st, g, f, s, write);
+}
+
+int launch_select_gcta(hipStream_t st, const PanelGeom &g, const double *num, const uint32_t *miss, const uint32_t *miss_diag,
+                       const unsigned long long *d_nlocus, const double *colterm, const double *uvterm, const SelectArgs &s, SelPass pass,
+                       double *diag)
+{
+    SelGcta f{GctaArgs{num, miss, d_nlocus, miss_diag, colterm, uvterm, g.row0, g.col0, g.ncols_pad}};
+    return run_select_grm(st, g, f, s, pass, diag);
+}
+
+int launch_select_cov(hipStream_t st, const PanelGeom &g, const double *num, double scale, const SelectArgs &s, SelPass pass, double *diag)
+{
+    SelCov f{CovArgs{num, scale}};
+    return run_select_grm(st, g, f, s, pass, diag);
+}
+
+int launch_select_eigmix(hipStream_t st, const PanelGeom &g, const double *num, const double *dd, const uint32_t *het, const double *dmiss,
+                         const double *dsq, const double *d_sumden, int diagadj, double scale, const SelectArgs &s, SelPass pass, double *diag)
+{
+    SelEigmix f{EigmixArgs{num, dd, het, dmiss, dsq, d_sumden, diagadj, scale}};
+    return run_select_grm(st, g, f, s, pass, diag);
+}
+
+int launch_select_beta(hipStream_t st, const PanelGeom &g, const uint32_t *acc, int mode, double avg, double mn, const SelectArgs &s,
+                       SelPass pass, double *diag)
+{
+    SelBeta f{BetaArgs{acc, g.rows_pad * g.ncols_pad, mode, avg, mn}};
+    return run_select_grm(st, g, f, s, pass, diag);
 }
 
 }  // namespace snpgpu

@@ -964,6 +964,35 @@ int snpgpu_multi_pca_trace(snpgpu_multi *m, double *trace)
     return 0;
 }
 
+// snpgpu_multi_select_pairs for the sparse GRM; every panel writes its own rows of diag [N]
+int snpgpu_multi_select_grm(snpgpu_multi *m, const snpgpu_grm_sel_opts *o, int64_t capacity, int32_t *idx1, int32_t *idx2, double *value,
+                            double *diag, int64_t *n_found)
+{
+    const char *fn = "snpgpu_multi_select_grm";
+    const void *outs[3] = {idx1, idx2, value};
+    if (select_grm_check_opts(fn, o, capacity, outs, 3)) return 1;
+    if (o->what == SNPGPU_SEL_GRM_INDIV_BETA) { set_error(std::string(fn) + ": INDIV_BETA needs a full context, not the panels of a multi-device object"); return 1; }
+    if (!m) { set_error(std::string(fn) + ": NULL object"); return 1; }
+    if (m->kind != select_grm_kind(o->what)) { set_error(std::string(fn) + ": 'what' does not match the object's kind"); return 1; }
+    snpgpu_grm_sel_opts po = *o;
+    if (o->what == SNPGPU_SEL_GRM_EIGENSTRAT && !(o->trace_in > 0) && snpgpu_multi_pca_trace(m, &po.trace_in)) return 1;
+    std::vector<size_t> order(m->ctx.size());
+    for (size_t i = 0; i < order.size(); i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return m->ctx[a]->plan.row0 < m->ctx[b]->plan.row0; });
+    int64_t total = 0, stored = 0;
+    for (size_t i : order) {
+        const int64_t room = capacity - stored;
+        int64_t found = 0;
+        auto at = [&](auto *p) -> decltype(p) { return (p && room > 0) ? p + stored : nullptr; };
+        if (snpgpu_select_grm(m->ctx[i], &po, room, at(idx1), at(idx2), at(value), diag ? diag + m->ctx[i]->plan.row0 : nullptr, nullptr, &found)) return 1;
+        total += found;
+        stored += std::min(room, found);
+    }
+    (void)hipSetDevice(m->dev[0].device);
+    if (n_found) *n_found = total;
+    return 0;
+}
+
 int snpgpu_multi_pca_cov(snpgpu_multi *m, double *out_, int normalize, double *trace_xtx, int mem)
 {
     if (need(m, SNPGPU_PCA_COV, SNPGPU_PCA_COV, "snpgpu_multi_pca_cov")) return 1;

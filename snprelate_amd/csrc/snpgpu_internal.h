@@ -385,6 +385,18 @@ int launch_select_king_robust(hipStream_t st, const PanelGeom &g, const uint32_t
 int launch_select_king_homo(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const double *facc, double fscale, const double *w_const,
                             const double *msum, const uint32_t *called, const uint32_t *nosh, const SelectArgs &s, bool write);
 int launch_select_mom(hipStream_t st, const PanelGeom &g, const uint32_t *acc, const double *e, int constraint, const SelectArgs &s, bool write);
+// The GRM kinds (one value per pair, stored in s.kin; s.v0 / s.v1 are not used): the arguments of launch_fin_gcta / _cov / _eigmix /
+// _beta.  pass: the count pass, the write pass, or the diagonal -- diag[k] = the entry (row0 + k, row0 + k) for the panel's real rows
+// k < min(row1, N) - row0, by the same value function, whatever s.sel says.
+enum SelPass { SEL_COUNT = 0, SEL_WRITE = 1, SEL_DIAG = 2 };
+int launch_select_gcta(hipStream_t st, const PanelGeom &g, const double *num, const uint32_t *miss, const uint32_t *miss_diag,
+                       const unsigned long long *d_nlocus, const double *colterm, const double *uvterm, const SelectArgs &s, SelPass pass,
+                       double *diag);
+int launch_select_cov(hipStream_t st, const PanelGeom &g, const double *num, double scale, const SelectArgs &s, SelPass pass, double *diag);
+int launch_select_eigmix(hipStream_t st, const PanelGeom &g, const double *num, const double *dd, const uint32_t *het, const double *dmiss,
+                         const double *dsq, const double *d_sumden, int diagadj, double scale, const SelectArgs &s, SelPass pass, double *diag);
+int launch_select_beta(hipStream_t st, const PanelGeom &g, const uint32_t *acc, int mode, double avg, double mn, const SelectArgs &s,
+                       SelPass pass, double *diag);
 int launch_mirror_diag_tiles(hipStream_t st, const PanelGeom &g, double *num, int T);
 
 // context-level pieces shared between the ctx_*.hip files, eigen.hip and multi.hip
@@ -401,6 +413,16 @@ struct HomoTerms { double fscale; const double *w_const, *msum; const uint32_t *
 HomoTerms homo_terms(snpgpu_ctx *c);
 // the refusals of a selection that need neither a context nor a device (ctx_select.hip); `fn`: the public name
 int select_check_opts(const char *fn, const snpgpu_sel_opts *o, int64_t capacity, const void *const *outs, int n_outs);
+int select_grm_check_opts(const char *fn, const snpgpu_grm_sel_opts *o, int64_t capacity, const void *const *outs, int n_outs);
+// the context kind a GRM selection's `what` accumulates on
+inline int select_grm_kind(int what)
+{
+    return what == SNPGPU_SEL_GRM_GCTA ? SNPGPU_GRM_GCTA : what == SNPGPU_SEL_GRM_EIGENSTRAT ? SNPGPU_PCA_COV : what == SNPGPU_SEL_GRM_EIGMIX ? SNPGPU_EIGMIX
+                                                                                                                                         : SNPGPU_INDIV_BETA;
+}
+// individual beta (ctx_results.hip): the minimum of all raw values and the mean of the off-diagonal ones (launch_beta_reduce), as
+// snpgpu_indiv_beta(mode) takes them; `fn`: the public name
+int beta_terms(snpgpu_ctx *c, int mode, double *avg, double *mn, const char *fn);
 
 struct DevBuf {            // owns its device memory: released with the object, movable, not copyable
     void *p = nullptr;

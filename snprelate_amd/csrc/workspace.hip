@@ -27,6 +27,9 @@ struct WorkSpace {
     // the selection kept by snpgpu_gnrIBDPairs for snpgpu_gnrIBDPairs_get
     std::vector<int32_t> pair_idx1, pair_idx2;
     std::vector<double> pair_v0, pair_v1, pair_kin;
+    std::vector<int32_t> grm_idx1, grm_idx2;            // the sparse GRM of the last snpgpu_gnrGRMPairs
+    std::vector<double> grm_value, grm_diag;
+    double grm_pairs_avg = 0;
 };
 WorkSpace g_ws;
 
@@ -480,6 +483,55 @@ int snpgpu_gnrIBDPairs_get(int32_t *idx1, int32_t *idx2, double *v0, double *v1,
     if (v0) memcpy(v0, g_ws.pair_v0.data(), sizeof(double) * n);
     if (v1) memcpy(v1, g_ws.pair_v1.data(), sizeof(double) * n);
     if (kinship) memcpy(kinship, g_ws.pair_kin.data(), sizeof(double) * n);
+    return 0;
+}
+
+// The sparse GRM of the working space (include/snpgpu.h): one accumulation, a count, then the selection itself, as snpgpu_gnrIBDPairs
+int snpgpu_gnrGRMPairs(const char *method, double cutoff, const uint8_t *samp_sel, int, int, int64_t *n_found)
+{
+    const char *fn = "snpgpu_gnrGRMPairs";
+    if (!method) { set_error(std::string(fn) + ": Invalid 'method'!"); return 1; }
+    snpgpu_grm_sel_opts o{};
+    if (strcmp(method, "GCTA") == 0) o.what = SNPGPU_SEL_GRM_GCTA;
+    else if (strcmp(method, "Eigenstrat") == 0) o.what = SNPGPU_SEL_GRM_EIGENSTRAT;
+    else if (strcmp(method, "EIGMIX") == 0) { o.what = SNPGPU_SEL_GRM_EIGMIX; o.mode = 0; o.scale = 2.0; }      // as snpgpu_gnrGRM
+    else if (strcmp(method, "IndivBeta") == 0) { o.what = SNPGPU_SEL_GRM_INDIV_BETA; o.mode = 2; }
+    else if (strcmp(method, "Corr") == 0) {
+        set_error(std::string(fn) + ": method 'Corr' is not built for the sparse GRM (G_ij / sqrt(G_ii G_jj) needs the diagonal of every column, "
+                                    "which a row panel does not hold)");
+        return 1;
+    } else {
+        set_error(std::string(fn) + ": Invalid 'method' '" + method + "'!");
+        return 1;
+    }
+    if (need_ws(fn)) return 1;
+    o.cutoff = cutoff;
+    o.samp_sel = samp_sel;
+    g_ws.grm_idx1.clear(); g_ws.grm_idx2.clear(); g_ws.grm_value.clear(); g_ws.grm_diag.clear(); g_ws.grm_pairs_avg = 0;
+    CtxGuard g;
+    if (run_stream(select_grm_kind(o.what), 0, &g.c)) return 1;
+    int64_t n = 0;
+    if (snpgpu_select_grm(g.c, &o, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &n)) return 1;
+    g_ws.grm_idx1.resize((size_t)n); g_ws.grm_idx2.resize((size_t)n); g_ws.grm_value.resize((size_t)n);
+    g_ws.grm_diag.resize((size_t)g_ws.n_samp);
+    int64_t again = 0;
+    // (capacity 0 takes no pair output: with no pair found only the diagonal and the average are fetched)
+    if (snpgpu_select_grm(g.c, &o, n, n ? g_ws.grm_idx1.data() : nullptr, n ? g_ws.grm_idx2.data() : nullptr, n ? g_ws.grm_value.data() : nullptr,
+                          g_ws.grm_diag.data(), &g_ws.grm_pairs_avg, &again))
+        return 1;
+    if (again != n) { set_error(std::string(fn) + ": the selection changed between the count and the fetch"); return 1; }
+    if (n_found) *n_found = n;
+    return 0;
+}
+
+int snpgpu_gnrGRMPairs_get(int32_t *idx1, int32_t *idx2, double *value, double *diag, double *avg_val)
+{
+    const size_t n = g_ws.grm_idx1.size();
+    if (idx1 && n) memcpy(idx1, g_ws.grm_idx1.data(), sizeof(int32_t) * n);
+    if (idx2 && n) memcpy(idx2, g_ws.grm_idx2.data(), sizeof(int32_t) * n);
+    if (value && n) memcpy(value, g_ws.grm_value.data(), sizeof(double) * n);
+    if (diag && !g_ws.grm_diag.empty()) memcpy(diag, g_ws.grm_diag.data(), sizeof(double) * g_ws.grm_diag.size());
+    if (avg_val) *avg_val = g_ws.grm_pairs_avg;
     return 0;
 }
 
