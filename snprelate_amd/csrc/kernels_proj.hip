@@ -7,12 +7,10 @@
 // sample / the scaled loadings of that SNP) is wave-uniform -> scalar loads, SGPR operands of the fp64
 // FMAs; the 64 two-bit codes of a step are 16 wave-uniform bytes (sample-major words w2 for the SNP
 // kernels, the SNP-major packed rows for the sample kernel), each lane shifts out its own code.
+#include "proj_grid.h"
 #include "snpgpu_internal.h"
 
 namespace snpgpu {
-
-constexpr int PJ_KC_CORR = 8;     // output columns per wave pass of the SNP-side kernels (16 measured slower)
-constexpr int PJ_KC = 16;         //   ... of the sample-side kernel
 
 // code of lane l in a 16-byte group: dword l >> 4, bits 2 * (l & 15)
 __device__ __forceinline__ uint32_t lane_code(uint32_t w, int sh) { return (w >> sh) & 3u; }
@@ -143,16 +141,9 @@ int launch_proj_snp(hipStream_t st, int corr, const uint32_t *w2, int64_t ncols_
                     const double *ext_scale)
 {
     if (n_snp <= 0 || k <= 0) return 0;
-    const int kc = PJ_KC_CORR;
-    const int64_t gx = (n_snp + 255) / 256, gy = (k + kc - 1) / kc;
-    // about 8 waves per SIMD: split the samples when SNP groups x column passes are few
-    int64_t split = (8192 + gx * 4 * gy - 1) / (gx * 4 * gy);
-    if (split < 1) split = 1;
-    if (split > 64) split = 64;
-    int64_t per = ((N + split - 1) / split + 7) & ~(int64_t)7;
-    if (per < 256) per = 256;
-    split = (N + per - 1) / per;
-    dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)split);
+    const ProjGrid gr = proj_snp_grid(N, n_snp, k);
+    const int64_t per = gr.per;
+    dim3 grid((unsigned)gr.gx, (unsigned)gr.gy, (unsigned)gr.split);
     if (corr) {
         SNPGPU_HIP_CHECK(hipMemsetAsync(part, 0, sizeof(double) * 3 * (size_t)n_snp * (size_t)k, st));
         SNPGPU_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int) * 3 * (size_t)n_snp, st));
@@ -224,16 +215,9 @@ int launch_proj_samp(hipStream_t st, const uint8_t *packed, int64_t RB, int64_t 
                      int kp, int k, const double *af, const double *sc, double *out)
 {
     if (n_snp <= 0 || k <= 0) return 0;
-    const int64_t groups = (N + 63) / 64;
-    // enough waves to fill the chip: split the SNP range when there are few sample groups
-    int64_t split = (4096 + groups - 1) / groups;
-    if (split < 1) split = 1;
-    if (split > 64) split = 64;
-    int64_t per = (n_snp + split - 1) / split;
-    if (per < 64) per = 64;
-    split = (n_snp + per - 1) / per;
-    dim3 grid((unsigned)((groups + 3) / 4), (unsigned)((k + PJ_KC - 1) / PJ_KC), (unsigned)split);
-    hipLaunchKernelGGL(proj_samp_kernel, grid, dim3(256), 0, st, packed, RB, N, n_snp, per, sl, kp, k, af, sc, out);
+    const ProjGrid gr = proj_samp_grid(N, n_snp, k);
+    dim3 grid((unsigned)gr.gx, (unsigned)gr.gy, (unsigned)gr.split);
+    hipLaunchKernelGGL(proj_samp_kernel, grid, dim3(256), 0, st, packed, RB, N, n_snp, gr.per, sl, kp, k, af, sc, out);
     SNPGPU_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import oracle as orc
+import proj_ref
 from conftest import GOLDEN, synth_geno
 
 pytestmark = pytest.mark.gpu
@@ -172,12 +173,17 @@ def test_projector_vs_oracle_synthetic():
             np.testing.assert_allclose(af, ra, rtol=1e-14)
             np.testing.assert_allclose(sc, rs, rtol=1e-14)
             np.testing.assert_allclose(load, rl, rtol=1e-10, atol=1e-12)
+            # ... and the long-double reference at the bound of fp64 summation in any order (tests/proj_ref.py)
+            xl, _, _, xb = proj_ref.snp_loading(g, ev * np.sqrt((n - 1) / tr / w)[:, None], bayes)
+            assert (np.abs(load - xl) <= xb).all()
         sload = rl * 0.37
     with _lib.Projector(n, k, max_block_snps=1024) as p:
         for a, b in blocks:
             p.samp_loading_feed(g[a:b], sload[a:b], ra[a:b], rs[a:b])
         got = p.samp_loading()
     np.testing.assert_allclose(got, orc.pca_samp_loading(g, sload, ra, rs), rtol=1e-10, atol=1e-11)
+    xs, xb = proj_ref.add_feeds([proj_ref.samp_loading(g[a:b], sload[a:b], ra[a:b], rs[a:b]) for a, b in blocks])
+    assert (np.abs(got - xs) <= xb).all()
 
 
 def test_eigmix_loadings_vs_oracle(hapmap):

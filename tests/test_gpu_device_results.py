@@ -22,6 +22,7 @@ import pytest
 
 import mem_kinds as M
 import oracle as orc
+import proj_ref
 from conftest import synth_geno
 
 pytestmark = pytest.mark.gpu
@@ -602,9 +603,11 @@ def test_projector_device():
             keep_evs, evs_ptr = _dev(evs)
             p.set_eigvec(evs_ptr)
             rl, ra, rs = orc.pca_snp_loading(g, w, ev, tr, bayesian=bayes)
+            xl, _, _, xb = proj_ref.snp_loading(g, evs, bayes)       # in long double, with the bound of fp64 summation in any order
 
             def oracle(r, a, b):
                 np.testing.assert_allclose(r[0], rl[a:b], rtol=1e-10, atol=1e-12)
+                assert (np.abs(r[0] - xl[a:b]) <= xb[a:b]).all()
                 if r[1] is not None:
                     np.testing.assert_allclose(r[1], ra[a:b], rtol=1e-14)
                 if r[2] is not None:

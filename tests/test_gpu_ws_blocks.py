@@ -1,7 +1,8 @@
 """The block loop of the genotype working space (csrc/workspace.hip, ws_for_each_block): offsets and lengths at the 8192-SNP block
 boundaries, under an identity selection and under a snpgpu_ws_sel_snp_base filter that leaves the selected rows non-contiguous.
 37 samples (not a multiple of 4: every 2-bit row ends in padding codes), 2 % missing calls, monomorphic and all-missing SNPs at the
-start of the pool and around the first block boundary.  Everything is compared with numpy or with the oracle functions of the
+start of the pool and around the first block boundary; the per-block calls that index a caller's per-SNP vectors (the PCA and the
+EIGMIX loadings, both directions) get vectors that differ from SNP to SNP.  Everything is compared with numpy or with the oracle functions of the
 golden tests; the per-SNP references are computed once for the whole pool and indexed by the selected rows."""
 import ctypes
 
@@ -37,6 +38,7 @@ def pool():
     ev = np.random.default_rng(5).normal(size=(K, N_SAMP))
     load, avg, scale = orc.pca_snp_loading(g, EIGVAL, ev, TRACE)
     return dict(g=g, packed=np.ascontiguousarray(pack_2bit_rows(g)), af=af, maf=maf, mr=mr, keep=(num > 0) & (maf > 0), ev=ev,
+                eigmix_af=np.where(np.isnan(af), 0.5, af),
                 corr=orc.pca_snp_corr(g, ev), load=load, avg=avg, scale=scale)
 
 
@@ -91,5 +93,15 @@ def test_ws_block_boundaries(pool, n_sel, filtered):
         got = np.empty((K, N_SAMP), np.float64)
         _lib.check(L.snpgpu_gnrPCASampLoading(K, p(sload), p(ra), p(rs), 1, 0, p(got)))
         np.testing.assert_allclose(got, orc.pca_samp_loading(g, sload, ra, rs), rtol=1e-10, atol=1e-11)
+
+        # the EIGMIX twins hand avg + i0 and scale + i0 of their own vectors to every block
+        eaf = np.ascontiguousarray(pool["eigmix_af"][idx])
+        assert 0 < eaf[0] < 1                                    # (the one-SNP case has a finite scale)
+        eload = np.empty((n_sel, K), np.float64)
+        _lib.check(L.snpgpu_gnrEigMixSNPLoading(p(EIGVAL), p(ev), K, p(eaf), 1, 0, p(eload)))
+        np.testing.assert_allclose(eload, orc.eigmix_snp_loading(g, EIGVAL, ev, eaf), rtol=1e-10, atol=1e-12)
+        got = np.empty((K, N_SAMP), np.float64)
+        _lib.check(L.snpgpu_gnrEigMixSampLoading(K, p(sload), p(eaf), 1, 0, p(got)))
+        np.testing.assert_allclose(got, orc.eigmix_samp_loading(g, sload, eaf), rtol=1e-10, atol=1e-11)
     finally:
         L.snpgpu_ws_clear()
