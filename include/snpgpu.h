@@ -1237,6 +1237,46 @@ int snpgpu_diag_plan(int kind, int64_t n_samp, const snpgpu_opts *opts, int64_t 
  * the same result up to rounding).  0 for contexts without the scratch.  Waits for the context's stream. */
 int snpgpu_diag_carry_fallbacks(snpgpu_ctx *ctx, int64_t *count, int reset);
 
+/* ---- 1r. PC-Relate: ancestry-adjusted kinship (no reference counterpart) ------------------------------------
+ * Kinship, k0, k2 and inbreeding from genotype residuals under individual-specific allele frequencies (Conomos, Reiner, Weir,
+ * Thornton, AJHG 2016), fp64 throughout.  V = [1, pcs] is n_samp x (n_pc + 1); per SNP s, with T the training samples:
+ *   f_s = sum_{i in T, called} g_is / (2 #{i in T called}); g~_is = g_is where called, else 2 f_s; a SNP without a called training
+ *   sample contributes nothing.  beta_s = sum_{i in T} g~_is W_i with W = V_T (V_T^T V_T)^-1 (made on the host at creation);
+ *   mu_is = (beta_s0 + sum_d beta_sd V_id) / 2; (i, s) is valid iff called and maf_thresh <= mu_is <= 1 - maf_thresh.
+ * Over the valid (i, s), with R = g - 2 mu, c = mu (1 - mu), S = sqrt(c), gD = mu / 0 / 1 - mu for g = 0 / 1 / 2, I0 = [g = 0],
+ * I2 = [g = 2], A = mu^2, B = (1 - mu)^2, the n x n planes summed over all SNPs fed are, in the order of snpgpu_pcr_sums,
+ *   0 RR = sum R_i R_j   1 SS = sum S_i S_j   2 DD = sum gD_i gD_j   3 DC = sum gD_i c_j (not symmetric)   4 CC = sum c_i c_j
+ *   5 IBS0 = sum (I0_i I2_j + I2_i I0_j)   6 K0D = sum (A_i B_j + B_i A_j)   7 NS = the SNPs valid for both
+ * and kinship = RR / (4 SS); inbreed_i = 2 kinship_ii - 1; with e_i = 1 + inbreed_i,
+ *   k2 = (DD_ij - e_j DC_ij - e_i DC_ji + e_i e_j CC_ij) / CC_ij; k0 = IBS0 / K0D where kinship < 2^(-5/2), else 1 - 4 kinship + k2.
+ * A zero denominator gives NaN.  The diagonal goes through the same expressions: its kinship is (1 + f_i) / 2, its k0 and k2 carry
+ * no meaning.  Not built: the small-sample correction, per-variant scaling, row panels and multi-device objects, results in device
+ * memory, a sparse selection on the device, anything below fp64.
+ * Every sum has one owner and a fixed order (no atomics): the same feeds give the same bits.  A feed is cut into internal blocks
+ * whose nine operand planes stay within SNPGPU_PCR_STAGE_BYTES (environment, read at creation; default 1 GiB, at least 16 SNPs).
+ * Argument errors are refused before any HIP call; planes that do not fit the device's free memory are refused with both figures. */
+typedef struct snpgpu_pcr snpgpu_pcr;
+enum { SNPGPU_PCR_IBD = 1 };   /* also accumulate DD, DC, CC, IBS0, K0D; without it only RR, SS, NS */
+/* pcs: host [n_samp][n_pc], 0 <= n_pc <= 32, all finite; training: host [n_samp] (non-zero = in T) or NULL = all, at least
+ * n_pc + 2 samples; maf_thresh inside (0, 0.5); opts: device and stream are read.  Collinear PCs in T are refused. */
+int snpgpu_pcr_create(int64_t n_samp, int n_pc, const double *pcs, const uint8_t *training, double maf_thresh, int flags,
+                      const snpgpu_opts *opts, snpgpu_pcr **out);
+/* n_snp rows (SNPGPU_GENO_PACKED2 or SNPGPU_GENO_U8, host or device memory, as snpgpu_ld_feed takes them); returns when they have
+ * been read.  beta: host [n_snp][n_pc + 1] receiving the regression coefficients of these SNPs, or NULL */
+int snpgpu_pcr_feed(snpgpu_pcr *pcr, const void *geno, int64_t n_snp, int format, int mem, double *beta);
+/* host arrays, any may be NULL: kinship, k0, k2, nsnp n x n (row-major, full), inbreed [n].  k0 / k2 need SNPGPU_PCR_IBD.  May be
+ * called between feeds. */
+int snpgpu_pcr_result(snpgpu_pcr *pcr, double *kinship, double *inbreed, double *k0, double *k2, double *nsnp);
+/* one accumulated plane as a full host n x n matrix, `which` in the order above (2 ... 6 need SNPGPU_PCR_IBD) */
+int snpgpu_pcr_sums(snpgpu_pcr *pcr, int which, double *plane);
+/* stats[0] internal blocks, [1] product launches, [2] .. [5] HIP-event ms of the beta, operand, product and finaliser phases,
+ * [6] bytes of the resident planes, [7] SNPs of an internal block -- since creation */
+int snpgpu_pcr_stats(snpgpu_pcr *pcr, double *stats);
+int snpgpu_pcr_destroy(snpgpu_pcr *pcr);
+/* create / feed / result on the working space's selected SNPs and device (fed in its blocks) */
+int snpgpu_gnrPCRelate(int n_pc, const double *pcs, const uint8_t *training, double maf_thresh, int flags,
+                       double *kinship, double *inbreed, double *k0, double *k2, double *nsnp);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,8 @@ EXPORTS = [
     "snpgpu_gen_genotypes", "snpgpu_gen_line_host", "snpgpu_gen_stats",
     "snpgpu_grm_merge_stats",
     "snpgpu_mds", "snpgpu_mds_apply", "snpgpu_gnrMDS", "snpgpu_mds_stats",
+    "snpgpu_pcr_create", "snpgpu_pcr_feed", "snpgpu_pcr_result", "snpgpu_pcr_sums", "snpgpu_pcr_stats", "snpgpu_pcr_destroy",
+    "snpgpu_gnrPCRelate",
 ]
 FST_WC84, FST_WH02 = 1, 2
 FST_METHODS = ("W&C84", "W&H02")
@@ -84,6 +86,8 @@ PAIR_ELEM_INT32, PAIR_ELEM_BIT2 = 0, 1
 SEL_KING_ROBUST, SEL_KING_HOMO, SEL_MOM = 1, 2, 3
 SEL_GRM_GCTA, SEL_GRM_EIGENSTRAT, SEL_GRM_EIGMIX, SEL_GRM_INDIV_BETA = 1, 2, 3, 4
 LDSCORE_ADJUST, LDSCORE_SELF = 1, 2
+PCR_IBD = 1
+PCR_PLANES = ("RR", "SS", "DD", "DC", "CC", "IBS0", "K0D", "NS")      # snpgpu_pcr_sums' `which` = index
 
 
 class SnpGpuError(RuntimeError):
@@ -361,6 +365,13 @@ def lib():
     L.snpgpu_mds_apply.argtypes = [vp, i64, i64, c_int, vp, c_int, vp, c_int]
     L.snpgpu_gnrMDS.argtypes = [c_int, c_int, vp, vp, vp, ctypes.POINTER(dbl), ctypes.POINTER(c_int)]
     L.snpgpu_mds_stats.argtypes = [vp]
+    L.snpgpu_pcr_create.argtypes = [i64, c_int, vp, vp, dbl, c_int, ctypes.POINTER(Opts), ctypes.POINTER(vp)]
+    L.snpgpu_pcr_feed.argtypes = [vp, vp, i64, c_int, c_int, vp]
+    L.snpgpu_pcr_result.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.snpgpu_pcr_sums.argtypes = [vp, c_int, vp]
+    L.snpgpu_pcr_stats.argtypes = [vp, vp]
+    L.snpgpu_pcr_destroy.argtypes = [vp]
+    L.snpgpu_gnrPCRelate.argtypes = [c_int, vp, vp, dbl, c_int, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -2137,3 +2148,94 @@ def mds_stats():
     s = _stats("mds", 9)
     return dict(stage_ms=float(s[0]), scan_ms=float(s[1]), eigen_ms=float(s[2]), total_ms=float(s[3]), route=int(s[4]),
                 products=int(s[5]), product_ms=float(s[6]), windows=int(s[7]), pos_tol=float(s[8]))
+
+
+def _pcr_inputs(pcs, training, n_samp):
+    """(pcs as float64 [n][n_pc] or None, n_pc, training as uint8 [n] or None) of the PC-Relate calls"""
+    n_samp = int(n_samp)
+    p = None if pcs is None else np.ascontiguousarray(pcs, np.float64)
+    if p is not None and p.ndim == 1:
+        p = p.reshape(n_samp, -1) if p.size else None
+    if p is not None and (p.ndim != 2 or p.shape[0] != n_samp):
+        raise ValueError("'pcs' should have one row per sample")
+    t = None
+    if training is not None:
+        t = np.ascontiguousarray(np.asarray(training) != 0, np.uint8)
+        if t.shape != (n_samp,):
+            raise ValueError("'training' should have one flag per sample")
+    return p, (0 if p is None else int(p.shape[1])), t
+
+
+class PCRelate:
+    """One streaming PC-Relate object (snpgpu_pcr, include/snpgpu.h section 1r): feed SNP blocks, then result() / sums()."""
+
+    def __init__(self, n_samp, pcs=None, training=None, maf_thresh=0.01, ibd=True, device=0, stream=None):
+        self.n = int(n_samp)
+        p, self.n_pc, t = _pcr_inputs(pcs, training, self.n)
+        self.ibd = bool(ibd)
+        o = Opts(int(device), 0, 0, 0, 0, ctypes.c_void_p(stream) if stream else None)
+        h = ctypes.c_void_p()
+        self._h = None
+        check(lib().snpgpu_pcr_create(self.n, self.n_pc, _ptr(p), _ptr(t), float(maf_thresh), PCR_IBD if self.ibd else 0, ctypes.byref(o),
+                                      ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if self._h:
+            lib().snpgpu_pcr_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def feed(self, geno, fmt=None, n_snp=None, want_beta=False):
+        """geno: numpy uint8 rows (U8 or PACKED2) or a device address (int, with n_snp; PACKED2 unless fmt says U8).  want_beta: the
+        regression coefficients [n_snp][n_pc + 1] of these SNPs are returned."""
+        ptr, m, fmt, mem, _keep = _geno_input(geno, self.n, fmt, n_snp, device_fmt_default=GENO_PACKED2)
+        beta = np.empty((m, self.n_pc + 1), np.float64) if want_beta else None
+        check(lib().snpgpu_pcr_feed(self._h, ptr, m, fmt, mem, _ptr(beta)))
+        return beta
+
+    def result(self, probs=None):
+        """dict(kinship, inbreed, nsnp and -- probs, by default where the object accumulates them -- k0, k2)"""
+        probs = self.ibd if probs is None else bool(probs)
+        n = self.n
+        r = dict(kinship=np.empty((n, n), np.float64), inbreed=np.empty(n, np.float64), nsnp=np.empty((n, n), np.float64))
+        if probs:
+            r.update(k0=np.empty((n, n), np.float64), k2=np.empty((n, n), np.float64))
+        check(lib().snpgpu_pcr_result(self._h, _ptr(r["kinship"]), _ptr(r["inbreed"]), _ptr(r.get("k0")), _ptr(r.get("k2")), _ptr(r["nsnp"])))
+        return r
+
+    def sums(self, which):
+        """one accumulated plane (a name of PCR_PLANES or its index) as a full n x n matrix"""
+        w = PCR_PLANES.index(which) if isinstance(which, str) else int(which)
+        out = np.empty((self.n, self.n), np.float64)
+        check(lib().snpgpu_pcr_sums(self._h, w, _ptr(out)))
+        return out
+
+    def stats(self):
+        s = np.zeros(8, np.float64)
+        check(lib().snpgpu_pcr_stats(self._h, _ptr(s)))
+        return dict(blocks=int(s[0]), product_launches=int(s[1]), beta_ms=s[2], operand_ms=s[3], product_ms=s[4], final_ms=s[5],
+                    plane_bytes=int(s[6]), block_snps=int(s[7]))
+
+
+def gnr_pcrelate(n_samp, pcs=None, training=None, maf_thresh=0.01, ibd=True):
+    """snpgpu_gnrPCRelate on the working space of n_samp samples: the dict of PCRelate.result()"""
+    n = int(n_samp)
+    p, n_pc, t = _pcr_inputs(pcs, training, n)
+    r = dict(kinship=np.empty((n, n), np.float64), inbreed=np.empty(n, np.float64), nsnp=np.empty((n, n), np.float64))
+    if ibd:
+        r.update(k0=np.empty((n, n), np.float64), k2=np.empty((n, n), np.float64))
+    check(lib().snpgpu_gnrPCRelate(n_pc, _ptr(p), _ptr(t), float(maf_thresh), PCR_IBD if ibd else 0, _ptr(r["kinship"]), _ptr(r["inbreed"]),
+                                   _ptr(r.get("k0")), _ptr(r.get("k2")), _ptr(r["nsnp"])))
+    return r

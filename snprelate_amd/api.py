@@ -1033,7 +1033,7 @@ def snpgdsPairIBDMLELogLik(geno1, geno2, allele_freq, k0=float("nan"), k1=float(
     return ll
 
 
-_IBD_NOT_PER_PAIR = ("sample_id", "snp_id", "afreq")
+_IBD_NOT_PER_PAIR = ("sample_id", "snp_id", "afreq", "inbreed")
 
 
 def _full_matrix(x, n, name):
@@ -2747,3 +2747,57 @@ def snpgdsMDS(obj, k=2, method="ibs", sample_id=None, snp_id=None, autosome_only
         gof = np.array([w.sum() / np.abs(a).sum(), w.sum() / np.maximum(a, 0).sum()])
     return dict(sample_id=None if sample_id is None else np.asarray(sample_id), points=points, eigenval=w, GOF=gof, trace=r["trace"],
                 n_pos=k1, route=r["route"])
+
+
+def snpgdsPCRelate(gdsobj, pcs, n_pcs=None, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True,
+                   maf=float("nan"), missing_rate=float("nan"), training_id=None, maf_thresh=0.01, ibd_probs=True, verbose=True,
+                   device=0):
+    """Ancestry-adjusted relatedness by PC-Relate (Conomos, Reiner, Weir, Thornton, AJHG 2016) on the GPU (snpgpu_gnrPCRelate,
+    include/snpgpu.h section 1r; no reference counterpart, and agreement with another package's output is not tested: the
+    definitions of DESIGN.md 31 are the specification).  Every SNP is regressed on the leading principal components over the
+    training samples; kinship, k0, k2 and inbreeding come from the residuals under individual-specific allele frequencies.
+
+    pcs: a snpgdsPCA / snpgdsEIGMIX result (its rows are matched to the selected samples by sample_id and the first n_pcs columns
+    of eigenvect are used; all of them by default) or an array with one row per selected sample, in their order (n_pcs columns of
+    it; an array without columns, or n_pcs = 0, adjusts for nothing but the mean).  training_id: the samples the regression is
+    fitted on (unrelated ones, as a rule), all by default.  maf_thresh: an (individual, SNP) whose individual-specific frequency
+    lies outside [maf_thresh, 1 - maf_thresh] is left out.  ibd_probs=False accumulates the kinship planes only (3 of 8).
+    Returns dict(sample_id, snp_id, kinship, k0, k1, k2, nsnp, inbreed): n x n matrices and inbreed [n]; k0 / k1 / k2 are None
+    without ibd_probs.  The diagonal of kinship is (1 + inbreed) / 2, that of k0 / k1 / k2 carries no meaning.
+    snpgdsIBDSelection(result, kinship_cutoff) tabulates it like any IBD object."""
+    ws = _init_file2("PC-Relate: kinship adjusted for principal components:", gdsobj, sample_id, snp_id, autosome_only, remove_monosnp,
+                     maf, missing_rate, 1, verbose, device)
+    n = ws["n_samp"]
+    ids = np.asarray(ws["sample_id"])
+    if isinstance(pcs, dict):
+        if "eigenvect" not in pcs or "sample_id" not in pcs or pcs["eigenvect"] is None:
+            raise TypeError("'pcs' should be a snpgdsPCA / snpgdsEIGMIX result or an array with one row per sample")
+        pid = np.asarray(pcs["sample_id"])
+        order = np.argsort(pid, kind="stable")
+        pos = np.searchsorted(pid[order], ids)
+        pos[pos >= len(pid)] = 0
+        if len(pid) == 0 or not np.array_equal(pid[order][pos], ids):
+            raise ValueError("Some of the selected samples are not in 'pcs$sample.id'.")
+        mat = np.asarray(pcs["eigenvect"], np.float64)[order[pos]]
+    else:
+        mat = np.asarray(pcs, np.float64)
+        if mat.ndim == 1:
+            mat = mat.reshape(n, -1) if mat.size else mat.reshape(n, 0)
+        if mat.ndim != 2 or mat.shape[0] != n:
+            raise ValueError("'pcs' should have one row per selected sample (%d)" % n)
+    if n_pcs is not None:
+        if isinstance(n_pcs, bool) or not isinstance(n_pcs, (int, np.integer)) or n_pcs < 0 or n_pcs > mat.shape[1]:
+            raise ValueError("'n_pcs' should be in 0 .. %d" % mat.shape[1])
+        mat = mat[:, :int(n_pcs)]
+    mat = np.ascontiguousarray(mat)
+    train = None
+    if training_id is not None:
+        want = np.asarray(training_id)
+        train = np.isin(ids, want)
+        if int(train.sum()) != len(np.unique(want)):
+            raise ValueError("Some of training.id do not exist!")
+    _cat(verbose, "    # of principal components: %d\n    # of training samples: %d" % (mat.shape[1], n if train is None else int(train.sum())))
+    r = _lib.gnr_pcrelate(n, mat if mat.shape[1] else None, train, maf_thresh=maf_thresh, ibd=bool(ibd_probs))
+    k0, k2 = r.get("k0"), r.get("k2")
+    return dict(sample_id=ids, snp_id=ws["snp_id"], kinship=r["kinship"], k0=k0, k1=None if k0 is None else 1.0 - k0 - k2, k2=k2,
+                nsnp=r["nsnp"], inbreed=r["inbreed"])
