@@ -129,8 +129,10 @@ int snpgpu_host_wait(snpgpu_ctx *ctx, const void *host_buf);
 int snpgpu_counts(snpgpu_ctx *ctx, int64_t *n_snp_total, int64_t *n_locus);
 /* Optional HIP-event timing of the dominant pair kernel launches inside snpgpu_feed
  * (events are recorded on the context's stream around each launch).  `which`: 0 = bit-plane
- * pair kernel, 1 = MFMA SYRK kernel.  Returns the summed kernel time and launch count since
- * timing was (re-)enabled. */
+ * pair kernel, 1 = MFMA SYRK kernel.  Returns the summed kernel time and the number of timed
+ * spans since timing was (re-)enabled: one span per feed block for the counters, one per table and
+ * feed block for the SYRK family, whatever number of kernel launches a span holds
+ * (snpgpu_diag_syrk_launches counts those). */
 int snpgpu_set_timing(snpgpu_ctx *ctx, int enable);
 int snpgpu_get_timing(snpgpu_ctx *ctx, int which, double *ms_sum, int64_t *launches);
 /* size (elements) of the packed slab this context's panel produces */
@@ -1276,6 +1278,11 @@ int snpgpu_pcr_destroy(snpgpu_pcr *pcr);
 /* create / feed / result on the working space's selected SNPs and device (fed in its blocks) */
 int snpgpu_gnrPCRelate(int n_pc, const double *pcs, const uint8_t *training, double maf_thresh, int flags,
                        double *kinship, double *inbreed, double *k0, double *k2, double *nsnp);
+
+/* Diagnostic: kernel launches of the SYRK family that the feeds of this context have enqueued since it was created -- with
+ * SNPGPU_RUN_INNER=0 one per fp32 run of a block, otherwise one per block and kernel.  snpgpu_get_timing's `launches` counts the
+ * timed spans instead: one per table and feed block. */
+int snpgpu_diag_syrk_launches(snpgpu_ctx *ctx, int64_t *count);
 
 #ifdef __cplusplus
 }

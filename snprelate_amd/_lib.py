@@ -74,6 +74,7 @@ EXPORTS = [
     "snpgpu_mds", "snpgpu_mds_apply", "snpgpu_gnrMDS", "snpgpu_mds_stats",
     "snpgpu_pcr_create", "snpgpu_pcr_feed", "snpgpu_pcr_result", "snpgpu_pcr_sums", "snpgpu_pcr_stats", "snpgpu_pcr_destroy",
     "snpgpu_gnrPCRelate",
+    "snpgpu_diag_syrk_launches",
 ]
 FST_WC84, FST_WH02 = 1, 2
 FST_METHODS = ("W&C84", "W&H02")
@@ -186,6 +187,7 @@ def lib():
     L.snpgpu_diag_device_pci.argtypes = [c_int, ctypes.c_char_p, c_int]
     L.snpgpu_diag_plan.argtypes = [c_int, i64, ctypes.POINTER(Opts), i64, ctypes.c_char_p, c_int]
     L.snpgpu_diag_carry_fallbacks.argtypes = [vp, ctypes.POINTER(i64), c_int]
+    L.snpgpu_diag_syrk_launches.argtypes = [vp, ctypes.POINTER(i64)]
     L.snpgpu_synth_block.argtypes = [vp, i64, i64, i64, ctypes.c_uint32, dbl, c_int, c_int, c_int, vp]
     L.snpgpu_create.argtypes = [c_int, i64, ctypes.POINTER(Opts), ctypes.POINTER(vp)]
     L.snpgpu_destroy.argtypes = [vp]
@@ -615,6 +617,12 @@ class Accumulator:
         (snpgpu_diag_carry_fallbacks; 0 for contexts without the scratch)."""
         n = ctypes.c_int64(0)
         check(lib().snpgpu_diag_carry_fallbacks(self._h, ctypes.byref(n), int(bool(reset))))
+        return n.value
+
+    def syrk_launches(self):
+        """Kernel launches of the SYRK family enqueued by this context's feeds since it was created (snpgpu_diag_syrk_launches)."""
+        n = ctypes.c_int64(0)
+        check(lib().snpgpu_diag_syrk_launches(self._h, ctypes.byref(n)))
         return n.value
 
     def set_timing(self, on=True):

@@ -291,12 +291,14 @@ static int feed_syrk(snpgpu_ctx *c, int64_t n_snp)
             o.copy_lut_bytes = one_w ? 0 : (int64_t)((const char *)c->homo_lut[1].p - (const char *)c->homo_lut[0].p);
             o.copy_acc_elems = c->plane();
             o.form = p.homo_form;
+            o.n_launched = &c->syrk_launches;
             EvScope ev(c, 1);      // (one span per table, as the timing has always counted them)
             if (i == 0 && launch_syrk_uv(st, c->syrk_panel(c->wt, 0), o)) return 1;
             continue;
         }
         EvScope ev(c, 1);
         if (!p.mm_h3) {
+            c->syrk_launches++;
             if (launch_syrk(st, c->tg_mm, wt, p.ncols_pad, (const float2 *)c->lut[i].p, b.n_q, c->plane_f64(i), p.ncols_pad, p.acc_tiles_c, skip))
                 return 1;
             continue;
@@ -312,6 +314,7 @@ static int feed_syrk(snpgpu_ctx *c, int64_t n_snp)
         h.promote_snps = p.h3_promote;
         h.work_x1 = (x1m && c->x1_blocks) ? (const int4 *)c->x1_work.p : nullptr; h.n_blocks_x1 = c->x1_blocks;
         h.d_short_runs = (i == 0 && short_runs) ? c->d_short_runs() : nullptr;
+        h.n_launched = &c->syrk_launches;
         if (launch_syrk_h3(st, c->syrk_panel(x1e ? c->wt12 : c->wt, i), h)) return 1;
         if (uv) {
             SyrkUvOpts o;
@@ -321,6 +324,7 @@ static int feed_syrk(snpgpu_ctx *c, int64_t n_snp)
             o.run_chunks = b.uv_runs > 1 ? b.uv_cpr : 0; o.n_target = b.uv_q;
             o.form = p.uv_form;
             o.pace_src = c->uvpace.p; o.pace = p.uvc_pace;
+            o.n_launched = &c->syrk_launches;
             if (p.uvc_carry_all) { o.carry_scr = c->uvcarry.p; o.carry_flags = (unsigned int *)c->uvcarry_flags.p; o.carry_slots = p.uvc_carry_slots; }
             if (launch_syrk_uv(st, c->syrk_panel(c->wt, i), o)) return 1;
         }

@@ -385,6 +385,7 @@ struct snpgpu_ctx {
     double frozen_scale = 1.0;
     void *blas = nullptr;         // rocblas_handle, created on first use
     bool timing = false;
+    int64_t syrk_launches = 0;    // kernel launches of launch_syrk / launch_syrk_h3 / launch_syrk_uv since creation (snpgpu_diag_syrk_launches)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[2];  // [0] pair popcount, [1] SYRK
 
     // feed-block scratch

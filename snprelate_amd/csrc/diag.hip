@@ -308,6 +308,16 @@ extern "C" int snpgpu_diag_carry_fallbacks(snpgpu_ctx *c, int64_t *count, int re
     return 0;
 }
 
+// kernel launches of the SYRK family (launch_syrk, launch_syrk_h3, launch_syrk_uv) since the context was created: host-side count of
+// what was enqueued, whichever of two launches of a block the device flag lets work.  (snpgpu_get_timing counts timed SPANS: one
+// per table and feed block, however many launches the block's fp32 runs take.)
+extern "C" int snpgpu_diag_syrk_launches(snpgpu_ctx *c, int64_t *count)
+{
+    if (!c || !count) { set_error("snpgpu_diag_syrk_launches: invalid arguments"); return 1; }
+    *count = c->syrk_launches;
+    return 0;
+}
+
 // ---- snpgpu_diag_plan: names of the kernels a block takes under a plan (what launch_pair_i8 / launch_syrk_h3 / launch_syrk_uv run)
 static const char *uv_form_kernel(UvForm f)
 {

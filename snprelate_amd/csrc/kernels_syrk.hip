@@ -563,9 +563,12 @@ int launch_syrk_h3(hipStream_t st, const SyrkPanel &p, const SyrkH3Opts &o)
     const int p3 = H3_PROMOTE / H3_LUTCH;                                    // three products: 512-SNP chunks
     const int p2e = (o.promote_snps > 0 ? o.promote_snps : H3_PROMOTE_EXACT) / (H3_LUTCH / 2);   // exact rows: 256-SNP chunks
     const int p2c = H3_PROMOTE / H3_LUTCH;                                   // constant row table: 512-SNP chunks
-    if (o.a_kind < 0 || (o.a_kind == 0 && o.d_missing))
+    int64_t launched = 0;
+    if (o.a_kind < 0 || (o.a_kind == 0 && o.d_missing)) {
+        launched++;
         hipLaunchKernelGGL((syrk_h3_kernel<3, false>), dim3((unsigned)o.n_blocks), dim3(256), 0, st, p.w8, p.ncols_pad, o.lut, o.n_q, p.acc, p.ld, p.tiles_c, o.work,
                            o.d_skip_if_zero, o.a_kind == 0 ? o.d_missing : nullptr, p.n_rows_real, 0, p3);
+    }
     if (o.a_kind == 0 && o.work_x1 && !o.d_missing) {
         const int n_chunk = (o.n_q + (X1_CHS / 16) - 1) / (X1_CHS / 16);       // table chunks of the block; one launch per fp32 run
         const int run = std::max(1, (o.promote_snps > 0 ? o.promote_snps : H3_PROMOTE_EXACT) / X1_CHS);
@@ -580,16 +583,21 @@ int launch_syrk_h3(hipStream_t st, const SyrkPanel &p, const SyrkH3Opts &o)
         for (int k = 0; k < g.count(); k++)
             for (int half = 0; half < (g.group ? 1 : short_div); half++) {   // (one launch per run, short_div = 2: see the kernel's branch for it)
                 const RunLaunch L = g.at(k);
+                launched++;
                 hipLaunchKernelGGL(syrk_x1_kernel, dim3(L.grid), dim3(256), 0, st, p.w8, p.ncols_pad, o.lut, o.n_q, p.acc, p.ld, p.tiles_c, o.work_x1,
                                    o.d_skip_if_zero, p.n_rows_real, L.chunk_lo, L.chunk_hi, L.n_runs, run, g.group ? L.run_group : half, L.n_items8,
                                    short_div > 1 ? o.d_short_runs : nullptr, short_div);
             }
-    } else if (o.a_kind == 0)
+    } else if (o.a_kind == 0) {
+        launched++;
         hipLaunchKernelGGL((syrk_h3_kernel<2, true>), dim3((unsigned)o.n_blocks), dim3(256), 0, st, p.w8, p.ncols_pad, o.lut, o.n_q, p.acc, p.ld, p.tiles_c,
                            o.work, o.d_skip_if_zero, o.d_missing, p.n_rows_real, o.a_kind, p2e > 0 ? p2e : 1);
-    else if (o.a_kind > 0)
+    } else if (o.a_kind > 0) {
+        launched++;
         hipLaunchKernelGGL((syrk_h3_kernel<2, false>), dim3((unsigned)o.n_blocks), dim3(256), 0, st, p.w8, p.ncols_pad, o.lut, o.n_q, p.acc, p.ld, p.tiles_c,
                            o.work, o.d_skip_if_zero, nullptr, p.n_rows_real, o.a_kind, p2c);
+    }
+    if (o.n_launched) *o.n_launched += launched;
     SNPGPU_HIP_CHECK(hipGetLastError());
     return 0;
 }

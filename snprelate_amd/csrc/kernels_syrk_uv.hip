@@ -891,6 +891,7 @@ int launch_syrk_uv(hipStream_t st, const SyrkPanel &p, const SyrkUvOpts &o)
         // a launch of ONE run takes the run's flush factor as an argument; the others find it from the run index and n_target
         const double fscale = (!g.group && o.n_target > 1) ? uv_run_factor(k % o.n_target) : 1.0;
         const int n_target = g.group ? o.n_target : 1;
+        if (o.n_launched) ++*o.n_launched;
         if (uv16 >= 2)
             hipLaunchKernelGGL(syrk_uv16c_kernel, dim3(L.grid), dim3(256), 0, st, p.w8, p.ncols_pad, o.lut, o.n_q, p.acc, p.ld, p.tiles_c, o.work_x1,
                                o.d_missing, p.n_rows_real, L.chunk_lo, L.chunk_hi, fscale, L.n_runs, L.run_chunks, n_target, L.run_group, L.n_items8,

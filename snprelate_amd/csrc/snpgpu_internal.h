@@ -299,6 +299,7 @@ struct SyrkH3Opts {
     const uint2 *lut = nullptr;
     int n_q = 0, a_kind = -1, promote_snps = 0;
     const unsigned long long *d_skip_if_zero = nullptr, *d_missing = nullptr, *d_short_runs = nullptr;
+    int64_t *n_launched = nullptr;               // where given: raised by one per kernel launch (snpgpu_diag_syrk_launches)
 };
 int launch_syrk_h3(hipStream_t st, const SyrkPanel &p, const SyrkH3Opts &o);
 struct SyrkUvOpts {
@@ -316,6 +317,7 @@ struct SyrkUvOpts {
     void *carry_scr = nullptr;                   // ConvertedCarry: the carry scratch (nullptr: off), its flag words, slots per XCD
     unsigned int *carry_flags = nullptr;
     int carry_slots = 0;
+    int64_t *n_launched = nullptr;               // as SyrkH3Opts::n_launched
 };
 int launch_syrk_uv(hipStream_t st, const SyrkPanel &p, const SyrkUvOpts &o);
 int launch_syrk(hipStream_t st, const TileGrid &tg, const uint32_t *w8, int64_t ncols_pad, const float2 *lut,

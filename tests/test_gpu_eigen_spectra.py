@@ -29,6 +29,11 @@ ROUTES = {
     "one_panel": (1, {}, {}),
     "three_panels": (3, {}, {}),
     "fp64_products": (3, {}, {"fp32_until": -1.0}),
+    # the all-fp64 phase by its switch, and fp32 products that convert the fp64 plane on the fly: the form the solver takes by itself
+    # when the device has no room for the fp32 copy of the plane (eigen.hip, ctx_panel_matmul_enqueue) -- at these sizes only the
+    # switches reach them
+    "fp64_phase_by_switch": (3, {"SNPGPU_EIG_FP32": "0"}, {}),
+    "fp32_without_the_copy": (3, {"SNPGPU_EIG_F32_PANEL": "0"}, {}),
     "no_mixed_cycles": (3, {"SNPGPU_EIG_MIXED": "0"}, {}),
     "rocblas_products": (3, {"SNPGPU_EIG_BLAS": "1"}, {}),
     "large_n_algebra": (3, LARGE_N, {}),
@@ -79,10 +84,50 @@ def test_krylov_routes(name, near, kind, route, monkeypatch):
             E.check_topk(w, v, full, k, "%s %s %s k=%d (%d products, %d fp32)" % (DATA_IDS[DATA.index((name, near))], kind, route, k,
                                                                                  info["matmuls"], info["matmuls_fp32"]), ref=ref)
             assert info["max_rel_residual"] < 1e-9
-            if route in ("fp64_products", "rocblas_products"):
+            if route in ("fp64_products", "rocblas_products") or env.get("SNPGPU_EIG_FP32") == "0":
                 assert info["matmuls_fp32"] == 0
+            if env.get("SNPGPU_EIG_F32_PANEL") == "0":
+                assert info["matmuls_fp32"] > 0
     finally:
         _close(panels)
+
+
+def test_fp32_panel_product_without_the_fp32_copy(monkeypatch):
+    """snpgpu_pca_panel_matmul_f32 with SNPGPU_EIG_F32_PANEL=0 (the fp64 plane converted on the fly, no fp32 copy beside it) on the
+    case and at the bound of test_panel_product_fp32_form (tests/test_gpu_api_golden.py): three row panels of 2331 samples, 53
+    vectors, error below 4e-7 of the sum of |terms|.  Whether it equals the copy form bit for bit is printed, not asserted: both
+    round the same fp64 entries to fp32, the copy once and this form at every use."""
+    import torch
+    from snprelate_amd import _lib
+    from snprelate_amd.dist import panel_rows
+    n, L, m = 2331, 900, 53
+    g = synth_geno(n, L, missing=0.02, seed=18)
+    dev = torch.device("cuda", 0)
+    qh = np.random.default_rng(1).normal(size=(m, n)) * (1.0 + np.arange(m)[:, None])
+    q = torch.from_numpy(qh).to(dev)
+    with _lib.Accumulator(_lib.PCA_COV, n, max_block_snps=1024) as a:
+        a.feed(g)
+        cov = orc.tri_to_full(a.pca_cov(packed=True, normalize=False)[0], n)
+    ref = (qh @ cov) * 0.25
+    bounds = panel_rows(n, 3)
+    out = {}
+    for form in ("copy", "on_the_fly"):
+        if form == "on_the_fly":
+            monkeypatch.setenv("SNPGPU_EIG_F32_PANEL", "0")
+        y = torch.zeros_like(q)
+        for r in range(3):
+            with _lib.Accumulator(_lib.PCA_COV, n, row_begin=bounds[r], row_end=bounds[r + 1], max_block_snps=1024) as a:
+                a.feed(g)
+                torch.cuda.synchronize()
+                a.pca_panel_matmul(0.25, q.data_ptr(), m, y.data_ptr(), fp32=True)
+                torch.cuda.synchronize()
+        out[form] = y.cpu().numpy()
+    bound = 0.25 * (np.abs(qh) @ np.abs(cov))
+    err = {form: float((np.abs(y - ref) / bound).max()) for form, y in out.items()}
+    print("fp32 panel product: error / sum |terms| copy %.2e on the fly %.2e (bound 4e-7); bit-equal to the copy form: %s"
+          % (err["copy"], err["on_the_fly"], np.array_equal(out["copy"], out["on_the_fly"])), flush=True)
+    assert err["on_the_fly"] < 4e-7 and err["copy"] < 4e-7, err
+    assert err["on_the_fly"] > 1e-12                                      # it IS an fp32 form
 
 
 @pytest.mark.parametrize("kind", KINDS)

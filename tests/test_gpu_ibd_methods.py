@@ -25,10 +25,12 @@ pytestmark = pytest.mark.gpu
 MAX_NITER_DIFFS = 2
 MARGIN = 1e-11
 MAX_INSIDE = 0.05
+# ... of the non-NaN pairs: what the comparison masks.  The restatement's own figure, from CPU method-of-moments starts
+# (tests/ibd_pairs_ref.py, mode 1) over SIMPLEX_CASES: 0, 1, 1, 1, 0, 0, 0, 0, 2 and 2 of 200 pairs, at most 0.010 of a case.
 
 
 def _compare_simplex(k0, k1, ll, nit, want, reltol, label=""):
-    """the pass criteria of a simplex comparison; returns the fraction of pairs inside the margin"""
+    """the pass criteria of a simplex comparison; returns the fraction of the non-NaN pairs inside the margin"""
     wl = want["loglik"]
     assert np.array_equal(np.isnan(k0), np.isnan(want["k0"])) and np.array_equal(np.isnan(k1), np.isnan(want["k1"]))
     nan = np.isnan(want["k0"])
@@ -46,7 +48,9 @@ def _compare_simplex(k0, k1, ll, nit, want, reltol, label=""):
     assert (rel[firm] <= 1e-9).all(), "max relative loglik difference %g" % rel[firm].max(initial=0)
     convtol = np.maximum(reltol * (np.abs(wl) + abs(reltol)), mref.DBL_EPSILON)      # |y[0]| ~ |L|: the stop test's own scale
     assert (ll[loose] >= wl[loose] - 2 * convtol[loose]).all()
-    return loose.mean()
+    inside = float(loose.sum()) / max(int((~nan).sum()), 1)
+    print("%s: decision margin firm at %.4f of the %d non-NaN pairs (cap on the rest: %.2f)" % (label, 1 - inside, int((~nan).sum()), MAX_INSIDE))
+    return inside
 
 
 def _compare_jacquard(D, ll, nit, want, label=""):

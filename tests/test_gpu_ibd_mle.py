@@ -13,14 +13,29 @@ from snprelate_amd.gds import pack_2bit_rows, unpack_2bit_rows
 pytestmark = pytest.mark.gpu
 
 
-def _compare(k0, k1, niter, r, check_niter=True):
-    """the pass criteria of the reference comparison, on the pairs (r['i'], r['j']) of full n x n results"""
+def _firm_shares(r):
+    """(share of the non-NaN pairs with a firm stopping margin, share with a firm candidate gap), from the reference alone: what the
+    comparison below does NOT mask.  A comparison that demands equality only where the reference is firm goes blind when few pairs are."""
+    ok = ~np.isnan(r["k0"])
+    scale = 1e-9 * np.abs(np.where(np.isfinite(r["loglik"]), r["loglik"], 0))
+    n = max(int(ok.sum()), 1)
+    return float(((r["stop_margin"] > scale) & ok).sum()) / n, float(((r["cand_gap"] > scale) & ok).sum()) / n
+
+
+def _compare(k0, k1, niter, r, check_niter=True, min_firm_stop=None, min_firm_cand=None, what=""):
+    """the pass criteria of the reference comparison, on the pairs (r['i'], r['j']) of full n x n results; min_firm_*: the least share
+    of the non-NaN pairs whose stopping margin / candidate gap must be firm for the comparison to count"""
     i, j = r["i"], r["j"]
     g0, g1 = k0[i, j], k1[i, j]
     assert np.array_equal(np.isnan(g0), np.isnan(r["k0"])) and np.array_equal(np.isnan(g1), np.isnan(r["k1"]))
     scale = 1e-9 * np.abs(np.where(np.isfinite(r["loglik"]), r["loglik"], 0))
     firm_stop = r["stop_margin"] > scale
     firm_cand = r["cand_gap"] > scale
+    share_stop, share_cand = _firm_shares(r)
+    print("%s: firm stopping margin at %.4f of the %d non-NaN pairs, firm candidate gap at %.4f"
+          % (what or "ibd_mle", share_stop, int((~np.isnan(r["k0"])).sum()), share_cand), flush=True)
+    assert min_firm_stop is None or share_stop >= min_firm_stop, "niter is compared at %.4f of the pairs only" % share_stop
+    assert min_firm_cand is None or share_cand >= min_firm_cand, "the coefficients are compared at %.4f of the pairs only" % share_cand
     if check_niter:
         gn = niter[i, j]
         bad = firm_stop & (gn != r["niter"])
@@ -70,7 +85,20 @@ CASES = [
     (130, 1000, 0.0, False, 5, None, True),
     (130, 17, 0.3, True, 1000, None, False),
     (64, 1000, 0.3, True, 1000, 1e-4, True),
+    # The two short cases at 30 % missing calls above leave a pair some eight SNPs: the likelihood is flat, the EM creeps towards
+    # its limit at a linear rate close to 1 (median 54 / 43 iterations, some pairs 1000), and |L - L_old| then comes down on the
+    # tolerance 1.5e-8 |L| in steps smaller than the firmness scale 1e-9 |L| -- some iterate lands within the scale of the
+    # tolerance, and the stopping margin of 62 % / 57 % of the pairs is not firm (no seed changes that: 47 ... 71 % over four
+    # seeds, from the reference alone).  Their niter is therefore compared at well under half of the pairs.  The same shapes and
+    # inputs at reltol = 1e-6: the steps at the tolerance are 70 times the scale, 99.0 % / 98.6 % of the margins are firm, and the
+    # EM still takes a median of 28 / 21 and up to 579 / 698 iterations.
+    (63, 16, 0.3, True, 1000, 1e-6, True),
+    (130, 17, 0.3, True, 1000, 1e-6, False),
 ]
+# least share of firm stopping margins by case: 0.99 with 1000 SNPs, 0.90 for the two added cases (reference: 0.990, 0.986); the two
+# short cases at the default tolerance are known to be mostly masked (reference: 0.381, 0.433) and state no floor
+FIRM_STOP = {c: 0.99 for c in CASES if c[1] == 1000}
+FIRM_STOP.update({c: 0.90 for c in CASES[-2:]})
 
 
 @pytest.mark.parametrize("case", CASES, ids=["-".join(map(str, c)) for c in CASES])
@@ -88,7 +116,7 @@ def test_edge_shapes(case):
     want = ref.ibd_mle(g, af, max_niter, reltol, cc)
     k0, k1, nit, gaf = _lib.ibd_mle(_scramble_padding(p, n), n, af, max_niter, reltol, cc)
     assert np.array_equal(gaf, want["afreq"])
-    _compare(k0, k1, nit, want)
+    _compare(k0, k1, nit, want, min_firm_stop=FIRM_STOP.get(case), min_firm_cand=0.99, what="-".join(map(str, case)))
 
 
 def test_all_missing_pair_and_duplicates():

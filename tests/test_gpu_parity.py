@@ -5,6 +5,7 @@ import pytest
 
 import oracle as orc
 from conftest import synth_geno
+from kernel_paths import PAIR_BACKEND_ENVS, SYRK_BACKEND_ENVS
 
 pytestmark = pytest.mark.gpu
 
@@ -22,20 +23,14 @@ def _feed_blocks(acc, g, block):
 SIZES = [(37, 301, 100), (279, 1000, 333), (600, 2500, 1024), (1030, 4100, 4096)]
 
 
-@pytest.fixture(params=["mfma_i8", "mfma_i8_no_fp4", "mfma_fp4_nomiss_only", "popcount"])
+@pytest.fixture(params=list(PAIR_BACKEND_ENVS))
 def pair_backend(request, monkeypatch):
     """The forms of the IBS/KING/beta counters: exact MFMA contractions (default: MX-fp4 for IBS / KING-robust / individual beta
     and GCTA's both-missing counts, int8 for KING-homo), the same with the int8 forms of all of them, with the int8 form of the
-    general kernels only, and bit-plane popcounts.  The library reads the variables when a context is created."""
-    if request.param == "mfma_i8_no_fp4":
-        monkeypatch.setenv("SNPGPU_PAIR_BACKEND", "mfma_i8")
-        monkeypatch.setenv("SNPGPU_PAIR_FP4", "0")
-        monkeypatch.setenv("SNPGPU_GCTA_MISS_FP4", "0")
-    elif request.param == "mfma_fp4_nomiss_only":     # int8 general kernels beside the fp4 two-product kernel
-        monkeypatch.setenv("SNPGPU_PAIR_BACKEND", "mfma_i8")
-        monkeypatch.setenv("SNPGPU_PAIR_FP4_GENERAL", "0")
-    else:
-        monkeypatch.setenv("SNPGPU_PAIR_BACKEND", request.param)
+    general kernels only, and bit-plane popcounts.  The library reads the variables when a context is created.  The environments are
+    those of tests/kernel_paths.py, where tests/test_cpu_kernel_paths.py holds every value to select a path of its own."""
+    for name, value in PAIR_BACKEND_ENVS[request.param].items():
+        monkeypatch.setenv(name, value)
     return request.param
 
 
@@ -161,7 +156,7 @@ def test_refused_create_leaves_the_process_usable(monkeypatch):
     assert np.array_equal(np.isfinite(got), np.isfinite(ref))
 
 
-@pytest.fixture(params=["f16", "f16_uvc", "f16_uv16", "f16_uv32", "f16_x1", "f16_2w", "h3", "f32"])
+@pytest.fixture(params=list(SYRK_BACKEND_ENVS))
 def syrk_backend(request, monkeypatch):
     """The SYRK kernels behind GRM / PCA.  f16 (default): blocks without missing calls take the single-product kernel
     (syrk_uv16c_kernel on v_mfma_f32_16x16x32_f16; f16_uv32: syrk_uv_kernel, its 32 x 32 x 16 form: SNP weight = product of two fp16
@@ -169,20 +164,11 @@ def syrk_backend(request, monkeypatch):
     kernel (syrk_x1_kernel: exact row operand x hi / lo-split column operand); f16_x1: the exact-row kernel for every
     block (SNPGPU_SYRK_UV=0); f16_2w: the same arithmetic at two waves per SIMD (syrk_h3_kernel<2, true>,
     SNPGPU_SYRK_X1=0); h3: the round-1 three-product split (SNPGPU_SYRK=h3); f32: fp32 MFMAs (SNPGPU_SYRK=f32)."""
-    if request.param in ("f16_uvc", "f16_uv16"):   # round 6: f16_uv16 = syrk_uv16_kernel (operands looked up in LDS tables, one launch of (tile, run)
-        monkeypatch.setenv("SNPGPU_SYRK", "f16")        # items); f16_uvc = syrk_uv16c_kernel as (tile, run) items without the LDS carry (SNPGPU_SYRK_UV16=2);
-        monkeypatch.setenv("SNPGPU_SYRK_UV16", "1" if request.param == "f16_uv16" else "2")      # the default f16 walks a tile's runs itself
-    elif request.param == "f16_uv32":       # round 6: the 32 x 32 x 16 form of the single-product kernel (default: 16 x 16 x 32, syrk_uv16_kernel)
-        monkeypatch.setenv("SNPGPU_SYRK", "f16")
-        monkeypatch.setenv("SNPGPU_SYRK_UV16", "0")
-    elif request.param == "f16_2w":
-        monkeypatch.setenv("SNPGPU_SYRK", "f16")
-        monkeypatch.setenv("SNPGPU_SYRK_X1", "0")
-    elif request.param == "f16_x1":
-        monkeypatch.setenv("SNPGPU_SYRK", "f16")
-        monkeypatch.setenv("SNPGPU_SYRK_UV", "0")
-    else:
-        monkeypatch.setenv("SNPGPU_SYRK", request.param)
+    # round 6: f16_uv16 = syrk_uv16_kernel (operands looked up in LDS tables, one launch of (tile, run) items); f16_uvc =
+    # syrk_uv16c_kernel as (tile, run) items without the LDS carry (SNPGPU_SYRK_UV16=2); the default f16 walks a tile's runs itself;
+    # f16_uv32 = the 32 x 32 x 16 form of the single-product kernel.  The environments are those of tests/kernel_paths.py.
+    for name, value in SYRK_BACKEND_ENVS[request.param].items():
+        monkeypatch.setenv(name, value)
     return request.param
 
 

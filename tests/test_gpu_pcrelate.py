@@ -241,6 +241,23 @@ def test_small_stage_takes_several_internal_blocks(monkeypatch):
         assert np.array_equal(planes[k], r["planes"][k])
 
 
+def test_forced_block_size_takes_several_internal_blocks(monkeypatch):
+    """SNPGPU_PCR_BLOCK_SNPS=48 cuts the same feed at the same SNPs inside a staging window of the default size (RowBlocks::open):
+    eleven blocks and their launches as above, the planes at the same bounds, the counters bit for bit"""
+    case = (130, 500, 5, 0.3, "all")
+    r = run(case)
+    monkeypatch.setenv("SNPGPU_PCR_BLOCK_SNPS", "48")
+    planes, st = _fed_in(case, [0, 500])
+    assert st["block_snps"] > 500                                  # the window itself would hold the feed in one block
+    assert st["blocks"] == 11 and st["product_launches"] == 33
+    assert st["plane_bytes"] == 8 * 8 * 130 * 130
+    for k in R.PLANES:
+        tol = R.plane_bound(r["ref"]["mag"][k], 500, 5)
+        assert float(np.abs(planes[k].astype(LD) - r["ref"]["planes"][k]).max()) <= tol, k
+    for k in ("IBS0", "NS"):
+        assert np.array_equal(planes[k], r["planes"][k])
+
+
 # ---- 7. formats and memory -------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("case", [(65, 1030, 1, 0.03, "all"), (257, 500, 5, 0.03, "fifth")])

@@ -174,6 +174,17 @@ def test_hwe_extreme_tables_and_large_counts():
     _check_hwe(_lib.hwe_counts(cnt), cnt, "synthetic counts up to N = 1e5")
 
 
+# The comparison of niter is masked where the restatement's stopping margin is not firm.  Largest share of the compared samples that
+# may be masked, per fixture, with the restatement's own figure beside it (computed on the CPU from tests/inb_ref.py alone):
+MLE_NOT_FIRM = {                                          # cap       the restatement's figure
+    "HapMap": 0.02,                                       #           2 of 279 = 0.0072
+    "synthetic, given frequencies": 0.0,                  #           0 of 19
+    "synthetic, estimated frequencies": 0.06,             #           1 of 19 = 0.0526
+    "slow": 0.0,                                          #           0 of 1
+    "never stopping": 0.0,                                #           0 of 6
+}
+
+
 def _check_mle(g, p_in, reltol, name):
     n = g.shape[1]
     F, nit, p_used = _lib.ind_inb(pack_2bit_rows(g), n, "mle", allele_freq=p_in, reltol=reltol, fmt=_lib.GENO_PACKED2)
@@ -199,6 +210,7 @@ def _check_mle(g, p_in, reltol, name):
           "kernel %.2f ms" % (name, compared, worst, Q.MLE_F_TOL, soft, 100.0 * soft / max(compared, 1), int(nit.max()),
                               st["mle_lane_steps_useful"] / max(st["mle_lane_steps_issued"], 1), st["mle_ms"]))
     assert soft <= 0.10 * compared, name
+    assert soft <= MLE_NOT_FIRM[name] * compared, "%s: niter is compared at %d of %d samples only" % (name, compared - soft, compared)
     return F, nit
 
 
