@@ -1252,8 +1252,8 @@ int snpgpu_diag_carry_fallbacks(snpgpu_ctx *ctx, int64_t *count, int reset);
  * and kinship = RR / (4 SS); inbreed_i = 2 kinship_ii - 1; with e_i = 1 + inbreed_i,
  *   k2 = (DD_ij - e_j DC_ij - e_i DC_ji + e_i e_j CC_ij) / CC_ij; k0 = IBS0 / K0D where kinship < 2^(-5/2), else 1 - 4 kinship + k2.
  * A zero denominator gives NaN.  The diagonal goes through the same expressions: its kinship is (1 + f_i) / 2, its k0 and k2 carry
- * no meaning.  Not built: the small-sample correction, per-variant scaling, row panels and multi-device objects, results in device
- * memory, a sparse selection on the device, anything below fp64.
+ * no meaning.  Not built: the small-sample correction, per-variant scaling, multi-device objects, results in device memory,
+ * anything below fp64.  (Row panels and the selection of related pairs on the device: the end of this section.)
  * Every sum has one owner and a fixed order (no atomics): the same feeds give the same bits.  A feed is cut into internal blocks
  * whose nine operand planes stay within SNPGPU_PCR_STAGE_BYTES (environment, read at creation; default 1 GiB, at least 16 SNPs).
  * Argument errors are refused before any HIP call; planes that do not fit the device's free memory are refused with both figures. */
@@ -1278,6 +1278,45 @@ int snpgpu_pcr_destroy(snpgpu_pcr *pcr);
 /* create / feed / result on the working space's selected SNPs and device (fed in its blocks) */
 int snpgpu_gnrPCRelate(int n_pc, const double *pcs, const uint8_t *training, double maf_thresh, int flags,
                        double *kinship, double *inbreed, double *k0, double *k2, double *nsnp);
+
+/* Row panels.  A panel object keeps rows [row_begin, row_end) x columns [row_begin, n_samp) of every plane as a
+ * slab -- three without SNPGPU_PCR_IBD, nine with it: the eight planes and CD with CD_ij = DC_ji, the half of DC a panel's rows do
+ * not hold (accumulated for the columns >= row_end only: inside the diagonal block DC holds both halves) -- and the diagonal tiles of RR and SS for the inbreeding of all n_samp samples.  Its internal blocks and tiles are the
+ * full object's: after the same feeds every sum, result and selected value equals, bit for bit, what an object of
+ * snpgpu_pcr_create with the same arguments holds at the same (i, j), however the rows are cut into panels.
+ * row_begin: a non-negative multiple of 128; row_begin < row_end <= n_samp, row_end a multiple of 128 or n_samp.  The other
+ * arguments, the checks and the refusal of memory that does not fit: as snpgpu_pcr_create.  snpgpu_pcr_feed, snpgpu_pcr_stats ([6]:
+ * the bytes of slabs and strips) and snpgpu_pcr_destroy take a panel handle; snpgpu_pcr_result and snpgpu_pcr_sums refuse it. */
+int snpgpu_pcr_create_panel(int64_t n_samp, int n_pc, const double *pcs, const uint8_t *training, double maf_thresh, int flags,
+                            int64_t row_begin, int64_t row_end, const snpgpu_opts *opts, snpgpu_pcr **out);
+/* The rows and columns of the panel of snpgpu_pcr_result's matrices: host [row_end - row_begin][n_samp - row_begin], row-major, any
+ * may be NULL; inbreed [n_samp], all samples.  A full handle is the panel [0, n_samp).  May be called between feeds. */
+int snpgpu_pcr_panel_result(snpgpu_pcr *pcr, double *kinship, double *inbreed, double *k0, double *k2, double *nsnp);
+/* one accumulated plane in the same shape; `which` as snpgpu_pcr_sums, or 8 = CD: DC transposed */
+int snpgpu_pcr_panel_sums(snpgpu_pcr *pcr, int which, double *plane);
+/* the two product launches a panel adds to a full object's, in HIP-event ms since creation: ms2[0] the CD job (DC's other half,
+ * stored transposed), ms2[1] the strips of diagonal tiles.  Both are part of snpgpu_pcr_stats' [4] as well; 0 for a full handle. */
+int snpgpu_pcr_panel_stats(snpgpu_pcr *pcr, double *ms2);
+/* The related pairs of a panel (or of a full handle), selected on the device from the resident sums: row_begin <= idx1 < row_end,
+ * idx1 < idx2 < n_samp, samp_sel[idx1] && samp_sel[idx2] (host [n_samp], NULL = all), kinship >= kinship_cutoff; a NaN kinship is
+ * never selected, a non-finite cutoff selects every pair.  Order: idx1 ascending, then idx2 ascending.  The values are what
+ * snpgpu_pcr_result holds at (idx2, idx1), the entry snpgdsIBDSelection reads.  Host outputs, any may be NULL: the first `capacity`
+ * pairs are stored, nothing behind them; *n_found = all selected pairs; capacity 0 takes no pair output (count only); inbreed
+ * [n_samp] is written whatever the capacity.  k0 / k2 need SNPGPU_PCR_IBD. */
+typedef struct snpgpu_pcr_sel_opts { double kinship_cutoff; const uint8_t *samp_sel; } snpgpu_pcr_sel_opts;
+int snpgpu_pcr_select(snpgpu_pcr *pcr, const snpgpu_pcr_sel_opts *o, int64_t capacity, int32_t *idx1, int32_t *idx2,
+                      double *kinship, double *k0, double *k2, double *nsnp, double *inbreed, int64_t *n_found);
+/* the last snpgpu_pcr_select of this thread: HIP-event ms of {count pass, scan, write pass}, then the whole call on the host clock */
+int snpgpu_pcr_select_stats(double *ms4);
+/* The related pairs of the working space's selected SNPs, panel by panel in ascending row order: create, feed every block as
+ * snpgpu_gnrPCRelate does, select, append.  panel_rows: a positive multiple of 128, or >= the number of samples (one panel), or 0 =
+ * the largest multiple of 128 that fits the device's free memory beside the selection's outputs of all its pairs; the pairs found
+ * never depend on it.  The result is kept until
+ * the next call or snpgpu_ws_clear; snpgpu_gnrPCRelatePairs_get copies it (*n_found entries each, inbreed [n_samp]; k0 / k2 only
+ * with SNPGPU_PCR_IBD). */
+int snpgpu_gnrPCRelatePairs(int n_pc, const double *pcs, const uint8_t *training, double maf_thresh, int flags, int64_t panel_rows,
+                            double kinship_cutoff, const uint8_t *samp_sel, int verbose, int64_t *n_found, int64_t *n_panels);
+int snpgpu_gnrPCRelatePairs_get(int32_t *idx1, int32_t *idx2, double *kinship, double *k0, double *k2, double *nsnp, double *inbreed);
 
 /* Diagnostic: kernel launches of the SYRK family that the feeds of this context have enqueued since it was created -- with
  * SNPGPU_RUN_INNER=0 one per fp32 run of a block, otherwise one per block and kernel.  snpgpu_get_timing's `launches` counts the

@@ -74,6 +74,8 @@ EXPORTS = [
     "snpgpu_mds", "snpgpu_mds_apply", "snpgpu_gnrMDS", "snpgpu_mds_stats",
     "snpgpu_pcr_create", "snpgpu_pcr_feed", "snpgpu_pcr_result", "snpgpu_pcr_sums", "snpgpu_pcr_stats", "snpgpu_pcr_destroy",
     "snpgpu_gnrPCRelate",
+    "snpgpu_pcr_create_panel", "snpgpu_pcr_panel_result", "snpgpu_pcr_panel_sums", "snpgpu_pcr_panel_stats", "snpgpu_pcr_select", "snpgpu_pcr_select_stats",
+    "snpgpu_gnrPCRelatePairs", "snpgpu_gnrPCRelatePairs_get",
     "snpgpu_diag_syrk_launches",
 ]
 FST_WC84, FST_WH02 = 1, 2
@@ -89,6 +91,8 @@ SEL_GRM_GCTA, SEL_GRM_EIGENSTRAT, SEL_GRM_EIGMIX, SEL_GRM_INDIV_BETA = 1, 2, 3, 
 LDSCORE_ADJUST, LDSCORE_SELF = 1, 2
 PCR_IBD = 1
 PCR_PLANES = ("RR", "SS", "DD", "DC", "CC", "IBS0", "K0D", "NS")      # snpgpu_pcr_sums' `which` = index
+PCR_SLABS = PCR_PLANES + ("CD",)                                       # snpgpu_pcr_panel_sums': CD = DC transposed
+PCR_TILE = 128                                                         # a panel's row_begin is a multiple of it
 
 
 class SnpGpuError(RuntimeError):
@@ -124,6 +128,10 @@ class MultiStatus(ctypes.Structure):   # snpgpu_multi_status
 class SelOpts(ctypes.Structure):       # snpgpu_sel_opts
     _fields_ = [("what", ctypes.c_int32), ("kinship_constraint", ctypes.c_int32), ("family", ctypes.c_void_p), ("e", ctypes.c_void_p),
                 ("kinship_cutoff", ctypes.c_double), ("samp_sel", ctypes.c_void_p)]
+
+
+class PcrSelOpts(ctypes.Structure):    # snpgpu_pcr_sel_opts
+    _fields_ = [("kinship_cutoff", ctypes.c_double), ("samp_sel", ctypes.c_void_p)]
 
 
 class GrmSelOpts(ctypes.Structure):    # snpgpu_grm_sel_opts
@@ -374,6 +382,14 @@ def lib():
     L.snpgpu_pcr_stats.argtypes = [vp, vp]
     L.snpgpu_pcr_destroy.argtypes = [vp]
     L.snpgpu_gnrPCRelate.argtypes = [c_int, vp, vp, dbl, c_int, vp, vp, vp, vp, vp]
+    L.snpgpu_pcr_create_panel.argtypes = [i64, c_int, vp, vp, dbl, c_int, i64, i64, ctypes.POINTER(Opts), ctypes.POINTER(vp)]
+    L.snpgpu_pcr_panel_result.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.snpgpu_pcr_panel_sums.argtypes = [vp, c_int, vp]
+    L.snpgpu_pcr_panel_stats.argtypes = [vp, vp]
+    L.snpgpu_pcr_select.argtypes = [vp, ctypes.POINTER(PcrSelOpts), i64, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(i64)]
+    L.snpgpu_pcr_select_stats.argtypes = [vp]
+    L.snpgpu_gnrPCRelatePairs.argtypes = [c_int, vp, vp, dbl, c_int, i64, dbl, vp, c_int, ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.snpgpu_gnrPCRelatePairs_get.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -2235,6 +2251,125 @@ class PCRelate:
         check(lib().snpgpu_pcr_stats(self._h, _ptr(s)))
         return dict(blocks=int(s[0]), product_launches=int(s[1]), beta_ms=s[2], operand_ms=s[3], product_ms=s[4], final_ms=s[5],
                     plane_bytes=int(s[6]), block_snps=int(s[7]))
+
+    def panel_stats(self):
+        """snpgpu_pcr_panel_stats: ms of the CD job and of the strips of diagonal tiles (both inside stats()["product_ms"])"""
+        s = np.zeros(2, np.float64)
+        check(lib().snpgpu_pcr_panel_stats(self._h, _ptr(s)))
+        return dict(cd_ms=float(s[0]), strip_ms=float(s[1]))
+
+    def panel_result(self, probs=None):
+        """result() through snpgpu_pcr_panel_result, which takes a full object as the panel [0, n)"""
+        return _pcr_panel_result(self._h, (self.n, self.n), self.n, self.ibd if probs is None else bool(probs))
+
+    def panel_sums(self, which):
+        """sums() through snpgpu_pcr_panel_sums (a name of PCR_SLABS or its index; "CD": DC transposed)"""
+        return _pcr_panel_sums(self._h, (self.n, self.n), which)
+
+    def select(self, cutoff, samp_sel=None, capacity=None, probs=None):
+        """snpgpu_pcr_select: the related pairs of this object's rows, selected on the device.  dict(idx1, idx2, kinship, nsnp, inbreed,
+        n_found and -- probs, by default where the object accumulates them -- k0, k2).  capacity=None: a count, then all pairs; a
+        number: at most so many pairs are stored (0: count only, the pair arrays are empty)."""
+        probs = self.ibd if probs is None else bool(probs)
+        mask = None
+        if samp_sel is not None:
+            mask = np.ascontiguousarray(np.asarray(samp_sel) != 0, np.uint8)
+            if mask.shape != (self.n,):
+                raise ValueError("'samp_sel' should have one flag per sample")
+        o = PcrSelOpts(float(cutoff), None if mask is None else mask.ctypes.data)
+        found = ctypes.c_int64(0)
+        inb = np.empty(self.n, np.float64)
+        if capacity is None:
+            check(lib().snpgpu_pcr_select(self._h, ctypes.byref(o), 0, None, None, None, None, None, None, None, ctypes.byref(found)))
+            capacity = found.value
+        m = int(capacity)
+        r = dict(idx1=np.empty(m, np.int32), idx2=np.empty(m, np.int32), kinship=np.empty(m, np.float64), nsnp=np.empty(m, np.float64))
+        if probs:
+            r.update(k0=np.empty(m, np.float64), k2=np.empty(m, np.float64))
+        out = [_ptr(r[k]) if m > 0 and k in r else None for k in ("idx1", "idx2", "kinship", "k0", "k2", "nsnp")]
+        check(lib().snpgpu_pcr_select(self._h, ctypes.byref(o), m, *out, _ptr(inb), ctypes.byref(found)))
+        k = min(m, found.value)
+        for name in list(r):
+            r[name] = r[name][:k]
+        r.update(inbreed=inb, n_found=int(found.value))
+        return r
+
+
+def pcr_select_stats():
+    """dict of snpgpu_pcr_select_stats for the last select on this thread"""
+    s = np.zeros(4, np.float64)
+    check(lib().snpgpu_pcr_select_stats(_ptr(s)))
+    return dict(count_ms=float(s[0]), scan_ms=float(s[1]), write_ms=float(s[2]), total_ms=float(s[3]))
+
+
+class PCRelatePanel(PCRelate):
+    """A PC-Relate object that holds the row panel rows = (r0, r1) x columns [r0, n) (snpgpu_pcr_create_panel): feed as a PCRelate;
+    result() / sums() give [r1 - r0][n - r0] arrays equal to the full object's [r0:r1, r0:] (inbreed: all n samples)."""
+
+    def __init__(self, n_samp, rows, pcs=None, training=None, maf_thresh=0.01, ibd=True, device=0, stream=None):
+        self.n = int(n_samp)
+        self.rows = (int(rows[0]), int(rows[1]))
+        p, self.n_pc, t = _pcr_inputs(pcs, training, self.n)
+        self.ibd = bool(ibd)
+        o = Opts(int(device), 0, 0, 0, 0, ctypes.c_void_p(stream) if stream else None)
+        h = ctypes.c_void_p()
+        self._h = None
+        check(lib().snpgpu_pcr_create_panel(self.n, self.n_pc, _ptr(p), _ptr(t), float(maf_thresh), PCR_IBD if self.ibd else 0,
+                                            self.rows[0], self.rows[1], ctypes.byref(o), ctypes.byref(h)))
+        self._h = h
+
+    @property
+    def shape(self):
+        return (self.rows[1] - self.rows[0], self.n - self.rows[0])
+
+    def result(self, probs=None):
+        return _pcr_panel_result(self._h, self.shape, self.n, self.ibd if probs is None else bool(probs))
+
+    def sums(self, which):
+        """one accumulated slab (a name of PCR_SLABS or its index) as [r1 - r0][n - r0]"""
+        return _pcr_panel_sums(self._h, self.shape, which)
+
+    panel_result, panel_sums = result, sums         # (the base class's would shape them n x n)
+
+
+def _pcr_panel_result(h, shape, n, probs):
+    r = dict(kinship=np.empty(shape, np.float64), inbreed=np.empty(n, np.float64), nsnp=np.empty(shape, np.float64))
+    if probs:
+        r.update(k0=np.empty(shape, np.float64), k2=np.empty(shape, np.float64))
+    check(lib().snpgpu_pcr_panel_result(h, _ptr(r["kinship"]), _ptr(r["inbreed"]), _ptr(r.get("k0")), _ptr(r.get("k2")), _ptr(r["nsnp"])))
+    return r
+
+
+def _pcr_panel_sums(h, shape, which):
+    w = PCR_SLABS.index(which) if isinstance(which, str) else int(which)
+    out = np.empty(shape, np.float64)
+    check(lib().snpgpu_pcr_panel_sums(h, w, _ptr(out)))
+    return out
+
+
+def gnr_pcrelate_pairs(n_samp, pcs=None, training=None, maf_thresh=0.01, ibd=True, panel_rows=0, kinship_cutoff=float("nan"),
+                       samp_sel=None, verbose=False):
+    """snpgpu_gnrPCRelatePairs on the working space of n_samp samples: dict(idx1, idx2, kinship, nsnp, inbreed, n_panels and, with
+    ibd, k0, k2); panel_rows 0: as many rows per panel as the device holds"""
+    n = int(n_samp)
+    p, n_pc, t = _pcr_inputs(pcs, training, n)
+    mask = None
+    if samp_sel is not None:
+        mask = np.ascontiguousarray(np.asarray(samp_sel) != 0, np.uint8)
+        if mask.shape != (n,):
+            raise ValueError("'samp_sel' should have one flag per sample")
+    found, panels = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(lib().snpgpu_gnrPCRelatePairs(n_pc, _ptr(p), _ptr(t), float(maf_thresh), PCR_IBD if ibd else 0, int(panel_rows), float(kinship_cutoff),
+                                        _ptr(mask), int(bool(verbose)), ctypes.byref(found), ctypes.byref(panels)))
+    m = found.value
+    r = dict(idx1=np.empty(m, np.int32), idx2=np.empty(m, np.int32), kinship=np.empty(m, np.float64), nsnp=np.empty(m, np.float64),
+             inbreed=np.empty(n, np.float64))
+    if ibd:
+        r.update(k0=np.empty(m, np.float64), k2=np.empty(m, np.float64))
+    check(lib().snpgpu_gnrPCRelatePairs_get(_ptr(r["idx1"]), _ptr(r["idx2"]), _ptr(r["kinship"]), _ptr(r.get("k0")), _ptr(r.get("k2")),
+                                            _ptr(r["nsnp"]), _ptr(r["inbreed"])))
+    r["n_panels"] = int(panels.value)
+    return r
 
 
 def gnr_pcrelate(n_samp, pcs=None, training=None, maf_thresh=0.01, ibd=True):

@@ -394,6 +394,25 @@ def write_sparse_grm(prefix, sample_id, idx1, idx2, value, diag, samp_sel=None):
         f.writelines("%d\t%d\t%.17g\n" % t for t in zip(row[order].tolist(), col[order].tolist(), val[order].tolist()))
 
 
+def _pairs_samp_sel(fn, samp_sel, n, dense=None):
+    """samp_sel of the calls that select pairs on the device -- a logical vector over the n working samples or strictly increasing
+    0-based indices -- as a uint8 mask, None for all.  dense: the calls whose matrices serve any other selection (for the message)."""
+    if samp_sel is None:
+        return None
+    sel = np.asarray(samp_sel)
+    if sel.dtype.kind == "b" and sel.shape == (n,):
+        mask = sel
+    elif sel.dtype.kind in "iu" and sel.ndim == 1 and (sel.size == 0 or (sel.min() >= 0 and sel.max() < n and np.all(np.diff(sel) > 0))):
+        mask = np.zeros(n, bool)
+        mask[sel] = True
+    else:
+        msg = "%s: 'samp.sel' should be a logical vector over the %d samples or strictly increasing indices" % (fn, n)
+        if dense:
+            msg += "; for a permuting or repeating selection use snpgdsIBDSelection on the matrices of %s" % dense
+        raise ValueError(msg)
+    return np.ascontiguousarray(mask, np.uint8)
+
+
 def snpgdsGRMPairs(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True,
                    maf=float("nan"), missing_rate=0.01, method="GCTA", cutoff=0.05, samp_sel=None, num_thread=1,
                    with_id=True, out_fn=None, verbose=True, device=0):
@@ -421,17 +440,7 @@ def snpgdsGRMPairs(gdsobj, sample_id=None, snp_id=None, autosome_only=True, remo
     ws = _init_file2("Genetic Relationship Matrix (GRM, %s):" % mtxt, gdsobj, sample_id, snp_id,
                      autosome_only, remove_monosnp, maf, missing_rate, num_thread, verbose, device)
     n = ws["n_samp"]
-    mask = None
-    if samp_sel is not None:
-        sel = np.asarray(samp_sel)
-        if sel.dtype.kind == "b" and sel.shape == (n,):
-            mask = sel
-        elif sel.dtype.kind in "iu" and sel.ndim == 1 and (sel.size == 0 or (sel.min() >= 0 and sel.max() < n and np.all(np.diff(sel) > 0))):
-            mask = np.zeros(n, bool)
-            mask[sel] = True
-        else:
-            raise ValueError("snpgdsGRMPairs: 'samp.sel' should be a logical vector over the %d samples or strictly increasing indices" % n)
-        mask = np.ascontiguousarray(mask, np.uint8)
+    mask = _pairs_samp_sel("snpgdsGRMPairs", samp_sel, n)
     L = _lib.lib()
     found = ctypes.c_int64(0)
     _lib.check(L.snpgpu_gnrGRMPairs(method.encode(), float(cutoff), _lib._ptr(mask), ws["num_thread"], int(bool(verbose)), ctypes.byref(found)))
@@ -1127,18 +1136,7 @@ def snpgdsIBDPairs(gdsobj, method="KING-robust", kinship_cutoff=float("nan"), sa
                      gdsobj, sample_id, snp_id, autosome_only, remove_monosnp, maf, missing_rate, num_thread, verbose, device,
                      allele_freq=allele_freq if mom else None)
     n = ws["n_samp"]
-    mask = None
-    if samp_sel is not None:
-        sel = np.asarray(samp_sel)
-        if sel.dtype.kind == "b" and sel.shape == (n,):
-            mask = sel
-        elif sel.dtype.kind in "iu" and sel.ndim == 1 and (sel.size == 0 or (sel.min() >= 0 and sel.max() < n and np.all(np.diff(sel) > 0))):
-            mask = np.zeros(n, bool)
-            mask[sel] = True
-        else:
-            raise ValueError("snpgdsIBDPairs: 'samp.sel' should be a logical vector over the %d samples or strictly increasing indices; "
-                             "for a permuting or repeating selection use snpgdsIBDSelection on the matrices of snpgdsIBDKING / snpgdsIBDMoM" % n)
-        mask = np.ascontiguousarray(mask, np.uint8)
+    mask = _pairs_samp_sel("snpgdsIBDPairs", samp_sel, n, "snpgdsIBDKING / snpgdsIBDMoM")
     fam = _family_codes(family_id, sample_id, ws, verbose and method == "KING-robust") if method == "KING-robust" else None
     af_in = ws["allele_freq"] if mom else None
     L = _lib.lib()
@@ -2749,24 +2747,9 @@ def snpgdsMDS(obj, k=2, method="ibs", sample_id=None, snp_id=None, autosome_only
                 n_pos=k1, route=r["route"])
 
 
-def snpgdsPCRelate(gdsobj, pcs, n_pcs=None, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True,
-                   maf=float("nan"), missing_rate=float("nan"), training_id=None, maf_thresh=0.01, ibd_probs=True, verbose=True,
-                   device=0):
-    """Ancestry-adjusted relatedness by PC-Relate (Conomos, Reiner, Weir, Thornton, AJHG 2016) on the GPU (snpgpu_gnrPCRelate,
-    include/snpgpu.h section 1r; no reference counterpart, and agreement with another package's output is not tested: the
-    definitions of DESIGN.md 31 are the specification).  Every SNP is regressed on the leading principal components over the
-    training samples; kinship, k0, k2 and inbreeding come from the residuals under individual-specific allele frequencies.
-
-    pcs: a snpgdsPCA / snpgdsEIGMIX result (its rows are matched to the selected samples by sample_id and the first n_pcs columns
-    of eigenvect are used; all of them by default) or an array with one row per selected sample, in their order (n_pcs columns of
-    it; an array without columns, or n_pcs = 0, adjusts for nothing but the mean).  training_id: the samples the regression is
-    fitted on (unrelated ones, as a rule), all by default.  maf_thresh: an (individual, SNP) whose individual-specific frequency
-    lies outside [maf_thresh, 1 - maf_thresh] is left out.  ibd_probs=False accumulates the kinship planes only (3 of 8).
-    Returns dict(sample_id, snp_id, kinship, k0, k1, k2, nsnp, inbreed): n x n matrices and inbreed [n]; k0 / k1 / k2 are None
-    without ibd_probs.  The diagonal of kinship is (1 + inbreed) / 2, that of k0 / k1 / k2 carries no meaning.
-    snpgdsIBDSelection(result, kinship_cutoff) tabulates it like any IBD object."""
-    ws = _init_file2("PC-Relate: kinship adjusted for principal components:", gdsobj, sample_id, snp_id, autosome_only, remove_monosnp,
-                     maf, missing_rate, 1, verbose, device)
+def _pcr_match(ws, pcs, n_pcs, training_id, verbose):
+    """(ids, pcs as [n][n_pcs] float64, training flags or None) of the PC-Relate calls: `pcs` and `training_id` matched to the working
+    samples"""
     n = ws["n_samp"]
     ids = np.asarray(ws["sample_id"])
     if isinstance(pcs, dict):
@@ -2797,7 +2780,66 @@ def snpgdsPCRelate(gdsobj, pcs, n_pcs=None, sample_id=None, snp_id=None, autosom
         if int(train.sum()) != len(np.unique(want)):
             raise ValueError("Some of training.id do not exist!")
     _cat(verbose, "    # of principal components: %d\n    # of training samples: %d" % (mat.shape[1], n if train is None else int(train.sum())))
+    return ids, mat, train
+
+
+def snpgdsPCRelate(gdsobj, pcs, n_pcs=None, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True,
+                   maf=float("nan"), missing_rate=float("nan"), training_id=None, maf_thresh=0.01, ibd_probs=True, verbose=True,
+                   device=0):
+    """Ancestry-adjusted relatedness by PC-Relate (Conomos, Reiner, Weir, Thornton, AJHG 2016) on the GPU (snpgpu_gnrPCRelate,
+    include/snpgpu.h section 1r; no reference counterpart, and agreement with another package's output is not tested: the
+    definitions of DESIGN.md 31 are the specification).  Every SNP is regressed on the leading principal components over the
+    training samples; kinship, k0, k2 and inbreeding come from the residuals under individual-specific allele frequencies.
+
+    pcs: a snpgdsPCA / snpgdsEIGMIX result (its rows are matched to the selected samples by sample_id and the first n_pcs columns
+    of eigenvect are used; all of them by default) or an array with one row per selected sample, in their order (n_pcs columns of
+    it; an array without columns, or n_pcs = 0, adjusts for nothing but the mean).  training_id: the samples the regression is
+    fitted on (unrelated ones, as a rule), all by default.  maf_thresh: an (individual, SNP) whose individual-specific frequency
+    lies outside [maf_thresh, 1 - maf_thresh] is left out.  ibd_probs=False accumulates the kinship planes only (3 of 8).
+    Returns dict(sample_id, snp_id, kinship, k0, k1, k2, nsnp, inbreed): n x n matrices and inbreed [n]; k0 / k1 / k2 are None
+    without ibd_probs.  The diagonal of kinship is (1 + inbreed) / 2, that of k0 / k1 / k2 carries no meaning.
+    snpgdsIBDSelection(result, kinship_cutoff) tabulates it like any IBD object."""
+    ws = _init_file2("PC-Relate: kinship adjusted for principal components:", gdsobj, sample_id, snp_id, autosome_only, remove_monosnp,
+                     maf, missing_rate, 1, verbose, device)
+    ids, mat, train = _pcr_match(ws, pcs, n_pcs, training_id, verbose)
+    n = ws["n_samp"]
     r = _lib.gnr_pcrelate(n, mat if mat.shape[1] else None, train, maf_thresh=maf_thresh, ibd=bool(ibd_probs))
     k0, k2 = r.get("k0"), r.get("k2")
     return dict(sample_id=ids, snp_id=ws["snp_id"], kinship=r["kinship"], k0=k0, k1=None if k0 is None else 1.0 - k0 - k2, k2=k2,
                 nsnp=r["nsnp"], inbreed=r["inbreed"])
+
+
+def snpgdsPCRelatePairs(gdsobj, pcs, n_pcs=None, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True,
+                        maf=float("nan"), missing_rate=float("nan"), training_id=None, maf_thresh=0.01, ibd_probs=True,
+                        kinship_cutoff=2 ** -5.5, samp_sel=None, panel_rows=None, verbose=True, device=0):
+    """The related pairs of a PC-Relate run without its n x n matrices (snpgpu_gnrPCRelatePairs, include/snpgpu.h section 1r;
+    DESIGN.md 31a).  The result equals snpgdsIBDSelection(snpgdsPCRelate(gdsobj, pcs, ...), kinship_cutoff, samp_sel) column for
+    column and bit for bit: the sums are accumulated on the GPU one row panel at a time and only the selected pairs come back, so
+    device memory is that of one panel and host memory is proportional to the number of pairs.
+
+    pcs, n_pcs, training_id, maf_thresh, ibd_probs and the SNP / sample filters: as snpgdsPCRelate.  kinship_cutoff: pairs with
+    kinship >= it are kept (the default 2^-5.5 is the lower edge of third-degree relatives; a non-finite cutoff keeps every pair).
+    samp_sel: a logical vector over the working samples or strictly increasing 0-based indices, as for snpgdsIBDPairs.  panel_rows:
+    rows of one panel -- a multiple of 128, or at least the number of samples for a single panel; None: as many as the device holds.
+    The pairs found never depend on it.
+    Returns dict(sample_id, snp_id, ID1, ID2, idx1, idx2, kinship, k0, k1, k2, nsnp, inbreed, n_panels): one entry per pair in the
+    order of snpgdsIBDSelection (ID1 = sample_id[idx1] ascending, then ID2 = sample_id[idx2]), inbreed [n] for all samples; k0 / k1 /
+    k2 are None without ibd_probs."""
+    if isinstance(kinship_cutoff, (bool, np.bool_)) or not isinstance(kinship_cutoff, (int, float, np.integer, np.floating)):
+        raise TypeError("is.numeric(kinship.cutoff) is not TRUE")
+    if panel_rows is not None and (isinstance(panel_rows, bool) or not isinstance(panel_rows, (int, np.integer)) or panel_rows < 1):
+        raise ValueError("'panel_rows' should be None or a positive multiple of %d" % _lib.PCR_TILE)
+    ws = _init_file2("PC-Relate: kinship adjusted for principal components, related pairs only:", gdsobj, sample_id, snp_id, autosome_only,
+                     remove_monosnp, maf, missing_rate, 1, verbose, device)
+    ids, mat, train = _pcr_match(ws, pcs, n_pcs, training_id, verbose)
+    n = ws["n_samp"]
+    mask = _pairs_samp_sel("snpgdsPCRelatePairs", samp_sel, n, "snpgdsPCRelate")
+    r = _lib.gnr_pcrelate_pairs(n, mat if mat.shape[1] else None, train, maf_thresh=maf_thresh, ibd=bool(ibd_probs),
+                                panel_rows=0 if panel_rows is None else int(panel_rows), kinship_cutoff=float(kinship_cutoff),
+                                samp_sel=mask, verbose=False)
+    k0, k2 = r.get("k0"), r.get("k2")
+    m = len(r["idx1"])
+    _cat(verbose, "%d pair%s selected in %d panel%s" % (m, "" if m == 1 else "s", r["n_panels"], "" if r["n_panels"] == 1 else "s"))
+    return dict(sample_id=ids, snp_id=ws["snp_id"], ID1=ids[r["idx1"]], ID2=ids[r["idx2"]], idx1=r["idx1"], idx2=r["idx2"],
+                kinship=r["kinship"], k0=k0, k1=None if k0 is None else 1.0 - k0 - k2, k2=k2, nsnp=r["nsnp"], inbreed=r["inbreed"],
+                n_panels=r["n_panels"])

@@ -147,11 +147,17 @@ int launch_pcr_operands(hipStream_t st, const uint8_t *rows, int64_t rb, int m, 
 // [k = lane >> 4], B[k = lane >> 4][j = lane & 15]; D: column lane & 15, rows (lane >> 4) + 4 r.
 constexpr int PCR_LDS_STRIDE = PCR_TILE + 16;
 
-__global__ __launch_bounds__(256) void pcr_product_kernel(PcrJobs jobs, int64_t n, int64_t n_pad, int m, int tri)
+// The job says where the tile goes (pcrelate_device.h): a full plane, a row panel's slab, the panel's CD slab (the product's tile
+// (J, I), stored transposed) or a strip of diagonal tiles.  Whatever the destination, the tile is the same instruction sequence
+// over K, so a panel holds the full object's bits.
+__global__ __launch_bounds__(256) void pcr_product_kernel(PcrJobs jobs, int64_t n, int64_t n_pad, int m, int tri, int tile0, int tile0_col)
 {
-    const int I = (int)blockIdx.y, J = (int)blockIdx.x;
-    if (tri && I > J) return;
     const PcrJob job = jobs.j[blockIdx.z];
+    const bool diag = job.mode == PCR_JOB_DIAG, transposed = job.mode == PCR_JOB_TRANSPOSED;
+    if (diag && blockIdx.y != 0) return;
+    const int gI = diag ? (int)blockIdx.x : tile0 + (int)blockIdx.y, gJ = diag ? (int)blockIdx.x : tile0_col + (int)blockIdx.x;
+    if (tri && gI > gJ) return;
+    const int I = transposed ? gJ : gI, J = transposed ? gI : gJ;      // the product's tile
     __shared__ double sX[PCR_KB][PCR_LDS_STRIDE];
     __shared__ double sY[PCR_KB][PCR_LDS_STRIDE];
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -207,6 +213,7 @@ __global__ __launch_bounds__(256) void pcr_product_kernel(PcrJobs jobs, int64_t 
     }
     // this workgroup is the tile's only owner in this launch: plain loads and stores
     double *__restrict__ C = job.c;
+    const int64_t col0 = diag ? (int64_t)J * PCR_TILE : job.col0;
 #pragma unroll
     for (int ti = 0; ti < 4; ti++)
 #pragma unroll
@@ -215,16 +222,18 @@ __global__ __launch_bounds__(256) void pcr_product_kernel(PcrJobs jobs, int64_t 
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const int64_t i = (int64_t)I * PCR_TILE + wi + 16 * ti + lk + 4 * r;
-                if (i < n && j < n) C[i * n + j] += acc[ti][tj][r];
+                const int64_t di = transposed ? j : i, dj = transposed ? i : j;        // where the entry is stored
+                if (di < job.row_end && dj < n) C[(di - job.row0) * job.ld + (dj - col0)] += acc[ti][tj][r];
             }
         }
 }
 
-int launch_pcr_products(hipStream_t st, const PcrJobs &jobs, int n_jobs, int64_t n, int64_t n_pad, int m, bool tri)
+int launch_pcr_products(hipStream_t st, const PcrJobs &jobs, int n_jobs, int64_t n, int64_t n_pad, int m, bool tri, int tile0, int nt_rows,
+                        int tile0_col, int nt_cols)
 {
-    if (m <= 0 || n_jobs <= 0) return 0;
-    const unsigned nt = (unsigned)(n_pad / PCR_TILE);
-    hipLaunchKernelGGL(pcr_product_kernel, dim3(nt, nt, (unsigned)n_jobs), dim3(256), 0, st, jobs, n, n_pad, m, tri ? 1 : 0);
+    if (m <= 0 || n_jobs <= 0 || nt_rows <= 0 || nt_cols <= 0) return 0;
+    hipLaunchKernelGGL(pcr_product_kernel, dim3((unsigned)nt_cols, (unsigned)nt_rows, (unsigned)n_jobs), dim3(256), 0, st, jobs, n, n_pad, m,
+                       tri ? 1 : 0, tile0, tile0_col);
     SNPGPU_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -238,13 +247,14 @@ __device__ __forceinline__ double pcr_sym(const double *__restrict__ P, int64_t 
 
 // inbreed_i = 2 kinship_ii - 1 and e_i = 1 + inbreed_i, written as the definitions read (no contraction: a host restatement of
 // these few operations gives the same bits)
-__global__ __launch_bounds__(256) void pcr_diag_kernel(const double *__restrict__ RR, const double *__restrict__ SS, int64_t n,
-                                                       double *__restrict__ inbreed, double *__restrict__ e)
+__global__ __launch_bounds__(256) void pcr_diag_kernel(const double *__restrict__ RR, const double *__restrict__ SS, int64_t n, int64_t ld,
+                                                       int64_t wrap, double *__restrict__ inbreed, double *__restrict__ e)
 {
 #pragma clang fp contract(off)
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double kin = RR[i * n + i] / (4.0 * SS[i * n + i]);
+    const int64_t at = i * ld + (wrap ? i % wrap : i);
+    const double kin = RR[at] / (4.0 * SS[at]);
     const double f = 2.0 * kin - 1.0;
     inbreed[i] = f;
     e[i] = 1.0 + f;
@@ -270,9 +280,9 @@ __global__ __launch_bounds__(256) void pcr_final_kernel(PcrPlanes P, int64_t n, 
     if (k0) k0[idx] = kin < PCR_KIN_SPLIT ? pcr_sym(P.p[PCR_IBS0], n, i, j) / pcr_sym(P.p[PCR_K0D], n, i, j) : 1.0 - 4.0 * kin + v2;
 }
 
-int launch_pcr_diag(hipStream_t st, const PcrPlanes &P, int64_t n, double *inbreed, double *e)
+int launch_pcr_diag(hipStream_t st, const double *RR, const double *SS, int64_t n, int64_t ld, int64_t wrap, double *inbreed, double *e)
 {
-    hipLaunchKernelGGL(pcr_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P.p[PCR_RR], P.p[PCR_SS], n, inbreed, e);
+    hipLaunchKernelGGL(pcr_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, RR, SS, n, ld, wrap, inbreed, e);
     SNPGPU_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -298,6 +308,48 @@ __global__ __launch_bounds__(256) void pcr_plane_kernel(const double *__restrict
 int launch_pcr_plane(hipStream_t st, const double *P, int64_t n, bool sym, int64_t r0, int64_t rows, double *out)
 {
     hipLaunchKernelGGL(pcr_plane_kernel, dim3((unsigned)((rows * n + 255) / 256)), dim3(256), 0, st, P, n, sym ? 1 : 0, r0, rows, out);
+    SNPGPU_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- results through a view ----------------------------------------------------------------------------------------------------
+// The same results for a row panel, or for a full object read as the panel [0, n): rows [r0, r0 + rows) x columns [col0, n).
+__global__ __launch_bounds__(256) void pcr_view_final_kernel(PcrView v, int64_t n, int64_t r0, int64_t rows, const double *__restrict__ e,
+                                                             double *__restrict__ kinship, double *__restrict__ k0, double *__restrict__ k2,
+                                                             double *__restrict__ nsnp)
+{
+    const int64_t nc = n - v.col0, idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= rows * nc) return;
+    const int64_t i = r0 + idx / nc, j = v.col0 + idx % nc;
+    double kin = 0.0, v0 = 0.0, v2 = 0.0;
+    pcr_pair_values(v, e, i, j, k0 || k2, kin, v0, v2);
+    if (kinship) kinship[idx] = kin;
+    if (nsnp) nsnp[idx] = v.sym(PCR_NS, i, j);
+    if (k0) k0[idx] = v0;
+    if (k2) k2[idx] = v2;
+}
+
+__global__ __launch_bounds__(256) void pcr_view_plane_kernel(PcrView v, int which, int64_t n, int64_t r0, int64_t rows, double *__restrict__ out)
+{
+    const int64_t nc = n - v.col0, idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= rows * nc) return;
+    const int64_t i = r0 + idx / nc, j = v.col0 + idx % nc;
+    out[idx] = which == PCR_CD ? v.dc(j, i) : which == PCR_DC ? v.dc(i, j) : v.sym(which, i, j);
+}
+
+int launch_pcr_view_final(hipStream_t st, const PcrView &v, int64_t n, int64_t r0, int64_t rows, const double *e, double *kinship, double *k0,
+                          double *k2, double *nsnp)
+{
+    const int64_t cells = rows * (n - v.col0);
+    hipLaunchKernelGGL(pcr_view_final_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, v, n, r0, rows, e, kinship, k0, k2, nsnp);
+    SNPGPU_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_pcr_view_plane(hipStream_t st, const PcrView &v, int which, int64_t n, int64_t r0, int64_t rows, double *out)
+{
+    const int64_t cells = rows * (n - v.col0);
+    hipLaunchKernelGGL(pcr_view_plane_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, v, which, n, r0, rows, out);
     SNPGPU_HIP_CHECK(hipGetLastError());
     return 0;
 }

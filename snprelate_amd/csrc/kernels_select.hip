@@ -15,7 +15,10 @@
 // loop (a panel may have more rows than grid.y allows).
 // The sparse GRM (snpgpu_select_grm) is the same walk over the GCTA / covariance / EIGMIX / IndivBeta value functions,
 // one value per pair, plus a small kernel for the diagonal.
+// PC-Relate (snpgpu_pcr_select) is the same walk over the finaliser's expressions on the resident fp64 sums of a row
+// panel, four values per pair.
 #include "fin_values.h"
+#include "pcrelate_device.h"
 
 #include <cmath>
 
@@ -80,13 +83,28 @@ struct SelOne {
     }
 };
 
+// PC-Relate: what pcr_view_final_kernel writes at (j, i), the entry of the lower triangle that snpgdsIBDSelection reads for the pair
+// i < j (k2's two DC terms are subtracted in the other order at (i, j)); v0 = k0, v1 = k2, the fourth value = nsnp.  The slabs are
+// row-major with their own origin: the walk's rel / relf are not used.
+struct SelPcr {
+    PcrView v;
+    const double *e;
+    int probs;
+    __device__ __forceinline__ void values(int64_t, int64_t, int64_t i, int64_t j, double &v0, double &v1, double &kin) const
+    {
+        pcr_pair_values(v, e, j, i, probs != 0, kin, v0, v1);
+    }
+    __device__ __forceinline__ double fourth(int64_t i, int64_t j) const { return v.sym(PCR_NS, j, i); }
+};
+
 struct SelOut {
     int32_t *idx1, *idx2; double *v0, *v1, *kin;       // any may be nullptr
     int64_t capacity;
+    double *v2;                                        // NV = 4 only
 };
 
 // WRITE = false: counts[seg] = hits of the segment;  WRITE = true: the hits stored from offsets[seg] on.  NV: values stored per pair
-// (3: v0, v1, kin;  1: kin alone)
+// (4: v0, v1, kin and f.fourth(i, j);  3: v0, v1, kin;  1: kin alone)
 template <class F, bool WRITE, int NV = 3>
 __global__ __launch_bounds__(64 * SEL_WAVES) void select_kernel(PanelGeom g, F f, const uint8_t *__restrict__ sel, int all, double cutoff,
                                                                uint32_t *__restrict__ counts, const int64_t *__restrict__ offsets, SelOut o)
@@ -121,11 +139,14 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void select_kernel(PanelGeom g, F f
                     if (hit && pos < o.capacity) {
                         if (o.idx1) o.idx1[pos] = (int32_t)i;
                         if (o.idx2) o.idx2[pos] = (int32_t)j;
-                        if (NV == 3) {
+                        if (NV >= 3) {
                             if (o.v0) o.v0[pos] = v0;
                             if (o.v1) o.v1[pos] = v1;
                         }
                         if (o.kin) o.kin[pos] = kin;
+                        if constexpr (NV == 4) {
+                            if (o.v2) o.v2[pos] = f.fourth(i, j);
+                        }
                     }
                     off += __popcll(m);
                     if (off >= o.capacity) break;
@@ -177,7 +198,7 @@ int run_select(hipStream_t st, const PanelGeom &g, const F &f, const SelectArgs 
     if (nrows <= 0) return 0;
     const unsigned grid = (unsigned)(nrows < SELECT_MAX_GRID ? nrows : SELECT_MAX_GRID);
     const int all = std::isfinite(s.cutoff) ? 0 : 1;
-    SelOut o{s.idx1, s.idx2, s.v0, s.v1, s.kin, s.capacity};
+    SelOut o{s.idx1, s.idx2, s.v0, s.v1, s.kin, s.capacity, s.v2};
     if (write)
         hipLaunchKernelGGL((select_kernel<F, true, NV>), dim3(grid), dim3(64 * SEL_WAVES), 0, st, g, f, s.sel, all, s.cutoff, s.counts, s.offsets, o);
     else
@@ -226,6 +247,13 @@ int launch_select_mom(hipStream_t st, const PanelGeom &g, const uint32_t *acc, c
 {
     SelMom f{MomArgs{acc, g.rows_pad * g.ncols_pad, e[0], e[1], e[2], e[3], e[4], constraint}};
     return run_select(st, g, f, s, write);
+}
+
+int launch_select_pcr(hipStream_t st, const PcrView &v, int64_t n, const double *e, bool probs, const SelectArgs &s, bool write)
+{
+    const PanelGeom g{n, v.row0, v.row1, v.col0, v.row1 - v.row0, v.ld, 0};
+    SelPcr f{v, e, probs ? 1 : 0};
+    return run_select<SelPcr, 4>(st, g, f, s, write);
 }
 
 int launch_select_gcta(hipStream_t st, const PanelGeom &g, const double *num, const uint32_t *miss, const uint32_t *miss_diag,

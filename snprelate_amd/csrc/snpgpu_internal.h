@@ -378,6 +378,7 @@ struct SelectArgs {
     const uint8_t *sel; double cutoff;
     uint32_t *counts; int64_t *offsets;
     int64_t capacity; int32_t *idx1, *idx2; double *v0, *v1, *kin;
+    double *v2 = nullptr;      // the fourth value of a kind that has one (launch_select_pcr: nsnp)
 };
 // the context kind a selection's `what` accumulates on
 inline int select_kind(int what) { return what == SNPGPU_SEL_KING_ROBUST ? SNPGPU_KING_ROBUST : what == SNPGPU_SEL_KING_HOMO ? SNPGPU_KING_HOMO : SNPGPU_IBS; }

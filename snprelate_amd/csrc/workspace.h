@@ -34,6 +34,9 @@ struct ProjGuard {
 };
 int proj_open(int n_eig, ProjGuard &g);     // a projector of the working space's samples and device, WS_BLOCK SNPs per block
 
+// the pairs kept by snpgpu_gnrPCRelatePairs (pcrelate.hip) go with the working space: snpgpu_ws_clear releases them
+void ws_pcr_pairs_clear();
+
 // grm_avg_value, src/genPCA.cpp:1605: written by snpgpu_gnrGRM, snpgpu_gnrIBD_Beta and snpgpu_gnrGRMMerge, read by snpgpu_gnrGRM_avg_val
 extern double g_grm_avg_value;
 

@@ -195,6 +195,7 @@ int snpgpu_ws_set_geno(const void *geno, int64_t n_snp, int64_t n_samp, int form
 int snpgpu_ws_clear(void)
 {
     g_ws = WorkSpace();
+    ws_pcr_pairs_clear();
     return 0;
 }
 
