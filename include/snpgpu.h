@@ -1318,6 +1318,54 @@ int snpgpu_gnrPCRelatePairs(int n_pc, const double *pcs, const uint8_t *training
                             double kinship_cutoff, const uint8_t *samp_sel, int verbose, int64_t *n_found, int64_t *n_panels);
 int snpgpu_gnrPCRelatePairs_get(int32_t *idx1, int32_t *idx2, double *kinship, double *k0, double *k2, double *nsnp, double *inbreed);
 
+/* ---- 1s. Ancestry proportions by EM (no reference counterpart) -----------------------------------------------
+ * The likelihood model of FRAPPE (Tang et al. 2005) and ADMIXTURE: g_ij ~ Binomial(2, sum_k q_ik f_kj) over the called genotypes
+ * (a code of 3 contributes nothing anywhere), fp64 throughout.  State: Q [n_samp][n_pop], rows on the simplex, and F [m][n_pop],
+ * the frequency of the counted allele of SNP j in population k, kept inside [f_min, 1 - f_min].  One iteration from (Q, F):
+ *   h1_ij = sum_k q_ik f_kj            h0_ij = sum_k q_ik (1 - f_kj)      (h0 is its own sum of positive terms, not 1 - h1)
+ *   w1_ij = g_ij / h1_ij               w0_ij = (2 - g_ij) / h0_ij
+ *   a_ik  = sum_j (w1_ij f_kj + w0_ij (1 - f_kj))      q'_ik = q_ik a_ik / sum_k' q_ik' a_ik'   (no called SNP: the row stays)
+ *   u_kj  = f_kj sum_i w1_ij q_ik      v_kj = (1 - f_kj) sum_i w0_ij q_ik
+ *   f'_kj = clamp(u_kj / (u_kj + v_kj), f_min, 1 - f_min)                                        (u + v = 0: f_kj stays)
+ *   L(Q, F) = sum_ij g_ij log h1_ij + (2 - g_ij) log h0_ij
+ * Q' and F' are both made from the old (Q, F): one pass over the genotypes per iteration.  With SNPGPU_ADMIX_FIX_F only Q moves
+ * (supervised estimation, projection onto given frequencies).
+ * Every sum has one owner and a fixed order (no atomics).  The per-SNP sums are cut at the absolute sample indices s * 4096, the
+ * per-sample sums at the absolute SNP indices s * 1024, the parts are folded in ascending order, L is the fold of the SNPs' parts by
+ * one workgroup: the bits depend neither on how the rows were cut into feeds, nor on their format or memory kind, nor on block_snps.
+ * Not built: acceleration (SQUAREM, quasi-Newton), cross-validation, multi-device objects, results in device memory, anything
+ * below fp64.  Argument errors and calls out of order are refused before any HIP call: snpgpu_admix_create makes none, host rows
+ * fed before the device is open are copied and wait, and so do the values of snpgpu_admix_set; the first run, get or feed of device
+ * rows opens the device and takes what waits.  An object that does not fit the device's free memory is refused there with both
+ * figures. */
+typedef struct snpgpu_admix snpgpu_admix;
+enum { SNPGPU_ADMIX_FIX_F = 1 };   /* snpgpu_admix_run: F stays, only Q moves */
+/* n_pop in 2 ... 32; max_snps: the rows the object can take (they stay resident as 2-bit rows); f_min inside (0, 0.5); block_snps:
+ * the SNPs of an internal block of a pass, a multiple of 16 up to 2^20, or 0 = all of max_snps (at most 2^20: nothing is staged
+ * per block, so the free memory sets no smaller one); opts: device and stream are read. */
+int snpgpu_admix_create(int64_t n_samp, int n_pop, int64_t max_snps, double f_min, int64_t block_snps, const snpgpu_opts *opts,
+                        snpgpu_admix **out);
+/* appends n_snp rows (SNPGPU_GENO_PACKED2 or SNPGPU_GENO_U8, host or device memory, as snpgpu_pcr_feed takes them); returns when
+ * they have been read */
+int snpgpu_admix_feed(snpgpu_admix *ad, const void *geno, int64_t n_snp, int format, int mem);
+/* host q [n_samp][n_pop]: finite, non-negative, every row with a positive sum (normalised on entry); host f [rows fed][n_pop]: finite
+ * (clamped on entry).  Either may be NULL = keep.  Rows fed after f was set need f set again. */
+int snpgpu_admix_set(snpgpu_admix *ad, const double *q, const double *f);
+/* Up to max_iter iterations t = 0, 1, ...; loglik [max_iter + 1] (host): loglik[t] = L of the state before iteration t, which falls
+ * out of the pass that makes it.  Stops after iteration t >= 1 when loglik[t] - loglik[t - 1] < tol; then one likelihood-only pass:
+ * *n_done iterations were made and loglik[*n_done] belongs to the state snpgpu_admix_get returns.  max_iter = 0 evaluates L.  The
+ * passes run back to back on the object's stream; the host reads one scalar per pass. */
+int snpgpu_admix_run(snpgpu_admix *ad, int max_iter, double tol, int flags, double *loglik, int *n_done);
+/* host q [n_samp][n_pop], f [rows F was set for][n_pop]; either may be NULL */
+int snpgpu_admix_get(snpgpu_admix *ad, double *q, double *f);
+/* stats[0] internal blocks of the last pass, [1] kernel launches, [2] HIP-event ms of the passes, [3] resident bytes, [4] SNPs of an
+ * internal block, [5] iterations -- since creation */
+int snpgpu_admix_stats(snpgpu_admix *ad, double *stats);
+int snpgpu_admix_destroy(snpgpu_admix *ad);
+/* create / feed / set / run / get on the working space's selected SNPs and device; q, f: the starting values (both required) */
+int snpgpu_gnrAdmix(int n_pop, double f_min, int64_t block_snps, const double *q, const double *f, int max_iter, double tol, int flags,
+                    double *loglik, int *n_done, double *q_res, double *f_res);
+
 /* Diagnostic: kernel launches of the SYRK family that the feeds of this context have enqueued since it was created -- with
  * SNPGPU_RUN_INNER=0 one per fp32 run of a block, otherwise one per block and kernel.  snpgpu_get_timing's `launches` counts the
  * timed spans instead: one per table and feed block. */

@@ -6,4 +6,4 @@ interface for that path.  There is no CPU fallback.
 """
 from . import _lib  # noqa: F401
 from ._lib import Accumulator, SnpGpuError  # noqa: F401
-from .api import snpgdsAlleleSwitch, snpgdsCombineGeno, snpgdsSNPList, snpgdsSNPListIntersect, snpgdsCutTree, snpgdsGDS2BED, snpgdsGDS2Eigen, snpgdsGDS2PED, snpgdsGetGeno, snpgdsGRMPairs, snpgdsHCluster, snpgdsHWE, snpgdsIBDMLEPairs, snpgdsIBDPairs, snpgdsIBDSelection, snpgdsIndInb, snpgdsIndInbCoef, snpgdsMDS, snpgdsOpenBED, snpgdsOpenGEN, snpgdsOpenPED, snpgdsOpenVCF, snpgdsOption, snpgdsPairIBD, snpgdsPairIBDMLELogLik, snpgdsPairScore, snpgdsPCRelate, snpgdsPCRelatePairs, snpgdsSampMissRate, snpgdsSelectSNP  # noqa: F401,E402
+from .api import snpgdsAlleleSwitch, snpgdsCombineGeno, snpgdsSNPList, snpgdsSNPListIntersect, snpgdsCutTree, snpgdsGDS2BED, snpgdsGDS2Eigen, snpgdsGDS2PED, snpgdsGetGeno, snpgdsGRMPairs, snpgdsHCluster, snpgdsHWE, snpgdsIBDMLEPairs, snpgdsIBDPairs, snpgdsIBDSelection, snpgdsIndInb, snpgdsIndInbCoef, snpgdsMDS, snpgdsOpenBED, snpgdsOpenGEN, snpgdsOpenPED, snpgdsOpenVCF, snpgdsOption, snpgdsPairIBD, snpgdsPairIBDMLELogLik, snpgdsPairScore, snpgdsPCRelate, snpgdsPCRelatePairs, snpgdsAdmix, snpgdsAdmixProp, snpgdsAdmixTable, snpgdsSampMissRate, snpgdsSelectSNP  # noqa: F401,E402

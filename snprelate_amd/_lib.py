@@ -77,6 +77,8 @@ EXPORTS = [
     "snpgpu_pcr_create_panel", "snpgpu_pcr_panel_result", "snpgpu_pcr_panel_sums", "snpgpu_pcr_panel_stats", "snpgpu_pcr_select", "snpgpu_pcr_select_stats",
     "snpgpu_gnrPCRelatePairs", "snpgpu_gnrPCRelatePairs_get",
     "snpgpu_diag_syrk_launches",
+    "snpgpu_admix_create", "snpgpu_admix_feed", "snpgpu_admix_set", "snpgpu_admix_run", "snpgpu_admix_get", "snpgpu_admix_stats",
+    "snpgpu_admix_destroy", "snpgpu_gnrAdmix",
 ]
 FST_WC84, FST_WH02 = 1, 2
 FST_METHODS = ("W&C84", "W&H02")
@@ -93,6 +95,7 @@ PCR_IBD = 1
 PCR_PLANES = ("RR", "SS", "DD", "DC", "CC", "IBS0", "K0D", "NS")      # snpgpu_pcr_sums' `which` = index
 PCR_SLABS = PCR_PLANES + ("CD",)                                       # snpgpu_pcr_panel_sums': CD = DC transposed
 PCR_TILE = 128                                                         # a panel's row_begin is a multiple of it
+ADMIX_FIX_F = 1                                                        # snpgpu_admix_run: F stays, only Q moves
 
 
 class SnpGpuError(RuntimeError):
@@ -390,6 +393,14 @@ def lib():
     L.snpgpu_pcr_select_stats.argtypes = [vp]
     L.snpgpu_gnrPCRelatePairs.argtypes = [c_int, vp, vp, dbl, c_int, i64, dbl, vp, c_int, ctypes.POINTER(i64), ctypes.POINTER(i64)]
     L.snpgpu_gnrPCRelatePairs_get.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.snpgpu_admix_create.argtypes = [i64, c_int, i64, dbl, i64, ctypes.POINTER(Opts), ctypes.POINTER(vp)]
+    L.snpgpu_admix_feed.argtypes = [vp, vp, i64, c_int, c_int]
+    L.snpgpu_admix_set.argtypes = [vp, vp, vp]
+    L.snpgpu_admix_run.argtypes = [vp, c_int, dbl, c_int, vp, ctypes.POINTER(c_int)]
+    L.snpgpu_admix_get.argtypes = [vp, vp, vp]
+    L.snpgpu_admix_stats.argtypes = [vp, vp]
+    L.snpgpu_admix_destroy.argtypes = [vp]
+    L.snpgpu_gnrAdmix.argtypes = [c_int, dbl, i64, vp, vp, c_int, dbl, c_int, vp, ctypes.POINTER(c_int), vp, vp]
     _lib = L
     return L
 
@@ -2382,3 +2393,99 @@ def gnr_pcrelate(n_samp, pcs=None, training=None, maf_thresh=0.01, ibd=True):
     check(lib().snpgpu_gnrPCRelate(n_pc, _ptr(p), _ptr(t), float(maf_thresh), PCR_IBD if ibd else 0, _ptr(r["kinship"]), _ptr(r["inbreed"]),
                                    _ptr(r.get("k0")), _ptr(r.get("k2")), _ptr(r["nsnp"])))
     return r
+
+
+def _admix_matrix(x, rows, k, name):
+    """x as float64 [rows][k] (None stays None)"""
+    if x is None:
+        return None
+    a = np.ascontiguousarray(x, np.float64)
+    if a.shape != (int(rows), int(k)):
+        raise ValueError("'%s' should be a %d x %d matrix" % (name, rows, k))
+    return a
+
+
+class Admix:
+    """One EM object for ancestry proportions (snpgpu_admix, include/snpgpu.h section 1s): feed SNP rows, set(q, f), run(), get().
+    Creation makes no HIP call; the first feed or set opens the device."""
+
+    def __init__(self, n_samp, n_pop, max_snps, f_min=1e-6, block_snps=0, device=0, stream=None):
+        self.n, self.k, self.max_snps = int(n_samp), int(n_pop), int(max_snps)
+        self.m = 0                  # rows fed
+        self.f_rows = 0             # rows F was set for
+        o = Opts(int(device), 0, 0, 0, 0, ctypes.c_void_p(stream) if stream else None)
+        h = ctypes.c_void_p()
+        self._h = None
+        check(lib().snpgpu_admix_create(self.n, self.k, self.max_snps, float(f_min), int(block_snps), ctypes.byref(o), ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if self._h:
+            lib().snpgpu_admix_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def feed(self, geno, fmt=None, n_snp=None):
+        """geno: numpy uint8 rows (U8 or PACKED2) or a device address (int, with n_snp; PACKED2 unless fmt says U8)"""
+        ptr, m, fmt, mem, _keep = _geno_input(geno, self.n, fmt, n_snp, device_fmt_default=GENO_PACKED2)
+        check(lib().snpgpu_admix_feed(self._h, ptr, m, fmt, mem))
+        self.m += m
+
+    def set(self, q=None, f=None):
+        """q [n][K] (rows normalised on entry), f [rows fed][K] (clamped on entry); None keeps what is there"""
+        q = _admix_matrix(q, self.n, self.k, "q")
+        f = _admix_matrix(f, self.m, self.k, "f")
+        check(lib().snpgpu_admix_set(self._h, _ptr(q), _ptr(f)))
+        if f is not None:
+            self.f_rows = self.m
+
+    def run(self, max_iter, tol=1e-4, fix_f=False):
+        """(loglik [n_done + 1], n_done): loglik[t] belongs to the state before iteration t, the last entry to the state get() returns"""
+        if int(max_iter) < 0:
+            raise ValueError("'max_iter' should be non-negative")
+        ll = np.full(int(max_iter) + 1, np.nan, np.float64)
+        done = ctypes.c_int(0)
+        check(lib().snpgpu_admix_run(self._h, int(max_iter), float(tol), ADMIX_FIX_F if fix_f else 0, _ptr(ll), ctypes.byref(done)))
+        return ll[:done.value + 1].copy(), done.value
+
+    def get(self):
+        """(Q [n][K], F [rows F was set for][K]; F is None while it has no values)"""
+        q = np.empty((self.n, self.k), np.float64)
+        f = np.empty((self.f_rows, self.k), np.float64) if self.f_rows else None
+        check(lib().snpgpu_admix_get(self._h, _ptr(q), _ptr(f)))
+        return q, f
+
+    def stats(self):
+        s = np.zeros(6, np.float64)
+        check(lib().snpgpu_admix_stats(self._h, _ptr(s)))
+        return dict(blocks=int(s[0]), launches=int(s[1]), pass_ms=float(s[2]), resident_bytes=int(s[3]), block_snps=int(s[4]),
+                    iterations=int(s[5]))
+
+
+def gnr_admix(n_samp, n_snp, q, f, f_min=1e-6, max_iter=500, tol=1e-4, fix_f=False, block_snps=0):
+    """snpgpu_gnrAdmix on the working space of n_samp samples and n_snp selected SNPs: (Q, F, loglik [n_done + 1], n_done)"""
+    n, m = int(n_samp), int(n_snp)
+    q = np.ascontiguousarray(q, np.float64)
+    if q.ndim != 2 or q.shape[0] != n:
+        raise ValueError("'q' should have one row per sample")
+    k = int(q.shape[1])
+    f = _admix_matrix(f, m, k, "f")
+    if int(max_iter) < 0:
+        raise ValueError("'max_iter' should be non-negative")
+    ll = np.full(int(max_iter) + 1, np.nan, np.float64)
+    done = ctypes.c_int(0)
+    qo, fo = np.empty((n, k), np.float64), np.empty((m, k), np.float64)
+    check(lib().snpgpu_gnrAdmix(k, float(f_min), int(block_snps), _ptr(q), _ptr(f), int(max_iter), float(tol), ADMIX_FIX_F if fix_f else 0,
+                                _ptr(ll), ctypes.byref(done), _ptr(qo), _ptr(fo)))
+    return qo, fo, ll[:done.value + 1].copy(), done.value

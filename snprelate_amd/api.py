@@ -43,6 +43,9 @@ INTEGRATION.md):
     snpgdsCombineGeno             R/AllUtilities.R:1285-1583 (data sets merged: the genotypes spliced on the GPU)
     snpgdsAlleleSwitch            R/AllUtilities.R:1686-1751 (a data set re-coded against given A alleles, the rows flipped on the GPU)
     snpgdsMDS                     no reference counterpart: the tutorial's cmdscale(1 - ibs$ibs, k), the eigenpairs found on the GPU
+    snpgdsAdmixProp               R/PCA.R:347-425  (admixture proportions from eigenvectors, on the host)
+    snpgdsAdmixTable              R/PCA.R:525-556  (their summary by group, on the host)
+    snpgdsAdmix                   no reference counterpart: ancestry proportions by EM on the binomial likelihood, on the GPU
 
 All arithmetic on genotype matrices runs on the MI355X through libsnpgpu.so
 (`_lib`); there is no CPU fallback.  The one exception is snpgdsIndInbCoef, which
@@ -2843,3 +2846,218 @@ def snpgdsPCRelatePairs(gdsobj, pcs, n_pcs=None, sample_id=None, snp_id=None, au
     return dict(sample_id=ids, snp_id=ws["snp_id"], ID1=ids[r["idx1"]], ID2=ids[r["idx2"]], idx1=r["idx1"], idx2=r["idx2"],
                 kinship=r["kinship"], k0=k0, k1=None if k0 is None else 1.0 - k0 - k2, k2=k2, nsnp=r["nsnp"], inbreed=r["inbreed"],
                 n_panels=r["n_panels"])
+
+
+def _admix_groups(groups, sample_id, what):
+    """`groups` of snpgdsAdmixProp / snpgdsAdmix: an ordered dict name -> sample ids.  Returns (names, one index array into sample_id
+    per group -- match(): the first occurrence -- and whether any id is in more than one group); an unknown id raises with the
+    reference's message."""
+    if not isinstance(groups, dict):
+        raise TypeError("is.list(groups) is not TRUE")
+    if len(groups) <= 1:
+        raise TypeError("length(groups) > 1 is not TRUE")
+    where = {}
+    for i, s in enumerate(list(np.asarray(sample_id))):
+        where.setdefault(s, i)
+    index, seen, overlap = [], set(), False
+    for i, (name, ids) in enumerate(groups.items()):
+        if isinstance(ids, (str, bytes, dict)) or not hasattr(ids, "__len__"):
+            raise ValueError("`groups' should be a list of sample IDs with respect to multiple groups.")
+        ids = list(np.asarray(ids).ravel()) if len(ids) else []
+        if any(s not in where for s in ids):
+            raise ValueError("`groups[[%d]]' includes sample(s) not existing in `%s'." % (i + 1, what))
+        if any(s in seen for s in ids):
+            overlap = True
+        seen.update(ids)
+        index.append(np.array([where[s] for s in ids], np.int64))
+    return list(groups.keys()), index, overlap
+
+
+def snpgdsAdmixProp(eigobj, groups, bound=False):
+    """Admixture proportions from an eigen-analysis (R/PCA.R:347-425; Zheng & Weir 2016): with G groups of reference samples, the
+    first G - 1 eigenvectors are mapped linearly so that the mean of group g over its own samples is the unit vector e_g.
+    eigobj: a snpgdsPCA / snpgdsEIGMIX result (sample_id, eigenvect [n][k]); groups: an ordered dict name -> sample ids, 2 ... k + 1
+    groups (overlapping groups warn); bound=True clips to [0, 1] and renormalises the rows.  Returns dict(sample_id, groups, prop
+    [n][G]) -- the reference's matrix with its dimnames.  Computed on the host, as in the reference."""
+    if not isinstance(eigobj, dict) or eigobj.get("sample_id") is None:
+        raise TypeError("'eigobj' should be a snpgdsPCA / snpgdsEIGMIX result with 'sample_id' and 'eigenvect'")
+    vect = eigobj.get("eigenvect")
+    if vect is None or np.ndim(vect) != 2:
+        raise TypeError("is.matrix(eigobj$eigenvect) is not TRUE")
+    vect = np.asarray(vect, np.float64)
+    if not isinstance(groups, dict):
+        raise TypeError("is.list(groups) is not TRUE")
+    if len(groups) <= 1:
+        raise TypeError("length(groups) > 1 is not TRUE")
+    if len(groups) > vect.shape[1] + 1:
+        raise ValueError("`eigobj' should have more eigenvectors than what is specified in `groups'.")
+    names, index, overlap = _admix_groups(groups, eigobj["sample_id"], "eigobj$sample.id")
+    if overlap:
+        warnings.warn("There are some overlapping between group sample IDs.")
+    if not isinstance(bound, (bool, np.bool_)):
+        raise TypeError("is.logical(bound) is not TRUE")
+    G = len(names)
+    E = vect[:, :G - 1]
+    mat = np.array([E[k].mean(axis=0) if len(k) else np.full(G - 1, np.nan) for k in index]).reshape(G, G - 1)
+    if np.isnan(mat).any():
+        raise ValueError("The eigenvectors should not have missing value!")
+    t_p = mat[G - 1]
+    t_r = np.linalg.inv(mat[:G - 1] - t_p[None, :])
+    new_p = (E - t_p[None, :]) @ t_r
+    new_p = np.column_stack([new_p, 1.0 - new_p.sum(axis=1)])
+    if bound:
+        new_p[new_p < 0] = 0.0
+        new_p[new_p > 1] = 1.0
+        new_p = new_p / new_p.sum(axis=1, keepdims=True)
+    return dict(sample_id=np.asarray(eigobj["sample_id"]), groups=names, prop=new_p)
+
+
+def snpgdsAdmixTable(propmat, group, sort=False):
+    """Summary of admixture proportions by group (R/PCA.R:525-556).  propmat: a snpgdsAdmixProp / snpgdsAdmix result or a numeric
+    [n][G] matrix; group: one label per row (None / NaN = NA: in no group).  Returns a dict with one entry per proportion column (its
+    group name, or its index for a plain matrix): the reference's data frame as dict(group, num, mean, sd, min, max), one row per
+    level of factor(group) -- the sorted labels -- with NaN proportions ignored (na.rm: a group whose proportions are all NaN keeps its
+    row, with a NaN mean) and sd in its n - 1 form.  sort=True orders the rows by decreasing mean."""
+    names = None
+    if isinstance(propmat, dict):
+        names = list(propmat["groups"])
+        propmat = propmat["prop"]
+    p = np.asarray(propmat)
+    if p.ndim != 2 or p.dtype.kind not in "fiu":
+        raise TypeError("is.numeric(propmat), is.matrix(propmat) are not all TRUE")
+    p = p.astype(np.float64)
+    if group is None or isinstance(group, (str, bytes)) or not hasattr(group, "__len__") or len(group) != p.shape[0]:
+        raise TypeError("is.vector(group) | is.factor(group), nrow(propmat) == length(group) are not all TRUE")
+    if not isinstance(sort, (bool, np.bool_)):
+        raise TypeError("is.logical(sort) is not TRUE")
+    labels = list(group)
+    na = [lab is None or (isinstance(lab, (float, np.floating)) and math.isnan(lab)) for lab in labels]
+    levels = sorted(set(lab for lab, m in zip(labels, na) if not m))
+    if names is None:
+        names = list(range(p.shape[1]))
+    ans = {}
+    for c, name in enumerate(names):
+        rows = []
+        for grp in levels:
+            x = np.array([(not m) and lab == grp for lab, m in zip(labels, na)], bool)
+            if not x.any():
+                continue
+            y = p[x, c]
+            y = y[~np.isnan(y)]
+            rows.append((grp, int(x.sum()), float(y.mean()) if y.size else float("nan"),
+                         float(y.std(ddof=1)) if y.size > 1 else float("nan"),
+                         float(y.min()) if y.size else float("inf"), float(y.max()) if y.size else float("-inf")))
+        if sort:
+            # order(mean, decreasing=TRUE): stable, NA last
+            rows = [rows[i] for i in sorted(range(len(rows)), key=lambda i: (math.isnan(rows[i][2]), -rows[i][2] if not math.isnan(rows[i][2]) else 0.0))]
+        ans[name] = dict(group=[r[0] for r in rows], num=np.array([r[1] for r in rows], np.int64),
+                         mean=np.array([r[2] for r in rows], np.float64), sd=np.array([r[3] for r in rows], np.float64),
+                         min=np.array([r[4] for r in rows], np.float64), max=np.array([r[5] for r in rows], np.float64))
+    return ans
+
+
+def admix_seeded_start(n_samp, k, p, seed, f_min):
+    """The seeded start of snpgdsAdmix without groups, so that it can be restated: with numpy.random.Generator(numpy.random.Philox(seed)),
+    first Q = n_samp x k uniforms on [0.5, 1.5) with normalised rows, then F = clamp(p_j + 0.2 (U - 0.5), f_min, 1 - f_min) with U
+    len(p) x k uniforms on [0, 1) and p the all-sample frequencies."""
+    rng = np.random.Generator(np.random.Philox(int(seed)))
+    q = 0.5 + rng.random((int(n_samp), int(k)))
+    q = q / q.sum(axis=1, keepdims=True)
+    p = np.asarray(p, np.float64)
+    f = np.clip(p[:, None] + 0.2 * (rng.random((len(p), int(k))) - 0.5), f_min, 1.0 - f_min)
+    return q, f
+
+
+def _admix_pop_freq(ws, pop, n_pop, device):
+    """(f [m][n_pop], p [m]): allele frequencies sum g / (2 called) of the working space's SNPs per population of `pop` (exact counters
+    of snpgpu_pop_counts) and over all samples; a SNP without a called sample in a population takes p_j there, or 0.5 without any"""
+    acnt, cnt = _lib.pop_counts(ws["packed"], ws["n_samp"], pop, n_pop, fmt=_lib.GENO_PACKED2, device=device)
+    a_all, c_all = acnt.sum(axis=1, dtype=np.int64), cnt.sum(axis=1, dtype=np.int64)
+    p = np.where(c_all > 0, a_all / np.maximum(c_all, 1), 0.5)
+    f = np.where(cnt > 0, acnt / np.maximum(cnt, 1), p[:, None])
+    return f, p
+
+
+def snpgdsAdmix(gdsobj, k=None, groups=None, supervised=False, sample_id=None, snp_id=None, autosome_only=True, remove_monosnp=True,
+                maf=float("nan"), missing_rate=float("nan"), q_start=None, f_start=None, seed=1, max_iter=500, tol=1e-4, f_min=1e-6,
+                with_afreq=True, verbose=True, device=0):
+    """Ancestry proportions by maximum likelihood on the GPU (snpgpu_gnrAdmix, include/snpgpu.h section 1s; no reference
+    counterpart, and agreement with another package's output is not tested: the definitions of DESIGN.md 32 are the specification).
+    The model is that of FRAPPE (Tang et al. 2005) and ADMIXTURE: g_ij ~ Binomial(2, sum_k q_ik f_kj) over the called genotypes,
+    fitted by EM in fp64 -- one pass over all genotypes per iteration, Q and F both updated from the old state.
+
+    groups: an ordered dict name -> sample ids as for snpgdsAdmixProp, but overlapping groups are refused; k defaults to (and must
+    equal) the number of groups.  F then starts from the groups' allele frequencies (exact counters; a SNP no sample of the group was
+    called at takes the all-sample frequency, or 0.5) and Q at 1 / k; column c belongs to group c.  supervised=True (needs groups)
+    holds F fixed: every sample is projected onto the groups' frequencies.  Without groups, k is required and the start is seeded on
+    the host (admix_seeded_start: numpy.random.Philox(seed); Q rows normalised uniforms on [0.5, 1.5), F = clamp(p_j + 0.2 (U - 0.5))).
+    q_start [n][k] / f_start [m][k] override either start, e.g. q_start=snpgdsAdmixProp(eig, groups, bound=True)["prop"] (in the
+    order of the selected samples).  The EM stops when an iteration raises the log-likelihood by less than tol, or after max_iter.
+    Returns dict(sample_id, snp_id, groups, prop [n][k], afreq [m][k] (None without with_afreq), loglik (the trace: one entry per
+    iteration made, plus the likelihood of the returned state), niter, converged).
+
+    The column labels of an unsupervised run are arbitrary (any permutation of the populations has the same likelihood).  Plain EM is
+    slow to converge: hundreds of iterations are usual, and a small tol stops on slow progress rather than at the optimum.  Not
+    built: acceleration (SQUAREM, quasi-Newton), cross-validation for the choice of k, multi-device objects, results in device
+    memory, anything below fp64."""
+    if not isinstance(supervised, (bool, np.bool_)):
+        raise TypeError("is.logical(supervised) is not TRUE")
+    if groups is None and supervised:
+        raise ValueError("'supervised=True' needs 'groups'.")
+    if groups is None and k is None:
+        raise ValueError("'k' is required without 'groups'.")
+    if groups is not None and (not isinstance(groups, dict) or len(groups) < 2):
+        raise ValueError("'groups' should be a dict of at least two groups of sample IDs.")
+    if k is None:
+        k = len(groups)
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 2 or k > 32:
+        raise ValueError("'k' should be an integer in 2 .. 32")
+    k = int(k)
+    if groups is not None and k != len(groups):
+        raise ValueError("'k' should be the number of groups (%d)" % len(groups))
+    if not (isinstance(f_min, (int, float, np.integer, np.floating)) and 0.0 < f_min < 0.5):
+        raise ValueError("'f_min' should be inside (0, 0.5)")
+    if isinstance(max_iter, (bool, np.bool_)) or not isinstance(max_iter, (int, np.integer)) or max_iter < 0:
+        raise ValueError("'max_iter' should be a non-negative integer")
+    if not isinstance(tol, (int, float, np.integer, np.floating)) or math.isnan(tol):
+        raise ValueError("'tol' should be a number")
+    ws = _init_file2("Ancestry proportions by EM:", gdsobj, sample_id, snp_id, autosome_only, remove_monosnp, maf, missing_rate, 1,
+                     verbose, device)
+    n, m = ws["n_samp"], ws["n_snp"]
+    ids = np.asarray(ws["sample_id"])
+    if m < 1:
+        raise ValueError("No SNP in the working dataset.")
+    names = None
+    q0 = f0 = None
+    if groups is not None:
+        names, index, overlap = _admix_groups(groups, ids, "the selected samples")
+        if overlap:
+            raise ValueError("There are some overlapping between group sample IDs.")
+        if any(len(ix) == 0 for ix in index):
+            raise ValueError("Each group should have at least one sample.")
+        pop = np.full(n, k, np.int32)                       # the rest: samples in no group
+        for g, ix in enumerate(index):
+            pop[ix] = g
+        if f_start is None:
+            f0 = _admix_pop_freq(ws, pop, k + 1 if (pop == k).any() else k, device)[0][:, :k]
+        if q_start is None:
+            q0 = np.full((n, k), 1.0 / k)
+    elif f_start is None or q_start is None:
+        # the all-sample frequencies sum g / (2 called) of the working space's SNPs, from its exact per-SNP counters; none called: 0.5
+        p = np.empty(m, np.float64)
+        _lib.check(_lib.lib().snpgpu_ws_snp_rate_freq(_lib._ptr(p), None, None))
+        q0, f0 = admix_seeded_start(n, k, np.where(np.isnan(p), 0.5, p), seed, f_min)
+    if q_start is not None:
+        q0 = np.ascontiguousarray(q_start, np.float64)
+        if q0.shape != (n, k):
+            raise ValueError("'q_start' should be a %d x %d matrix (selected samples x k)" % (n, k))
+    if f_start is not None:
+        f0 = np.ascontiguousarray(f_start, np.float64)
+        if f0.shape != (m, k):
+            raise ValueError("'f_start' should be a %d x %d matrix (selected SNPs x k)" % (m, k))
+    _cat(verbose, "    # of populations: %d%s\n    max. iterations: %d, tol: %g" % (k, " (supervised)" if supervised else "", max_iter, tol))
+    q, f, ll, done = _lib.gnr_admix(n, m, q0, f0, f_min=float(f_min), max_iter=int(max_iter), tol=float(tol), fix_f=bool(supervised))
+    converged = bool(done >= 2 and ll[done - 1] - ll[done - 2] < tol)
+    _cat(verbose, "%d iteration%s, log-likelihood %.6f%s" % (done, "" if done == 1 else "s", ll[-1], "" if converged else " (not converged)"))
+    return dict(sample_id=ids, snp_id=ws["snp_id"], groups=names, prop=q, afreq=f if with_afreq else None, loglik=ll, niter=done,
+                converged=converged)
